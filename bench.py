@@ -2,6 +2,8 @@
 """Benchmark of the Color-NeuS render hot path on MI355X.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full     ... and every side measurement listed below
+    python bench.py ... --dump-outputs DIR                      ... and what the last timed step computed, as DIR/<name>.npy
     python bench.py --gpus N ...          starts the N ranks itself (a child torch.distributed.run, before any GPU call); same as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     ... --scaling strong --rays-total 4096      BASELINE config C4: a fixed 4096-ray batch split over the N ranks (512 per GPU at N = 8)
@@ -11,12 +13,22 @@ renderer block (config/Color_NeuS_dtu.yml: 8x256 SDF net, 4x256 colour net, 4x25
 samples in 4 up-sampling steps) over one batch of synthetic rays of an 800x800 view; inputs resident in HBM.  Rays shard across
 ranks (weak scaling by default: --rays is per GPU).  Rank 0 prints ONE JSON line.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+Everything else it can measure takes runs of its own and is behind --full (the --no-* switches deselect single legs of a --full run).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step computed -- the loss, the renderer's output dict, every
+parameter gradient and every updated parameter -- as DIR/<name>.npy (float32; float64 tensors stay float64, integer tensors become float64).
+Above 64 MB in all, the largest arrays are cut to a fixed, seeded sample of their flattened entries (the same entries on every run of the
+same arguments).  Inputs (weights, rays, jitter) are seeded, so two builds can be compared output for output.
+
+Extra objects on the JSON line with --full:
   roofline            dominant kernel: algorithmic HBM bytes per launch (operand matrices read once + outputs written once,
                       DESIGN.md section 4) / per-launch HIP-event time against the 8 TB/s HBM3E peak (hbm_frac), and its matrix-core
                       work (3 f16 MFMAs per fp32 product) against the 2.5 PFLOP/s dense f16 peak (mfma_frac).  Measured in a second,
                       event-instrumented pass over the same steps.
   kernel_breakdown    per kernel family: ms per step, GB/s (algorithmic), TFLOP/s -- includes the sampler / compositor kernels.
+  strong_scaling      N > 1, weak scaling: the same invocation's BASELINE C4 figure (--rays-total rays of one view split over the ranks, and the
+                      same batch on one GPU of the node).
   step_ms             per-step HIP-event times of the K timed steps (events on the launch stream, rank 0): median, p10, p90, and the
                       rate the median implies (SURVEY 8d protocol); `value` itself stays K steps over the barrier-to-barrier wall time.
   inference           forward-only rays/s (validate_image, NeuS_Trainer.py:216-277) without and with the early-termination compaction
@@ -59,6 +71,11 @@ def parse():
     ap.add_argument("--rays-total", type=int, default=4096, help="rays per step over ALL GPUs (--scaling strong)")
     ap.add_argument("--no-optim", action="store_true", help="time fwd+loss+bwd only (skip clip + Adam)")
     ap.add_argument("--torch-optim", action="store_true", help="torch._foreach clip + torch fused Adam instead of the library's one-launch clip+Adam")
+    ap.add_argument("--full", action="store_true", help="also measure every side leg (roofline, kernel breakdown, per-step event times, small batches, "
+                                                         "loss_only, inference, C5, the PyTorch and CPU baselines, the strong-scaling leg at N > 1); "
+                                                         "a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, renderer outputs, gradients, updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-small-batch", action="store_true")
@@ -87,6 +104,41 @@ def clip_per_parameter_(params, max_norm=1.0):
     torch._foreach_mul_(grads, coefs)
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(folder, loss, out, module, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: loss, renderer outputs, parameter gradients and parameters after the step as <folder>/<name>.npy.  Over `limit` bytes in
+    all, every array longer than a common length k is cut to k entries of its flattened form, chosen by a generator seeded from the array's
+    name and size (k: the largest length that fits the limit), so that runs with the same arguments write the same entries."""
+    import zlib
+    import numpy as np
+    arrays = {"loss": loss}
+    for k, v in (out or {}).items():
+        if torch.is_tensor(v):
+            arrays["out." + k] = v
+    for k, p in module.named_parameters():
+        arrays["param." + k] = p
+        if p.grad is not None:
+            arrays["grad." + k] = p.grad
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 or not v.dtype.is_floating_point else torch.float32)
+              for k, v in arrays.items()}
+    size = lambda v, n: min(v.numel(), n) * v.element_size()
+    keep = max(v.numel() for v in arrays.values())
+    if sum(size(v, keep) for v in arrays.values()) > limit:
+        lo, hi = 1, keep                           # largest common length that fits
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if sum(size(v, mid) for v in arrays.values()) <= limit else (lo, mid - 1)
+        keep = lo
+    os.makedirs(folder, exist_ok=True)
+    for k, v in arrays.items():
+        if v.numel() > keep:   # (arrays that fit keep their shape; a cut one is its sample, flat)
+            g = torch.Generator().manual_seed(zlib.crc32(k.encode()) + v.numel())
+            v = v.reshape(-1)[torch.randperm(v.numel(), generator=g)[:keep].sort().values]
+        np.save(os.path.join(folder, k + ".npy"), v.numpy())
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a launcher: start the N ranks as a CHILD `torch.distributed.run` (never an exec: this process
     has made no GPU call, and stays that way), let the children inherit stdout / stderr (rank 0 prints the JSON line) and exit with
@@ -108,6 +160,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -150,7 +204,7 @@ def main():
     params0 = params = list(renderer.parameters())
     lib = cn.load_library(emu) if emu else cn.load_library()
     assert emu or lib.backend == "hip-gfx950"
-    if emu:   # every extra leg measures the GPU: off
+    if emu or not args.full:   # a plain run times the headline step only; under emulation every extra leg would measure the host: off
         args.no_roofline = args.no_small_batch = args.no_torch_gpu_baseline = args.no_inference = args.no_c5 = args.no_cpu_baseline = args.no_loss_only = True
     if args.torch_optim:
         opt = torch.optim.Adam(params, lr=5e-4, betas=(0.9, 0.99), fused=True)
@@ -164,6 +218,7 @@ def main():
     # parameters (tests/test_graph_step.py).  Not the default: it measured no faster than the enqueued step (see --graph's help).
     use_graph = (not emu and world == 1 and args.graph and not args.torch_optim and not args.torch_loss and not args.no_optim)
     graphs = {}
+    last = {} if args.dump_outputs else None   # --dump-outputs: the renderer outputs of the latest step (a graph's are its static buffers)
 
     if args.scaling == "strong":
         if args.rays_total % world:
@@ -223,6 +278,8 @@ def main():
                 o, d, rgb, msel, near, far = raygen._generate(lib, idx, r, c2w_, focal_, Hh, Ww, True, False, image=image_, mask=mask_,
                                                               origin=None, radius=1.0, want_nearfar=True)
                 out = renderer(o, d, near, far, t_rand=t)
+                if last is not None:
+                    last["out"] = out
                 loss, _ = cn.compute_loss_fused(out, rgb, msel, library=lib)
                 for p in params0:
                     p.grad = None
@@ -251,6 +308,8 @@ def main():
             out = rnd(o, d, near, far, training_outputs=outputs, t_rand=parallel.draw_jitter(rg, rank, world, "cpu"))
         else:
             out = rnd(o, d, near, far, training_outputs=outputs)
+        if last is not None:
+            last["out"] = out
         if args.torch_loss:    # the torch restatement of compute_loss (and its sharded counterpart)
             if nw == 1:
                 loss, _ = cn.compute_loss(out, gt, mask)
@@ -314,7 +373,9 @@ def main():
         return (r if r is not None else R) * world * nsteps / dts
 
     step_times = []
-    dt, loss = timed(args.steps, args.warmup, per_step=step_times)
+    dt, loss = timed(args.steps, args.warmup, per_step=step_times if args.full else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last.get("out"), renderer)
     Rg = R * world
     ms_per_step = dt / args.steps * 1e3
     value = Rg * args.steps / dt
@@ -341,7 +402,7 @@ def main():
     # config C4 -- ONE batch of --rays-total rays (4096) of one view and its jitter draw split over the ranks (512 rays per GPU at 8 GPUs), same
     # protocol (barrier + synchronise on both sides, max over ranks), next to the SAME batch as one step on one GPU of this node (rank 0 alone, the
     # other ranks wait at the barrier), so that the strong-scaling efficiency does not need a second invocation.
-    if world > 1 and not strong and args.rays_total % world == 0:
+    if args.full and world > 1 and not strong and args.rays_total % world == 0:
         n_s = max(2, min(args.steps, 60))
         w_s = max(1, min(args.warmup, 10))
         rs = args.rays_total // world

@@ -86,9 +86,9 @@ def test_bench_eight_ranks_c4_shape_matches_single_process():
 
 
 def test_default_invocation_carries_both_scaling_figures():
-    """The driver's command is fixed (`bench.py --gpus N`, weak scaling): the same invocation must also yield the strong-scaling figure of BASELINE C4
+    """The driver's command is fixed (`bench.py --gpus N --full`, weak scaling): the same invocation must also yield the strong-scaling figure of BASELINE C4
     -- a `strong_scaling` object: --rays-total rays of ONE view split over the ranks, the same batch on one rank alone, speed-up and efficiency."""
-    d = _run(2, 16, extra=("--rays", "8"), scaling="weak")
+    d = _run(2, 16, extra=("--rays", "8", "--full"), scaling="weak")
     assert d["scaling"] == "weak" and d["n_gpus"] == 2 and d["config"]["rays_per_step_per_gpu"] == 8 and d["config"]["rays_per_step_total"] == 16
     s = d["strong_scaling"]
     assert s["scaling"] == "strong" and s["rays_total"] == 16 and s["rays_per_gpu"] == 8 and s["unit"] == "rays/s"
@@ -97,7 +97,60 @@ def test_default_invocation_carries_both_scaling_figures():
     assert abs(one["value"] - 16 / (one["ms_per_step"] * 1e-3)) <= 1e-3 * one["value"] + 0.1
     assert abs(s["speedup_vs_one_gpu_same_batch"] - one["ms_per_step"] / s["ms_per_step"]) < 2e-3 * s["speedup_vs_one_gpu_same_batch"] + 1e-3
     assert abs(s["efficiency_vs_n1_same_batch"] - s["speedup_vs_one_gpu_same_batch"] / 2) < 1e-3
-    assert "strong_scaling" not in _run(1, 16, extra=("--rays", "8"), scaling="weak")     # one rank: nothing to split
+    assert "strong_scaling" not in _run(1, 16, extra=("--rays", "8", "--full"), scaling="weak")     # one rank: nothing to split
+
+
+def test_plain_run_times_the_headline_step_only():
+    """Without --full the line holds the headline figure and nothing that takes a run of its own (here: the strong-scaling side leg at N = 2)."""
+    d = _run(2, 16, extra=("--rays", "8"), scaling="weak")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and abs(d["value"] - 16 * 2 / (d["ms_per_step"] * 2e-3)) <= 1e-3 * d["value"] + 0.1
+    for k in ("strong_scaling", "step_ms", "roofline", "kernel_breakdown", "small_batch", "loss_only", "inference", "c5", "torch_gpu_baseline", "cpu_baseline"):
+        assert k not in d, k
+
+
+def test_dump_outputs_same_arguments_same_arrays(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, renderer outputs, gradients and updated parameters as float32 / float64 .npy files; two runs
+    with the same arguments start from the same inputs and (on this deterministic build) write the same arrays; the 64 MB bound cuts arrays to a
+    fixed sample."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    runs = []
+    for i in range(2):
+        folder = tmp_path / ("run%d" % i)
+        d = _run(1, 16, extra=("--dump-outputs", str(folder)))
+        files = sorted(os.listdir(folder))
+        assert "loss.npy" in files and "out.color_fine.npy" in files
+        assert any(f.startswith("grad.sdf_network.") for f in files) and any(f.startswith("param.sdf_network.") for f in files)
+        arrs = {f: np.load(folder / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= bench.DUMP_LIMIT_BYTES
+        assert arrs["out.color_fine.npy"].shape == (16, 3)
+        assert abs(float(arrs["loss.npy"]) - d["config"]["final_loss"]) <= 1e-6 * abs(d["config"]["final_loss"])
+        runs.append(arrs)
+    assert runs[0].keys() == runs[1].keys()
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+    # the bound: a small limit keeps every array within it and cuts the longest ones to the same seeded entries each time
+    import torch
+    g = torch.Generator().manual_seed(0)
+    lin = torch.nn.Linear(64, 32)
+    lin.weight.grad = torch.randn(32, 64, generator=g)
+    out = {"big": torch.randn(1000, 3, generator=g), "small": torch.randn(5, generator=g)}
+    cut = []
+    for i in range(2):
+        folder = tmp_path / ("cut%d" % i)
+        bench.dump_outputs(str(folder), torch.tensor(1.5), out, lin, limit=4 * 1200)
+        arrs = {f: np.load(folder / f) for f in sorted(os.listdir(folder))}
+        assert sum(a.nbytes for a in arrs.values()) <= 4 * 1200
+        assert arrs["out.small.npy"].shape == (5,) and arrs["param.bias.npy"].shape == (32,)
+        big = out["big"].reshape(-1).numpy()
+        assert np.isin(arrs["out.big.npy"], big).all() and arrs["out.big.npy"].size < big.size
+        cut.append(arrs)
+    for f in cut[0]:
+        assert np.array_equal(cut[0][f], cut[1][f]), f
 
 
 def test_plain_gpus_2_starts_two_ranks():

@@ -1,78 +1,90 @@
-"""Container-only (skipped where /root/reference is absent, i.e. on the GPU box): the drop-in claim against the REAL reference.
+"""The drop-in claim against the reference, from what the reference itself recorded (tests/golden/reference_dropin.npz, written by
+tools/gen_dropin_golden.py from the reference's own config files, classes and registry builder).
 
-The native classes are registered into the reference's own RENDERER registry (lib/utils/builder.py:252-309), built by the
-reference's own build_from_cfg (builder.py:9-47) from its own config/Color_NeuS_dtu.yml, and must load the reference renderer's
-state_dict with strict=True; a forward on the CPU-emulation build is compared with the reference module on the same rays."""
+The native classes are registered into a registry of the reference's form (register_module(name=, force=, module=)), built from the
+MODEL.RENDERER nodes of the reference's config/*.yml, and must take a state_dict with exactly the names and shapes of the reference
+renderer's (strict=True); a forward on the CPU-emulation build is compared with the reference module's outputs on the same rays, with the
+same weights (the native module's seeded init reproduces the reference's: checked against the recorded per-tensor sums)."""
+import json
 import os
-import sys
 
+import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import ref_import  # noqa: E402
+import _golden as G
+import _native as N
+import color_neus_amd as cn
 
-import _native as N  # noqa: E402
-import color_neus_amd as cn  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_import.reference_available(), reason="reference checkout not present (GPU box)")
+FIXTURE = os.path.join(G.GOLDEN, "reference_dropin.npz")
 
 
 @pytest.fixture(scope="module")
-def reference():
-    Color_NeuS, NeuS, CN, mods = ref_import.import_reference()
-    from lib.utils import builder
-    return dict(Color_NeuS=Color_NeuS, NeuS=NeuS, CN=CN, builder=builder)
+def fx():
+    return np.load(FIXTURE)
+
+
+class _Node(dict):
+    __getattr__ = dict.__getitem__
+
+
+def _wrap(d):
+    return _Node({k: _wrap(v) if isinstance(v, dict) else v for k, v in d.items()})
+
+
+def _node(fx, yml):
+    return _wrap(json.loads(str(fx["cfg:" + yml])))
+
+
+class _Registry:
+    """a registry of the reference's form: register_module(name=, force=, module=), looked up by the node's TYPE"""
+
+    def __init__(self):
+        self._module_dict = {}
+
+    def register_module(self, name=None, force=False, module=None):
+        assert name not in self._module_dict or force
+        self._module_dict[name] = module
+        return module
+
+    def build(self, node):
+        return self._module_dict[node["TYPE"]](node)
 
 
 @pytest.mark.parametrize("yml,cls_name", [("Color_NeuS_dtu.yml", "ColorNeuSRenderer"), ("NeuS_dtu.yml", "NeuSRenderer"),
                                           ("Color_NeuS_iho.yml", "ColorNeuSRenderer"), ("Color_NeuS_bmvs.yml", "ColorNeuSRenderer")])
-def test_register_build_and_strict_load(reference, yml, cls_name):
-    import yaml
-    builder, CN = reference["builder"], reference["CN"]
-    with open(os.path.join(ref_import.REFERENCE_ROOT, "config", yml)) as f:
-        node = CN(yaml.safe_load(f))["MODEL"]["RENDERER"]
-    reg = builder.RENDERER
-    saved = dict(reg._module_dict)
-    try:
-        ref_r = builder.build_from_cfg(node, reg)                      # the reference's own class
-        assert type(ref_r).__module__.startswith("lib.models.renderers")
-        cn.register_into(reg)                                          # one line in a user's train.py
-        ours = builder.build_from_cfg(node, reg)
-        assert type(ours).__name__ == cls_name and isinstance(ours, cn.NeuSRenderer)
-        sd = ref_r.state_dict()
-        missing, unexpected = ours.load_state_dict(sd, strict=True)
-        assert not missing and not unexpected
-        assert [k for k, _ in ours.named_parameters()] and set(dict(ours.named_parameters())) == set(dict(ref_r.named_parameters()))
-        for k, p in ref_r.named_parameters():
-            assert dict(ours.named_parameters())[k].shape == p.shape, k
-    finally:
-        reg._module_dict.clear()
-        reg._module_dict.update(saved)
+def test_register_build_and_strict_load(fx, yml, cls_name):
+    node = _node(fx, yml)
+    reg = _Registry()
+    cn.register_into(reg)                                              # one line in a user's train.py
+    ours = reg.build(node)
+    assert type(ours).__name__ == cls_name and isinstance(ours, cn.NeuSRenderer)
+    ref_sd = json.loads(str(fx["sd:" + yml]))
+    sd = {k: torch.zeros(shape) for k, shape in ref_sd}               # the reference renderer's state_dict: names and shapes
+    missing, unexpected = ours.load_state_dict(sd, strict=True)
+    assert not missing and not unexpected
+    ref_params = json.loads(str(fx["params:" + yml]))
+    assert [k for k, _ in ours.named_parameters()] and set(dict(ours.named_parameters())) == set(ref_params)
+    shapes = dict((k, shape) for k, shape in ref_sd)
+    for k, p in ours.named_parameters():
+        assert list(p.shape) == shapes[k], k
 
 
 @pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
-def test_forward_matches_live_reference_on_same_rays(reference):
-    """Same cfg node, same state_dict, same rays through both modules (perturb off): per-ray outputs to 1e-4 (init regime, G3)."""
-    import yaml
-    builder, CN = reference["builder"], reference["CN"]
-    with open(os.path.join(ref_import.REFERENCE_ROOT, "config", "Color_NeuS_dtu.yml")) as f:
-        node = CN(yaml.safe_load(f))["MODEL"]["RENDERER"]
+def test_forward_matches_live_reference_on_same_rays(fx):
+    """Same cfg node, same weights, same rays through both modules (perturb off): per-ray outputs to 1e-4 (init regime, G3)."""
+    node = _node(fx, "Color_NeuS_dtu.yml")
     torch.manual_seed(0)
-    ref_r = reference["Color_NeuS"](node)
     ours = cn.ColorNeuSRenderer(node, library=N.EMU_LIB)
-    ours.load_state_dict(ref_r.state_dict(), strict=True)
-    g = torch.Generator().manual_seed(1)
-    o = torch.nn.functional.normalize(torch.randn(6, 3, generator=g), dim=-1) * 2.7
-    d = torch.nn.functional.normalize(torch.randn(6, 3, generator=g) * 0.3 - o, dim=-1)
-    from lib.models.tools.ray_utils import near_far_from_sphere
-    near, far = near_far_from_sphere(o, d)
-    a = ref_r(o, d, near.squeeze(), far.squeeze(), perturb_overwrite=0)
-    b = ours(o, d, near.squeeze(), far.squeeze(), perturb_overwrite=0)
+    for k, v in ours.state_dict().items():                            # the reference's weights at the same seed
+        s = np.array([float(v.double().sum()), float(v.double().abs().sum())])
+        assert np.allclose(s, fx["fwd:wsum:" + k], rtol=1e-9, atol=0), (k, s, fx["fwd:wsum:" + k])
+    o, d = torch.from_numpy(fx["fwd:rays_o"]), torch.from_numpy(fx["fwd:rays_d"])
+    near, far = torch.from_numpy(fx["fwd:near"]), torch.from_numpy(fx["fwd:far"])
+    b = ours(o, d, near, far, perturb_overwrite=0)
     assert float((b["z_vals"] - b["z_vals"].sort(-1).values).abs().max()) == 0.0
     for k in ("color_fine", "depth", "weight_sum", "gradient_error", "global_color"):
-        ra = a[k].detach().reshape(-1)
+        ra = torch.from_numpy(fx["fwd:out_" + k]).reshape(-1)
         err = float((b[k].detach().reshape(-1) - ra).abs().max()) / max(float(ra.abs().max()), 1e-30)
         assert err < 1e-4, (k, err)
-    assert set(a.keys()) <= set(b.keys())
+    assert set(json.loads(str(fx["fwd:keys"]))) <= set(b.keys())

@@ -6,7 +6,7 @@ python -m pytest tests/test_hip_parity.py tests/test_edge_batches.py tests/test_
 tail -5 gpurun_out/r06s/parity.txt
 cp color-neus_amd/libcolorneus_hip.so /tmp/lib_default.so
 cp /tmp/lib_default.so tools/ab/libs/chain16.so
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
 for rep in 1 2 3; do
   for v in chain32 chain16; do
     cp tools/ab/libs/$v.so color-neus_amd/libcolorneus_hip.so

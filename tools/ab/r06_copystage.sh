@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 cp color-neus_amd/libcolorneus_hip.so /tmp/lib_default.so
-ARGS="--steps 100 --warmup 10 --no-optim --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
+ARGS="--full --steps 100 --warmup 10 --no-optim --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
 for rep in 1 2 3; do
   for v in cur exp_copystage; do
     cp tools/ab/libs/$v.so color-neus_amd/libcolorneus_hip.so

@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r06w
 python -m pytest tests/test_hip_parity.py tests/test_edge_batches.py tests/test_forward_only.py -x -q -m gpu 2>&1 | tail -4 > gpurun_out/r06w/parity.txt
 tail -2 gpurun_out/r06w/parity.txt
 cp color-neus_amd/libcolorneus_hip.so /tmp/lib_default.so
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
 for rep in 1 2 3; do
   for v in tpose direct; do
     cp tools/ab/libs/$v.so color-neus_amd/libcolorneus_hip.so

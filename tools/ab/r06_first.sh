@@ -13,5 +13,6 @@ for rep in 1 2 3; do
 done > gpurun_out/r06a/ab_tr.txt 2>&1
 cp /tmp/lib_default.so color-neus_amd/libcolorneus_hip.so
 python tools/energy_ledger.py --seconds 4 > gpurun_out/r06a/energy_ledger.txt 2> gpurun_out/r06a/energy_ledger.err
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-torch-gpu-baseline --no-c5 > gpurun_out/r06a/bench.json 2> gpurun_out/r06a/bench.err
+RES=${RES:-results}; mkdir -p "$RES"
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-torch-gpu-baseline --no-c5 > "$RES/bench.json" 2> "$RES/bench.err"
 cat gpurun_out/r06a/parity.txt gpurun_out/r06a/ab_tr.txt; head -30 gpurun_out/r06a/energy_ledger.txt

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r06c
 python -m pytest tests/test_graph_step.py tests/test_clip_adam.py -x -q -m gpu 2>&1 | tail -15 > gpurun_out/r06c/graph_tests.txt
 cat gpurun_out/r06c/graph_tests.txt
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-roofline --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-roofline --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
 for rep in 1 2; do
   for v in graph nograph; do
     F=""; [ $v = nograph ] && F="--no-graph"

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r06v
 cp color-neus_amd/libcolorneus_hip.so /tmp/lib_default.so
-ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
+ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-small-batch --no-torch-gpu-baseline --no-inference --no-c5 --no-loss-only"
 for rep in 1 2 3; do
   for v in shfl swap c16swap; do
     cp tools/ab/libs/$v.so color-neus_amd/libcolorneus_hip.so

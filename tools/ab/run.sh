@@ -3,7 +3,7 @@
 for round in 1 2 3; do
   for v in base new; do
     cp tools/ab/libcolorneus_hip_$v.so color-neus_amd/libcolorneus_hip.so
-    python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-small-batch 2>/dev/null | python -c "
+    python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-small-batch 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 kb = {k['kernel']: k['ms_per_step'] for k in d['kernel_breakdown']}

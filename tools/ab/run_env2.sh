@@ -4,7 +4,7 @@
 R=${3:-4096}
 for round in 1 2 3; do
   for v in "$1" "$2"; do
-    env $v python bench.py --rays $R --steps 40 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-small-batch --no-inference --no-c5 --no-loss-only 2>/dev/null | python -c "
+    env $v python bench.py --full --rays $R --steps 40 --warmup 8 --no-cpu-baseline --no-torch-gpu-baseline --no-small-batch --no-inference --no-c5 --no-loss-only 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 kb = {k['kernel']: k['ms_per_step'] for k in d['kernel_breakdown']}

@@ -2,7 +2,7 @@
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for rays in (32, 128, 512, 2048):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rays", str(rays), "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rays", str(rays), "--steps", "30", "--warmup", "5", "--no-cpu-baseline",
                           "--no-torch-gpu-baseline", "--no-small-batch"], capture_output=True, text=True).stdout.strip().split("\n")[-1]
     d = json.loads(out)
     kb = {k["kernel"]: k for k in d["kernel_breakdown"]}
