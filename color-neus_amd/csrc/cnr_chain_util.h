@@ -89,7 +89,9 @@ __device__ __forceinline__ void chain_put16(const f32x16& a, float sc, unsigned 
 
 // ------------------------------------------------------------------------------------------------
 // One MFMA phase of a chain-fused kernel: NKB k16 blocks of the transposed product acc[j][rt] += W_frag(kb) x Act_frag(kb, rt) as straight-line
-// code (3 x v_mfma_f32_32x32x16_f16 per product: hi x lo, lo x hi, hi x hi).
+// code (3 x v_mfma_f32_32x32x16_f16 per product: hi x lo, lo x hi, hi x hi).  These kernels stay on 32 x 32 x 16: converted to 16 x 16 x 32 they were
+// 1-8 % slower in three forms (profiles/r06_ab_chain_mfma16.txt): they run below the board's power limit, so cheaper MFMAs do not buy time as they do
+// in layer_dw.
 //   * the weight fragments come from a 4-deep register ring: blocks kb0 .. kb0 + 3 must already be in flight (chain_wprime); block kb + 4 is
 //     requested as soon as the MFMAs of block kb have read their slot;
 //   * the activation fragments of block kb + 1 are read from LDS into a second register set BEFORE the MFMAs of block kb;
@@ -134,33 +136,6 @@ __device__ __forceinline__ void chain_mfma_blocks(f32x16 (&acc)[CB][RT], f16x8 (
         a2[cur ^ 1][rt] = *reinterpret_cast<const f16x8*>(Ab + rt * 32 * CH_ALD + aplane + (gk + 1) * 32);
       }
     }
-#ifdef CNR_CHAIN_MFMA16_PROBE
-    // TIMING PROBE ONLY (wrong results): the same FLOP, fragment registers and accumulator registers issued as v_mfma_f32_16x16x32_f16.  It measured the chain
-    // kernels 15-27 % faster (profiles/r06_probe_chain_mfma16.txt) and MISLED: the real conversion (tools/ab/exp_chain_mfma16.patch: k32 fragment layout, a lane
-    // owning two points x 8 columns, parity-green on the GPU) is 5-8 % SLOWER than this 32 x 32 x 16 form (profiles/r06_ab_chain_mfma16.txt) -- the probe's wrong
-    // activations change what the matrix pipe is fed (zero-heavy operands draw far less power: tools/mfma_power.py), these kernels run below the board's power
-    // limit (so cheaper MFMAs do not buy time as they do in layer_dw), and the 16 x 16 lane ownership costs the epilogue two cross-lane steps per row maximum.
-#define PROBE16(W, A)                                                                                                        \
-    _Pragma("unroll") for (int j = 0; j < CB; ++j) _Pragma("unroll") for (int rt = 0; rt < RT; ++rt) {                      \
-      typedef float pf4 __attribute__((ext_vector_type(4)));                                                                 \
-      f32x16& c = acc[j][rt];                                                                                                \
-      if (gk & 1) {                                                                                                          \
-        pf4 s0 = {c[8], c[9], c[10], c[11]}, s1 = {c[12], c[13], c[14], c[15]};                                              \
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[gk & 3][j], A[cur][rt], s0, 0, 0, 0);                                  \
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[gk & 3][j], A[cur][(rt + 1) % RT], s1, 0, 0, 0);                       \
-        c[8] = s0[0]; c[9] = s0[1]; c[10] = s0[2]; c[11] = s0[3]; c[12] = s1[0]; c[13] = s1[1]; c[14] = s1[2]; c[15] = s1[3]; \
-      } else {                                                                                                               \
-        pf4 s0 = {c[0], c[1], c[2], c[3]}, s1 = {c[4], c[5], c[6], c[7]};                                                    \
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[gk & 3][j], A[cur][rt], s0, 0, 0, 0);                                  \
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(W[gk & 3][j], A[cur][(rt + 1) % RT], s1, 0, 0, 0);                       \
-        c[0] = s0[0]; c[1] = s0[1]; c[2] = s0[2]; c[3] = s0[3]; c[4] = s1[0]; c[5] = s1[1]; c[6] = s1[2]; c[7] = s1[3];       \
-      }                                                                                                                      \
-    }
-    PROBE16(wr2, a1)
-    PROBE16(wr1, a2)
-    PROBE16(wr1, a1)
-#undef PROBE16
-#else
 #pragma unroll
     for (int j = 0; j < CB; ++j)
 #pragma unroll
@@ -173,7 +148,6 @@ __device__ __forceinline__ void chain_mfma_blocks(f32x16 (&acc)[CB][RT], f16x8 (
     for (int j = 0; j < CB; ++j)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) acc[j][rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr1[gk & 3][j], a1[cur][rt], acc[j][rt], 0, 0, 0);
-#endif
     if (gk + 4 < NTOT) chain_wload<CB>(wr1, wr2, gk & 3, wlane, nkb_w, kb0 + gk + 4);
     __builtin_amdgcn_sched_barrier(0);
   }

@@ -9,10 +9,9 @@
 // product path): the tuning words are read from the environment as well.
 //
 //   environment variable     member            meaning
-//   CNR_NO_FUSED             no_fused          per-layer launches instead of every chain-fused kernel (value chain, saving chains, gradient chain)
+//   CNR_NO_FUSED             no_fused          per-layer launches instead of every chain-fused kernel (value chain, saving chains)
 //   CNR_NO_CHAIN_FWD         no_chain_fwd      per-layer launches instead of the chain-fused colour + relight forward
 //   CNR_NO_CHAIN_SDF         no_chain_sdf      per-layer launches instead of the chain-fused saving SDF forward
-//   CNR_CHAIN_GRAD           chain_grad        opt-in: the chain-fused gradient chain (slower than its 8 launches; kept parity-green)
 //   CNR_NO_FDW               no_fdw            separate layer and weight-gradient launches instead of layer_dw_kernel (and sweep0_dw_kernel)
 //   CNR_FDW_SPLIT            fdw_split         the fused launches' partial-sum slots filled by the two separate kernels
 //   CNR_NO_TOP_FUSE          no_top_fuse       the top SDF layer's backward as launches of its own
@@ -39,7 +38,7 @@
 namespace cnr {
 
 struct DebugFlags {
-  bool no_fused = false, no_chain_fwd = false, no_chain_sdf = false, chain_grad = false, no_fdw = false, fdw_split = false, no_top_fuse = false,
+  bool no_fused = false, no_chain_fwd = false, no_chain_sdf = false, no_fdw = false, fdw_split = false, no_top_fuse = false,
        no_head_bwd = false, no_head_fwd = false, no_strip_bwd = false, no_sampler_fuse = false, no_sweep0 = false, no_narrow_bwd = false,
        no_narrow_dx = false, disable_ws = false, ws_generic = false, ws_nostream = false, dw_fp32 = false, dw_bf16 = false, roctx = false;
   int ws_serp = 1;

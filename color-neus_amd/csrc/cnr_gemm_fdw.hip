@@ -9,7 +9,7 @@
 // has 512 KB.  So a launch is split into COLUMN HALVES: a workgroup owns 128 output columns (weights: 128 KB) and the matching
 // [256 x 128] block of dW (128 KB); the two halves of a point range run on the same XCD (blocks b and b + 8), so the second read of the
 // input tile is an L2 hit.  Inside a workgroup the waves are specialised (one of each kind per SIMD):
-//   waves 0..3 "P"  weight-stationary layer product of their 32 columns (3 x v_mfma_f32_32x32x16_f16 per k16 block, as cnr_gemm_ws.h),
+//   waves 0..3 "P"  weight-stationary layer product of their 32 columns (3 x v_mfma_f32_16x16x32_f16 per k32 block, as cnr_gemm_ws.h),
 //                   fused epilogue with 16-byte global accesses, and -- from the side inputs the epilogue fetched anyway -- the tile of the
 //                   epilogue-side operand Ep, scaled and split hi / lo, written row-major ([point][column], one 8-byte store per plane and 4 columns) into LDS;
 //   waves 4..7 "D"  stage the input tile S (HBM -> registers -> exact power-of-two row scale -> f16 hi / lo planes in LDS, the operand of
@@ -28,11 +28,8 @@ namespace cnr {
 
 // Round 6: the MFMA SHAPE.  v_mfma_f32_16x16x32_f16 is 12 % cheaper per FLOP than v_mfma_f32_32x32x16_f16 on random operands and holds the clock 15 % higher
 // (profiles/r06_mfma_shapes.txt: 1950 against 1705 TFLOP/s with the matrix pipe alone at the board's power limit) -- and this kernel's time is its joules.
-// FD_MFMA16 = 1: product and weight gradient on 16 x 16 x 32 blocks (same LDS planes, same register budget: 128 weight registers, 16 / 128 accumulators);
-// 0: the 32 x 32 x 16 form (A/B builds).
-#ifndef FD_MFMA16
-#define FD_MFMA16 1
-#endif
+// So product and weight gradient run on 16 x 16 x 32 blocks (same LDS planes, same register budget: 128 weight registers, 16 / 128 accumulators);
+// the 32 x 32 x 16 form was 2 % slower per step (profiles/r06_ab_mfma16_layer_dw.txt) and was removed.
 typedef float fd_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int FD_TP = 32;                        // points per tile
 constexpr int FD_ALD = 256 * 2 + 16;             // bytes per LDS row of one S plane (+16: conflict-free ds_read_b128 of the product fragments)
@@ -134,7 +131,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
   if (isP) {
     // ================================================================ P waves
     const int c0 = half * 128 + wave * 32;               // first output column of this wave
-#if FD_MFMA16
     // weights of this wave's 2 x 16 output columns as B fragments of the 16 x 16 x 32 MFMA: lane (n = lane & 15, kg = lane >> 4) holds W[c0 + 16 cb + n][32 kb + 8 kg ..]
     constexpr int NKB2 = NKB / 2;
     f16x8 w1[NKB2][2], w2[NKB2][2];
@@ -147,17 +143,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         w2[kb][cb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 32);
       }
     }
-#else
-    f16x8 w1[NKB], w2[NKB];
-    {
-      const unsigned short* wp = g.Wp + (long)(c0 + (lane & 31)) * g.ldw + (lane >> 5) * 8;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        w1[kb] = *reinterpret_cast<const f16x8*>(wp + kb * 16);
-        w2[kb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 16);
-      }
-    }
-#endif
     const int ecol = c0 + (lane & 7) * 4;
     const f4 wsc = *reinterpret_cast<const f4*>(g.wscale + ecol);
     const f4 bias4 = epi_bias4(g.E, ecol);
@@ -183,7 +168,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
 #pragma unroll
         for (int q = 0; q < 4; ++q) zq[q] = g.A.a[(t * FD_TP + (lane >> 3) + 8 * q) * g.A.lda + 256];
       }
-#if FD_MFMA16
       fd_f32x4 acc[2][2];   // [row block of 16 points][column block of 16 columns]
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
@@ -221,27 +205,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) T[(16 * rb + 4 * q4 + r) * FD_TLD + 16 * cb + cl] = acc[rb][cb][r];
       }
-#else
-      f32x16 acc;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-      const unsigned char* Ab = B + (lane & 31) * FD_ALD + (lane >> 5) * 16;
-      if (!(dbg & 4))
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) {
-        const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + kb * 32);
-        const f16x8 a2 = *reinterpret_cast<const f16x8*>(Ab + FD_APLANE + kb * 32);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w2[kb], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, w1[kb], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w1[kb], acc, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const float* rs = reinterpret_cast<const float*>(B + 2 * FD_APLANE);
-      const float* ssr = rs + 32;
-      const int hi = lane >> 5, cl = lane & 31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * hi) * FD_TLD + cl] = acc[r];
-#endif
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       const long tn = FD_TILE(i + ahead < nlast ? i + ahead : nlast);
@@ -337,7 +300,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     if (dbg & 8) __builtin_amdgcn_s_setprio(0); else if (dbg & 16) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(2);
     const int wd = wave - 4, dt = tid - 256;
     const int srow = dt >> 4, scol = (dt & 15) * 4;
-#if FD_MFMA16
     const int m = lane & 15, kg = lane >> 4;   // result blocks: column m, rows 4 kg + r
     fd_f32x4 acc[4][8];                        // [block of 16 S columns (rows of dW)][block of 16 Ep columns]: 128 registers
 #pragma unroll
@@ -346,16 +308,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
       for (int j = 0; j < 8; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-#else
-    const int m = lane & 31, kg = lane >> 5;
-    f32x16 acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-#endif
     struct RawTile { f4 r[2][4]; float se[2]; };
     f4 cs[4];
     const f4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -418,7 +370,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     auto d_dw = [&](int i, int ab) {
       const unsigned char* B = smem + ab * FD_ABUF;
       const unsigned char* Yb = smem + FD_OFF_Y + (i & 1) * FD_YBUF;
-#if FD_MFMA16
       {
         // ONE k32 step covers the tile's 32 points.  This lane's 8-byte piece of a [4 points][16 columns] block: k group kg = lane >> 4 holds points
         // 16 (kg >> 1) + 2 (kg & 1) + 4 r + h (the two 16-lane groups of a 32-lane half are then 8 banks apart, the four rows 16 banks: conflict-free)
@@ -443,34 +394,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
           }
         }
       }
-#else
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        // this lane's 8-byte piece of a [4 points][16 columns] block: point row kb * 16 + 2 kg + 4 r (h = 1: one row below), 4 columns at pcol
-        const int prow = kb * 16 + kg * 2 + 4 * ((lane & 15) >> 2), pcol = (m & 16) + (lane & 3) * 4;
-        f16x8 a[2][2];
-#pragma unroll
-        for (int it = 0; it < 2; ++it)
-#pragma unroll
-          for (int pl = 0; pl < 2; ++pl) {
-            a[it][pl] = ws_tr8(B + pl * FD_APLANE + prow * FD_ALD + (wd * 64 + it * 32 + pcol) * 2, FD_ALD);
-          }
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) {
-          const unsigned char* ysrc = Yb + prow * FD_YLD + (jt * 32 + pcol) * 2;
-          const f16x8 b1 = ws_tr8(ysrc, FD_YLD);
-          const f16x8 b2 = ws_tr8(ysrc + FD_YPLANE, FD_YLD);
-          f32x16 c0 = acc[0][jt], c1 = acc[1][jt];
-          c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b2, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b2, c1, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][1], b1, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][1], b1, c1, 0, 0, 0);
-          c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b1, c0, 0, 0, 0);
-          c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b1, c1, 0, 0, 0);
-          acc[0][jt] = c0; acc[1][jt] = c1;
-        }
-      }
-#endif
     };
     int Gd = FD_GBIG;
     // weight-gradient contribution of tile i (buffer abp): fold the tile's exponent into the running one first
@@ -482,21 +405,12 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         if (Gd < FD_GBIG) {   // exact power-of-two rescale of what has been accumulated under the old exponent
           const int dlt = mq + 1 - Gd;
           const float u1 = ldexpf(1.0f, dlt / 2), u2 = ldexpf(1.0f, dlt - dlt / 2);
-#if FD_MFMA16
 #pragma unroll
           for (int sb = 0; sb < 4; ++sb)
 #pragma unroll
             for (int eb = 0; eb < 8; ++eb)
 #pragma unroll
               for (int r = 0; r < 4; ++r) acc[sb][eb][r] = acc[sb][eb][r] * u1 * u2;
-#else
-#pragma unroll
-          for (int it = 0; it < 2; ++it)
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) acc[it][jt][r] = acc[it][jt][r] * u1 * u2;
-#endif
         }
         Gd = mq + 1;
       }
@@ -554,7 +468,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     if (Gd >= FD_GBIG) Gd = 0;
     const float u1 = ldexpf(1.0f, -(Gd / 2)), u2 = ldexpf(1.0f, -(Gd - Gd / 2));
     float* X = reinterpret_cast<float*>(smem + wd * (32 * 33 * 4));
-#if FD_MFMA16
     // a lane holds dW[s = 16 sb + 4 kg + r][e = 16 eb + m] of each block.  Natural form: 64-byte row pieces; transposed form: 32 x 32 regions (2 x 2 blocks)
     // through the per-wave LDS tile so that both forms store whole 128-byte row pieces where they can
 #pragma unroll
@@ -593,33 +506,6 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
           __builtin_amdgcn_wave_barrier();
         }
       }
-#else
-#pragma unroll
-    for (int it = 0; it < 2; ++it)
-#pragma unroll
-      for (int jt = 0; jt < 4; ++jt) {
-        const int s0 = wd * 64 + it * 32, e0 = half * 128 + jt * 32;
-        if (!f.transposed) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int s = s0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-            if (s < f.Npad) out[(long)s * f.ldk + e0 + m] = acc[it][jt][r] * u1 * u2;
-          }
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) X[((r & 3) + 8 * (r >> 2) + 4 * kg) * 33 + m] = acc[it][jt][r] * u1 * u2;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int e = 2 * r + kg;
-            if (e0 + e < f.Npad) out[(long)(e0 + e) * f.ldk + s0 + m] = X[m * 33 + e];
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-        }
-      }
-#endif
     if (want_cs) {   // bias gradient: the 16 row owners of a column group are folded in a fixed order below
       float* C = reinterpret_cast<float*>(smem + 4 * (32 * 33 * 4));
 #pragma unroll

@@ -22,17 +22,10 @@ namespace cnr {
 // (exact).  Measured (tools/probes/ws_probe.hip): max error 8.3e-7 vs float64 where the FP32 FMA chain of v_mfma_f32_32x32x2_f32 has
 // 1.1e-6 -- also with rows spanning 12 orders of magnitude -- at 3 x 32 = 96 MFMA cycles per k16 block instead of 8 x 64 = 512.
 // No weight traffic after the prologue, 16 accumulator registers, one barrier per 32 points.
-// ================================================================================================
-#ifndef WS_MFMA16
-#define WS_MFMA16 1   // the stream form of the layer kernel on v_mfma_f32_16x16x32_f16 (0: 32 x 32 x 16, A/B builds)
-#endif
-#ifndef WS_GEN_MFMA16
-// ... and the general form.  Built and parity-green on 16 x 16 x 32 too (then bit-identical to the stream form), but SLOWER there: 478 against 358 us for the
-// one general launch of a step (the 217-wide layer of the forward gradient chain; profiles/r06_ab_general_mfma16.txt) -- its k blocks sit behind run-time
-// guards, so nothing is scheduled across them.  It stays on 32 x 32 x 16: the two forms then agree to fp32 round-off, not to the bit
+// This general form stays on 32 x 32 x 16: on 16 x 16 x 32 it was 30 % slower (478 against 358 us; its k blocks sit behind run-time guards, so nothing is
+// scheduled across them; profiles/r06_ab_general_mfma16.txt).  It and the stream form below (16 x 16 x 32) therefore agree to fp32 round-off, not to the bit
 // (tests/test_hip_parity.py::test_stream_form_of_the_layer_kernel_matches_the_general_form).
-#define WS_GEN_MFMA16 0
-#endif
+// ================================================================================================
 typedef float ws_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int WS_TP = 32;
 constexpr int WS_THREADS = 512;
@@ -87,28 +80,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
   const int ncols_live = g.E.n_out + (g.E.tail_src ? g.E.tail_n : 0);
 
   // ---- resident weights (two f16 planes of this wave's 32 rows of W)
-#if WS_GEN_MFMA16
-  // v_mfma_f32_16x16x32_f16 like the stream form below (one arithmetic for every split-f16 layer product of the library): k32 blocks; when the
-  // number of live k16 blocks is odd, the lanes that hold the upper 16 k of the last block (lane >> 4 >= 2) carry zeros in both operands
-  constexpr int NKB2 = (NKB + 1) / 2;
-  f16x8 w1[NKB2][2], w2[NKB2][2];
-  const bool khi = (lane >> 4) >= 2;
-  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb) {
-    const unsigned short* wp = g.Wp + (long)(has_w ? c0 + 16 * cb + (lane & 15) : 0) * g.ldw + (lane >> 4) * 8;
-#pragma unroll
-    for (int kb = 0; kb < NKB2; ++kb) {
-      if (2 * kb < nkb) {
-        w1[kb][cb] = zero8; w2[kb][cb] = zero8;
-        if (!(khi && 2 * kb + 1 == nkb)) {
-          w1[kb][cb] = *reinterpret_cast<const f16x8*>(wp + kb * 32);
-          w2[kb][cb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 32);
-        }
-      }
-    }
-  }
-#else
   f16x8 w1[NKB], w2[NKB];
   {
     const unsigned short* wp = g.Wp + (long)(has_w ? c0 + (lane & 31) : 0) * g.ldw + (lane >> 5) * 8;
@@ -120,7 +91,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
       }
     }
   }
-#endif
   f4 wsc = {1.f, 1.f, 1.f, 1.f};               // inverse column scales of the 4 columns this lane finishes in the epilogue
   if (has_w) wsc = *reinterpret_cast<const f4*>(g.wscale + c0 + (lane & 7) * 4);
   const int ecol = c0 + (lane & 7) * 4;         // ... and their epilogue path / bias (fixed per lane for the whole launch)
@@ -189,28 +159,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
     }                                                                             \
   }
 #define WS_PUT_TILE(buf_, tile_) WS_PUT_SET(buf_, tile_, a)
-#if WS_GEN_MFMA16
-#define WS_MFMA(kb_)                                                                               \
-  if (2 * (kb_) < nkb) {                                                                           \
-    /* all four fragments of the block first: one exposed LDS round trip per k32 block, not one per row block */ \
-    f16x8 a1_[2], a2_[2];                                                                          \
-    _Pragma("unroll") for (int rb = 0; rb < 2; ++rb) {                                             \
-      a1_[rb] = *reinterpret_cast<const f16x8*>(Ab + rb * 16 * ald + (kb_) * 64);                  \
-      a2_[rb] = *reinterpret_cast<const f16x8*>(Ab + rb * 16 * ald + aplane + (kb_) * 64);         \
-    }                                                                                              \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-    _Pragma("unroll") for (int rb = 0; rb < 2; ++rb) {                                             \
-      if (2 * (kb_) + 1 == nkb) { if (khi) { a1_[rb] = zero8; a2_[rb] = zero8; } }   /* (uniform test first: the lane select only runs in an odd last block) */ \
-      _Pragma("unroll") for (int cb = 0; cb < 2; ++cb) {                                           \
-        ws_f32x4 c = acc[rb][cb];                                                                  \
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1_[rb], w2[kb_][cb], c, 0, 0, 0);              \
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2_[rb], w1[kb_][cb], c, 0, 0, 0);              \
-        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1_[rb], w1[kb_][cb], c, 0, 0, 0);              \
-        acc[rb][cb] = c;                                                                           \
-      }                                                                                            \
-    }                                                                                              \
-  }
-#else
 #define WS_MFMA(kb_)                                                                               \
   if ((kb_) < nkb) {                                                                               \
     const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + (kb_) * 32);                             \
@@ -219,7 +167,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, w1[kb_], acc, 0, 0, 0);                       \
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w1[kb_], acc, 0, 0, 0);                       \
   }
-#endif
 
   // Waves 0..3 (rows 0..15 of a tile) and waves 4..7 (rows 16..31) share the SIMDs pairwise and run half an iteration out of
   // phase: the late group converts + stores its half of tile t+1 (fetched one iteration earlier) and fetches tile t+2 BEFORE
@@ -229,20 +176,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
   // MFMAs + epilogue of tile t from LDS buffer buf
   auto compute = [&](const long tc, const int buf) {
     const long t = WS_TILE(tc);
-#if WS_GEN_MFMA16
-    ws_f32x4 acc[2][2];   // [row block of 16 points][column block of 16 columns]
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[rb][cb][j] = 0.0f;
-    const unsigned char* Ab = smem_b + buf * abuf + (lane & 15) * ald + (lane >> 4) * 16;
-    if (has_w) {
-      WS_MFMA(0) WS_MFMA(1) WS_MFMA(2) WS_MFMA(3) WS_MFMA(4) WS_MFMA(5) WS_MFMA(6) WS_MFMA(7)
-      if (K17) { WS_MFMA(NKB2 - 1) }
-    }
-#else
     f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
@@ -252,27 +185,14 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
       WS_MFMA(8) WS_MFMA(9) WS_MFMA(10) WS_MFMA(11) WS_MFMA(12) WS_MFMA(13) WS_MFMA(14) WS_MFMA(15)
       if (K17) { WS_MFMA(NKB - 1) }
     }
-#endif
     // epilogue of this 32 x 32 tile: undo the exact row / column scales, then the fused epilogue on 4 columns per lane.
     // The side inputs of all four row groups are requested first: one memory round trip per tile, and no load has to
     // wait behind the stores of the previous row group.
     if (c0 < ncols_live) {
       const float* rs = reinterpret_cast<const float*>(smem_b + buf * abuf + 2 * aplane);
-#if WS_GEN_MFMA16
-      {
-        const int q4 = lane >> 4, cl = lane & 15;   // result block: rows 4 q4 + r, column cl
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) T[(16 * rb + 4 * q4 + r) * WS_TLD + 16 * cb + cl] = acc[rb][cb][r];
-      }
-#else
       const int hi = lane >> 5, cl = lane & 31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * hi) * WS_TLD + cl] = acc[r];
-#endif
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       constexpr int EG = (EK == EK_SWEEP || EK == EK_VBACK) ? 2 : 4;   // row groups whose side inputs are in flight together (register budget)
@@ -383,18 +303,8 @@ inline int ws_next_rev() { static std::atomic<unsigned> parity{0}; return (int)(
 // The epilogue's side inputs (pre-activations, ReLU masks, the cotangent a value-backward launch adds to) are read once per launch: as NON-TEMPORAL loads they do not
 // push the lines the launch re-reads (its own input tile, the weights) or hands to the next launch (its output rows) out of L2 / Infinity Cache: +0.2-0.3 % of the step,
 // same bits (profiles/r06_ab_nt_side_inputs.txt).  The STAGED tile must stay a plain load: non-temporal there costs 2 % (the fused launches read it twice).
-// ... and the second-order cotangent a sweep launch writes on z (picked up by the value-backward chain many launches later) as a non-temporal store: +0.2 %
-#ifndef WS_NT_SWEEP
-#define WS_NT_SWEEP 1
-#endif
-#ifndef WS_NT_SIDE
-#define WS_NT_SIDE 1
-#endif
-#if WS_NT_SIDE
+// ... and the second-order cotangent a sweep launch writes on z (picked up by the value-backward chain many launches later) as a non-temporal store: +0.2 % (same record).
 #define WS_NTLOAD(p_) __builtin_nontemporal_load(reinterpret_cast<const f4*>(p_))
-#else
-#define WS_NTLOAD(p_) (*reinterpret_cast<const f4*>(p_))
-#endif
 template <int EK>
 __device__ __forceinline__ EpiRaw4 epi_fetch4_plain(const Epi& e, long row, int col) {
   EpiRaw4 r;
@@ -420,11 +330,7 @@ __device__ __forceinline__ void epi_finish4_plain(const Epi& e, long row, int co
     o1.y = softplus100_d2(zz.y) * (vv.y * e.vscale) * acc.y; o2.y = softplus100_d1(zz.y) * acc.y;
     o1.z = softplus100_d2(zz.z) * (vv.z * e.vscale) * acc.z; o2.z = softplus100_d1(zz.z) * acc.z;
     o1.w = softplus100_d2(zz.w) * (vv.w * e.vscale) * acc.w; o2.w = softplus100_d1(zz.w) * acc.w;
-#if WS_NT_SWEEP
     __builtin_nontemporal_store(o1, reinterpret_cast<f4*>(e.o1 + row * e.ld1 + col));   // (the second-order cotangent on z: picked up by the value-backward chain many launches later)
-#else
-    *reinterpret_cast<f4*>(e.o1 + row * e.ld1 + col) = o1;
-#endif
     *reinterpret_cast<f4*>(e.o2 + row * e.ld2 + col) = o2;
   } else if constexpr (EK == EK_VBACK) {
     const f4 zz = raw.a;
@@ -472,9 +378,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
   float* T = reinterpret_cast<float*>(smem_b + 2 * abuf) + wave * (32 * WS_TLD);
   const int c0 = g.col0 + wave * 32;
 
-#if WS_MFMA16
   // (round 6) the stream form on v_mfma_f32_16x16x32_f16 -- 12 % cheaper per FLOP than the 32 x 32 x 16 shape and a 15 % higher clock under the board's power
-  // limit (profiles/r06_mfma_shapes.txt): B fragments of this wave's 2 x 16 output columns, lane (n = lane & 15, kg = lane >> 4) holds W[c0 + 16 cb + n][32 kb + 8 kg ..]
+  // limit (profiles/r06_mfma_shapes.txt; against the 32 x 32 x 16 form: profiles/r06_ab_mfma16_ws_stream.txt): B fragments of this wave's 2 x 16 output columns, lane (n = lane & 15, kg = lane >> 4) holds W[c0 + 16 cb + n][32 kb + 8 kg ..]
   constexpr int NKB2 = NKB / 2;
   f16x8 w1[NKB2][2], w2[NKB2][2];
 #pragma unroll
@@ -486,17 +391,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
       w2[kb][cb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 32);
     }
   }
-#else
-  f16x8 w1[NKB], w2[NKB];
-  {
-    const unsigned short* wp = g.Wp + (long)(c0 + (lane & 31)) * g.ldw + (lane >> 5) * 8;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      w1[kb] = *reinterpret_cast<const f16x8*>(wp + kb * 16);
-      w2[kb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 16);
-    }
-  }
-#endif
   const f4 wsc = *reinterpret_cast<const f4*>(g.wscale + c0 + (lane & 7) * 4);
   const int ecol = c0 + (lane & 7) * 4;
   const f4 bias4 = epi_bias4(g.E, ecol);
@@ -566,7 +460,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
   }
   auto compute = [&](const long tc, const int buf) {
     const long t = WSS_TILE(tc < tlast ? tc : tlast);
-#if WS_MFMA16
     ws_f32x4 acc[2][2];   // [row block of 16 points][column block of 16 columns]
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
@@ -604,27 +497,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
 #pragma unroll
           for (int r = 0; r < 4; ++r) T[(16 * rb + 4 * q4 + r) * WS_TLD + 16 * cb + cl] = acc[rb][cb][r];
     }
-#else
-    f32x16 acc;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    const unsigned char* Ab = smem_b + buf * abuf + (lane & 31) * ald + (lane >> 5) * 16;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) {
-      const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + kb * 32);
-      const f16x8 a2 = *reinterpret_cast<const f16x8*>(Ab + aplane + kb * 32);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w2[kb], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, w1[kb], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w1[kb], acc, 0, 0, 0);
-    }
-    // (scheduling fences between the phases: the blocks are branch-free now, and an unconstrained scheduler hoists the next phase's loads
-    // across the MFMA block until the register file spills)
-    __builtin_amdgcn_sched_barrier(0);
-    const float* rs = reinterpret_cast<const float*>(smem_b + buf * abuf + 2 * aplane);
-    const int hi = lane >> 5, cl = lane & 31;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * hi) * WS_TLD + cl] = acc[r];
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if constexpr (EPRE) {

@@ -218,13 +218,12 @@ def test_results_do_not_depend_on_scratch_contents():
 
 
 @pytest.mark.parametrize("switch", ["CNR_DISABLE_WS", "CNR_WS_GENERIC", "CNR_DW_BF16", "CNR_DW_FP32", "CNR_WS_SERP=0", "CNR_WS_NOSTREAM",
-                                    "CNR_NO_FUSED", "CNR_NO_CHAIN_FWD", "CNR_NO_CHAIN_SDF", "CNR_CHAIN_GRAD", "CNR_NO_SWEEP0", "CNR_NO_NARROW_BWD", "CNR_NO_NARROW_DX"])
+                                    "CNR_NO_FUSED", "CNR_NO_CHAIN_FWD", "CNR_NO_CHAIN_SDF", "CNR_NO_SWEEP0", "CNR_NO_NARROW_BWD", "CNR_NO_NARROW_DX"])
 def test_fallback_kernels_keep_parity(switch):
     """The debugging switches select the fallback kernels (FP32-MFMA layer GEMM, interpreted weight-stationary kernel, split-bf16 and
     FP32-MFMA weight-gradient tiles, one walk direction for every layer launch, the general layer kernel instead of its stream form, the
-    per-layer launches instead of the chain-fused forward kernels, separate layer + weight-gradient launches for the narrow-input layers) or, for
-    CNR_CHAIN_GRAD, the opt-in chain-fused gradient chain.  They are
-    read once per process, so the G2 gate runs in a child process."""
+    per-layer launches instead of the chain-fused forward kernels, separate layer + weight-gradient launches for the narrow-input layers).
+    They are read once per process, so the G2 gate runs in a child process."""
     name, _, val = switch.partition("=")
     env = dict(os.environ, **{name: val or "1"})
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -552,10 +551,10 @@ np.savez(out, **res)
 def test_stream_form_of_the_layer_kernel_matches_the_general_form(tmp_path):
     """layer_gemm_ws_stream_kernel (per-wave-group loops, prefetched epilogue inputs; most layer launches of a step) against the general
     kernel (CNR_WS_NOSTREAM=1, child processes): same tiles, same split, same epilogue arithmetic.  Since round 6 the stream form issues its
-    products as v_mfma_f32_16x16x32_f16 and the general form stays on 32x32x16 (cnr_gemm_ws.h, WS_GEN_MFMA16: the general form is 30 % slower on the
+    products as v_mfma_f32_16x16x32_f16 and the general form stays on 32x32x16 (cnr_gemm_ws.h: the general form is 30 % slower on the
     other shape), so the fp32 accumulation order inside a product differs: every output and every gradient of a forward + backward pass must
     agree to fp32 round-off -- 1e-5 of the tensor's largest entry for the outputs, the fixture's own per-tensor float32 tolerance for the gradients
-    (a build with -DWS_GEN_MFMA16=1 is bit-identical: that was this test until then)."""
+    (the general form on 16x16x32, since removed, was bit-identical: that was this test until then)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
     for tag, extra in (("stream", {}), ("general", {"CNR_WS_NOSTREAM": "1"})):
