@@ -101,7 +101,8 @@ EXPORTS = ["cnr_abi_version", "cnr_backend_name", "cnr_last_error", "cnr_param_c
            "cnr_linear_scratch_bytes", "cnr_linear_forward", "cnr_linear_backward",
            "cnr_nerf_param_count", "cnr_nerf_param_info", "cnr_outside_z", "cnr_outside_z_backward", "cnr_background_ctx_bytes",
            "cnr_background_bwd_scratch_bytes", "cnr_background_forward", "cnr_background_backward", "cnr_composite_background_scratch_bytes",
-           "cnr_composite_background_forward", "cnr_composite_background_backward"]
+           "cnr_composite_background_forward", "cnr_composite_background_backward",
+           "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward"]
 
 
 class RenderLibrary:
@@ -141,6 +142,12 @@ class RenderLibrary:
         L.cnr_linear_forward.argtypes = [_FP, C.c_int64, C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_size_t, _FP]
         L.cnr_linear_backward.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t, _FP]
         L.cnr_vertex_color.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, _FP, _FP, C.c_size_t, _FP]
+        for f in ("cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes"):
+            getattr(L, f).restype = C.c_size_t
+            getattr(L, f).argtypes = [C.POINTER(CnrConfig), C.c_int64, C.c_int32]
+        L.cnr_sdf_query_forward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t, _FP]
+        L.cnr_sdf_query_backward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t,
+                                             C.POINTER(_FP), _FP, _FP, C.c_size_t, _FP]
         L.cnr_loss_scratch_bytes.restype = C.c_size_t
         L.cnr_loss_scratch_bytes.argtypes = [C.c_int64]
         L.cnr_loss_sums.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, C.c_size_t, _FP]

@@ -171,8 +171,33 @@ struct RaysGradFinish {  // d rays_o / d rays_d from the point cotangents (only 
 
 struct PbarFinish {   // total cotangent of p: colour/relight aux inputs + SDF value path + gradient path (PE second derivative)
   long P; const float* daux_c; const float* daux_r; const float* ebar0; const float* ebars; const float* E;
-  const float* ce0; const float* ces; const float* gbar_total; float scale; int multires; float* pbar;
+  const float* ce0; const float* ces; const float* gbar_total /* null: no cotangent on g (value-only SDF query), ce0 / ces unread */;
+  float scale; int multires; float* pbar;
 };
+
+// SDF point queries (cnr_sdf_query_forward / _backward): the caller's n dense rows <-> the P = round_up(n, kQueryTile) rows of the internal
+// buffers.  Padded rows hold the origin as input and zero cotangents; nothing is written past row n of a caller's buffer.
+// The forward also writes a tag into the context (kQueryCtxTag + want_grad); the backward's seed launch checks it against the backward's
+// want_grad and seeds NaN on a mismatch (a context without the gradient-path buffers, or no query context at all), so that every output of
+// such a call is NaN instead of silently wrong.  The library never synchronises, so the check cannot be a host-side error.
+constexpr int kQueryCtxTag = 0x53515900;
+struct QueryIn {     // pts [n][3] -> out [P][3], rows >= n zero; element 0 also writes *tag = tag_value
+  long n, P; const float* pts; float* out; int* tag; int tag_value;
+};
+struct QuerySeed {   // ztop [P][ldztop] = [d_feat | d_sdf * inv_scale | 0], gbar [P][4] = [d_grad | 0] (gbar may be null); null inputs are zero, rows >= n zero
+  long n, P; int F, ldztop; float inv_scale;
+  const float* d_sdf; const float* d_feat; const float* d_grad;
+  float* ztop; float* gbar;
+  const int* tag; int want_grad;   // the forward's tag; want_grad = 1 needs a forward with want_grad, 0 takes either
+};
+struct QueryOut {    // the first n rows of the internal buffers into the caller's dense ones; every pair may be null
+  long n; int F, ldf, ldg;
+  const float* sdf_in; const float* feat_in; const float* g_in;   // [P], [P][ldf], [P][ldg]
+  float* sdf; float* feat; float* g;                               // [n], [n][F], [n][3]
+};
+void be_query_in(const QueryIn& p, cnr_stream s);
+void be_query_seed(const QuerySeed& p, cnr_stream s);
+void be_query_out(const QueryOut& p, cnr_stream s);
 
 // ---- chain-fused kernels (cnr_chain.hip): a tile of points goes through all layers of a chain without leaving the CU
 struct PackJob {    // f16 planes [2][rows][ld] (be_split_planes) -> fragment-major planes Wf[8][ld/16][2][64][8] of the fused kernels

@@ -146,12 +146,14 @@ CNR_HD void body_pbar_finish(const PbarFinish& p, long pt) {
       float ebs = p.ebar0[pt * kEmb + 3 + 6 * k + c] + (p.ebars ? p.ebars[pt * kEmb + 3 + 6 * k + c] : 0.0f);
       float ebc = p.ebar0[pt * kEmb + 6 + 6 * k + c] + (p.ebars ? p.ebars[pt * kEmb + 6 + 6 * k + c] : 0.0f);
       x0bar += f * (co * ebs - s * ebc);
-      float ces = p.ce0[pt * kEmb + 3 + 6 * k + c] + (p.ces ? p.ces[pt * kEmb + 3 + 6 * k + c] : 0.0f);
-      float cec = p.ce0[pt * kEmb + 6 + 6 * k + c] + (p.ces ? p.ces[pt * kEmb + 6 + 6 * k + c] : 0.0f);
-      second += f * f * (-s * ces - co * cec);
+      if (p.gbar_total) {
+        float ces = p.ce0[pt * kEmb + 3 + 6 * k + c] + (p.ces ? p.ces[pt * kEmb + 3 + 6 * k + c] : 0.0f);
+        float cec = p.ce0[pt * kEmb + 6 + 6 * k + c] + (p.ces ? p.ces[pt * kEmb + 6 + 6 * k + c] : 0.0f);
+        second += f * f * (-s * ces - co * cec);
+      }
       f *= 2.0f;
     }
-    x0bar += p.gbar_total[pt * 4 + c] * p.scale * second;
+    if (p.gbar_total) x0bar += p.gbar_total[pt * 4 + c] * p.scale * second;
     float pb = x0bar * p.scale;
     if (p.daux_c) pb += p.daux_c[pt * kAux + c];
     if (p.daux_r) pb += p.daux_r[pt * kAux + c];
@@ -159,6 +161,62 @@ CNR_HD void body_pbar_finish(const PbarFinish& p, long pt) {
   }
   p.pbar[pt * 4 + 3] = 0.0f;
 }
+
+// SDF point queries: element i of the flat [P][3] padded copy of the points (rows >= n at the origin)
+CNR_HD void body_query_in(const QueryIn& p, long i) {
+  p.out[i] = i < p.n * 3 ? p.pts[i] : 0.0f;
+  if (i == 0) *p.tag = p.tag_value;
+}
+CNR_HD bool query_ctx_mismatch(const QuerySeed& p) {
+  const int t = *p.tag;
+  return p.want_grad ? t != kQueryCtxTag + 1 : (t != kQueryCtxTag && t != kQueryCtxTag + 1);
+}
+
+// four consecutive columns of a ZTOP row (i < P * ldztop / 4), then one gbar row each (i - P * ldztop / 4): one 16-byte store per element
+CNR_HD void body_query_seed(const QuerySeed& p, long i) {
+  const long q4 = p.ldztop / 4, nz = p.P * q4;
+  const float poison = query_ctx_mismatch(p) ? __builtin_nanf("") : 0.0f;   // NaN + x: every seed, hence every output, is NaN
+  if (i < nz) {
+    const long row = i / q4;
+    const int c0 = (int)(i - row * q4) * 4;
+    float v[4];
+    for (int j = 0; j < 4; ++j) {
+      const int c = c0 + j;
+      float t = 0.0f;
+      if (row < p.n) {
+        if (c < p.F) t = p.d_feat ? p.d_feat[row * p.F + c] : 0.0f;
+        else if (c == p.F) t = p.d_sdf ? p.d_sdf[row] * p.inv_scale : 0.0f;
+      }
+      v[j] = t + poison;
+    }
+    f4 o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+    *reinterpret_cast<f4*>(p.ztop + row * p.ldztop + c0) = o;
+  } else {
+    const long row = i - nz;
+    const bool live = row < p.n && p.d_grad;
+    f4 o;
+    o.x = (live ? p.d_grad[row * 3 + 0] : 0.0f) + poison; o.y = (live ? p.d_grad[row * 3 + 1] : 0.0f) + poison;
+    o.z = (live ? p.d_grad[row * 3 + 2] : 0.0f) + poison; o.w = 0.0f;
+    *reinterpret_cast<f4*>(p.gbar + row * 4) = o;
+  }
+}
+
+// element i of the concatenated outputs [sdf (n) | feat (n * F) | g (n * 3)] (absent outputs take no elements): consecutive threads write
+// consecutive addresses of one caller buffer
+CNR_HD void body_query_out(const QueryOut& p, long i) {
+  if (p.sdf) {
+    if (i < p.n) { p.sdf[i] = p.sdf_in[i]; return; }
+    i -= p.n;
+  }
+  if (p.feat) {
+    const long nf = p.n * p.F;
+    if (i < nf) { const long r = i / p.F; p.feat[i] = p.feat_in[r * p.ldf + (i - r * p.F)]; return; }
+    i -= nf;
+  }
+  const long r = i / 3;
+  p.g[i] = p.g_in[r * p.ldg + (i - r * 3)];
+}
+CNR_HD long query_out_count(const QueryOut& p) { return (p.sdf ? p.n : 0) + (p.feat ? p.n * p.F : 0) + (p.g ? p.n * 3 : 0); }
 
 // one ray of GenRays
 // An index outside [0, n_cams * H * W) (only a caller-supplied list can hold one) reads nothing: every output of that ray is NaN -- which

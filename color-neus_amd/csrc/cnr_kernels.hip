@@ -451,6 +451,14 @@ void be_fine_setup(const FineSetup& p, cnr_stream s) { fine_setup_launch(p, p.R 
 void be_coltop_bwd(const ColTopBwd& p, cnr_stream s) { coltop_bwd_launch(p, p.P, s); }
 void be_pbar_finish(const PbarFinish& p, cnr_stream s) { pbar_finish_launch(p, p.P, s); }
 
+// SDF point queries: the glue between the caller's dense rows and the padded rows of the render path's buffers
+CNR_PW_KERNEL(query_in, QueryIn, body_query_in)
+CNR_PW_KERNEL(query_seed, QuerySeed, body_query_seed)
+CNR_PW_KERNEL(query_out, QueryOut, body_query_out)
+void be_query_in(const QueryIn& p, cnr_stream s) { query_in_launch(p, p.P * 3, s); }
+void be_query_seed(const QuerySeed& p, cnr_stream s) { query_seed_launch(p, p.P * (p.ldztop / 4) + (p.gbar ? p.P : 0), s); }
+void be_query_out(const QueryOut& p, cnr_stream s) { query_out_launch(p, query_out_count(p), s); }
+
 
 // ------------------------------------------------------------------------------------------------
 // PE-Jacobian kernels: 16 lanes per point, lane j owns the column triple [3j, 3j+3) of the 48-wide rows

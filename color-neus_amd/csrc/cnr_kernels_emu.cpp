@@ -142,6 +142,9 @@ CNR_PW(be_grad_finish, GradFinish, body_grad_finish, p.P)
 CNR_PW(be_coltop_bwd, ColTopBwd, body_coltop_bwd, p.P)
 CNR_PW(be_gbar_finish, GbarFinish, body_gbar_finish, p.P)
 CNR_PW(be_pbar_finish, PbarFinish, body_pbar_finish, p.P)
+CNR_PW(be_query_in, QueryIn, body_query_in, p.P * 3)
+CNR_PW(be_query_seed, QuerySeed, body_query_seed, p.P * (p.ldztop / 4) + (p.gbar ? p.P : 0))
+CNR_PW(be_query_out, QueryOut, body_query_out, query_out_count(p))
 CNR_PW(be_outside_z, OutsideZ, body_outside_z, p.R)
 CNR_PW(be_outside_z_bwd, OutsideZBwd, body_outside_z_bwd, p.R)
 CNR_PW(be_bg_embed, BgEmbed, body_bg_embed, p.R* p.MF)

@@ -478,6 +478,19 @@ static bool head_bwd_static_ok(const Lin& q, int ldaux) {
   return !off && q.n <= 4 && q.k_int == 256 && q.ldw == 256 && (ldaux & 3) == 0;
 }
 
+// the slot counts of the weight-gradient launches over P points
+static void bwd_slots(long P, Bwd& b) {
+  long nch = P / 128;   // one workgroup per CU as soon as every chunk has a few 16-point slabs
+  if (nch < 1) nch = 1;
+  if (nch > 256) nch = 256;
+  b.nchunk = (int)nch;
+  b.chunk_pts = round_up((int)((P + nch - 1) / nch), 16);
+  b.fslots = fdw_slots(P);
+  b.cap_slots = b.fslots + (b.nchunk > b.fslots ? b.nchunk : b.fslots);   // a fused pair + either a second fused pair or a separate GEMM over nchunk slots
+  const long ntiles = (P + 31) / 32, tpw = (ntiles + 255) / 256;
+  b.cu_slots = ntiles > 0 ? (int)((ntiles + tpw - 1) / tpw) : 0;
+}
+
 static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
   const long P = R * m.M;
   b.ZTOP = a.f((size_t)P * x.ldztop);
@@ -513,19 +526,9 @@ static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
   auto shared = [&](int k) { return (k & 1) ? b.Z2[k >> 1] : b.VB[k >> 1]; };
   for (int i = 0; i < m.NR; ++i) b.D[i] = share ? shared(i) : a.f((size_t)P * m.Hr);
   for (int l = 0; l + 1 < m.NC; ++l) b.DC[l] = share ? shared(m.NR + l) : a.f((size_t)P * m.Hc);
-  long nch = P / 128;   // one workgroup per CU as soon as every chunk has a few 16-point slabs
-  if (nch < 1) nch = 1;
-  if (nch > 256) nch = 256;
-  b.nchunk = (int)nch;
-  b.chunk_pts = round_up((int)((P + nch - 1) / nch), 16);
-  b.fslots = fdw_slots(P);
-  b.cap_slots = b.fslots + (b.nchunk > b.fslots ? b.nchunk : b.fslots);   // a fused pair + either a second fused pair or a separate GEMM over nchunk slots
+  bwd_slots(P, b);
   // every layer keeps its own [slots][npad][ldw] partial sums (+ bias column sums) until one batched reduction at the end
   size_t tot = 0;
-  {
-    const long ntiles = (P + 31) / 32, tpw = (ntiles + 255) / 256;
-    b.cu_slots = ntiles > 0 ? (int)((ntiles + tpw - 1) / tpw) : 0;
-  }
   auto upd = [&](const Lin& q) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); };
   for (auto& q : m.sdf) upd(q);
   for (auto& q : m.col) upd(q);
@@ -542,7 +545,8 @@ static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
 }
 
 // ------------------------------------------------------------------------------------------------
-static void prep_all(Model& m, const float* const* params, cnr_stream s) {
+// sdf_only: the SDF layers alone (point queries: the other entries of params may be null)
+static void prep_all(Model& m, const float* const* params, cnr_stream s, bool sdf_only = false) {
   std::vector<PrepWeight> pw;
   std::vector<SplitJob> sj;
   auto prep = [&](Lin& q) {
@@ -561,15 +565,15 @@ static void prep_all(Model& m, const float* const* params, cnr_stream s) {
     sj.push_back(SplitJob{q.Wt, q.kpad, q.ldwt, q.Wtp, q.Wtps});
   };
   for (auto& q : m.sdf) prep(q);
-  for (auto& q : m.col) prep(q);
-  for (auto& q : m.rel) prep(q);
+  if (!sdf_only) for (auto& q : m.col) prep(q);
+  if (!sdf_only) for (auto& q : m.rel) prep(q);
   be_prep_weights(pw.data(), (int)pw.size(), s);            // effective weights of every layer: one launch
   be_split_planes_many(sj.data(), (int)sj.size(), s);       // their f16 planes (W and W^T): one launch
   std::vector<PackJob> pj;
   for (auto& q : m.sdf) if (q.Wf) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
   // the hidden layers of the ReLU stacks (chain-fused forward, cnr_chain_fwd.hip); their 3-wide heads stay fp32
-  for (auto& q : m.col) if (q.Wf && q.n == 256) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
-  for (auto& q : m.rel) if (q.Wf && q.n == 256) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
+  if (!sdf_only) for (auto& q : m.col) if (q.Wf && q.n == 256) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
+  if (!sdf_only) for (auto& q : m.rel) if (q.Wf && q.n == 256) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
   be_pack_frags_many(pj.data(), (int)pj.size(), s);         // fragment-major copies for the chain-fused kernels: one launch
 }
 
@@ -1116,6 +1120,211 @@ static void flush_dw(Bwd& b, cnr_stream s) {
   b.pending.clear();
 }
 
+// Steps 4-7 of the backward pass and the point cotangent of step 8: the complete first- and second-order backward of the SDF network, shared
+// by render_backward and cnr_sdf_query_backward (the render path issues the same launches with the same arguments in the same order as
+// before this was a function of its own).  Seeds: b.ZTOP (cotangent of the top layer's outputs [feat | sdf / scale | 0]) and b.gbar_a
+// (cotangent of grad_x sdf).  Entered inside an open range (be_range_push), which it closes after the weight-gradient reductions.
+struct SdfBwdArgs {
+  const float* daux_c = nullptr; const float* daux_r = nullptr;   // cotangents of the colour / relight aux rows [p g ..] (render) or null (query)
+  bool grad_path = true;    // false: no cotangent on grad_x sdf -- no gbar / second-order sweep (Z2 starts from zero), value pairs only
+  bool pts_grad = false;    // form ebar0 / ebars and the total point cotangent b.pbar (camera refinement, point queries)
+};
+static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const float* const* params, float* const* dP /* null: no weight gradients */,
+                         const SdfBwdArgs& sa, cnr_stream s) {
+  const float scale = m.c.sdf_scale;
+  const bool fdw = be_fdw_enabled() && dP != nullptr;   // (the fused layer + weight-gradient launches only where weight gradients are wanted)
+  const bool gfdw = fdw && sa.grad_path;
+  const bool rays_grad = sa.pts_grad;
+  const bool skipnet = has_skip(m);
+  // ---- 4. total d g and the tangent of the embedding
+  GbarFinish gb;
+  gb.P = P; gb.gbar_alpha = b.gbar_a; gb.daux_c = sa.daux_c; gb.daux_r = sa.daux_r; gb.E = x.E; gb.scale = scale;
+  gb.multires = m.c.sdf_multires; gb.gbar_total = b.gbar_t; gb.cbar = b.cbar;
+  if (sa.grad_path) be_gbar_finish(gb, s);
+  // ---- 5. second-order forward sweep (tangent of h_l in the direction induced by gbar)
+  const float inv_scale = 1.0f / scale;
+  auto qbar_view = [&](int l) {
+    View v;
+    v.kind = VK_DIRECT;
+    if (l == 0) { v.a = b.cbar; v.lda = kEmb; }
+    else { v.a = b.VB[l - 1]; v.lda = m.Hs; if (m.skip(l)) v.scale = kInvSqrt2; }   // skip: tail columns of VB[l-1] hold cbar
+    return v;
+  };
+  // the launches of steps 5 and 6 as descriptors: each SDF layer's two weight-gradient pairs go into one region of the partial-sum pool,
+  // [value pair (zbar_l, input_l) | gradient-chain pair (u_l, qbar_l)], each either fused into its layer launch (value pair: the
+  // value-backward launch l; gradient-chain pair: the sweep launch l) or left to the separate weight-gradient GEMM of step 7
+  auto sweep_gemm = [&](int l) {
+    const Lin& q = m.sdf[l];
+    LayerGemm g;
+    g.A = qbar_view(l);
+    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P;
+    g.E.kind = EK_SWEEP; g.E.n_out = q.n; g.E.z = x.Z[l]; g.E.ldz = m.Hs;
+    if (l == m.L - 1) { g.E.v = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; g.E.ldv = 0; g.E.vscale = inv_scale; }
+    else { g.E.v = x.V[l]; g.E.ldv = m.Hs; }
+    g.E.o1 = b.Z2[l]; g.E.ld1 = m.Hs; g.E.o2 = b.VB[l]; g.E.ld2 = m.Hs;
+    if (m.skip(l + 1)) { g.E.tail_src = b.cbar; g.E.ld_tail = kEmb; g.E.tail_n = m.emb; }
+    return g;
+  };
+  auto vback_gemm = [&](int l) {
+    const Lin& q = m.sdf[l];
+    LayerGemm g;
+    if (l == m.L) { g.A.kind = VK_DIRECT; g.A.a = b.ZTOP; g.A.lda = x.ldztop; }
+    else { g.A.kind = VK_DIRECT; g.A.a = b.Z2[l]; g.A.lda = m.Hs; }
+    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+    g.E.kind = EK_VBACK; g.E.n_out = q.k_int; g.E.z = x.Z[l - 1]; g.E.ldz = m.Hs; g.E.o1 = b.Z2[l - 1]; g.E.ld1 = m.Hs;
+    if (m.skip(l)) { g.E.scale = kInvSqrt2; g.E.split = m.sdf[l - 1].n; g.E.o2 = rays_grad ? b.ebars : nullptr; g.E.ld2 = kEmb; g.E.o2_off = skip_off(m);
+                     g.E.o2_acc = l != top_skip(m);   // (the value backward runs from the top layer down: the highest skip layer stores, the others add)
+                     g.E.vscale = kInvSqrt2; }   // (vscale: the scale of the layer's input view, for the fused launch's epilogue-side operand)
+    return g;
+  };
+  // value pair of layer l: X = zbar_l, Y = the layer's forward input
+  auto value_pair = [&](int l, DwGemm& d) {
+    if (l == m.L) { d.X[0].kind = VK_DIRECT; d.X[0].a = b.ZTOP; d.X[0].lda = x.ldztop; }
+    else { d.X[0].kind = VK_DIRECT; d.X[0].a = b.Z2[l]; d.X[0].lda = m.Hs; }
+    d.Y[0] = sdf_input_view(m, l, x.E, x.Z.data());
+    d.sx[0] = b.rsX0[l]; d.sy[0] = x.rsY[l];
+  };
+  // gradient-chain pair of layer l into operand slot i of d: X = u_l = sp'(z_l) v_l, Y = qbar_l
+  auto grad_pair = [&](int l, DwGemm& d, int i) {
+    if (l == m.L) {
+      d.X[i].kind = VK_CONST_COL0; d.X[i].a = b.ZTOP; d.X[i].lda = x.ldztop; d.X[i].scale = inv_scale; d.X[i].math_split = m.F;
+      d.Y[i].kind = VK_DIRECT; d.Y[i].a = b.VB[m.L - 1]; d.Y[i].lda = m.Hs;
+    } else {
+      d.X[i].a = x.Z[l]; d.X[i].lda = m.Hs;
+      if (l == m.L - 1) { d.X[i].kind = VK_SIGMUL_ROW; d.X[i].b = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; d.X[i].scale = inv_scale; }
+      else { d.X[i].kind = VK_SIGMUL; d.X[i].b = x.V[l]; d.X[i].ldb = m.Hs; }
+      d.Y[i] = qbar_view(l);
+      d.sx[i] = x.rsX1[l]; d.sy[i] = b.rsY1[l];
+    }
+  };
+  std::vector<DwRegion> sreg(m.L + 1);
+  std::vector<char> fuse_v(m.L + 1, 0), fuse_g(m.L + 1, 0);
+  for (int l = 0; l <= m.L; ++l) {
+    const Lin& q = m.sdf[l];
+    sreg[l] = take_region(q, b);
+    const bool sq = q.npad >= 224 && q.npad <= 256 && q.ldw == 256;
+    auto ok = [&](const LayerGemm& g) { return fdw_shape_ok(g); };
+    if (fdw && sq && l >= 1 && l < m.L && x.rsY[l] && ok(vback_gemm(l))) fuse_v[l] = 1;
+    if (gfdw && sq && l < m.L && x.rsX1[l] && ok(sweep_gemm(l))) fuse_g[l] = 1;
+    // narrow-input layer (the first SDF layer): the sweep launch forms the pair from its epilogue's side inputs, one slot per workgroup (cnr_sweep0.hip)
+    if (gfdw && !fuse_g[l] && l < m.L && q.npad == 256 && be_sweep0_ok(sweep_gemm(l)) && b.nchunk + be_sweep0_slots(P) <= region_slots(q, b)) fuse_g[l] = 2;
+  }
+  // The first layer (narrow input): the cotangent of its input columns (camera refinement) and its value pair in one pass over Z2[0]
+  // (cnr_narrow_bwd.hip) instead of a narrow layer launch + a weight-gradient launch
+  NarrowBwd nb0;
+  {
+    const Lin& q = m.sdf[0];
+    nb0.X = b.Z2[0]; nb0.ldx = m.Hs; nb0.Y = x.E; nb0.ldy = kEmb; nb0.ky = q.k_int; nb0.P = P;
+    if (rays_grad) {
+      nb0.Wp = q.Wtp; nb0.wp_stride = (long)q.kpad * q.ldwt; nb0.ldw = q.ldwt; nb0.w_rows = q.kpad; nb0.wscale = q.Wtps;
+      nb0.dx = b.ebar0; nb0.lddx = kEmb; nb0.ndx = m.emb;
+    }
+    nb0.partial = sreg[0].part; nb0.ldk = q.ldw; nb0.colsum = sreg[0].csum;
+  }
+  const bool use_nb0 = fdw && m.L >= 1 && !fuse_v[0] && fuse_g[0] != 0 && m.sdf[0].n == 256 && m.sdf[0].npad == 256 && m.Hs == 256 && be_narrow_bwd_ok(nb0) &&
+                       be_narrow_bwd_slots(P) + (fuse_g[0] == 2 ? be_sweep0_slots(P) : fuse_g[0] ? b.fslots : 0) <= region_slots(m.sdf[0], b);
+  // The top layer (F features + the sdf row, F == 256 = its input width) without launches of its own: its value-backward launch takes the
+  // sdf column of the cotangent as a rank-one update of the 256-wide product (k_extra) and forms the main 256 x 256 weight gradient like any
+  // other layer; the sdf ROW of the weight gradient is made of values two launches hold anyway -- the gradient-chain pair's unit vector
+  // makes it inv_scale * column sums of VB[L-1], the o2 output of the sweep launch of layer L-1 (xrow_mode 1), and the value pair adds
+  // sum zbar_sdf[pt] * softplus(z_{L-1})[pt][:], whose factors the value-backward launch has in its epilogue (xrow_mode 2).
+  const Lin& qtop = m.sdf[m.L];
+  LayerGemm gtop = vback_gemm(m.L);
+  gtop.K = 256; gtop.k_extra = 1;
+  const bool no_top = debug_flags().no_top_fuse;   // debugging aid: the top layer as three launches of its own
+  const bool top_fused = !no_top && fdw && be_fdw_xrow() && m.L >= 2 && fuse_g[m.L - 1] && m.F == 256 && qtop.n == 257 && qtop.k_int == 256 &&
+                         qtop.ldw == 256 && qtop.npad <= 288 && x.ldztop >= 260 && x.rsY[m.L] && !m.skip(m.L) && fdw_shape_ok(gtop);
+  if (top_fused) fuse_v[m.L] = 1;
+  DwFuse xrow1, xrow2;
+  xrow1.xrow_mode = 1; xrow1.xrow = sreg[m.L].part + (size_t)256 * qtop.ldw; xrow1.xrow_stride = (long)qtop.npad * qtop.ldw; xrow1.xrow_scale = inv_scale;
+  xrow2 = xrow1;
+  xrow2.xrow_mode = 2; xrow2.xrow_scale = 1.0f; xrow2.xbias = sreg[m.L].csum + 256; xrow2.xbias_stride = qtop.npad;
+  // slot groups of a region: the value pair first (it carries the bias column sums), the gradient-chain pair behind it; a pair takes
+  // fslots slots when it is fused and nchunk slots as a separate GEMM (one workgroup per slot: fewer would leave CUs idle); when neither is
+  // fused one launch over nchunk slots forms both
+  auto value_slots = [&](int l) { return (l == 0 && use_nb0) ? be_narrow_bwd_slots(P) : fuse_v[l] ? b.fslots : b.nchunk; };
+  auto grad_slots = [&](int l) { return !sa.grad_path ? 0 : (l == m.L && top_fused) ? 0 : fuse_g[l] == 2 ? be_sweep0_slots(P) : fuse_g[l] ? b.fslots : (fuse_v[l] ? b.nchunk : 0); };
+  if (!sa.grad_path)   // value path only: the value backward adds into Z2, which no sweep has written
+    for (int l = 0; l < m.L; ++l) be_memset_zero(b.Z2[l], (size_t)P * m.Hs * sizeof(float), s);
+  for (int l = 0; sa.grad_path && l < m.L; ++l) {
+    const Lin& q = m.sdf[l];
+    LayerGemm g = sweep_gemm(l);
+    if (fuse_g[l] == 2) {
+      be_sweep0_dw(g, sreg[l].part + (size_t)value_slots(l) * q.npad * q.ldw, q.ldw, s);
+    } else if (fuse_g[l]) {
+      DwGemm d;
+      d.npairs = 1; d.P = P;
+      grad_pair(l, d, 0);
+      d.sy[0] = nullptr;   // (a fused launch does not need qbar_l's row scales; the unfused fallback then takes the split-bf16 tiles)
+      fused_into_region(q, g, d, x.rsX1[l], 1, sreg[l], value_slots(l), b, false, s, 0, (top_fused && l == m.L - 1) ? &xrow1 : nullptr, l & 1);
+    } else {
+      g.rs_out = b.rsY1[l];
+      be_layer_gemm(g, s);
+    }
+  }
+  be_range_pop(); be_range_push("sdf value backward");
+  // ---- 6. value-path backward through the SDF net (in place: Z2[l] becomes the total cotangent of z_l)
+  for (int l = m.L; l >= 1; --l) {
+    const Lin& q = m.sdf[l];
+    const bool top = l == m.L && top_fused;
+    LayerGemm g = top ? gtop : vback_gemm(l);
+    if (fuse_v[l]) {
+      DwGemm d;
+      d.npairs = 1; d.P = P;
+      value_pair(l, d);
+      d.sx[0] = nullptr;
+      fused_into_region(q, g, d, x.rsY[l], 0, sreg[l], 0, b, true, s, 0, top ? &xrow2 : nullptr, ((m.L - l) & 1) ^ 1);
+    } else {
+      g.rs_out = b.rsX0[l];
+      be_layer_gemm(g, s);
+    }
+  }
+  if (use_nb0) be_narrow_bwd(nb0, s);
+  else if (rays_grad) {
+    const Lin& q = m.sdf[0];
+    LayerGemm g;
+    g.A.kind = VK_DIRECT; g.A.a = b.Z2[0]; g.A.lda = m.Hs;
+    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+    g.E.kind = EK_STORE; g.E.n_out = m.emb; g.E.o1 = b.ebar0; g.E.ld1 = kEmb;
+    be_layer_gemm(g, s);
+  }
+  be_range_pop(); be_range_push("weight gradients: leftovers + finish");
+  // ---- 7. SDF weight gradients that were not formed inside a layer launch: value pair (zbar_l, input_l) + gradient-chain pair (u_l, qbar_l)
+  for (int l = 0; dP && l <= m.L; ++l) {
+    const Lin& q = m.sdf[l];
+    const DwRegion& r = sreg[l];
+    if (!fuse_v[l] && !fuse_g[l]) {          // both pairs in one launch sharing the accumulators
+      DwGemm d;
+      d.npairs = sa.grad_path ? 2 : 1; d.P = P;
+      value_pair(l, d);
+      if (sa.grad_path) grad_pair(l, d, 1);
+      dw_into_region(q, d, r, 0, b.nchunk, P, true, s);
+    } else if (l == 0 && use_nb0) {          // (formed by the one-pass launch of step 6)
+    } else if (!fuse_v[l]) {                 // the value pair alone, into the leading slots
+      DwGemm d;
+      d.npairs = 1; d.P = P;
+      value_pair(l, d);
+      dw_into_region(q, d, r, 0, value_slots(l), P, true, s);
+    } else if (sa.grad_path && !fuse_g[l] && !(l == m.L && top_fused)) {   // the gradient-chain pair alone, behind the fused value pair
+      DwGemm d;
+      d.npairs = 1; d.P = P;
+      grad_pair(l, d, 0);
+      dw_into_region(q, d, r, value_slots(l), grad_slots(l), P, false, s);
+    }
+    finish_region(q, r, value_slots(l) + grad_slots(l), value_slots(l), b, params, dP);
+  }
+  flush_dw(b, s);   // all partial-sum reductions + weight-norm backward in one launch
+  be_range_pop();
+  // ---- 8 (first part). total cotangent of the points
+  if (rays_grad) {
+    PbarFinish pf;
+    pf.P = P; pf.daux_c = sa.daux_c; pf.daux_r = sa.daux_r; pf.ebar0 = b.ebar0; pf.ebars = skipnet ? b.ebars + skip_off(m) : nullptr;
+    pf.E = x.E; pf.ce0 = x.CE0; pf.ces = skipnet ? x.CES + skip_off(m) : nullptr; pf.gbar_total = sa.grad_path ? b.gbar_t : nullptr; pf.scale = scale;
+    pf.multires = m.c.sdf_multires; pf.pbar = b.pbar;
+    be_pbar_finish(pf, s);
+  }
+}
+
 static int render_backward(const cnr_config* cfg, const float* const* params, const cnr_render_inputs* in,
                            const cnr_render_outputs* out, const void* ctx, size_t ctx_bytes, const cnr_render_out_grads* go,
                            const cnr_render_in_grads* gi, void* scratch, size_t scratch_bytes, cnr_stream s) {
@@ -1145,7 +1354,6 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
   }
   const bool rays_grad = rays_out || nf_live;   // both need the total cotangent of the sample points
   float* const* dP = gi->d_params;
-  const bool skipnet = has_skip(m);
 
   RangeScope range_bwd("cnr_render_backward");
   be_range_push("compositor backward");
@@ -1283,190 +1491,11 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
     if (strips) strip_columns_of_last_finish(b);
   }
   be_range_pop(); be_range_push("sdf second-order sweep");
-  // ---- 4. total d g and the tangent of the embedding
-  GbarFinish gb;
-  gb.P = P; gb.gbar_alpha = b.gbar_a; gb.daux_c = b.dAUXc; gb.daux_r = m.has_relight ? b.dAUXr : nullptr; gb.E = x.E; gb.scale = scale;
-  gb.multires = m.c.sdf_multires; gb.gbar_total = b.gbar_t; gb.cbar = b.cbar;
-  be_gbar_finish(gb, s);
-  // ---- 5. second-order forward sweep (tangent of h_l in the direction induced by gbar)
-  const float inv_scale = 1.0f / scale;
-  auto qbar_view = [&](int l) {
-    View v;
-    v.kind = VK_DIRECT;
-    if (l == 0) { v.a = b.cbar; v.lda = kEmb; }
-    else { v.a = b.VB[l - 1]; v.lda = m.Hs; if (m.skip(l)) v.scale = kInvSqrt2; }   // skip: tail columns of VB[l-1] hold cbar
-    return v;
-  };
-  // the launches of steps 5 and 6 as descriptors: each SDF layer's two weight-gradient pairs go into one region of the partial-sum pool,
-  // [value pair (zbar_l, input_l) | gradient-chain pair (u_l, qbar_l)], each either fused into its layer launch (value pair: the
-  // value-backward launch l; gradient-chain pair: the sweep launch l) or left to the separate weight-gradient GEMM of step 7
-  auto sweep_gemm = [&](int l) {
-    const Lin& q = m.sdf[l];
-    LayerGemm g;
-    g.A = qbar_view(l);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P;
-    g.E.kind = EK_SWEEP; g.E.n_out = q.n; g.E.z = x.Z[l]; g.E.ldz = m.Hs;
-    if (l == m.L - 1) { g.E.v = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; g.E.ldv = 0; g.E.vscale = inv_scale; }
-    else { g.E.v = x.V[l]; g.E.ldv = m.Hs; }
-    g.E.o1 = b.Z2[l]; g.E.ld1 = m.Hs; g.E.o2 = b.VB[l]; g.E.ld2 = m.Hs;
-    if (m.skip(l + 1)) { g.E.tail_src = b.cbar; g.E.ld_tail = kEmb; g.E.tail_n = m.emb; }
-    return g;
-  };
-  auto vback_gemm = [&](int l) {
-    const Lin& q = m.sdf[l];
-    LayerGemm g;
-    if (l == m.L) { g.A.kind = VK_DIRECT; g.A.a = b.ZTOP; g.A.lda = x.ldztop; }
-    else { g.A.kind = VK_DIRECT; g.A.a = b.Z2[l]; g.A.lda = m.Hs; }
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
-    g.E.kind = EK_VBACK; g.E.n_out = q.k_int; g.E.z = x.Z[l - 1]; g.E.ldz = m.Hs; g.E.o1 = b.Z2[l - 1]; g.E.ld1 = m.Hs;
-    if (m.skip(l)) { g.E.scale = kInvSqrt2; g.E.split = m.sdf[l - 1].n; g.E.o2 = rays_grad ? b.ebars : nullptr; g.E.ld2 = kEmb; g.E.o2_off = skip_off(m);
-                     g.E.o2_acc = l != top_skip(m);   // (the value backward runs from the top layer down: the highest skip layer stores, the others add)
-                     g.E.vscale = kInvSqrt2; }   // (vscale: the scale of the layer's input view, for the fused launch's epilogue-side operand)
-    return g;
-  };
-  // value pair of layer l: X = zbar_l, Y = the layer's forward input
-  auto value_pair = [&](int l, DwGemm& d) {
-    if (l == m.L) { d.X[0].kind = VK_DIRECT; d.X[0].a = b.ZTOP; d.X[0].lda = x.ldztop; }
-    else { d.X[0].kind = VK_DIRECT; d.X[0].a = b.Z2[l]; d.X[0].lda = m.Hs; }
-    d.Y[0] = sdf_input_view(m, l, x.E, x.Z.data());
-    d.sx[0] = b.rsX0[l]; d.sy[0] = x.rsY[l];
-  };
-  // gradient-chain pair of layer l into operand slot i of d: X = u_l = sp'(z_l) v_l, Y = qbar_l
-  auto grad_pair = [&](int l, DwGemm& d, int i) {
-    if (l == m.L) {
-      d.X[i].kind = VK_CONST_COL0; d.X[i].a = b.ZTOP; d.X[i].lda = x.ldztop; d.X[i].scale = inv_scale; d.X[i].math_split = m.F;
-      d.Y[i].kind = VK_DIRECT; d.Y[i].a = b.VB[m.L - 1]; d.Y[i].lda = m.Hs;
-    } else {
-      d.X[i].a = x.Z[l]; d.X[i].lda = m.Hs;
-      if (l == m.L - 1) { d.X[i].kind = VK_SIGMUL_ROW; d.X[i].b = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; d.X[i].scale = inv_scale; }
-      else { d.X[i].kind = VK_SIGMUL; d.X[i].b = x.V[l]; d.X[i].ldb = m.Hs; }
-      d.Y[i] = qbar_view(l);
-      d.sx[i] = x.rsX1[l]; d.sy[i] = b.rsY1[l];
-    }
-  };
-  std::vector<DwRegion> sreg(m.L + 1);
-  std::vector<char> fuse_v(m.L + 1, 0), fuse_g(m.L + 1, 0);
-  for (int l = 0; l <= m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    sreg[l] = take_region(q, b);
-    const bool sq = q.npad >= 224 && q.npad <= 256 && q.ldw == 256;
-    auto ok = [&](const LayerGemm& g) { return fdw_shape_ok(g); };
-    if (fdw && sq && l >= 1 && l < m.L && x.rsY[l] && ok(vback_gemm(l))) fuse_v[l] = 1;
-    if (fdw && sq && l < m.L && x.rsX1[l] && ok(sweep_gemm(l))) fuse_g[l] = 1;
-    // narrow-input layer (the first SDF layer): the sweep launch forms the pair from its epilogue's side inputs, one slot per workgroup (cnr_sweep0.hip)
-    if (fdw && !fuse_g[l] && l < m.L && q.npad == 256 && be_sweep0_ok(sweep_gemm(l)) && b.nchunk + be_sweep0_slots(P) <= region_slots(q, b)) fuse_g[l] = 2;
-  }
-  // The first layer (narrow input): the cotangent of its input columns (camera refinement) and its value pair in one pass over Z2[0]
-  // (cnr_narrow_bwd.hip) instead of a narrow layer launch + a weight-gradient launch
-  NarrowBwd nb0;
-  {
-    const Lin& q = m.sdf[0];
-    nb0.X = b.Z2[0]; nb0.ldx = m.Hs; nb0.Y = x.E; nb0.ldy = kEmb; nb0.ky = q.k_int; nb0.P = P;
-    if (rays_grad) {
-      nb0.Wp = q.Wtp; nb0.wp_stride = (long)q.kpad * q.ldwt; nb0.ldw = q.ldwt; nb0.w_rows = q.kpad; nb0.wscale = q.Wtps;
-      nb0.dx = b.ebar0; nb0.lddx = kEmb; nb0.ndx = m.emb;
-    }
-    nb0.partial = sreg[0].part; nb0.ldk = q.ldw; nb0.colsum = sreg[0].csum;
-  }
-  const bool use_nb0 = fdw && m.L >= 1 && !fuse_v[0] && fuse_g[0] != 0 && m.sdf[0].n == 256 && m.sdf[0].npad == 256 && m.Hs == 256 && be_narrow_bwd_ok(nb0) &&
-                       be_narrow_bwd_slots(P) + (fuse_g[0] == 2 ? be_sweep0_slots(P) : fuse_g[0] ? b.fslots : 0) <= region_slots(m.sdf[0], b);
-  // The top layer (F features + the sdf row, F == 256 = its input width) without launches of its own: its value-backward launch takes the
-  // sdf column of the cotangent as a rank-one update of the 256-wide product (k_extra) and forms the main 256 x 256 weight gradient like any
-  // other layer; the sdf ROW of the weight gradient is made of values two launches hold anyway -- the gradient-chain pair's unit vector
-  // makes it inv_scale * column sums of VB[L-1], the o2 output of the sweep launch of layer L-1 (xrow_mode 1), and the value pair adds
-  // sum zbar_sdf[pt] * softplus(z_{L-1})[pt][:], whose factors the value-backward launch has in its epilogue (xrow_mode 2).
-  const Lin& qtop = m.sdf[m.L];
-  LayerGemm gtop = vback_gemm(m.L);
-  gtop.K = 256; gtop.k_extra = 1;
-  const bool no_top = debug_flags().no_top_fuse;   // debugging aid: the top layer as three launches of its own
-  const bool top_fused = !no_top && fdw && be_fdw_xrow() && m.L >= 2 && fuse_g[m.L - 1] && m.F == 256 && qtop.n == 257 && qtop.k_int == 256 &&
-                         qtop.ldw == 256 && qtop.npad <= 288 && x.ldztop >= 260 && x.rsY[m.L] && !m.skip(m.L) && fdw_shape_ok(gtop);
-  if (top_fused) fuse_v[m.L] = 1;
-  DwFuse xrow1, xrow2;
-  xrow1.xrow_mode = 1; xrow1.xrow = sreg[m.L].part + (size_t)256 * qtop.ldw; xrow1.xrow_stride = (long)qtop.npad * qtop.ldw; xrow1.xrow_scale = inv_scale;
-  xrow2 = xrow1;
-  xrow2.xrow_mode = 2; xrow2.xrow_scale = 1.0f; xrow2.xbias = sreg[m.L].csum + 256; xrow2.xbias_stride = qtop.npad;
-  // slot groups of a region: the value pair first (it carries the bias column sums), the gradient-chain pair behind it; a pair takes
-  // fslots slots when it is fused and nchunk slots as a separate GEMM (one workgroup per slot: fewer would leave CUs idle); when neither is
-  // fused one launch over nchunk slots forms both
-  auto value_slots = [&](int l) { return (l == 0 && use_nb0) ? be_narrow_bwd_slots(P) : fuse_v[l] ? b.fslots : b.nchunk; };
-  auto grad_slots = [&](int l) { return (l == m.L && top_fused) ? 0 : fuse_g[l] == 2 ? be_sweep0_slots(P) : fuse_g[l] ? b.fslots : (fuse_v[l] ? b.nchunk : 0); };
-  for (int l = 0; l < m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    LayerGemm g = sweep_gemm(l);
-    if (fuse_g[l] == 2) {
-      be_sweep0_dw(g, sreg[l].part + (size_t)value_slots(l) * q.npad * q.ldw, q.ldw, s);
-    } else if (fuse_g[l]) {
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      grad_pair(l, d, 0);
-      d.sy[0] = nullptr;   // (a fused launch does not need qbar_l's row scales; the unfused fallback then takes the split-bf16 tiles)
-      fused_into_region(q, g, d, x.rsX1[l], 1, sreg[l], value_slots(l), b, false, s, 0, (top_fused && l == m.L - 1) ? &xrow1 : nullptr, l & 1);
-    } else {
-      g.rs_out = b.rsY1[l];
-      be_layer_gemm(g, s);
-    }
-  }
-  be_range_pop(); be_range_push("sdf value backward");
-  // ---- 6. value-path backward through the SDF net (in place: Z2[l] becomes the total cotangent of z_l)
-  for (int l = m.L; l >= 1; --l) {
-    const Lin& q = m.sdf[l];
-    const bool top = l == m.L && top_fused;
-    LayerGemm g = top ? gtop : vback_gemm(l);
-    if (fuse_v[l]) {
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      value_pair(l, d);
-      d.sx[0] = nullptr;
-      fused_into_region(q, g, d, x.rsY[l], 0, sreg[l], 0, b, true, s, 0, top ? &xrow2 : nullptr, ((m.L - l) & 1) ^ 1);
-    } else {
-      g.rs_out = b.rsX0[l];
-      be_layer_gemm(g, s);
-    }
-  }
-  if (use_nb0) be_narrow_bwd(nb0, s);
-  else if (rays_grad) {
-    const Lin& q = m.sdf[0];
-    LayerGemm g;
-    g.A.kind = VK_DIRECT; g.A.a = b.Z2[0]; g.A.lda = m.Hs;
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
-    g.E.kind = EK_STORE; g.E.n_out = m.emb; g.E.o1 = b.ebar0; g.E.ld1 = kEmb;
-    be_layer_gemm(g, s);
-  }
-  be_range_pop(); be_range_push("weight gradients: leftovers + finish");
-  // ---- 7. SDF weight gradients that were not formed inside a layer launch: value pair (zbar_l, input_l) + gradient-chain pair (u_l, qbar_l)
-  for (int l = 0; l <= m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    const DwRegion& r = sreg[l];
-    if (!fuse_v[l] && !fuse_g[l]) {          // both pairs in one launch sharing the accumulators
-      DwGemm d;
-      d.npairs = 2; d.P = P;
-      value_pair(l, d);
-      grad_pair(l, d, 1);
-      dw_into_region(q, d, r, 0, b.nchunk, P, true, s);
-    } else if (l == 0 && use_nb0) {          // (formed by the one-pass launch of step 6)
-    } else if (!fuse_v[l]) {                 // the value pair alone, into the leading slots
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      value_pair(l, d);
-      dw_into_region(q, d, r, 0, value_slots(l), P, true, s);
-    } else if (!fuse_g[l] && !(l == m.L && top_fused)) {   // the gradient-chain pair alone, behind the fused value pair
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      grad_pair(l, d, 0);
-      dw_into_region(q, d, r, value_slots(l), grad_slots(l), P, false, s);
-    }
-    finish_region(q, r, value_slots(l) + grad_slots(l), value_slots(l), b, params, dP);
-  }
-  flush_dw(b, s);   // all partial-sum reductions + weight-norm backward in one launch
-  be_range_pop();
+  SdfBwdArgs args;
+  args.daux_c = b.dAUXc; args.daux_r = m.has_relight ? b.dAUXr : nullptr; args.grad_path = true; args.pts_grad = rays_grad;
+  sdf_backward(m, P, x, b, params, dP, args, s);
   // ---- 8. d rays (camera refinement configs)
   if (rays_grad) {
-    PbarFinish pf;
-    pf.P = P; pf.daux_c = b.dAUXc; pf.daux_r = m.has_relight ? b.dAUXr : nullptr; pf.ebar0 = b.ebar0; pf.ebars = skipnet ? b.ebars + skip_off(m) : nullptr;
-    pf.E = x.E; pf.ce0 = x.CE0; pf.ces = skipnet ? x.CES + skip_off(m) : nullptr; pf.gbar_total = b.gbar_t; pf.scale = scale;
-    pf.multires = m.c.sdf_multires; pf.pbar = b.pbar;
-    be_pbar_finish(pf, s);
     RaysGradFinish rg;
     rg.R = R; rg.M = m.M; rg.d = in->rays_d; rg.z = out->z_vals; rg.sample_dist = 2.0f / (float)m.S; rg.pbar = b.pbar;
     rg.daux_dir_c = (m.c.col_mode != 1 && m.nv > 0) ? b.dAUXc : nullptr;
@@ -1502,7 +1531,7 @@ static int sdf_eval_impl(const cnr_config* cfg, const float* const* params, cons
   EvalBuf e;
   layout_eval(m, chunk, a, e);
   if (a.off > scratch_bytes) return fail("scratch too small: need %zu bytes, got %zu", a.off, scratch_bytes);
-  prep_all(m, params, s);
+  prep_all(m, params, s, true);   // (the SDF layers are all it runs: the other entries of params may be null)
   float* Zp[kMaxLayers];
   for (int l = 0; l < m.L; ++l) Zp[l] = (l & 1) ? e.Zb : e.Za;
   for (long start = 0; start < n; start += chunk) {
@@ -1547,6 +1576,169 @@ static void layout_vc(Model& m, long n, Arena& a, Ctx& x) {
   x.HC.resize(m.NC - 1);
   for (int l = 0; l + 1 < m.NC; ++l) x.HC[l] = a.f((size_t)n * m.Hc);
   a.f(1024);
+}
+
+// ------------------------------------------------------------------------------------------------
+// SDF point queries (cnr_sdf_query_*): sdf_network.forward / .gradient (fields.py:81-115) at the caller's points and their backward -- the
+// render path's SDF chains and its SDF backward (sdf_backward) on P = round_up(n, kQueryTile) rows.  Padded rows sit at the origin (finite
+// activations), carry zero cotangents (an all-zero row gets a zero row scale, which the split-f16 weight-gradient products treat as a zero
+// row) and are never copied out.  The forward stores the row scales the training forward stores, so the backward makes the same fused choices
+// (fuse_v / fuse_g, use_nb0, top_fused) as a render backward over the same number of points.
+// ------------------------------------------------------------------------------------------------
+constexpr long kQueryTile = 128;
+static long query_rows(long n) { return (n + kQueryTile - 1) / kQueryTile * kQueryTile; }
+
+struct QueryBuf { Ctx x; int* tag = nullptr; float* pts = nullptr; float* feat = nullptr; int ldf = 0; };
+// the context: SDF weights, the tag (QueryIn), padded points, E, Z[l], the sdf / feature rows and the row scales rsY; with want_grad
+// BEHIND them V[l], CE0 / CES, the gradient rows and rsX1 -- so that a value-only backward finds the value-path buffers at the same
+// offsets whichever form the forward took
+static void layout_query(Model& m, long P, bool want_grad, Arena& a, QueryBuf& q) {
+  for (auto& l : m.sdf) place_lin(l, a);
+  Ctx& x = q.x;
+  q.tag = reinterpret_cast<int*>(a.f(64));
+  q.pts = a.f((size_t)P * 3);
+  x.E = a.f((size_t)P * kEmb);
+  x.sdf = a.f(P);
+  q.ldf = round_up(m.F, 16);
+  q.feat = a.f((size_t)P * q.ldf);
+  x.Z.resize(m.L); x.V.assign(m.L, nullptr);
+  for (int l = 0; l < m.L; ++l) x.Z[l] = a.f((size_t)P * m.Hs);
+  x.ldztop = round_up(m.F + 1, 16);
+  x.rsY.assign(m.L + 1, nullptr); x.rsX1.assign(m.L, nullptr);
+  for (int l = 1; l <= m.L; ++l) x.rsY[l] = a.f(P);
+  x.AUX = want_grad ? a.f((size_t)P * kAux) : nullptr;   // (be_grad_finish also writes g into AUX[., 3:6]; nothing reads it here)
+  x.gbuf = want_grad ? a.f((size_t)P * 3) : nullptr;
+  x.CE0 = want_grad ? a.f((size_t)P * kEmb) : nullptr;
+  x.CES = want_grad ? a.f((size_t)P * kEmb) : nullptr;
+  if (want_grad) for (int l = 0; l + 1 < m.L; ++l) x.V[l] = a.f((size_t)P * m.Hs);
+  if (want_grad) for (int l = 1; l < m.L; ++l) x.rsX1[l] = a.f(P);
+  a.f(1024);   // slack (see layout_ctx)
+}
+
+// the backward scratch: the SDF part of layout_bwd (seeds, second-order and value cotangents, the partial-sum pool of the SDF layers)
+static void layout_query_bwd(const Model& m, long P, bool grad_path, const Ctx& x, Arena& a, Bwd& b) {
+  b.ZTOP = a.f((size_t)P * x.ldztop);
+  b.gbar_a = grad_path ? a.f((size_t)P * 4) : nullptr;
+  b.gbar_t = grad_path ? a.f((size_t)P * 4) : nullptr;
+  b.cbar = grad_path ? a.f((size_t)P * kEmb) : nullptr;
+  b.ebar0 = a.f((size_t)P * kEmb);
+  b.ebars = a.f((size_t)P * kEmb);
+  b.pbar = a.f((size_t)P * 4);
+  b.VB.assign(m.L, nullptr); b.Z2.resize(m.L);
+  for (int l = 0; l < m.L; ++l) { if (grad_path) b.VB[l] = a.f((size_t)P * m.Hs); b.Z2[l] = a.f((size_t)P * m.Hs); }
+  bwd_slots(P, b);
+  size_t tot = 0;
+  for (auto& q : m.sdf) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); }
+  b.partial_floats = tot;
+  b.partial = a.f(tot);
+  b.partial_off = 0;
+  b.pending.clear();
+  b.rsX0.assign(m.L + 1, nullptr); b.rsY1.assign(m.L + 1, nullptr);
+  for (int l = 1; l <= m.L; ++l) b.rsX0[l] = a.f(P);
+  if (grad_path) for (int l = 1; l < m.L; ++l) b.rsY1[l] = a.f(P);
+  b.rsD = nullptr;
+  a.f(1024);   // slack (see layout_ctx)
+}
+
+static size_t query_ctx_bytes(const cnr_config* cfg, long n, bool want_grad) {
+  Model m;
+  if (build_model(cfg, m) || n <= 0) return 0;
+  Arena a(nullptr);
+  QueryBuf q{};
+  layout_query(m, query_rows(n), want_grad, a, q);
+  return a.off;
+}
+
+static size_t query_bwd_scratch_bytes(const cnr_config* cfg, long n, bool want_grad) {
+  Model m;
+  if (build_model(cfg, m) || n <= 0) return 0;
+  Arena a(nullptr), sa(nullptr);
+  QueryBuf q{};
+  layout_query(m, query_rows(n), want_grad, a, q);
+  Bwd b{};
+  layout_query_bwd(m, query_rows(n), want_grad, q.x, sa, b);
+  return sa.off;
+}
+
+static int sdf_query_forward(const cnr_config* cfg, const float* const* params, const float* pts, long n, bool want_grad, float* sdf, float* feat,
+                             float* grad, void* ctx, size_t ctx_bytes, cnr_stream s) {
+  Model m;
+  if (build_model(cfg, m)) return -1;
+  if (!params || !pts || !sdf || !ctx) return fail("null argument");
+  if (n <= 0) return fail("n_points must be positive");
+  if (want_grad != (grad != nullptr)) return fail("the grad buffer is given iff want_grad");
+  const long P = query_rows(n);
+  Arena a(ctx);
+  QueryBuf q{};
+  layout_query(m, P, want_grad, a, q);
+  if (a.off > ctx_bytes) return fail("context buffer too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  Ctx& x = q.x;
+  const float scale = m.c.sdf_scale;
+  RangeScope range_("sdf query forward");
+  prep_all(m, params, s, true);
+  QueryIn qi;
+  qi.n = n; qi.P = P; qi.pts = pts; qi.out = q.pts; qi.tag = q.tag; qi.tag_value = kQueryCtxTag + (want_grad ? 1 : 0);
+  be_query_in(qi, s);
+  EmbedPts ep;
+  ep.pts = q.pts; ep.n = P; ep.res = 0; ep.start = 0;
+  for (int c = 0; c < 3; ++c) { ep.bmin[c] = 0.f; ep.bmax[c] = 0.f; }
+  ep.scale = scale; ep.multires = m.c.sdf_multires; ep.E = x.E; ep.AUX = x.AUX;
+  be_embed_pts(ep, s);
+  sdf_chain(m, P, x.E, x.Z.data(), x.sdf, q.feat, q.ldf, 1.0f / scale, s, x.rsY.data());
+  if (want_grad) {
+    sdf_grad_chain(m, P, x.E, x.Z.data(), x.V.data(), x.CE0, x.CES, s, x.rsX1.data());
+    GradFinish gf;
+    gf.P = P; gf.E = x.E; gf.ce0 = x.CE0; gf.ces = has_skip(m) ? x.CES + skip_off(m) : nullptr; gf.scale = scale; gf.multires = m.c.sdf_multires;
+    gf.grad_out = x.gbuf; gf.AUX = x.AUX; gf.neg_g_as_view = 0; gf.multires_view = 0;
+    gf.featx = nullptr; gf.ldfx = 0; gf.F = m.F;
+    be_grad_finish(gf, s);
+  }
+  QueryOut qo;
+  qo.n = n; qo.F = m.F; qo.ldf = q.ldf; qo.ldg = 3;
+  qo.sdf_in = x.sdf; qo.feat_in = q.feat; qo.g_in = x.gbuf;
+  qo.sdf = sdf; qo.feat = feat; qo.g = want_grad ? grad : nullptr;
+  be_query_out(qo, s);
+  return check_backend("sdf_query_forward");
+}
+
+static int sdf_query_backward(const cnr_config* cfg, const float* const* params, long n, bool want_grad, const float* d_sdf, const float* d_feat,
+                              const float* d_grad, const void* ctx, size_t ctx_bytes, float* const* d_params, float* d_pts, void* scratch,
+                              size_t scratch_bytes, cnr_stream s) {
+  Model m;
+  if (build_model(cfg, m)) return -1;
+  if (!params || !ctx || !scratch) return fail("null argument");
+  if (n <= 0) return fail("n_points must be positive");
+  if (d_grad && !want_grad) return fail("d_grad needs a forward with want_grad");
+  const long P = query_rows(n);
+  Arena a(const_cast<void*>(ctx));
+  QueryBuf q{};
+  layout_query(m, P, want_grad, a, q);
+  if (a.off > ctx_bytes) return fail("context buffer too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  // no cotangent on the gradient: the second-order half of the backward is identically zero and is not run
+  const bool grad_path = want_grad && d_grad != nullptr;
+  Arena sa(scratch);
+  Bwd b{};
+  layout_query_bwd(m, P, grad_path, q.x, sa, b);
+  if (sa.off > scratch_bytes) return fail("backward scratch too small: need %zu bytes, got %zu", sa.off, scratch_bytes);
+  if (!d_params && !d_pts) return 0;
+  RangeScope range_("sdf query backward");
+  QuerySeed qs;
+  qs.n = n; qs.P = P; qs.F = m.F; qs.ldztop = q.x.ldztop; qs.inv_scale = 1.0f / m.c.sdf_scale;
+  qs.d_sdf = d_sdf; qs.d_feat = d_feat; qs.d_grad = d_grad; qs.ztop = b.ZTOP; qs.gbar = grad_path ? b.gbar_a : nullptr;
+  qs.tag = q.tag; qs.want_grad = grad_path ? 1 : 0;   // (a value-only backward reads only the buffers every form of the forward wrote)
+  be_query_seed(qs, s);
+  be_range_push("sdf second-order sweep");
+  SdfBwdArgs args;
+  args.grad_path = grad_path; args.pts_grad = d_pts != nullptr;
+  sdf_backward(m, P, q.x, b, params, d_params, args, s);
+  if (d_pts) {
+    QueryOut qo;
+    qo.n = n; qo.F = m.F; qo.ldf = 0; qo.ldg = 4;
+    qo.sdf_in = nullptr; qo.feat_in = nullptr; qo.g_in = b.pbar;
+    qo.sdf = nullptr; qo.feat = nullptr; qo.g = d_pts;
+    be_query_out(qo, s);
+  }
+  return check_backend("sdf_query_backward");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2488,6 +2680,22 @@ int cnr_vertex_color(const cnr_config* cfg, const float* const* params, const fl
     }
   }
   return check_backend("vertex_color");
+}
+
+size_t cnr_sdf_query_ctx_bytes(const cnr_config* cfg, int64_t n_points, int32_t want_grad) { return query_ctx_bytes(cfg, n_points, want_grad != 0); }
+size_t cnr_sdf_query_bwd_scratch_bytes(const cnr_config* cfg, int64_t n_points, int32_t want_grad) {
+  return query_bwd_scratch_bytes(cfg, n_points, want_grad != 0);
+}
+int cnr_sdf_query_forward(const cnr_config* cfg, const float* const* params, const float* pts, int64_t n_points, int32_t want_grad, float* sdf,
+                          float* feat, float* grad, void* ctx, size_t ctx_bytes, void* stream) {
+  return sdf_query_forward(cfg, params, pts, n_points, want_grad != 0, sdf, feat, grad, ctx, ctx_bytes, (cnr_stream)stream);
+}
+int cnr_sdf_query_backward(const cnr_config* cfg, const float* const* params, const float* pts, int64_t n_points, int32_t want_grad,
+                           const float* d_sdf, const float* d_feat, const float* d_grad, const void* ctx, size_t ctx_bytes,
+                           float* const* d_params, float* d_pts, void* scratch, size_t scratch_bytes, void* stream) {
+  (void)pts;   // (the context holds the padded copy the forward embedded)
+  return sdf_query_backward(cfg, params, n_points, want_grad != 0, d_sdf, d_feat, d_grad, ctx, ctx_bytes, d_params, d_pts, scratch, scratch_bytes,
+                            (cnr_stream)stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@ import math
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .config import RenderConfig, config_from_node
@@ -240,8 +241,133 @@ def _embed_dim(multires, d=3):
     return d * (1 + 2 * multires) if multires > 0 else d
 
 
+# Points per library call of an SDF point query: a larger query is split into calls of at most this many points, fewer when the context
+# and backward scratch of that many points (cnr_sdf_query_ctx_bytes + cnr_sdf_query_bwd_scratch_bytes) would exceed _QUERY_MAX_BYTES.
+_QUERY_MAX_POINTS = 1 << 20
+_QUERY_MAX_BYTES = 16 << 30
+
+
+class _SdfQueryBinding:
+    """What ``_SDFNet``'s query methods need besides its own parameters: the library and the C config.  Held as a plain attribute (not a
+    module, no parameters or buffers: state_dict and named_parameters stay those of the reference); a deepcopy shares it, since it holds
+    nothing of the copied module."""
+
+    def __init__(self, library, rcfg):
+        self._library_arg = library
+        self._lib_obj = None
+        self.ccfg = _lib.c_config(rcfg)
+        self.d_out = rcfg.sdf_d_out
+        self._names = None
+        self._max_pts = {}
+
+    def __deepcopy__(self, memo):
+        return self
+
+    @property
+    def lib(self):
+        if self._lib_obj is None:
+            lib = self._library_arg
+            self._lib_obj = lib if isinstance(lib, _lib.RenderLibrary) else _lib.load_library(lib)
+        return self._lib_obj
+
+    def names(self):
+        """(number of canonical parameters, sdf_network parameter names in canonical order, without the prefix)."""
+        if self._names is None:
+            inv = self.lib.param_inventory(self.ccfg)
+            self._names = (len(inv), [n[len("sdf_network."):] for n, _, _ in inv if n.startswith("sdf_network.")])
+        return self._names
+
+    def max_points(self, want_grad):
+        """Points per call (see _QUERY_MAX_POINTS), from the library's size functions: fixed part + per-point part at two sizes."""
+        if want_grad not in self._max_pts:
+            L, wg = self.lib.lib, int(want_grad)
+            size = lambda n: L.cnr_sdf_query_ctx_bytes(C.byref(self.ccfg), n, wg) + L.cnr_sdf_query_bwd_scratch_bytes(C.byref(self.ccfg), n, wg)
+            n0 = 1 << 16
+            per_pt = (size(2 * n0) - size(n0)) / n0
+            fixed = size(n0) - per_pt * n0
+            fit = int((_QUERY_MAX_BYTES - fixed) / per_pt) // 128 * 128
+            self._max_pts[want_grad] = max(128, min(_QUERY_MAX_POINTS, fit))
+        return self._max_pts[want_grad]
+
+    def param_array(self, tensors):
+        """The canonical inventory as a pointer array: the sdf_network entries (the leading ones) from ``tensors``, NULL for the others."""
+        nall, names = self.names()
+        ptrs = [None] * nall
+        for i, t in enumerate(tensors):
+            ptrs[i] = t.data_ptr() if t is not None else None
+        return (C.c_void_p * nall)(*ptrs)
+
+    def forward(self, x, params, want_grad, want_feat, keep_ctx):
+        """cnr_sdf_query_forward on the float32 [n, 3] points x (0 < n): (sdf [n, 1], feat [n, F] or None, grad [n, 3] or None, ctx or None)."""
+        L, n, dev = self.lib, x.shape[0], x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        sdf = torch.empty(n, 1, **f32)
+        feat = torch.empty(n, self.d_out - 1, **f32) if want_feat else None
+        grad = torch.empty(n, 3, **f32) if want_grad else None
+        nb = L.lib.cnr_sdf_query_ctx_bytes(C.byref(self.ccfg), n, int(want_grad))
+        cbuf = torch.empty(nb, dtype=torch.uint8, device=dev)
+        rc = L.lib.cnr_sdf_query_forward(C.byref(self.ccfg), self.param_array(params), _ptr(x), n, int(want_grad), _ptr(sdf), _ptr(feat),
+                                         _ptr(grad), _ptr(cbuf), nb, _stream_of(x))
+        L.check(rc, "cnr_sdf_query_forward")
+        return sdf, feat, grad, (cbuf if keep_ctx else None)
+
+
+class _SdfQueryFunction(torch.autograd.Function):
+    """autograd edge around cnr_sdf_query_forward / cnr_sdf_query_backward: outputs sdf [n, 1], then feat [n, F] (want_feat), then
+    grad = d sdf / d x [n, 3] (want_grad).  The backward is the library's complete first- and second-order SDF backward, run once with
+    whatever cotangents arrived; it is not itself differentiable (third order)."""
+
+    @staticmethod
+    def forward(ctx, binding, want_grad, want_feat, x, *params):
+        plist = [p.detach().contiguous() for p in params]
+        sdf, feat, grad, cbuf = binding.forward(x.detach(), plist, want_grad, want_feat, keep_ctx=True)
+        ctx.binding, ctx.want_grad, ctx.want_feat = binding, want_grad, want_feat
+        ctx.save_for_backward(x.detach(), cbuf, *plist)
+        ctx.set_materialize_grads(False)   # unused outputs arrive as None and go to the library as NULL
+        return tuple(t for t in (sdf, feat, grad) if t is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gouts):
+        binding, L = ctx.binding, ctx.binding.lib
+        x, cbuf, *plist = ctx.saved_tensors
+        gouts = list(gouts)
+        d_sdf = gouts.pop(0)
+        d_feat = gouts.pop(0) if ctx.want_feat else None
+        d_grad = gouts.pop(0) if ctx.want_grad else None
+        cont = lambda g: g.contiguous().float() if g is not None else None
+        d_sdf, d_feat, d_grad = cont(d_sdf), cont(d_feat), cont(d_grad)
+        n, dev = x.shape[0], x.device
+        need_x, need_p = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        d_x = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_x else None
+        dparams, flat, darr = [None] * len(plist), None, None
+        if need_p:
+            # one flat buffer of the sdf_network parameters in canonical order: a step with point losses only hands optim.flat_view_of_grads
+            # one buffer; when the step also renders, this backward runs first (its node is newer), autograd adopts these views as the sdf
+            # .grad tensors and adds the render's sdf gradients into them, while the colour / relight gradients stay in the render's buffer:
+            # flat_view_of_grads over all parameters is then None and the all-reduce takes its gathered-copy path (same values, one copy)
+            flat = torch.empty(sum(p.numel() for p in plist), dtype=torch.float32, device=dev)
+            off = 0
+            for i, p in enumerate(plist):
+                dparams[i] = flat[off:off + p.numel()].view(p.shape)
+                off += p.numel()
+            darr = C.cast(binding.param_array(dparams), C.POINTER(C.c_void_p))
+        if need_x or need_p:
+            wg = int(ctx.want_grad)
+            nb = L.lib.cnr_sdf_query_bwd_scratch_bytes(C.byref(binding.ccfg), n, wg)
+            scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+            rc = L.lib.cnr_sdf_query_backward(C.byref(binding.ccfg), binding.param_array(plist), _ptr(x), n, wg, _ptr(d_sdf), _ptr(d_feat),
+                                              _ptr(d_grad), _ptr(cbuf), cbuf.numel(), darr, _ptr(d_x), _ptr(scratch), nb, _stream_of(x))
+            L.check(rc, "cnr_sdf_query_backward")
+        res = (None, None, None, d_x) + tuple(d if need else None for d, need in zip(dparams, ctx.needs_input_grad[4:]))
+        del dparams, flat
+        return res
+
+
 class _SDFNet(nn.Module):
-    """Parameters of SDFNetwork with its geometric initialisation (fields.py:31-75)."""
+    """SDFNetwork (fields.py:12-115): its parameters with the geometric initialisation (fields.py:31-75), and its methods forward / sdf /
+    sdf_hidden_appearance / gradient evaluated by the library (cnr_sdf_query_*, differentiable to second order in the parameters and the
+    points).  The renderer attaches the library binding after construction."""
 
     def __init__(self, c: RenderConfig):
         super().__init__()
@@ -268,6 +394,77 @@ class _SDFNet(nn.Module):
                     b.zero_()
                     nn.init.normal_(w, 0.0, math.sqrt(2) / math.sqrt(out_dim))
             setattr(self, f"lin{l}", _wrap(w, b, c.sdf_weight_norm))
+        self._query = None   # _SdfQueryBinding, set by the renderer
+
+    # -- the reference's methods (fields.py:81-115) ------------------------------------------------------------------------------------------
+    def _query_params(self):
+        named = dict(self.named_parameters())
+        return [named[k] for k in self._query.names()[1]]
+
+    def _run(self, x, want_grad, want_feat):
+        """(sdf [n, 1], feat [n, F] or None, grad [n, 3] or None) at the float32 points x [n, 3], through the autograd function when a
+        gradient can flow, as a plain query otherwise; split into calls of at most max_points points."""
+        if self._query is None:
+            raise RuntimeError("sdf_network has no library binding (it is built by NeuSRenderer / ColorNeuSRenderer)")
+        q = self._query
+        params = self._query_params()
+        n, dev = x.shape[0], x.device
+        if n == 0:   # (the C ABI takes n_points > 0)
+            e = lambda w: torch.zeros(0, w, dtype=torch.float32, device=dev)
+            return e(1), (e(q.d_out - 1) if want_feat else None), (e(3) if want_grad else None)
+        track = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        step = q.max_points(want_grad)
+        parts = []
+        for s0 in range(0, n, step):
+            xs = x[s0:s0 + step]
+            if track:
+                outs = list(_SdfQueryFunction.apply(q, want_grad, want_feat, xs, *params))
+                parts.append((outs.pop(0), outs.pop(0) if want_feat else None, outs.pop(0) if want_grad else None))
+            else:
+                with torch.no_grad():
+                    parts.append(q.forward(xs.detach().contiguous(), [p.detach().contiguous() for p in params], want_grad, want_feat,
+                                           keep_ctx=False)[:3])
+        if len(parts) == 1:
+            return parts[0]
+        cat = lambda i: torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None
+        return cat(0), cat(1), cat(2)
+
+    @staticmethod
+    def _points(x):
+        return x.reshape(-1, 3).to(torch.float32).contiguous()
+
+    def forward(self, inputs):
+        """[n, d_out]: sdf (= h_top[0] / scale) followed by the d_out - 1 features (fields.py:81-96)."""
+        sdf, feat, _ = self._run(self._points(inputs), False, True)
+        return torch.cat([sdf, feat], dim=-1)
+
+    def sdf(self, x):
+        """[n, 1] (fields.py:98-99); without a gradient to form it is the library's plain sdf evaluation (cnr_sdf_eval)."""
+        x = self._points(x)
+        if self._query is not None and x.shape[0] > 0 and not (torch.is_grad_enabled() and
+                                                               (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return self._sdf_eval(x)
+        return self._run(x, False, False)[0]
+
+    def sdf_hidden_appearance(self, x):
+        return self.forward(x)
+
+    def gradient(self, x):
+        """[n, 1, 3]: d sdf / d x (fields.py:105-115), differentiable in the points and the parameters (the eikonal term's double
+        backward); like the reference it sets x.requires_grad."""
+        x.requires_grad_(True)
+        return self._run(self._points(x), True, False)[2].unsqueeze(1)
+
+    def _sdf_eval(self, x):
+        q, n = self._query, x.shape[0]
+        L = q.lib
+        params = [p.detach().contiguous() for p in self._query_params()]
+        out = torch.empty(n, 1, dtype=torch.float32, device=x.device)
+        nb = L.lib.cnr_sdf_eval_scratch_bytes(C.byref(q.ccfg), n)
+        scratch = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        rc = L.lib.cnr_sdf_eval(C.byref(q.ccfg), q.param_array(params), _ptr(x), n, 1.0, _ptr(out), _ptr(scratch), nb, _stream_of(x))
+        L.check(rc, "cnr_sdf_eval")
+        return out
 
 
 class _ColorNet(nn.Module):
@@ -334,6 +531,7 @@ class NeuSRenderer(nn.Module):
         self._lib_obj = None
         self._ccfg = _lib.c_config(rcfg)
         self._order = None
+        self.sdf_network._query = _SdfQueryBinding(library, rcfg)   # (a plain attribute: no child module, no state)
 
     # -- library plumbing -------------------------------------------------------------------------------------------
     @property

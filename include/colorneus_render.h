@@ -284,10 +284,35 @@ int cnr_sample_pdf_u(const float* bins, const float* weights, const float* u, in
 int cnr_up_sample(const float* rays_o, const float* rays_d, const float* z_vals /* [R][n] */, const float* sdf /* [R][n] */, int64_t n_rays,
                   int32_t n, int32_t n_importance, float inv_s, float* out /* [R][n_importance] */, void* stream);
 
-/* sdf_network.sdf(pts): out[i] = sign * sdf(pts[i]); extract_fields uses sign = -1 (NeuS.py:416) */
+/* sdf_network.sdf(pts): out[i] = sign * sdf(pts[i]); extract_fields uses sign = -1 (NeuS.py:416).  Here and in cnr_sdf_grid* only the
+ * sdf_network.* entries of params are read (the others may be NULL). */
 size_t cnr_sdf_eval_scratch_bytes(const cnr_config* cfg, int64_t n_points);
 int cnr_sdf_eval(const cnr_config* cfg, const float* const* params, const float* pts, int64_t n_points, float sign,
                  float* out, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- differentiable SDF point queries: sdf_network.forward / .sdf / .gradient (SDFNetwork, fields.py:81-115) at arbitrary points and their
+ * backward, through the render path's SDF chains and its first- and second-order SDF backward (the fused layer + weight-gradient launches).
+ *   forward : sdf[i] = h_top[0] / scale, feat[i][:] = h_top[1:] (F = sdf_d_out - 1), and with want_grad != 0 grad[i] = d sdf / d x in world
+ *             coordinates; sdf is required, feat may be NULL, grad is given iff want_grad.  ctx (cnr_sdf_query_ctx_bytes) keeps what the
+ *             backward reads; the backward only reads it, so it may run any number of times on one forward.
+ *   backward: cotangents d_sdf [n], d_feat [n][F], d_grad [n][3] (each may be NULL = zero; d_grad only after a forward with want_grad) ->
+ *             the gradients of the sdf_network.* entries of the canonical inventory in d_params (overwritten; the other entries are not
+ *             touched and may be NULL; d_params == NULL: no weight-gradient launches at all) and d_pts [n][3] (or NULL), the total cotangent
+ *             of the points: value path + the Hessian applied to d_grad.  want_grad = 1 needs a forward with want_grad = 1 (the forward tags the
+ *             context; on a mismatch every output of the backward is NaN -- nothing synchronises, so it cannot be an error code); a
+ *             want_grad = 0 backward takes either context.
+ * params: the canonical inventory (cnr_param_info); only its sdf_network.* entries are read, the others may be NULL.  n_points > 0.
+ * Internally the rows are padded to a multiple of 128 (padded rows at the origin with zero cotangents; nothing is written past row n of a
+ * caller's buffer).  Without a cotangent on the gradient the second-order half of the backward is skipped. */
+size_t cnr_sdf_query_ctx_bytes(const cnr_config* cfg, int64_t n_points, int32_t want_grad);
+size_t cnr_sdf_query_bwd_scratch_bytes(const cnr_config* cfg, int64_t n_points, int32_t want_grad);
+int cnr_sdf_query_forward(const cnr_config* cfg, const float* const* params, const float* pts /* [n][3] */, int64_t n_points, int32_t want_grad,
+                          float* sdf /* [n] */, float* feat /* [n][F] or NULL */, float* grad /* [n][3] iff want_grad */, void* ctx, size_t ctx_bytes,
+                          void* stream);
+int cnr_sdf_query_backward(const cnr_config* cfg, const float* const* params, const float* pts /* the forward's points */, int64_t n_points,
+                           int32_t want_grad, const float* d_sdf /* [n] or NULL */, const float* d_feat /* [n][F] or NULL */,
+                           const float* d_grad /* [n][3] or NULL */, const void* ctx, size_t ctx_bytes, float* const* d_params /* or NULL */,
+                           float* d_pts /* [n][3] or NULL */, void* scratch, size_t scratch_bytes, void* stream);
 
 /* extract_fields: u[x][y][z] = -sdf on linspace(bmin,bmax,res)^3 (NeuS.py:14-28); bmin/bmax are HOST floats */
 size_t cnr_sdf_grid_scratch_bytes(const cnr_config* cfg, int32_t resolution);
