@@ -266,6 +266,18 @@ struct Arena {
   }
 };
 
+// Lay out and check: layout_checked runs a layout function over a caller's buffer and refuses a buffer that is too small -- THE wording of that message;
+// layout_size is the dry run behind every *_bytes query of the ABI (the same layout function, so a query cannot disagree with its entry point).
+template <class Layout> static size_t layout_size(void* buf, Layout&& layout) {
+  Arena a(buf);
+  layout(a);
+  return a.off;
+}
+template <class Layout> static int layout_checked(const char* what, void* buf, size_t bytes, Layout&& layout) {
+  const size_t need = layout_size(buf, layout);
+  return need > bytes ? fail("%s too small: need %zu bytes, got %zu", what, need, bytes) : 0;
+}
+
 struct Ctx {   // forward-saved state
   // effective weights live in the Lin structs
   float *E, *AUX, *sdf, *featx, *hry, *CE0, *CES, *gcol, *relit, *eik_partial, *eik_sums;
@@ -303,6 +315,29 @@ static void layout_weights(Model& m, Arena& a) {
   for (auto& q : m.rel) place_lin(q, a);
 }
 
+// The weight operand of a layer launch over P rows: y = x W^T (fwd_gemm: W, its planes and row scales) or dx = dy W (bwd_gemm: the
+// transposed copies).  THE place where a Lin becomes LayerGemm fields; a call site sets only its input view, its epilogue and what differs.
+static LayerGemm fwd_gemm(const Lin& q, long P) {
+  LayerGemm g;
+  g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P;
+  return g;
+}
+static LayerGemm bwd_gemm(const Lin& q, long P) {   // (w_rows stays at its default: the launches take round_up(N, 32) rows of W^T)
+  LayerGemm g;
+  g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+  return g;
+}
+// ... and of the one-pass narrow backward (cnr_narrow_bwd.hip), which stages all kpad rows of the W^T planes
+static void narrow_bwd_weights(NarrowBwd& nb, const Lin& q) {
+  const LayerGemm t = bwd_gemm(q, 0);
+  nb.Wp = t.Wp; nb.wp_stride = t.wp_stride; nb.ldw = t.ldw; nb.w_rows = q.kpad; nb.wscale = t.wscale;
+}
+static View direct_view(const float* a, int lda) {
+  View v;
+  v.a = a; v.lda = lda;
+  return v;
+}
+
 // shapes the chain-fused forward of the ReLU stacks takes (cnr_chain_fwd.hip).  THE definition: relu_chains_fused below starts with this test (what it
 // checks after that are buffer pointers), and layout_ctx_infer decides by it that the forward-only layout needs no hidden-layer buffers.
 static bool relu_fused_shapes(const Model& m) {
@@ -330,116 +365,130 @@ static bool relu_fused_shapes(const Model& m) {
   return true;
 }
 
-// Forward-only layout (cnr_render_forward_only): the same buffers as layout_ctx for everything the forward kernels exchange, but nothing that
-// only the backward pass reads: two ping-pong buffers instead of the L - 1 saved V_l, no row scales, the hidden layers of the ReLU stacks
-// not at all when they run chain-fused (two ping-pong buffers + the relight y-layer's input otherwise), compact copies for the
-// early-termination compaction only where the per-layer chains need them (the chain-fused form reads rows through the index list).
-static void layout_ctx_infer(Model& m, long R, Arena& a, Ctx& x) {
-  const long P = R * m.M;
-  x.infer = true;
-  x.infer_fused = relu_fused_shapes(m) && be_relu_chain_fwd_enabled();
-  layout_weights(m, a);
+// ------------------------------------------------------------------------------------------------
+// The buffer groups that the context layouts share.  Every a.f() rounds to 256 bytes on its own, so the size of a layout does not depend on
+// the order of its groups; the training layouts (layout_ctx, layout_bwd) keep theirs fixed all the same, and with it every offset of the
+// timed path.
+// ------------------------------------------------------------------------------------------------
+// geometry of P points: the embedding, the aux rows [p g PE(view)], the sdf and the colour net's input rows [feat | aux | 0]
+static void place_geometry(const Model& m, long P, Arena& a, Ctx& x) {
   x.E = a.f((size_t)P * kEmb);
   x.AUX = a.f((size_t)P * kAux);
   x.sdf = a.f(P);
   x.ldfx = round_up(m.F + kAux, 16);
   x.featx = a.f((size_t)P * x.ldfx);
-  x.ldy = m.has_relight ? m.Hr + 16 : 0;
+}
+// the embedding cotangents of the gradient chain and the two per-point colours
+static void place_grad_colors(long P, Arena& a, Ctx& x) {
   x.CE0 = a.f((size_t)P * kEmb);
   x.CES = a.f((size_t)P * kEmb);
   x.gcol = a.f((size_t)P * 4);
   x.relit = a.f((size_t)P * 4);
+}
+// what a render keeps per ray, and the gradient / relight rows of callers that do not take them as outputs
+static void place_ray_state(const Model& m, long R, Arena& a, Ctx& x) {
   x.eik_partial = a.f((size_t)R * 2);
   x.eik_sums = a.f(64);
-  x.gbuf = a.f((size_t)P * 3);
-  x.delta_s = m.has_relight ? a.f((size_t)P * 3) : nullptr;
-  x.Z.resize(m.L); x.V.resize(m.L);
+  x.gbuf = a.f((size_t)R * m.M * 3);
+  x.delta_s = m.has_relight ? a.f((size_t)R * m.M * 3) : nullptr;
+}
+static void place_sdf_z(const Model& m, long P, Arena& a, Ctx& x) {
+  x.Z.resize(m.L);
   for (int l = 0; l < m.L; ++l) x.Z[l] = a.f((size_t)P * m.Hs);
-  float* vpp[2] = {m.L >= 2 ? a.f((size_t)P * m.Hs) : nullptr, m.L >= 3 ? a.f((size_t)P * m.Hs) : nullptr};
-  for (int l = 0; l + 1 < m.L; ++l) x.V[l] = vpp[l & 1];        // the gradient chain's launch l reads V[l] and writes V[l - 1]
-  if (m.L >= 1) x.V[m.L - 1] = nullptr;
+  x.ldztop = round_up(m.F + 1, 16);
+}
+// V[l] of the gradient chain: one buffer per layer where a backward pass reads them again, two ping-pong buffers otherwise (the chain's
+// launch l reads V[l] and writes V[l - 1]).  V[L - 1] stays null: it is the broadcast row W_top[0,:]/scale
+static void place_sdf_v(const Model& m, long P, bool saved, Arena& a, Ctx& x) {
+  x.V.assign(m.L, nullptr);
+  float* pp[2] = {nullptr, nullptr};
+  if (!saved && m.L >= 2) pp[0] = a.f((size_t)P * m.Hs);
+  if (!saved && m.L >= 3) pp[1] = a.f((size_t)P * m.Hs);
+  for (int l = 0; l + 1 < m.L; ++l) x.V[l] = saved ? a.f((size_t)P * m.Hs) : pp[l & 1];
+}
+static void place_sampler(const Model& m, long R, Arena& a, Ctx& x) {
+  const long Ps = R * m.S;
+  x.sE = a.f((size_t)Ps * kEmb);
+  x.sZa = a.f((size_t)Ps * m.Hs);
+  x.sZb = a.f((size_t)Ps * m.Hs);
+  x.s_sdf0 = a.f(Ps);
+  x.s_sdf = a.f((size_t)R * m.M);
+  x.s_newz = a.f((size_t)R * 64);
+  x.s_newsdf = a.f((size_t)R * 64);
+}
+// early-termination compaction: the index list with its per-ray counts / offsets and, where the per-layer chains run on the kept samples
+// (copies), compact copies of their inputs and outputs (the chain-fused form reads its rows through the index list)
+static void place_compaction(long R, long P, bool copies, Arena& a, Ctx& x) {
+  x.featx_c = copies ? a.f((size_t)P * x.ldfx) : nullptr;
+  x.aux_c = copies ? a.f((size_t)P * kAux) : nullptr;
+  x.gcol_c = copies ? a.f((size_t)P * 4) : nullptr;
+  x.relit_c = copies ? a.f((size_t)P * 4) : nullptr;
+  x.delta_c = copies ? a.f((size_t)P * 4) : nullptr;
+  x.p_idx = reinterpret_cast<int*>(a.f(P));
+  x.p_counts = reinterpret_cast<int*>(a.f(R));
+  x.p_offsets = reinterpret_cast<int*>(a.f(R + 1));
+}
+// per-point row scales rs[lo .. hi) of a stack of n launches (null elsewhere)
+static void place_row_scales(std::vector<float*>& rs, int n, int lo, int hi, long P, Arena& a) {
+  rs.assign(n, nullptr);
+  for (int l = lo; l < hi; ++l) rs[l] = a.f(P);
+}
+static void place_slack(Arena& a) { a.f(1024); }   // GEMM tiles may read (never use) a few columns past the last row of a buffer
+
+// Forward-only layout (cnr_render_forward_only): the same buffers as layout_ctx for everything the forward kernels exchange, but nothing that
+// only the backward pass reads: two ping-pong buffers instead of the L - 1 saved V_l, no row scales, the hidden layers of the ReLU stacks
+// not at all when they run chain-fused (two ping-pong buffers + the relight y-layer's input otherwise), compact copies for the
+// early-termination compaction only where the per-layer chains need them.
+static void layout_ctx_infer(Model& m, long R, Arena& a, Ctx& x) {
+  const long P = R * m.M;
+  x.infer = true;
+  x.infer_fused = relu_fused_shapes(m) && be_relu_chain_fwd_enabled();
+  layout_weights(m, a);
+  place_geometry(m, P, a, x);
+  x.ldy = m.has_relight ? m.Hr + 16 : 0;
+  place_grad_colors(P, a, x);
+  place_ray_state(m, R, a, x);
+  place_sdf_z(m, P, a, x);
+  place_sdf_v(m, P, false, a, x);
   x.HC.assign(m.NC - 1, nullptr);
   x.HR.assign(m.NR, nullptr);
   x.hry = nullptr;
-  x.featx_c = x.aux_c = x.gcol_c = x.relit_c = x.delta_c = nullptr;
   if (!x.infer_fused) {
     const int hw = m.Hc > m.Hr ? m.Hc : m.Hr;
     float* hpp[2] = {a.f((size_t)P * hw), a.f((size_t)P * hw)};
     x.hry = m.has_relight ? a.f((size_t)P * x.ldy) : nullptr;
     for (int l = 0; l + 1 < m.NC; ++l) x.HC[l] = hpp[l & 1];
     for (int i = 0; i < m.NR; ++i) x.HR[i] = (i == m.c.rel_y_in_layer - 1) ? x.hry : hpp[i & 1];
-    x.featx_c = a.f((size_t)P * x.ldfx);
-    x.aux_c = a.f((size_t)P * kAux);
-    x.gcol_c = a.f((size_t)P * 4);
-    x.relit_c = a.f((size_t)P * 4);
-    x.delta_c = a.f((size_t)P * 4);
   }
-  const long Ps = R * m.S;
-  x.sE = a.f((size_t)Ps * kEmb);
-  x.sZa = a.f((size_t)Ps * m.Hs);
-  x.sZb = a.f((size_t)Ps * m.Hs);
-  x.s_sdf0 = a.f(Ps);
-  x.s_sdf = a.f((size_t)R * m.M);
-  x.s_newz = a.f((size_t)R * 64);
-  x.s_newsdf = a.f((size_t)R * 64);
-  x.p_idx = reinterpret_cast<int*>(a.f(P));
-  x.p_counts = reinterpret_cast<int*>(a.f(R));
-  x.p_offsets = reinterpret_cast<int*>(a.f(R + 1));
-  x.ldztop = round_up(m.F + 1, 16);
+  place_sampler(m, R, a, x);
+  place_compaction(R, P, !x.infer_fused, a, x);
   x.rsY.assign(m.L + 1, nullptr); x.rsX1.assign(m.L, nullptr); x.rsC.assign(m.NC, nullptr); x.rsR.assign(m.NR, nullptr);
-  a.f(1024);   // slack (see layout_ctx)
+  place_slack(a);
 }
 
+// Training layout (cnr_render_forward / cnr_render_backward / cnr_sample_z).  The order of the groups is part of it: see above.
 static void layout_ctx(Model& m, long R, Arena& a, Ctx& x) {
   const long P = R * m.M;
   layout_weights(m, a);
-  x.E = a.f((size_t)P * kEmb);
-  x.AUX = a.f((size_t)P * kAux);
-  x.sdf = a.f(P);
-  x.ldfx = round_up(m.F + kAux, 16);
-  x.featx = a.f((size_t)P * x.ldfx);
+  place_geometry(m, P, a, x);
   x.ldy = m.has_relight ? m.Hr + 16 : 0;
   x.hry = m.has_relight ? a.f((size_t)P * x.ldy) : nullptr;
-  x.CE0 = a.f((size_t)P * kEmb);
-  x.CES = a.f((size_t)P * kEmb);
-  x.gcol = a.f((size_t)P * 4);
-  x.relit = a.f((size_t)P * 4);
-  x.eik_partial = a.f((size_t)R * 2);
-  x.eik_sums = a.f(64);
-  x.gbuf = a.f((size_t)P * 3);
-  x.delta_s = m.has_relight ? a.f((size_t)P * 3) : nullptr;
-  x.Z.resize(m.L); x.V.resize(m.L);
-  for (int l = 0; l < m.L; ++l) x.Z[l] = a.f((size_t)P * m.Hs);
-  for (int l = 0; l + 1 < m.L; ++l) x.V[l] = a.f((size_t)P * m.Hs);
-  if (m.L >= 1) x.V[m.L - 1] = nullptr;   // broadcast row W_top[0,:]/scale
+  place_grad_colors(P, a, x);
+  place_ray_state(m, R, a, x);
+  place_sdf_z(m, P, a, x);
+  place_sdf_v(m, P, true, a, x);
   x.HC.resize(m.NC - 1);
   for (int l = 0; l + 1 < m.NC; ++l) x.HC[l] = a.f((size_t)P * m.Hc);
   x.HR.resize(m.NR);
   for (int i = 0; i < m.NR; ++i) x.HR[i] = (i == m.c.rel_y_in_layer - 1) ? x.hry : a.f((size_t)P * m.Hr);
-  // sampler
-  const long Ps = R * m.S;
-  x.sE = a.f((size_t)Ps * kEmb);
-  x.sZa = a.f((size_t)Ps * m.Hs);
-  x.sZb = a.f((size_t)Ps * m.Hs);
-  x.s_sdf0 = a.f(Ps);
-  x.s_sdf = a.f((size_t)R * m.M);
-  x.s_newz = a.f((size_t)R * 64);
-  x.s_newsdf = a.f((size_t)R * 64);
-  x.featx_c = a.f((size_t)P * x.ldfx);
-  x.aux_c = a.f((size_t)P * kAux);
-  x.gcol_c = a.f((size_t)P * 4);
-  x.relit_c = a.f((size_t)P * 4);
-  x.delta_c = a.f((size_t)P * 4);
-  x.p_idx = reinterpret_cast<int*>(a.f(P));
-  x.p_counts = reinterpret_cast<int*>(a.f(R));
-  x.p_offsets = reinterpret_cast<int*>(a.f(R + 1));
-  x.ldztop = round_up(m.F + 1, 16);
-  x.rsY.assign(m.L + 1, nullptr); x.rsX1.assign(m.L, nullptr); x.rsC.assign(m.NC, nullptr); x.rsR.assign(m.NR, nullptr);
-  for (int l = 1; l <= m.L; ++l) x.rsY[l] = a.f(P);
-  for (int l = 1; l < m.L; ++l) x.rsX1[l] = a.f(P);
-  for (int l = 0; l + 1 < m.NC; ++l) x.rsC[l] = a.f(P);
-  for (int i = 0; i + 1 < m.NR; ++i) x.rsR[i] = a.f(P);
-  a.f(1024);   // slack: GEMM tiles may read (never use) a few columns past the last row of a buffer
+  place_sampler(m, R, a, x);
+  place_compaction(R, P, true, a, x);
+  // per-point row scales of GEMM operands that the weight-gradient GEMMs read again (see Ctx)
+  place_row_scales(x.rsY, m.L + 1, 1, m.L + 1, P, a);
+  place_row_scales(x.rsX1, m.L, 1, m.L, P, a);
+  place_row_scales(x.rsC, m.NC, 0, m.NC - 1, P, a);
+  place_row_scales(x.rsR, m.NR, 0, m.NR - 1, P, a);
+  place_slack(a);
 }
 
 struct Bwd {   // backward scratch
@@ -478,23 +527,61 @@ static bool head_bwd_static_ok(const Lin& q, int ldaux) {
   return !off && q.n <= 4 && q.k_int == 256 && q.ldw == 256 && (ldaux & 3) == 0;
 }
 
+// point chunks (slots) of a separate weight-gradient GEMM: one workgroup per CU as soon as every chunk has a few 16-point slabs
+static int dw_chunks(long P) {
+  const long nch = P / 128;
+  return nch < 1 ? 1 : nch > 256 ? 256 : (int)nch;
+}
+
 // the slot counts of the weight-gradient launches over P points
 static void bwd_slots(long P, Bwd& b) {
-  long nch = P / 128;   // one workgroup per CU as soon as every chunk has a few 16-point slabs
-  if (nch < 1) nch = 1;
-  if (nch > 256) nch = 256;
-  b.nchunk = (int)nch;
-  b.chunk_pts = round_up((int)((P + nch - 1) / nch), 16);
+  b.nchunk = dw_chunks(P);
+  b.chunk_pts = round_up((int)((P + b.nchunk - 1) / b.nchunk), 16);
   b.fslots = fdw_slots(P);
   b.cap_slots = b.fslots + (b.nchunk > b.fslots ? b.nchunk : b.fslots);   // a fused pair + either a second fused pair or a separate GEMM over nchunk slots
   const long ntiles = (P + 31) / 32, tpw = (ntiles + 255) / 256;
   b.cu_slots = ntiles > 0 ? (int)((ntiles + tpw - 1) / tpw) : 0;
 }
 
+// The SDF half of the backward scratch (sdf_backward: render backward and point-query backward), as the groups between which the render
+// layout places its own buffers.  grad_path = false (a query backward without a cotangent on the gradient) leaves out what only the
+// second-order sweep touches.
+static void place_sdf_seeds(long P, bool grad_path, const Ctx& x, Arena& a, Bwd& b) {
+  b.ZTOP = a.f((size_t)P * x.ldztop);
+  b.gbar_a = grad_path ? a.f((size_t)P * 4) : nullptr;
+}
+static void place_sdf_cotangents(long P, bool grad_path, Arena& a, Bwd& b) {
+  b.gbar_t = grad_path ? a.f((size_t)P * 4) : nullptr;
+  b.cbar = grad_path ? a.f((size_t)P * kEmb) : nullptr;
+  b.ebar0 = a.f((size_t)P * kEmb);
+  b.ebars = a.f((size_t)P * kEmb);
+  b.pbar = a.f((size_t)P * 4);
+}
+static void place_sdf_sweeps(const Model& m, long P, bool grad_path, Arena& a, Bwd& b) {
+  b.VB.assign(m.L, nullptr); b.Z2.resize(m.L);
+  for (int l = 0; l < m.L; ++l) { if (grad_path) b.VB[l] = a.f((size_t)P * m.Hs); b.Z2[l] = a.f((size_t)P * m.Hs); }
+}
+// the slot counts over P points and the partial-sum pool: every layer keeps its own [slots][npad][ldw] partial sums (+ bias column sums)
+// until one batched reduction at the end
+static void place_dw_pool(std::initializer_list<const std::vector<Lin>*> stacks, long P, Arena& a, Bwd& b) {
+  bwd_slots(P, b);
+  size_t tot = 0;
+  for (auto* st : stacks)
+    for (auto& q : *st) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); }
+  b.partial_floats = tot;
+  b.partial = a.f(tot);
+  b.partial_off = 0;
+  b.pending.clear();
+}
+// row scales of the SDF cotangents z-bar_l (value pairs) and, with the gradient path, q-bar_l (gradient-chain pairs)
+static void place_sdf_bwd_row_scales(const Model& m, long P, bool grad_path, Arena& a, Bwd& b) {
+  place_row_scales(b.rsX0, m.L + 1, 1, m.L + 1, P, a);
+  place_row_scales(b.rsY1, m.L + 1, 1, grad_path ? m.L : 1, P, a);
+}
+
 static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
   const long P = R * m.M;
-  b.ZTOP = a.f((size_t)P * x.ldztop);
-  b.gbar_a = a.f((size_t)P * 4);
+  place_sdf_seeds(P, true, x, a, b);
   // The 3-wide cotangents of the two heads: packed 16-byte rows when both heads take the streaming head kernel (it reads one float4 per point),
   // 16-float rows for the narrow GEMM launches otherwise (they read whole 64-byte rows: the compositor's backward then moves 58 KB per ray
   // where 12 KB are live)
@@ -509,14 +596,9 @@ static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
   b.drd_alpha = a.f((size_t)R * 3);
   b.dAUXc = a.f((size_t)P * kAux);
   b.dAUXr = a.f((size_t)P * kAux);
-  b.gbar_t = a.f((size_t)P * 4);
-  b.cbar = a.f((size_t)P * kEmb);
-  b.ebar0 = a.f((size_t)P * kEmb);
-  b.ebars = a.f((size_t)P * kEmb);
-  b.pbar = a.f((size_t)P * 4);
+  place_sdf_cotangents(P, true, a, b);
   b.dzparts = m.I == 0 ? a.f((size_t)P * 2) : nullptr;
-  b.VB.resize(m.L); b.Z2.resize(m.L);
-  for (int l = 0; l < m.L; ++l) { b.VB[l] = a.f((size_t)P * m.Hs); b.Z2[l] = a.f((size_t)P * m.Hs); }
+  place_sdf_sweeps(m, P, true, a, b);
   // The cotangents of the relight / colour hidden layers (steps 2 and 3 of the backward pass) are dead before the second-order sweep (step 5)
   // writes the first VB / Z2 buffer, and everything runs on one stream: they share that memory where the widths agree (7 KB per point less)
   b.D.resize(m.NR);
@@ -526,22 +608,10 @@ static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
   auto shared = [&](int k) { return (k & 1) ? b.Z2[k >> 1] : b.VB[k >> 1]; };
   for (int i = 0; i < m.NR; ++i) b.D[i] = share ? shared(i) : a.f((size_t)P * m.Hr);
   for (int l = 0; l + 1 < m.NC; ++l) b.DC[l] = share ? shared(m.NR + l) : a.f((size_t)P * m.Hc);
-  bwd_slots(P, b);
-  // every layer keeps its own [slots][npad][ldw] partial sums (+ bias column sums) until one batched reduction at the end
-  size_t tot = 0;
-  auto upd = [&](const Lin& q) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); };
-  for (auto& q : m.sdf) upd(q);
-  for (auto& q : m.col) upd(q);
-  for (auto& q : m.rel) upd(q);
-  b.partial_floats = tot;
-  b.partial = a.f(tot);
-  b.partial_off = 0;
-  b.pending.clear();
-  b.rsX0.assign(m.L + 1, nullptr); b.rsY1.assign(m.L + 1, nullptr);
-  for (int l = 1; l <= m.L; ++l) b.rsX0[l] = a.f(P);
-  for (int l = 1; l < m.L; ++l) b.rsY1[l] = a.f(P);
+  place_dw_pool({&m.sdf, &m.col, &m.rel}, P, a, b);
+  place_sdf_bwd_row_scales(m, P, true, a, b);
   b.rsD = a.f(P);
-  a.f(1024);   // slack (see layout_ctx)
+  place_slack(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -641,12 +711,10 @@ static void sdf_chain(const Model& m, long n, const float* E, float* const* Z, f
   if (feat_out && sdf_save_chain_fused(m, n, E, Z, sdf_out, feat_out, ld_feat, top_scale, rs, s)) return;
   for (int l = 0; l <= m.L; ++l) {
     const Lin& q = m.sdf[l];
-    LayerGemm g;
+    LayerGemm g = fwd_gemm(q, n);
     g.A = sdf_input_view(m, l, E, Z);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.K = q.k_int; g.P = n;
     if (rs && (l < m.L || feat_out)) g.rs_out = rs[l];
     if (l < m.L) {
-      g.N = q.n;
       g.E.kind = EK_STORE; g.E.n_out = q.n; g.E.bias = q.bias; g.E.o1 = Z[l]; g.E.ld1 = m.Hs;
       if (m.skip(l + 1)) { g.E.tail_src = E; g.E.ld_tail = kEmb; g.E.tail_n = m.emb; }   // next layer reads [h | e]
     } else if (feat_out) {
@@ -726,18 +794,17 @@ static void sdf_grad_chain(const Model& m, long P, const float* E, const float* 
     const Lin& q = m.sdf[l];
     if (l >= 1 && m.skip(l) && V[l - 1] && round_up(m.sdf[l - 1].n, 16) > m.sdf[l - 1].n)
       be_zero_cols(V[l - 1], m.Hs, m.sdf[l - 1].n, round_up(m.sdf[l - 1].n, 16), P, s);
-    LayerGemm g;
+    LayerGemm g = bwd_gemm(q, P);
     g.A.a = Z[l]; g.A.lda = m.Hs;
     if (l == m.L - 1) { g.A.kind = VK_SIGMUL_ROW; g.A.b = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; g.A.scale = inv_scale; }   // v_{L-1} = W_top[0,:]/scale
     else { g.A.kind = VK_SIGMUL; g.A.b = V[l]; g.A.ldb = m.Hs; }
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
     if (rs) g.rs_out = rs[l];
     if (l == 0) {
       g.E.kind = EK_STORE; g.E.n_out = m.emb; g.E.o1 = CE0; g.E.ld1 = kEmb;
       // the 39-column end of the chain as one streaming pass over z_0 / v_0 with the W^T planes in LDS (cnr_narrow_bwd.hip, its product-only form)
       NarrowBwd nb;
       nb.X = Z[0]; nb.ldx = m.Hs; nb.Xb = g.A.b; nb.ldxb = g.A.ldb; nb.P = P;
-      nb.Wp = q.Wtp; nb.wp_stride = (long)q.kpad * q.ldwt; nb.ldw = q.ldwt; nb.w_rows = q.kpad; nb.wscale = q.Wtps;
+      narrow_bwd_weights(nb, q);
       nb.dx = CE0; nb.lddx = kEmb; nb.ndx = m.emb;
       if (g.A.kind == VK_SIGMUL && g.A.scale == 1.0f && g.rs_out == nullptr && q.n == 256 && m.Hs == 256 && be_narrow_bwd_ok(nb)) { be_narrow_bwd(nb, s); continue; }
     } else if (m.skip(l)) {
@@ -758,6 +825,38 @@ static int top_skip(const Model& m) {   // the highest layer fed by a skip conne
 static bool has_skip(const Model& m) {
   for (int l = 1; l < m.L; ++l) if (m.skip(l)) return true;
   return false;
+}
+
+// E (and AUX[., 0:3] where the context has aux rows) of n explicit points, or of n lattice points from index `start` on when pts is null
+static void embed_points(const Model& m, const float* pts, long n, float* E, float* AUX, cnr_stream s, const float* bmin = nullptr,
+                         const float* bmax = nullptr, int res = 0, long start = 0) {
+  EmbedPts ep;
+  ep.pts = pts; ep.n = n; ep.res = res; ep.start = start;
+  for (int c = 0; c < 3; ++c) { ep.bmin[c] = bmin ? bmin[c] : 0.f; ep.bmax[c] = bmax ? bmax[c] : 0.f; }
+  ep.scale = m.c.sdf_scale; ep.multires = m.c.sdf_multires; ep.E = E; ep.AUX = AUX;
+  be_embed_pts(ep, s);
+}
+
+// The point pipeline on the P embedded points of a filled context: SDF value chain (sdf, feature rows into featx, Z[l]) -> analytic gradient
+// chain -> be_grad_finish (the gradient rows; g and, where asked, PE(view) into the aux rows).  Row scales are stored where the context
+// holds them (rsY / rsX1 entries that are not null), AUX is written where the context has it.
+struct PointOpts {
+  bool grad = true;             // false: the value chain alone
+  float* grad_out = nullptr;    // [P][3]
+  bool aux_to_featx = true;     // the aux row is copied behind the features (the colour net's input rows)
+  int neg_g_as_view = 0;        // vertex colouring: view_dirs = -g
+  int multires_view = 0;
+};
+static void point_pipeline(const Model& m, long P, const Ctx& x, const PointOpts& o, cnr_stream s) {
+  const float scale = m.c.sdf_scale;
+  { RangeScope r_("sdf value chain"); sdf_chain(m, P, x.E, x.Z.data(), x.sdf, x.featx, x.ldfx, 1.0f / scale, s, x.rsY.data()); }
+  if (!o.grad) return;
+  { RangeScope r_("sdf gradient chain"); sdf_grad_chain(m, P, x.E, x.Z.data(), x.V.data(), x.CE0, x.CES, s, x.rsX1.data()); }
+  GradFinish gf;
+  gf.featx = o.aux_to_featx ? x.featx : nullptr; gf.ldfx = o.aux_to_featx ? x.ldfx : 0; gf.F = m.F;
+  gf.P = P; gf.E = x.E; gf.ce0 = x.CE0; gf.ces = has_skip(m) ? x.CES + skip_off(m) : nullptr; gf.scale = scale; gf.multires = m.c.sdf_multires;
+  gf.grad_out = o.grad_out; gf.AUX = x.AUX; gf.neg_g_as_view = o.neg_g_as_view; gf.multires_view = o.multires_view;
+  be_grad_finish(gf, s);
 }
 
 static View color_input_view(const Model& m, int l, const Ctx& x) {
@@ -781,9 +880,8 @@ static bool head_fwd(const Lin& q, const LayerGemm& g, cnr_stream s) {
 static void color_chain(const Model& m, long P, const Ctx& x, cnr_stream s, const int* P_dev = nullptr) {
   for (int l = 0; l < m.NC; ++l) {
     const Lin& q = m.col[l];
-    LayerGemm g;
-    g.A = color_input_view(m, l, x);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P; g.P_dev = P_dev;
+    LayerGemm g = fwd_gemm(q, P);
+    g.A = color_input_view(m, l, x); g.P_dev = P_dev;
     g.E.bias = q.bias; g.E.n_out = q.n;
     if (!P_dev && (size_t)l < x.rsC.size()) g.rs_out = x.rsC[l];
     if (l + 1 < m.NC) { g.E.kind = EK_RELU; g.E.o1 = x.HC[l]; g.E.ld1 = m.Hc; }
@@ -807,17 +905,15 @@ static View relight_input_view(const Model& m, int i /* rl_mlp index, -1 = in_la
 static void relight_chain(const Model& m, long P, const Ctx& x, float* delta_out, cnr_stream s, const int* P_dev = nullptr) {
   {
     const Lin& q = m.rel[0];
-    LayerGemm g;
-    g.A = relight_input_view(m, -1, x);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P; g.P_dev = P_dev;
+    LayerGemm g = fwd_gemm(q, P);
+    g.A = relight_input_view(m, -1, x); g.P_dev = P_dev;
     g.E.kind = EK_RELU; g.E.bias = q.bias; g.E.n_out = q.n; g.E.o1 = x.HR[0]; g.E.ld1 = hr_ld(m, x, 0);
     be_layer_gemm(g, s);
   }
   for (int i = 0; i < m.NR; ++i) {
     const Lin& q = m.rel[1 + i];
-    LayerGemm g;
-    g.A = relight_input_view(m, i, x);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P; g.P_dev = P_dev;
+    LayerGemm g = fwd_gemm(q, P);
+    g.A = relight_input_view(m, i, x); g.P_dev = P_dev;
     g.E.bias = q.bias; g.E.n_out = q.n;
     if (!P_dev && (size_t)i < x.rsR.size()) g.rs_out = x.rsR[i];
     if (i + 1 < m.NR) { g.E.kind = EK_RELU; g.E.o1 = x.HR[i + 1]; g.E.ld1 = hr_ld(m, x, i + 1); }
@@ -899,6 +995,22 @@ static bool relu_chains_fused(const Model& m, long P, const Ctx& x, float* delta
   return be_relu_chain_fwd(c, s);
 }
 
+// Early termination, first half: the weights (they need only sdf and its gradient; the colour buffers hold nothing yet), per-ray counts of the
+// samples with weight >= eps, their offsets, and the gather pass -- pg arrives with what the caller's form of it takes (compact copies, or
+// outputs to zero for the dropped samples) and gets the index list here
+static void prune_select(const CompositeFwd& cf, float eps, const Ctx& x, PruneGather pg, cnr_stream s) {
+  CompositeFwd cw = cf;
+  cw.color = nullptr; cw.gcolor = nullptr; cw.delta = nullptr; cw.delta_ray_sum = nullptr;
+  be_composite_fwd(cw, s);
+  PruneCount pc; pc.weights = cf.weights; pc.R = cf.R; pc.M = cf.M; pc.eps = eps; pc.counts = x.p_counts;
+  be_prune_count(pc, s);
+  PruneScan ps; ps.counts = x.p_counts; ps.R = cf.R; ps.offsets = x.p_offsets;
+  be_prune_scan(ps, s);
+  pg.weights = cf.weights; pg.R = cf.R; pg.M = cf.M; pg.eps = eps; pg.offsets = x.p_offsets; pg.idx = x.p_idx;
+  pg.featx = x.featx; pg.ldfx = x.ldfx; pg.aux = x.AUX;
+  be_prune_gather(pg, s);
+}
+
 static int check_backend(const char* what) {
   char msg[256];
   if (be_check_last_error(msg, sizeof msg) != 0) return fail("%s: %s", what, msg);
@@ -914,10 +1026,9 @@ static int render_forward(const cnr_config* cfg, const float* const* params, con
   if (!params || !in || !out || !ctx) return fail("null argument");
   const long R = in->n_rays;
   if (R <= 0) return fail("n_rays must be positive");
-  Arena a(ctx);
   Ctx x;
-  if (infer) layout_ctx_infer(m, R, a, x); else layout_ctx(m, R, a, x);
-  if (a.off > ctx_bytes) return fail("%s buffer too small: need %zu bytes, got %zu", infer ? "scratch" : "context", a.off, ctx_bytes);
+  auto layout = [&](Arena& a) { if (infer) layout_ctx_infer(m, R, a, x); else layout_ctx(m, R, a, x); };
+  if (layout_checked(infer ? "scratch buffer" : "context buffer", ctx, ctx_bytes, layout)) return -1;
   if (!out->z_vals || !out->weights || !out->color_fine || !out->cdf_fine || !out->inside_sphere ||
       !out->weight_sum || !out->weight_max || !out->depth || !out->s_val || !out->gradient_error)
     return fail("missing output buffer");
@@ -942,13 +1053,9 @@ static int render_forward(const cnr_config* cfg, const float* const* params, con
   fs.o = in->rays_o; fs.d = in->rays_d; fs.z = out->z_vals; fs.R = R; fs.M = m.M; fs.sample_dist = 2.0f / (float)m.S;
   fs.scale = scale; fs.multires = m.c.sdf_multires; fs.multires_view = m.mv; fs.E = x.E; fs.AUX = x.AUX;
   be_fine_setup(fs, s);
-  { RangeScope r_("sdf value chain"); sdf_chain(m, P, x.E, x.Z.data(), x.sdf, x.featx, x.ldfx, 1.0f / scale, s, x.rsY.data()); }
-  { RangeScope r_("sdf gradient chain"); sdf_grad_chain(m, P, x.E, x.Z.data(), x.V.data(), x.CE0, x.CES, s, x.rsX1.data()); }
-  GradFinish gf;
-  gf.featx = x.featx; gf.ldfx = x.ldfx; gf.F = m.F;
-  gf.P = P; gf.E = x.E; gf.ce0 = x.CE0; gf.ces = has_skip(m) ? x.CES + skip_off(m) : nullptr; gf.scale = scale; gf.multires = m.c.sdf_multires;
-  gf.grad_out = g_out; gf.AUX = x.AUX; gf.neg_g_as_view = 0; gf.multires_view = m.mv;
-  be_grad_finish(gf, s);
+  PointOpts po;
+  po.grad_out = g_out; po.multires_view = m.mv;
+  point_pipeline(m, P, x, po, s);
   CompositeFwd cf;
   cf.o = in->rays_o; cf.d = in->rays_d; cf.z = out->z_vals; cf.R = R; cf.M = m.M; cf.sample_dist = 2.0f / (float)m.S;
   cf.sdf = x.sdf; cf.g = g_out;
@@ -962,34 +1069,23 @@ static int render_forward(const cnr_config* cfg, const float* const* params, con
   if (m.has_relight && out->delta_relight_ray_sum) { cf.delta = delta_out; cf.delta_ray_sum = out->delta_relight_ray_sum; }
 
   if (in->prune_eps > 0.0f && x.infer_fused) {
-    // early termination on the forward-only path: weights first (they need only sdf and its gradient), a ballot / popcount pass per ray builds
-    // the list of samples with weight >= eps (and zeroes the colour outputs of the others), and the chain-fused colour + relight launch reads
-    // its rows through that list and writes the kept samples' outputs in place -- no compact copies, no scatter
-    { CompositeFwd cw = cf; cw.color = nullptr; cw.gcolor = nullptr; cw.delta = nullptr; cw.delta_ray_sum = nullptr;   // weights only: the colour
-      be_composite_fwd(cw, s); }                                                                                       // buffers hold nothing yet
-    PruneCount pc; pc.weights = out->weights; pc.R = R; pc.M = m.M; pc.eps = in->prune_eps; pc.counts = x.p_counts;
-    be_prune_count(pc, s);
-    PruneScan ps; ps.counts = x.p_counts; ps.R = R; ps.offsets = x.p_offsets;
-    be_prune_scan(ps, s);
-    PruneGather pg; pg.weights = out->weights; pg.R = R; pg.M = m.M; pg.eps = in->prune_eps; pg.offsets = x.p_offsets; pg.idx = x.p_idx;
-    pg.featx = x.featx; pg.ldfx = x.ldfx; pg.featx_c = nullptr; pg.aux = x.AUX; pg.aux_c = nullptr;
+    // early termination on the forward-only path: a ballot / popcount pass per ray builds the list of samples with weight >= eps (and zeroes
+    // the colour outputs of the others), and the chain-fused colour + relight launch reads its rows through that list and writes the kept
+    // samples' outputs in place -- no compact copies, no scatter
+    PruneGather pg;
+    pg.featx_c = nullptr; pg.aux_c = nullptr;
     pg.zero_gcol = x.gcol; pg.zero_relit = m.has_relight ? x.relit : nullptr; pg.zero_delta = delta_out;
-    be_prune_gather(pg, s);
+    prune_select(cf, in->prune_eps, x, pg, s);
     if (!relu_chains_fused(m, P, x, delta_out, s, x.p_offsets + R, x.p_idx)) return fail("render_forward_only: the chain-fused colour / relight launch refused its shapes");
   } else if (in->prune_eps > 0.0f) {
-    // inference-only early termination: weights first (they need only sdf and its gradient), then the colour / relight networks
-    // on the compacted list of samples with weight >= eps, scattered back into zero-filled per-sample buffers
+    // inference-only early termination: the colour / relight networks on the compacted list of samples with weight >= eps, scattered
+    // back into zero-filled per-sample buffers
     be_memset_zero(x.gcol, (size_t)P * 4 * sizeof(float), s);
     be_memset_zero(x.relit, (size_t)P * 4 * sizeof(float), s);
     if (m.has_relight) be_memset_zero(out->delta_relight, (size_t)P * 3 * sizeof(float), s);
-    { CompositeFwd cw = cf; cw.color = nullptr; cw.gcolor = nullptr; cw.delta = nullptr; cw.delta_ray_sum = nullptr; be_composite_fwd(cw, s); }   // weights only
-    PruneCount pc; pc.weights = out->weights; pc.R = R; pc.M = m.M; pc.eps = in->prune_eps; pc.counts = x.p_counts;
-    be_prune_count(pc, s);
-    PruneScan ps; ps.counts = x.p_counts; ps.R = R; ps.offsets = x.p_offsets;
-    be_prune_scan(ps, s);
-    PruneGather pg; pg.weights = out->weights; pg.R = R; pg.M = m.M; pg.eps = in->prune_eps; pg.offsets = x.p_offsets; pg.idx = x.p_idx;
-    pg.featx = x.featx; pg.ldfx = x.ldfx; pg.featx_c = x.featx_c; pg.aux = x.AUX; pg.aux_c = x.aux_c;
-    be_prune_gather(pg, s);
+    PruneGather pg;
+    pg.featx_c = x.featx_c; pg.aux_c = x.aux_c;
+    prune_select(cf, in->prune_eps, x, pg, s);
     Ctx xc = x;   // the chains run on the compact buffers; only the device knows how many rows they hold
     xc.featx = x.featx_c; xc.AUX = x.aux_c; xc.gcol = x.gcol_c; xc.relit = x.relit_c;
     const int* kept = x.p_offsets + R;
@@ -1120,6 +1216,38 @@ static void flush_dw(Bwd& b, cnr_stream s) {
   b.pending.clear();
 }
 
+// Backward of one layer of a ReLU stack (relight rl_mlp, colour): g = the launch that forms the cotangent of the layer's input, d = its
+// weight-gradient pair (X = the output cotangent, Y = the forward input, sy = rs_in, the row scales the forward saved for that input).
+// A narrow head takes the streaming head kernel; otherwise the extra input columns of a 256 + few wide layer go to the strip launch and the
+// rest is one fused layer + weight-gradient launch where the shape allows, or a layer launch and a weight-gradient launch.
+// rev: walk direction of a fused launch, opposite to the launch that wrote this one's input (the head kernel walks upwards, then the
+// stack alternates).  head: the stack's top layer, whose cotangent rows are packed (b.ldtop != kTop) only for the head kernel.
+static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* rs_in, int rev, bool head, Bwd& b, const float* const* params,
+                           float* const* dP, cnr_stream s) {
+  if (head_bwd_ok(q, g)) { run_head_bwd(q, g, b, params, dP, s); return 0; }
+  if (head && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");   // (layout_bwd decides both from the same predicate)
+  const DwRegion r = take_region(q, b);
+  const bool strips = strip_bwd_ok(q, g, d);
+  StripBwd sb;
+  if (strips) sb = take_strips(q, g, d, r, b);
+  const int kmain = strips ? 256 : 0;
+  // layer launch + weight gradient in one launch where the shape allows (cnr_gemm_fdw.hip)
+  const bool fused = be_fdw_enabled() && fdw_shape_ok(g) && rs_in && q.npad == 256 && q.ldw <= 320;
+  if (fused) {
+    fused_into_region(q, g, d, rs_in, 0, r, 0, b, true, s, kmain, nullptr, rev);
+  } else {
+    if (q.n > 32) g.rs_out = b.rsD;
+    be_layer_gemm(g, s);
+    d.sx[0] = g.rs_out;
+    dw_into_region(q, d, r, 0, b.nchunk, g.P, true, s, kmain);
+  }
+  if (strips) be_strip_bwd(sb, s);
+  const int nslots = fused ? b.fslots : b.nchunk;
+  finish_region(q, r, nslots, nslots, b, params, dP);
+  if (strips) strip_columns_of_last_finish(b);
+  return 0;
+}
+
 // Steps 4-7 of the backward pass and the point cotangent of step 8: the complete first- and second-order backward of the SDF network, shared
 // by render_backward and cnr_sdf_query_backward (the render path issues the same launches with the same arguments in the same order as
 // before this was a function of its own).  Seeds: b.ZTOP (cotangent of the top layer's outputs [feat | sdf / scale | 0]) and b.gbar_a
@@ -1155,9 +1283,8 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
   // value-backward launch l; gradient-chain pair: the sweep launch l) or left to the separate weight-gradient GEMM of step 7
   auto sweep_gemm = [&](int l) {
     const Lin& q = m.sdf[l];
-    LayerGemm g;
+    LayerGemm g = fwd_gemm(q, P);
     g.A = qbar_view(l);
-    g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = P;
     g.E.kind = EK_SWEEP; g.E.n_out = q.n; g.E.z = x.Z[l]; g.E.ldz = m.Hs;
     if (l == m.L - 1) { g.E.v = m.sdf[m.L].W + (long)m.F * m.sdf[m.L].ldw; g.E.ldv = 0; g.E.vscale = inv_scale; }
     else { g.E.v = x.V[l]; g.E.ldv = m.Hs; }
@@ -1167,10 +1294,8 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
   };
   auto vback_gemm = [&](int l) {
     const Lin& q = m.sdf[l];
-    LayerGemm g;
-    if (l == m.L) { g.A.kind = VK_DIRECT; g.A.a = b.ZTOP; g.A.lda = x.ldztop; }
-    else { g.A.kind = VK_DIRECT; g.A.a = b.Z2[l]; g.A.lda = m.Hs; }
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+    LayerGemm g = bwd_gemm(q, P);
+    g.A = l == m.L ? direct_view(b.ZTOP, x.ldztop) : direct_view(b.Z2[l], m.Hs);
     g.E.kind = EK_VBACK; g.E.n_out = q.k_int; g.E.z = x.Z[l - 1]; g.E.ldz = m.Hs; g.E.o1 = b.Z2[l - 1]; g.E.ld1 = m.Hs;
     if (m.skip(l)) { g.E.scale = kInvSqrt2; g.E.split = m.sdf[l - 1].n; g.E.o2 = rays_grad ? b.ebars : nullptr; g.E.ld2 = kEmb; g.E.o2_off = skip_off(m);
                      g.E.o2_acc = l != top_skip(m);   // (the value backward runs from the top layer down: the highest skip layer stores, the others add)
@@ -1179,8 +1304,7 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
   };
   // value pair of layer l: X = zbar_l, Y = the layer's forward input
   auto value_pair = [&](int l, DwGemm& d) {
-    if (l == m.L) { d.X[0].kind = VK_DIRECT; d.X[0].a = b.ZTOP; d.X[0].lda = x.ldztop; }
-    else { d.X[0].kind = VK_DIRECT; d.X[0].a = b.Z2[l]; d.X[0].lda = m.Hs; }
+    d.X[0] = l == m.L ? direct_view(b.ZTOP, x.ldztop) : direct_view(b.Z2[l], m.Hs);
     d.Y[0] = sdf_input_view(m, l, x.E, x.Z.data());
     d.sx[0] = b.rsX0[l]; d.sy[0] = x.rsY[l];
   };
@@ -1216,7 +1340,7 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
     const Lin& q = m.sdf[0];
     nb0.X = b.Z2[0]; nb0.ldx = m.Hs; nb0.Y = x.E; nb0.ldy = kEmb; nb0.ky = q.k_int; nb0.P = P;
     if (rays_grad) {
-      nb0.Wp = q.Wtp; nb0.wp_stride = (long)q.kpad * q.ldwt; nb0.ldw = q.ldwt; nb0.w_rows = q.kpad; nb0.wscale = q.Wtps;
+      narrow_bwd_weights(nb0, q);
       nb0.dx = b.ebar0; nb0.lddx = kEmb; nb0.ndx = m.emb;
     }
     nb0.partial = sreg[0].part; nb0.ldk = q.ldw; nb0.colsum = sreg[0].csum;
@@ -1282,9 +1406,8 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
   if (use_nb0) be_narrow_bwd(nb0, s);
   else if (rays_grad) {
     const Lin& q = m.sdf[0];
-    LayerGemm g;
-    g.A.kind = VK_DIRECT; g.A.a = b.Z2[0]; g.A.lda = m.Hs;
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+    LayerGemm g = bwd_gemm(q, P);
+    g.A = direct_view(b.Z2[0], m.Hs);
     g.E.kind = EK_STORE; g.E.n_out = m.emb; g.E.o1 = b.ebar0; g.E.ld1 = kEmb;
     be_layer_gemm(g, s);
   }
@@ -1334,14 +1457,10 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
   if (in->prune_eps > 0.0f) return fail("cnr_render_backward: the forward pass ran with prune_eps > 0 (inference-only early termination)");
   const long R = in->n_rays;
   const long P = R * m.M;
-  Arena a(const_cast<void*>(ctx));
   Ctx x;
-  layout_ctx(m, R, a, x);
-  if (a.off > ctx_bytes) return fail("context buffer too small");
-  Arena sa(scratch);
   Bwd b;
-  layout_bwd(m, R, x, sa, b);
-  if (sa.off > scratch_bytes) return fail("backward scratch too small: need %zu bytes, got %zu", sa.off, scratch_bytes);
+  if (layout_checked("context buffer", const_cast<void*>(ctx), ctx_bytes, [&](Arena& a) { layout_ctx(m, R, a, x); })) return -1;
+  if (layout_checked("backward scratch", scratch, scratch_bytes, [&](Arena& a) { layout_bwd(m, R, x, a, b); })) return -1;
   const float scale = m.c.sdf_scale;
   const bool rays_out = gi->d_rays_o != nullptr || gi->d_rays_d != nullptr;
   if (rays_out && (!gi->d_rays_o || !gi->d_rays_d)) return fail("d_rays_o and d_rays_d must be given together");
@@ -1380,57 +1499,34 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
 
   be_range_pop(); be_range_push("relight chain backward");
   // ---- 2. relight chain backward
-  const bool fdw = be_fdw_enabled();   // layer launch + weight gradient in one launch where the shape allows (cnr_gemm_fdw.hip)
   if (m.has_relight) {
     const int y = m.c.rel_y_in_layer - 1;
     for (int i = m.NR - 1; i >= 0; --i) {
       const Lin& q = m.rel[1 + i];
       const float* dout = (i == m.NR - 1) ? b.dtop : b.D[i + 1];
       const int ldo = (i == m.NR - 1) ? b.ldtop : m.Hr;
-      LayerGemm g;
-      g.A.kind = VK_DIRECT; g.A.a = dout; g.A.lda = ldo;
-      g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+      LayerGemm g = bwd_gemm(q, P);
+      g.A = direct_view(dout, ldo);
       g.E.kind = EK_RELU_MASK; g.E.n_out = q.k_int; g.E.split = m.Hr; g.E.o1 = b.D[i]; g.E.ld1 = m.Hr;
       g.E.aux = x.HR[i]; g.E.ldaux = hr_ld(m, x, i); g.E.o2 = (i == y) ? b.gc_b : nullptr; g.E.ld2 = 4;
       DwGemm d;
       d.npairs = 1; d.P = P;
       d.X[0] = g.A; d.sy[0] = x.rsR[i];
       d.Y[0] = relight_input_view(m, i, x);
-      if (head_bwd_ok(q, g)) { run_head_bwd(q, g, b, params, dP, s); continue; }
-      if (i == m.NR - 1 && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");   // (layout_bwd decides both from the same predicate)
-      const DwRegion r = take_region(q, b);
-      const bool strips = strip_bwd_ok(q, g, d);
-      StripBwd sb;
-      if (strips) sb = take_strips(q, g, d, r, b);
-      const int kmain = strips ? 256 : 0;
-      if (fdw && fdw_shape_ok(g) && x.rsR[i] && q.npad == 256 && q.ldw <= 320) {
-        // (walk direction: opposite to the launch that wrote this one's input -- the head kernel walks upwards, then the chain alternates)
-        fused_into_region(q, g, d, x.rsR[i], 0, r, 0, b, true, s, kmain, nullptr, ((m.NR - 1 - i) & 1));
-        if (strips) be_strip_bwd(sb, s);
-        finish_region(q, r, b.fslots, b.fslots, b, params, dP);
-      } else {
-        if (q.n > 32) g.rs_out = b.rsD;
-        be_layer_gemm(g, s);
-        d.sx[0] = g.rs_out;
-        dw_into_region(q, d, r, 0, b.nchunk, P, true, s, kmain);
-        if (strips) be_strip_bwd(sb, s);
-        finish_region(q, r, b.nchunk, b.nchunk, b, params, dP);
-      }
-      if (strips) strip_columns_of_last_finish(b);
+      if (stack_layer_bwd(q, g, d, x.rsR[i], (m.NR - 1 - i) & 1, i == m.NR - 1, b, params, dP, s)) return -1;
     }
     {
       const Lin& q = m.rel[0];
-      LayerGemm g;
-      g.A.kind = VK_DIRECT; g.A.a = b.D[0]; g.A.lda = m.Hr;
-      g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+      LayerGemm g = bwd_gemm(q, P);
+      g.A = direct_view(b.D[0], m.Hr);
       g.E.kind = EK_STORE; g.E.n_out = q.k_int; g.E.o1 = b.dAUXr; g.E.ld1 = kAux;
       // one pass over D[0] for the cotangent of the layer's inputs, its weight gradient and its bias gradient (cnr_narrow_bwd.hip) ...
       NarrowBwd nb;
       nb.X = b.D[0]; nb.ldx = m.Hr; nb.Y = x.AUX; nb.ldy = kAux; nb.ky = q.k_int; nb.P = P;
-      nb.Wp = q.Wtp; nb.wp_stride = (long)q.kpad * q.ldwt; nb.ldw = q.ldwt; nb.w_rows = q.kpad; nb.wscale = q.Wtps;
+      narrow_bwd_weights(nb, q);
       nb.dx = b.dAUXr; nb.lddx = kAux; nb.ndx = q.k_int; nb.ldk = q.ldw;
       nb.partial = b.partial;   // (placeholder for the shape test; the region is taken below)
-      if (fdw && q.n == 256 && q.npad == 256 && m.Hr == 256 && be_narrow_bwd_ok(nb) && be_narrow_bwd_slots(P) <= region_slots(q, b)) {
+      if (be_fdw_enabled() && q.n == 256 && q.npad == 256 && m.Hr == 256 && be_narrow_bwd_ok(nb) && be_narrow_bwd_slots(P) <= region_slots(q, b)) {
         const DwRegion r = take_region(q, b);
         nb.partial = r.part; nb.colsum = r.csum;
         be_narrow_bwd(nb, s);
@@ -1455,9 +1551,8 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
     const Lin& q = m.col[l];
     const float* dout = (l == m.NC - 1) ? b.dctop : b.DC[l];
     const int ldo = (l == m.NC - 1) ? b.ldtop : m.Hc;
-    LayerGemm g;
-    g.A.kind = VK_DIRECT; g.A.a = dout; g.A.lda = ldo;
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = P;
+    LayerGemm g = bwd_gemm(q, P);
+    g.A = direct_view(dout, ldo);
     if (l > 0) {
       g.E.kind = EK_RELU_MASK; g.E.n_out = q.k_int; g.E.o1 = b.DC[l - 1]; g.E.ld1 = m.Hc; g.E.aux = x.HC[l - 1]; g.E.ldaux = m.Hc;
     } else {   // cotangent of [feat | aux]: feat part lands in ZTOP[., 0:F] (the sdf cotangent sits in column F), aux part in dAUXc
@@ -1469,26 +1564,7 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
     d.npairs = 1; d.P = P;
     d.X[0] = g.A; d.sy[0] = x.rsC[l];
     d.Y[0] = color_input_view(m, l, x);
-    if (head_bwd_ok(q, g)) { run_head_bwd(q, g, b, params, dP, s); continue; }
-    if (l == m.NC - 1 && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");
-    const DwRegion r = take_region(q, b);
-    const bool strips = strip_bwd_ok(q, g, d);
-    StripBwd sb;
-    if (strips) sb = take_strips(q, g, d, r, b);
-    const int kmain = strips ? 256 : 0;
-    if (fdw && fdw_shape_ok(g) && x.rsC[l] && q.npad == 256 && q.ldw <= 320) {
-      fused_into_region(q, g, d, x.rsC[l], 0, r, 0, b, true, s, kmain, nullptr, ((m.NC - 1 - l) & 1));
-      if (strips) be_strip_bwd(sb, s);
-      finish_region(q, r, b.fslots, b.fslots, b, params, dP);
-    } else {
-      if (q.n > 32) g.rs_out = b.rsD;
-      be_layer_gemm(g, s);
-      d.sx[0] = g.rs_out;
-      dw_into_region(q, d, r, 0, b.nchunk, P, true, s, kmain);
-      if (strips) be_strip_bwd(sb, s);
-      finish_region(q, r, b.nchunk, b.nchunk, b, params, dP);
-    }
-    if (strips) strip_columns_of_last_finish(b);
+    if (stack_layer_bwd(q, g, d, x.rsC[l], (m.NC - 1 - l) & 1, l == m.NC - 1, b, params, dP, s)) return -1;
   }
   be_range_pop(); be_range_push("sdf second-order sweep");
   SdfBwdArgs args;
@@ -1518,7 +1594,7 @@ static void layout_eval(Model& m, long chunk, Arena& a, EvalBuf& e) {
   e.E = a.f((size_t)chunk * kEmb);
   e.Za = a.f((size_t)chunk * m.Hs);
   e.Zb = a.f((size_t)chunk * m.Hs);
-  a.f(1024);
+  place_slack(a);
 }
 
 static int sdf_eval_impl(const cnr_config* cfg, const float* const* params, const float* pts, const float* bmin, const float* bmax,
@@ -1527,20 +1603,14 @@ static int sdf_eval_impl(const cnr_config* cfg, const float* const* params, cons
   if (build_model(cfg, m)) return -1;
   if (!params || !out || !scratch) return fail("null argument");
   const long chunk = n < kEvalChunk ? n : kEvalChunk;
-  Arena a(scratch);
   EvalBuf e;
-  layout_eval(m, chunk, a, e);
-  if (a.off > scratch_bytes) return fail("scratch too small: need %zu bytes, got %zu", a.off, scratch_bytes);
+  if (layout_checked("scratch", scratch, scratch_bytes, [&](Arena& a) { layout_eval(m, chunk, a, e); })) return -1;
   prep_all(m, params, s, true);   // (the SDF layers are all it runs: the other entries of params may be null)
   float* Zp[kMaxLayers];
   for (int l = 0; l < m.L; ++l) Zp[l] = (l & 1) ? e.Zb : e.Za;
   for (long start = 0; start < n; start += chunk) {
     const long cnt = (n - start) < chunk ? (n - start) : chunk;
-    EmbedPts ep;
-    ep.pts = pts ? pts + start * 3 : nullptr; ep.n = cnt; ep.res = res; ep.start = lattice_start + start;
-    for (int c = 0; c < 3; ++c) { ep.bmin[c] = bmin ? bmin[c] : 0.f; ep.bmax[c] = bmax ? bmax[c] : 0.f; }
-    ep.scale = m.c.sdf_scale; ep.multires = m.c.sdf_multires; ep.E = e.E; ep.AUX = nullptr;
-    be_embed_pts(ep, s);
+    embed_points(m, pts ? pts + start * 3 : nullptr, cnt, e.E, nullptr, s, bmin, bmax, res, lattice_start + start);
     sdf_chain(m, cnt, e.E, Zp, out + start, nullptr, 0, sign / m.c.sdf_scale, s);
   }
   return check_backend("sdf_eval");
@@ -1549,33 +1619,22 @@ static int sdf_eval_impl(const cnr_config* cfg, const float* const* params, cons
 static size_t eval_scratch_bytes(const cnr_config* cfg, long n) {
   Model m;
   if (build_model(cfg, m)) return 0;
-  Arena a(nullptr);
   EvalBuf e;
-  layout_eval(m, n < kEvalChunk ? n : kEvalChunk, a, e);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_eval(m, n < kEvalChunk ? n : kEvalChunk, a, e); });
 }
 
-// vertex colour: reuse the training context layout with R = chunk rays of M = 1... simpler: dedicated small layout
-struct VcBuf { Ctx x; };
+// vertex colour (cnr_vertex_color): the point pipeline and the colour stack on chunks of n points, nothing saved
 static void layout_vc(Model& m, long n, Arena& a, Ctx& x) {
   layout_weights(m, a);
-  x.E = a.f((size_t)n * kEmb);
-  x.AUX = a.f((size_t)n * kAux);
-  x.sdf = a.f(n);
-  x.ldfx = round_up(m.F + kAux, 16);
-  x.featx = a.f((size_t)n * x.ldfx);
+  place_geometry(m, n, a, x);
   x.hry = nullptr; x.ldy = 0;
-  x.CE0 = a.f((size_t)n * kEmb);
-  x.CES = a.f((size_t)n * kEmb);
-  x.gcol = a.f((size_t)n * 4);
-  x.relit = a.f((size_t)n * 4);   // reused as the [n][3] gradient buffer
-  x.Z.resize(m.L); x.V.resize(m.L);
-  for (int l = 0; l < m.L; ++l) x.Z[l] = a.f((size_t)n * m.Hs);
-  for (int l = 0; l + 1 < m.L; ++l) x.V[l] = a.f((size_t)n * m.Hs);
-  if (m.L >= 1) x.V[m.L - 1] = nullptr;
+  place_grad_colors(n, a, x);   // (relit serves as the [n][3] gradient buffer)
+  place_sdf_z(m, n, a, x);
+  place_sdf_v(m, n, true, a, x);
   x.HC.resize(m.NC - 1);
   for (int l = 0; l + 1 < m.NC; ++l) x.HC[l] = a.f((size_t)n * m.Hc);
-  a.f(1024);
+  x.rsY.assign(m.L + 1, nullptr); x.rsX1.assign(m.L, nullptr);
+  place_slack(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1588,10 +1647,10 @@ static void layout_vc(Model& m, long n, Arena& a, Ctx& x) {
 constexpr long kQueryTile = 128;
 static long query_rows(long n) { return (n + kQueryTile - 1) / kQueryTile * kQueryTile; }
 
-struct QueryBuf { Ctx x; int* tag = nullptr; float* pts = nullptr; float* feat = nullptr; int ldf = 0; };
-// the context: SDF weights, the tag (QueryIn), padded points, E, Z[l], the sdf / feature rows and the row scales rsY; with want_grad
-// BEHIND them V[l], CE0 / CES, the gradient rows and rsX1 -- so that a value-only backward finds the value-path buffers at the same
-// offsets whichever form the forward took
+struct QueryBuf { Ctx x; int* tag = nullptr; float* pts = nullptr; };
+// the context: SDF weights, the tag (QueryIn), padded points, E, Z[l], the sdf / feature rows (x.featx, without an aux part) and the row
+// scales rsY; with want_grad BEHIND them V[l], CE0 / CES, the gradient rows and rsX1 -- so that a value-only backward finds the value-path
+// buffers at the same offsets whichever form the forward took
 static void layout_query(Model& m, long P, bool want_grad, Arena& a, QueryBuf& q) {
   for (auto& l : m.sdf) place_lin(l, a);
   Ctx& x = q.x;
@@ -1599,65 +1658,44 @@ static void layout_query(Model& m, long P, bool want_grad, Arena& a, QueryBuf& q
   q.pts = a.f((size_t)P * 3);
   x.E = a.f((size_t)P * kEmb);
   x.sdf = a.f(P);
-  q.ldf = round_up(m.F, 16);
-  q.feat = a.f((size_t)P * q.ldf);
-  x.Z.resize(m.L); x.V.assign(m.L, nullptr);
-  for (int l = 0; l < m.L; ++l) x.Z[l] = a.f((size_t)P * m.Hs);
-  x.ldztop = round_up(m.F + 1, 16);
-  x.rsY.assign(m.L + 1, nullptr); x.rsX1.assign(m.L, nullptr);
-  for (int l = 1; l <= m.L; ++l) x.rsY[l] = a.f(P);
+  x.ldfx = round_up(m.F, 16);
+  x.featx = a.f((size_t)P * x.ldfx);
+  place_sdf_z(m, P, a, x);
+  place_row_scales(x.rsY, m.L + 1, 1, m.L + 1, P, a);
   x.AUX = want_grad ? a.f((size_t)P * kAux) : nullptr;   // (be_grad_finish also writes g into AUX[., 3:6]; nothing reads it here)
   x.gbuf = want_grad ? a.f((size_t)P * 3) : nullptr;
   x.CE0 = want_grad ? a.f((size_t)P * kEmb) : nullptr;
   x.CES = want_grad ? a.f((size_t)P * kEmb) : nullptr;
-  if (want_grad) for (int l = 0; l + 1 < m.L; ++l) x.V[l] = a.f((size_t)P * m.Hs);
-  if (want_grad) for (int l = 1; l < m.L; ++l) x.rsX1[l] = a.f(P);
-  a.f(1024);   // slack (see layout_ctx)
+  x.V.assign(m.L, nullptr);
+  if (want_grad) place_sdf_v(m, P, true, a, x);
+  place_row_scales(x.rsX1, m.L, 1, want_grad ? m.L : 1, P, a);
+  place_slack(a);
 }
 
-// the backward scratch: the SDF part of layout_bwd (seeds, second-order and value cotangents, the partial-sum pool of the SDF layers)
 static void layout_query_bwd(const Model& m, long P, bool grad_path, const Ctx& x, Arena& a, Bwd& b) {
-  b.ZTOP = a.f((size_t)P * x.ldztop);
-  b.gbar_a = grad_path ? a.f((size_t)P * 4) : nullptr;
-  b.gbar_t = grad_path ? a.f((size_t)P * 4) : nullptr;
-  b.cbar = grad_path ? a.f((size_t)P * kEmb) : nullptr;
-  b.ebar0 = a.f((size_t)P * kEmb);
-  b.ebars = a.f((size_t)P * kEmb);
-  b.pbar = a.f((size_t)P * 4);
-  b.VB.assign(m.L, nullptr); b.Z2.resize(m.L);
-  for (int l = 0; l < m.L; ++l) { if (grad_path) b.VB[l] = a.f((size_t)P * m.Hs); b.Z2[l] = a.f((size_t)P * m.Hs); }
-  bwd_slots(P, b);
-  size_t tot = 0;
-  for (auto& q : m.sdf) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); }
-  b.partial_floats = tot;
-  b.partial = a.f(tot);
-  b.partial_off = 0;
-  b.pending.clear();
-  b.rsX0.assign(m.L + 1, nullptr); b.rsY1.assign(m.L + 1, nullptr);
-  for (int l = 1; l <= m.L; ++l) b.rsX0[l] = a.f(P);
-  if (grad_path) for (int l = 1; l < m.L; ++l) b.rsY1[l] = a.f(P);
+  place_sdf_seeds(P, grad_path, x, a, b);
+  place_sdf_cotangents(P, grad_path, a, b);
+  place_sdf_sweeps(m, P, grad_path, a, b);
+  place_dw_pool({&m.sdf}, P, a, b);
+  place_sdf_bwd_row_scales(m, P, grad_path, a, b);
   b.rsD = nullptr;
-  a.f(1024);   // slack (see layout_ctx)
+  place_slack(a);
 }
 
 static size_t query_ctx_bytes(const cnr_config* cfg, long n, bool want_grad) {
   Model m;
   if (build_model(cfg, m) || n <= 0) return 0;
-  Arena a(nullptr);
   QueryBuf q{};
-  layout_query(m, query_rows(n), want_grad, a, q);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_query(m, query_rows(n), want_grad, a, q); });
 }
 
 static size_t query_bwd_scratch_bytes(const cnr_config* cfg, long n, bool want_grad) {
   Model m;
   if (build_model(cfg, m) || n <= 0) return 0;
-  Arena a(nullptr), sa(nullptr);
   QueryBuf q{};
-  layout_query(m, query_rows(n), want_grad, a, q);
   Bwd b{};
-  layout_query_bwd(m, query_rows(n), want_grad, q.x, sa, b);
-  return sa.off;
+  layout_size(nullptr, [&](Arena& a) { layout_query(m, query_rows(n), want_grad, a, q); });
+  return layout_size(nullptr, [&](Arena& a) { layout_query_bwd(m, query_rows(n), want_grad, q.x, a, b); });
 }
 
 static int sdf_query_forward(const cnr_config* cfg, const float* const* params, const float* pts, long n, bool want_grad, float* sdf, float* feat,
@@ -1668,34 +1706,21 @@ static int sdf_query_forward(const cnr_config* cfg, const float* const* params, 
   if (n <= 0) return fail("n_points must be positive");
   if (want_grad != (grad != nullptr)) return fail("the grad buffer is given iff want_grad");
   const long P = query_rows(n);
-  Arena a(ctx);
   QueryBuf q{};
-  layout_query(m, P, want_grad, a, q);
-  if (a.off > ctx_bytes) return fail("context buffer too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  if (layout_checked("context buffer", ctx, ctx_bytes, [&](Arena& a) { layout_query(m, P, want_grad, a, q); })) return -1;
   Ctx& x = q.x;
-  const float scale = m.c.sdf_scale;
   RangeScope range_("sdf query forward");
   prep_all(m, params, s, true);
   QueryIn qi;
   qi.n = n; qi.P = P; qi.pts = pts; qi.out = q.pts; qi.tag = q.tag; qi.tag_value = kQueryCtxTag + (want_grad ? 1 : 0);
   be_query_in(qi, s);
-  EmbedPts ep;
-  ep.pts = q.pts; ep.n = P; ep.res = 0; ep.start = 0;
-  for (int c = 0; c < 3; ++c) { ep.bmin[c] = 0.f; ep.bmax[c] = 0.f; }
-  ep.scale = scale; ep.multires = m.c.sdf_multires; ep.E = x.E; ep.AUX = x.AUX;
-  be_embed_pts(ep, s);
-  sdf_chain(m, P, x.E, x.Z.data(), x.sdf, q.feat, q.ldf, 1.0f / scale, s, x.rsY.data());
-  if (want_grad) {
-    sdf_grad_chain(m, P, x.E, x.Z.data(), x.V.data(), x.CE0, x.CES, s, x.rsX1.data());
-    GradFinish gf;
-    gf.P = P; gf.E = x.E; gf.ce0 = x.CE0; gf.ces = has_skip(m) ? x.CES + skip_off(m) : nullptr; gf.scale = scale; gf.multires = m.c.sdf_multires;
-    gf.grad_out = x.gbuf; gf.AUX = x.AUX; gf.neg_g_as_view = 0; gf.multires_view = 0;
-    gf.featx = nullptr; gf.ldfx = 0; gf.F = m.F;
-    be_grad_finish(gf, s);
-  }
+  embed_points(m, q.pts, P, x.E, x.AUX, s);
+  PointOpts po;
+  po.grad = want_grad; po.grad_out = x.gbuf; po.aux_to_featx = false;   // (the feature rows have no aux part here)
+  point_pipeline(m, P, x, po, s);
   QueryOut qo;
-  qo.n = n; qo.F = m.F; qo.ldf = q.ldf; qo.ldg = 3;
-  qo.sdf_in = x.sdf; qo.feat_in = q.feat; qo.g_in = x.gbuf;
+  qo.n = n; qo.F = m.F; qo.ldf = x.ldfx; qo.ldg = 3;
+  qo.sdf_in = x.sdf; qo.feat_in = x.featx; qo.g_in = x.gbuf;
   qo.sdf = sdf; qo.feat = feat; qo.g = want_grad ? grad : nullptr;
   be_query_out(qo, s);
   return check_backend("sdf_query_forward");
@@ -1710,16 +1735,12 @@ static int sdf_query_backward(const cnr_config* cfg, const float* const* params,
   if (n <= 0) return fail("n_points must be positive");
   if (d_grad && !want_grad) return fail("d_grad needs a forward with want_grad");
   const long P = query_rows(n);
-  Arena a(const_cast<void*>(ctx));
   QueryBuf q{};
-  layout_query(m, P, want_grad, a, q);
-  if (a.off > ctx_bytes) return fail("context buffer too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  if (layout_checked("context buffer", const_cast<void*>(ctx), ctx_bytes, [&](Arena& a) { layout_query(m, P, want_grad, a, q); })) return -1;
   // no cotangent on the gradient: the second-order half of the backward is identically zero and is not run
   const bool grad_path = want_grad && d_grad != nullptr;
-  Arena sa(scratch);
   Bwd b{};
-  layout_query_bwd(m, P, grad_path, q.x, sa, b);
-  if (sa.off > scratch_bytes) return fail("backward scratch too small: need %zu bytes, got %zu", sa.off, scratch_bytes);
+  if (layout_checked("backward scratch", scratch, scratch_bytes, [&](Arena& a) { layout_query_bwd(m, P, grad_path, q.x, a, b); })) return -1;
   if (!d_params && !d_pts) return 0;
   RangeScope range_("sdf query backward");
   QuerySeed qs;
@@ -1747,8 +1768,11 @@ static int sdf_query_backward(const cnr_config* cfg, const float* const* params,
 // ------------------------------------------------------------------------------------------------
 struct LinearOp { Lin q; int ldx = 0, ldy = 0; float *xp = nullptr, *yp = nullptr, *gp = nullptr, *dxp = nullptr; float* part = nullptr; int nchunk = 1; };
 
-static int linear_setup(long n, int k, int n_out, bool backward, Arena& a, LinearOp& op) {
+static int linear_check(long n, int k, int n_out) {
   if (n <= 0 || k < 1 || n_out < 1 || k > 4096 || n_out > 4096) return fail("linear: need n > 0, 1 <= k, n_out <= 4096");
+  return 0;
+}
+static void layout_linear(long n, int k, int n_out, bool backward, Arena& a, LinearOp& op) {
   Lin& q = op.q;
   q.n = n_out; q.k_ref = k; identity_seg(q); q.finish_dims(); q.wn = false;
   place_lin(q, a);
@@ -1758,14 +1782,10 @@ static int linear_setup(long n, int k, int n_out, bool backward, Arena& a, Linea
   if (backward) {
     op.gp = a.f((size_t)n * op.ldy);
     op.dxp = a.f((size_t)n * op.ldx);
-    long nch = n / 128;
-    if (nch < 1) nch = 1;
-    if (nch > 256) nch = 256;
-    op.nchunk = (int)nch;
+    op.nchunk = dw_chunks(n);
     op.part = a.f(round_up_sz((size_t)op.nchunk * q.npad * q.ldw, 64) + round_up_sz((size_t)op.nchunk * q.npad, 64));
   }
-  a.f(1024);
-  return 0;
+  place_slack(a);
 }
 
 static void linear_prep(LinearOp& op, const float* W, const float* b, cnr_stream s) {
@@ -1861,7 +1881,7 @@ static void layout_nerf(NerfModel& m, long n, Arena& a, NerfCtx& x) {
   x.dist = a.f(n);
   x.H.resize(m.D);
   for (int i = 0; i < m.D; ++i) x.H[i] = (i == m.skip_at) ? x.XH : a.f((size_t)n * m.W);
-  a.f(1024);
+  place_slack(a);
 }
 static int nerf_h_ld(const NerfModel& m, const NerfCtx& x, int i) { return i == m.skip_at ? x.ldxh : m.W; }
 static void nerf_prep(NerfModel& m, const float* const* params, cnr_stream s) {
@@ -1882,13 +1902,6 @@ static void nerf_prep(NerfModel& m, const float* const* params, cnr_stream s) {
   be_prep_weights(pw.data(), (int)pw.size(), s);
   be_split_planes_many(sj.data(), (int)sj.size(), s);
 }
-static LayerGemm nerf_fwd_gemm(const Lin& q, const float* in, int ld_in, long n) {
-  LayerGemm g;
-  g.A.kind = VK_DIRECT; g.A.a = in; g.A.lda = ld_in;
-  g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = n;
-  g.E.bias = q.bias; g.E.n_out = q.n;
-  return g;
-}
 static int background_forward(const cnr_nerf_config* cfg, const float* const* params, const float* rays_o, const float* rays_d, const float* z_feed,
                               long R, int MF, float sample_dist, float* alpha, float* color, void* ctx, size_t ctx_bytes, cnr_stream s) {
   NerfModel m;
@@ -1896,10 +1909,8 @@ static int background_forward(const cnr_nerf_config* cfg, const float* const* pa
   if (!params || !rays_o || !rays_d || !z_feed || !alpha || !color || !ctx) return fail("null argument");
   if (R <= 0 || MF < 1 || MF > kMaxRaySamples) return fail("background: n_rays > 0, 1 <= samples per ray <= %d", kMaxRaySamples);
   const long n = R * MF;
-  Arena a(ctx);
   NerfCtx x;
-  layout_nerf(m, n, a, x);
-  if (a.off > ctx_bytes) return fail("background context too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  if (layout_checked("background context", ctx, ctx_bytes, [&](Arena& a) { layout_nerf(m, n, a, x); })) return -1;
   nerf_prep(m, params, s);
   BgEmbed e;
   e.o = rays_o; e.d = rays_d; e.z_feed = z_feed; e.R = R; e.MF = MF; e.sample_dist = sample_dist; e.multires = cfg->multires; e.multires_view = cfg->multires_view;
@@ -1907,24 +1918,29 @@ static int background_forward(const cnr_nerf_config* cfg, const float* const* pa
   be_bg_embed(e, s);
   for (int i = 0; i < m.D; ++i) {
     const Lin& q = m.pts[i];
-    LayerGemm g = nerf_fwd_gemm(q, i == 0 ? x.E : x.H[i - 1], i == 0 ? x.lde : nerf_h_ld(m, x, i - 1), n);
-    g.E.kind = EK_RELU; g.E.o1 = x.H[i]; g.E.ld1 = nerf_h_ld(m, x, i);
+    LayerGemm g = fwd_gemm(q, n);
+    g.A = i == 0 ? direct_view(x.E, x.lde) : direct_view(x.H[i - 1], nerf_h_ld(m, x, i - 1));
+    g.E.kind = EK_RELU; g.E.bias = q.bias; g.E.n_out = q.n; g.E.o1 = x.H[i]; g.E.ld1 = nerf_h_ld(m, x, i);
     be_layer_gemm(g, s);
   }
   const float* hl = x.H[m.D - 1];
   const int ldh = nerf_h_ld(m, x, m.D - 1);
   {
-    LayerGemm g = nerf_fwd_gemm(m.alpha, hl, ldh, n);
-    g.Wp = nullptr; g.E.kind = EK_STORE; g.E.o1 = x.dens; g.E.ld1 = 1;
+    LayerGemm g = fwd_gemm(m.alpha, n);
+    g.A = direct_view(hl, ldh); g.Wp = nullptr;
+    g.E.kind = EK_STORE; g.E.bias = m.alpha.bias; g.E.n_out = m.alpha.n; g.E.o1 = x.dens; g.E.ld1 = 1;
     be_layer_gemm(g, s);
-    LayerGemm f = nerf_fwd_gemm(m.feat, hl, ldh, n);
-    f.E.kind = EK_STORE; f.E.o1 = x.FV; f.E.ld1 = x.ldfv;
+    LayerGemm f = fwd_gemm(m.feat, n);
+    f.A = direct_view(hl, ldh);
+    f.E.kind = EK_STORE; f.E.bias = m.feat.bias; f.E.n_out = m.feat.n; f.E.o1 = x.FV; f.E.ld1 = x.ldfv;
     be_layer_gemm(f, s);
-    LayerGemm v = nerf_fwd_gemm(m.view, x.FV, x.ldfv, n);
-    v.E.kind = EK_RELU; v.E.o1 = x.HV; v.E.ld1 = m.W / 2;
+    LayerGemm v = fwd_gemm(m.view, n);
+    v.A = direct_view(x.FV, x.ldfv);
+    v.E.kind = EK_RELU; v.E.bias = m.view.bias; v.E.n_out = m.view.n; v.E.o1 = x.HV; v.E.ld1 = m.W / 2;
     be_layer_gemm(v, s);
-    LayerGemm c = nerf_fwd_gemm(m.rgb, x.HV, m.W / 2, n);
-    c.Wp = nullptr; c.E.kind = EK_SIGMOID; c.E.o1 = color; c.E.ld1 = 3;
+    LayerGemm c = fwd_gemm(m.rgb, n);
+    c.A = direct_view(x.HV, m.W / 2); c.Wp = nullptr;
+    c.E.kind = EK_SIGMOID; c.E.bias = m.rgb.bias; c.E.n_out = m.rgb.n; c.E.o1 = color; c.E.ld1 = 3;
     be_layer_gemm(c, s);
   }
   BgAlpha ba;
@@ -1939,14 +1955,13 @@ static void layout_nerf_bwd(NerfModel& m, const NerfCtx& x, long n, Arena& a, Ne
   b.T = a.f((size_t)n * m.W); b.dEs = m.skip_at >= 0 ? a.f((size_t)n * x.lde) : nullptr; b.dE0 = a.f((size_t)n * x.lde); b.dp = a.f((size_t)n * 8);
   b.DZ.resize(m.D);
   for (int i = 0; i < m.D; ++i) b.DZ[i] = a.f((size_t)n * m.W);
-  long nch = n / 128; if (nch < 1) nch = 1; if (nch > 256) nch = 256;
-  b.nchunk = (int)nch;
+  b.nchunk = dw_chunks(n);
   std::vector<Lin*> all;
   nerf_layers(m, all);
   size_t tot = 0;
   for (Lin* q : all) tot += round_up_sz((size_t)b.nchunk * q->npad * q->ldw, 64) + round_up_sz((size_t)b.nchunk * q->npad, 64);
   b.part_floats = tot; b.part = a.f(tot);
-  a.f(1024);
+  place_slack(a);
 }
 // weight + bias gradient of one background layer: dW = sum_pt X (x) Y, db = column sums of X; queued for one batched finish
 static void nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int ldy, long n, NerfBwd& b, size_t& off, const float* const* params,
@@ -1954,7 +1969,7 @@ static void nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int l
   float* part = b.part + off; off += round_up_sz((size_t)b.nchunk * q.npad * q.ldw, 64);
   float* csum = b.part + off; off += round_up_sz((size_t)b.nchunk * q.npad, 64);
   DwGemm d;
-  d.npairs = 1; d.P = n; d.X[0].kind = VK_DIRECT; d.X[0].a = X; d.X[0].lda = ldx; d.Y[0].kind = VK_DIRECT; d.Y[0].a = Y; d.Y[0].lda = ldy;
+  d.npairs = 1; d.P = n; d.X[0] = direct_view(X, ldx); d.Y[0] = direct_view(Y, ldy);
   d.N = q.n; d.K = q.k_int; d.nchunk = b.nchunk; d.chunk_pts = round_up((int)((n + b.nchunk - 1) / b.nchunk), 16);
   d.partial = part; d.Npad = q.npad; d.ldk = q.ldw; d.colsum = csum; d.split_f16 = false;
   be_dw_gemm(d, s);
@@ -1965,13 +1980,6 @@ static void nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int l
   f.dg = nullptr; f.dv = dP[q.p_v]; f.db = dP[q.p_b]; f.row_rot = 0;
   pend.push_back(f);
 }
-static LayerGemm nerf_bwd_gemm(const Lin& q, const float* dout, int ldo, long n) {
-  LayerGemm g;
-  g.A.kind = VK_DIRECT; g.A.a = dout; g.A.lda = ldo;
-  g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = n;
-  g.E.n_out = q.k_int;
-  return g;
-}
 static int background_backward(const cnr_nerf_config* cfg, const float* const* params, const float* rays_o, const float* rays_d, const float* z_feed,
                                long R, int MF, float sample_dist, const void* ctx, size_t ctx_bytes, const float* color, const float* d_alpha,
                                const float* d_color, float* const* dP, float* d_rays_o, float* d_rays_d, float* d_z_feed, void* scratch,
@@ -1980,14 +1988,10 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   if (build_nerf(cfg, m)) return -1;
   if (!params || !rays_o || !rays_d || !z_feed || !ctx || !color || !dP || !d_rays_o || !d_rays_d || !d_z_feed || !scratch) return fail("null argument");
   const long n = R * MF;
-  Arena a(const_cast<void*>(ctx));
   NerfCtx x;
-  layout_nerf(m, n, a, x);
-  if (a.off > ctx_bytes) return fail("background context too small");
-  Arena sa(scratch);
   NerfBwd b;
-  layout_nerf_bwd(m, x, n, sa, b);
-  if (sa.off > scratch_bytes) return fail("background scratch too small: need %zu bytes, got %zu", sa.off, scratch_bytes);
+  if (layout_checked("background context", const_cast<void*>(ctx), ctx_bytes, [&](Arena& a) { layout_nerf(m, n, a, x); })) return -1;
+  if (layout_checked("background scratch", scratch, scratch_bytes, [&](Arena& a) { layout_nerf_bwd(m, x, n, a, b); })) return -1;
   std::vector<FinishWeight> pend;
   size_t off = 0;
   BgHeadsBwd hb;
@@ -1998,15 +2002,30 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   const int ldh = nerf_h_ld(m, x, m.D - 1);
   // rgb head: dW, cotangent of the view layer's pre-activation (ReLU mask)
   nerf_dw(m.rgb, b.dRGB, 16, x.HV, m.W / 2, n, b, off, params, dP, pend, s);
-  { LayerGemm g = nerf_bwd_gemm(m.rgb, b.dRGB, 16, n); g.Wp = nullptr; g.E.kind = EK_RELU_MASK; g.E.o1 = b.DHV; g.E.ld1 = m.W / 2; g.E.aux = x.HV; g.E.ldaux = m.W / 2; be_layer_gemm(g, s); }
+  {
+    LayerGemm g = bwd_gemm(m.rgb, n);
+    g.A = direct_view(b.dRGB, 16); g.Wp = nullptr;
+    g.E.kind = EK_RELU_MASK; g.E.n_out = m.rgb.k_int; g.E.o1 = b.DHV; g.E.ld1 = m.W / 2; g.E.aux = x.HV; g.E.ldaux = m.W / 2;
+    be_layer_gemm(g, s);
+  }
   // view layer: dW, cotangent of [feature | PE(view)]
   nerf_dw(m.view, b.DHV, m.W / 2, x.FV, x.ldfv, n, b, off, params, dP, pend, s);
-  { LayerGemm g = nerf_bwd_gemm(m.view, b.DHV, m.W / 2, n); g.E.kind = EK_SPLIT; g.E.split = m.W; g.E.o1 = b.dF; g.E.ld1 = m.W; g.E.o2 = b.dVE; g.E.ld2 = 32; be_layer_gemm(g, s); }
+  {
+    LayerGemm g = bwd_gemm(m.view, n);
+    g.A = direct_view(b.DHV, m.W / 2);
+    g.E.kind = EK_SPLIT; g.E.n_out = m.view.k_int; g.E.split = m.W; g.E.o1 = b.dF; g.E.ld1 = m.W; g.E.o2 = b.dVE; g.E.ld2 = 32;
+    be_layer_gemm(g, s);
+  }
   be_zero_cols(b.dVE, 32, m.nv, 32, n, s);
   // feature layer and density head: both read the last hidden activation
   nerf_dw(m.feat, b.dF, m.W, hl, ldh, n, b, off, params, dP, pend, s);
   nerf_dw(m.alpha, b.dDens, 16, hl, ldh, n, b, off, params, dP, pend, s);
-  { LayerGemm g = nerf_bwd_gemm(m.feat, b.dF, m.W, n); g.E.kind = EK_STORE; g.E.o1 = b.T; g.E.ld1 = m.W; be_layer_gemm(g, s); }
+  {
+    LayerGemm g = bwd_gemm(m.feat, n);
+    g.A = direct_view(b.dF, m.W);
+    g.E.kind = EK_STORE; g.E.n_out = m.feat.k_int; g.E.o1 = b.T; g.E.ld1 = m.W;
+    be_layer_gemm(g, s);
+  }
   if (ldh != m.W) return fail("background: the last layer cannot carry the skip concat");
   BgJoin bj;
   bj.n = n; bj.W = m.W; bj.T = b.T; bj.H = hl; bj.d_density = b.dDens; bj.ldd = 16; bj.w_alpha = m.alpha.W; bj.dZ = b.DZ[m.D - 1];
@@ -2016,7 +2035,8 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
     const float* in = i == 0 ? x.E : x.H[i - 1];
     const int ld_in = i == 0 ? x.lde : nerf_h_ld(m, x, i - 1);
     nerf_dw(q, b.DZ[i], m.W, in, ld_in, n, b, off, params, dP, pend, s);
-    LayerGemm g = nerf_bwd_gemm(q, b.DZ[i], m.W, n);
+    LayerGemm g = bwd_gemm(q, n);
+    g.A = direct_view(b.DZ[i], m.W); g.E.n_out = q.k_int;
     if (i == 0) { g.E.kind = EK_STORE; g.E.o1 = b.dE0; g.E.ld1 = x.lde; }
     else if (i - 1 == m.skip_at) {    // input [h | e]: h part through the ReLU mask of the layer below, e part to its own buffer
       g.E.kind = EK_RELU_MASK; g.E.split = m.W; g.E.o1 = b.DZ[i - 1]; g.E.ld1 = m.W; g.E.aux = x.H[i - 1]; g.E.ldaux = ld_in; g.E.o2 = b.dEs; g.E.ld2 = x.lde;
@@ -2039,8 +2059,6 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
 }
 
 constexpr long kVcChunk = 1 << 16;
-
-__attribute__((unused)) static void copy_rgb_stub() {}
 
 }  // namespace cnr
 
@@ -2074,31 +2092,24 @@ int cnr_param_info(const cnr_config* cfg, int index, char* name, int name_len, i
 size_t cnr_ctx_bytes(const cnr_config* cfg, int64_t n_rays) {
   Model m;
   if (build_model(cfg, m) || n_rays <= 0) return 0;
-  Arena a(nullptr);
   Ctx x;
-  layout_ctx(m, n_rays, a, x);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_ctx(m, n_rays, a, x); });
 }
 
 size_t cnr_bwd_scratch_bytes(const cnr_config* cfg, int64_t n_rays) {
   Model m;
   if (build_model(cfg, m) || n_rays <= 0) return 0;
-  Arena a(nullptr);
   Ctx x;
-  layout_ctx(m, n_rays, a, x);
-  Arena sa(nullptr);
   Bwd b;
-  layout_bwd(m, n_rays, x, sa, b);
-  return sa.off;
+  layout_size(nullptr, [&](Arena& a) { layout_ctx(m, n_rays, a, x); });
+  return layout_size(nullptr, [&](Arena& a) { layout_bwd(m, n_rays, x, a, b); });
 }
 
 size_t cnr_infer_scratch_bytes(const cnr_config* cfg, int64_t n_rays) {
   Model m;
   if (build_model(cfg, m) || n_rays <= 0) return 0;
-  Arena a(nullptr);
   Ctx x;
-  layout_ctx_infer(m, n_rays, a, x);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_ctx_infer(m, n_rays, a, x); });
 }
 
 int cnr_render_forward_only(const cnr_config* cfg, const float* const* params, const cnr_render_inputs* in, const cnr_render_outputs* out,
@@ -2117,10 +2128,8 @@ int cnr_sample_z(const cnr_config* cfg, const float* const* params, const cnr_re
   if (build_model(cfg, m)) return -1;
   if (!params || !in || !z_vals || !ctx) return fail("null argument");
   if (in->n_rays <= 0) return fail("n_rays must be positive");
-  Arena a(ctx);
   Ctx x;
-  layout_ctx(m, in->n_rays, a, x);
-  if (a.off > ctx_bytes) return fail("context buffer too small: need %zu bytes, got %zu", a.off, ctx_bytes);
+  if (layout_checked("context buffer", ctx, ctx_bytes, [&](Arena& a) { layout_ctx(m, in->n_rays, a, x); })) return -1;
   prep_all(m, params, (cnr_stream)stream);
   run_sampler(m, in, z_vals, x, (cnr_stream)stream);
   return check_backend("sample_z");
@@ -2448,26 +2457,23 @@ int cnr_mc_emit(const float* u, int32_t resolution, float threshold, const float
 
 
 size_t cnr_linear_scratch_bytes(int64_t n, int32_t k, int32_t n_out, int32_t backward) {
-  Arena a(nullptr);
   LinearOp op;
-  if (linear_setup(n, k, n_out, backward != 0, a, op)) return 0;
-  return a.off;
+  if (linear_check(n, k, n_out)) return 0;
+  return layout_size(nullptr, [&](Arena& a) { layout_linear(n, k, n_out, backward != 0, a, op); });
 }
 
 int cnr_linear_forward(const float* x, int64_t n, int32_t k, const float* W, const float* b, int32_t n_out, int32_t relu, float* y, void* scratch,
                        size_t scratch_bytes, void* stream) {
   if (!x || !W || !y || !scratch) return fail("null argument");
   cnr_stream s = (cnr_stream)stream;
-  Arena a(scratch);
   LinearOp op;
-  if (linear_setup(n, k, n_out, false, a, op)) return -1;
-  if (a.off > scratch_bytes) return fail("linear scratch too small: need %zu bytes, got %zu", a.off, scratch_bytes);
+  if (linear_check(n, k, n_out)) return -1;
+  if (layout_checked("linear scratch", scratch, scratch_bytes, [&](Arena& a) { layout_linear(n, k, n_out, false, a, op); })) return -1;
   Lin& q = op.q;
   linear_prep(op, W, b, s);
   pad_in(op.xp, op.ldx, x, k, n, s);
-  LayerGemm g;
-  g.A.kind = VK_DIRECT; g.A.a = op.xp; g.A.lda = op.ldx;
-  g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = n;
+  LayerGemm g = fwd_gemm(q, n);
+  g.A = direct_view(op.xp, op.ldx);
   g.E.kind = relu ? EK_RELU : EK_STORE; g.E.bias = b ? q.bias : nullptr; g.E.n_out = q.n; g.E.o1 = op.yp; g.E.ld1 = op.ldy;
   be_layer_gemm(g, s);
   be_copy_cols(y, n_out, op.yp, op.ldy, n_out, n, s);
@@ -2511,21 +2517,16 @@ int cnr_outside_z_backward(const float* t_rand, const int32_t* src, const float*
 size_t cnr_background_ctx_bytes(const cnr_nerf_config* cfg, int64_t n_rays, int32_t n_feed) {
   NerfModel m;
   if (build_nerf(cfg, m) || n_rays <= 0 || n_feed < 1) return 0;
-  Arena a(nullptr);
   NerfCtx x;
-  layout_nerf(m, n_rays * n_feed, a, x);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_nerf(m, n_rays * n_feed, a, x); });
 }
 size_t cnr_background_bwd_scratch_bytes(const cnr_nerf_config* cfg, int64_t n_rays, int32_t n_feed) {
   NerfModel m;
   if (build_nerf(cfg, m) || n_rays <= 0 || n_feed < 1) return 0;
-  Arena a(nullptr);
   NerfCtx x;
-  layout_nerf(m, n_rays * n_feed, a, x);
-  Arena sa(nullptr);
   NerfBwd b;
-  layout_nerf_bwd(m, x, n_rays * n_feed, sa, b);
-  return sa.off;
+  layout_size(nullptr, [&](Arena& a) { layout_nerf(m, n_rays * n_feed, a, x); });
+  return layout_size(nullptr, [&](Arena& a) { layout_nerf_bwd(m, x, n_rays * n_feed, a, b); });
 }
 int cnr_background_forward(const cnr_nerf_config* cfg, const float* const* params, const float* rays_o, const float* rays_d, const float* z_feed,
                            int64_t n_rays, int32_t n_feed, float sample_dist, float* alpha, float* color, void* ctx, size_t ctx_bytes, void* stream) {
@@ -2595,20 +2596,18 @@ int cnr_linear_backward(const float* x, const float* y, const float* dy, int64_t
                         float* dx, float* dW, float* db, void* scratch, size_t scratch_bytes, void* stream) {
   if (!x || !dy || !W || !dW || !scratch || (relu && !y)) return fail("null argument");
   cnr_stream s = (cnr_stream)stream;
-  Arena a(scratch);
   LinearOp op;
-  if (linear_setup(n, k, n_out, true, a, op)) return -1;
-  if (a.off > scratch_bytes) return fail("linear scratch too small: need %zu bytes, got %zu", a.off, scratch_bytes);
+  if (linear_check(n, k, n_out)) return -1;
+  if (layout_checked("linear scratch", scratch, scratch_bytes, [&](Arena& a) { layout_linear(n, k, n_out, true, a, op); })) return -1;
   Lin& q = op.q;
   linear_prep(op, W, nullptr, s);
   pad_in(op.xp, op.ldx, x, k, n, s);
   pad_in(op.gp, op.ldy, dy, n_out, n, s);
-  View dz;    // cotangent of the pre-activation: dy gated by the ReLU output
-  dz.kind = VK_DIRECT; dz.a = op.gp; dz.lda = op.ldy;
+  View dz = direct_view(op.gp, op.ldy);    // cotangent of the pre-activation: dy gated by the ReLU output
   if (relu) { pad_in(op.yp, op.ldy, y, n_out, n, s); dz.kind = VK_RELUGATE; dz.b = op.yp; dz.ldb = op.ldy; }
   // weight and bias gradients: dW[n_out][k] = sum_pt dz (x) x, db = column sums of dz
   DwGemm d;
-  d.npairs = 1; d.P = n; d.X[0] = dz; d.Y[0].kind = VK_DIRECT; d.Y[0].a = op.xp; d.Y[0].lda = op.ldx;
+  d.npairs = 1; d.P = n; d.X[0] = dz; d.Y[0] = direct_view(op.xp, op.ldx);
   d.N = q.n; d.K = q.k_int; d.nchunk = op.nchunk; d.chunk_pts = round_up((int)((n + op.nchunk - 1) / op.nchunk), 16);
   d.partial = op.part; d.Npad = q.npad; d.ldk = q.ldw;
   float* csum = op.part + round_up_sz((size_t)op.nchunk * q.npad * q.ldw, 64);
@@ -2621,9 +2620,8 @@ int cnr_linear_backward(const float* x, const float* y, const float* dy, int64_t
   f.dg = nullptr; f.dv = dW; f.db = db; f.row_rot = 0;
   be_finish_weights(&f, 1, s);
   if (dx) {
-    LayerGemm g;
+    LayerGemm g = bwd_gemm(q, n);
     g.A = dz;
-    g.W = q.Wt; g.ldw = q.ldwt; g.Wp = q.Wtp; g.wp_stride = (long)q.kpad * q.ldwt; g.wscale = q.Wtps; g.N = q.k_int; g.K = q.n; g.P = n;
     g.E.kind = EK_STORE; g.E.n_out = q.k_int; g.E.o1 = op.dxp; g.E.ld1 = op.ldx;
     be_layer_gemm(g, s);
     be_copy_cols(dx, k, op.dxp, op.ldx, k, n, s);
@@ -2634,10 +2632,8 @@ int cnr_linear_backward(const float* x, const float* y, const float* dy, int64_t
 size_t cnr_vertex_color_scratch_bytes(const cnr_config* cfg, int64_t n_points) {
   Model m;
   if (build_model(cfg, m) || n_points <= 0) return 0;
-  Arena a(nullptr);
   Ctx x;
-  layout_vc(m, n_points < kVcChunk ? n_points : kVcChunk, a, x);
-  return a.off;
+  return layout_size(nullptr, [&](Arena& a) { layout_vc(m, n_points < kVcChunk ? n_points : kVcChunk, a, x); });
 }
 
 int cnr_vertex_color(const cnr_config* cfg, const float* const* params, const float* verts, int64_t n_points, float* rgb,
@@ -2647,32 +2643,20 @@ int cnr_vertex_color(const cnr_config* cfg, const float* const* params, const fl
   if (!params || !verts || !rgb || !scratch) return fail("null argument");
   cnr_stream s = (cnr_stream)stream;
   const long chunk = n_points < kVcChunk ? n_points : kVcChunk;
-  Arena a(scratch);
   Ctx x;
-  layout_vc(m, chunk, a, x);
-  if (a.off > scratch_bytes) return fail("scratch too small: need %zu bytes, got %zu", a.off, scratch_bytes);
+  if (layout_checked("scratch", scratch, scratch_bytes, [&](Arena& a) { layout_vc(m, chunk, a, x); })) return -1;
   prep_all(m, params, s);
-  const float scale = m.c.sdf_scale;
   for (long start = 0; start < n_points; start += chunk) {
     const long cnt = (n_points - start) < chunk ? (n_points - start) : chunk;
-    EmbedPts ep;
-    ep.pts = verts + start * 3; ep.n = cnt; ep.res = 0; ep.start = 0;
-    for (int c = 0; c < 3; ++c) { ep.bmin[c] = 0.f; ep.bmax[c] = 0.f; }
-    ep.scale = scale; ep.multires = m.c.sdf_multires; ep.E = x.E; ep.AUX = x.AUX;
-    be_embed_pts(ep, s);
-    sdf_chain(m, cnt, x.E, x.Z.data(), x.sdf, x.featx, x.ldfx, 1.0f / scale, s);
-    sdf_grad_chain(m, cnt, x.E, x.Z.data(), x.V.data(), x.CE0, x.CES, s);
-    GradFinish gf;
-    gf.P = cnt; gf.E = x.E; gf.ce0 = x.CE0; gf.ces = has_skip(m) ? x.CES + skip_off(m) : nullptr; gf.scale = scale; gf.multires = m.c.sdf_multires;
-    gf.grad_out = x.relit; gf.AUX = x.AUX; gf.neg_g_as_view = (m.c.col_mode != 1) ? 1 : 0; gf.multires_view = m.mv;
-    gf.featx = x.featx; gf.ldfx = x.ldfx; gf.F = m.F;
-    be_grad_finish(gf, s);
+    embed_points(m, verts + start * 3, cnt, x.E, x.AUX, s);
+    PointOpts po;
+    po.grad_out = x.relit; po.neg_g_as_view = (m.c.col_mode != 1) ? 1 : 0; po.multires_view = m.mv;
+    point_pipeline(m, cnt, x, po, s);
     // colour chain with the final layer written straight into the caller's [n][3] buffer
     for (int l = 0; l < m.NC; ++l) {
       const Lin& q = m.col[l];
-      LayerGemm g;
+      LayerGemm g = fwd_gemm(q, cnt);
       g.A = color_input_view(m, l, x);
-      g.W = q.W; g.ldw = q.ldw; g.Wp = q.Wp; g.wp_stride = (long)q.wpad * q.ldw; g.w_rows = q.wpad; g.wscale = q.Wps; g.N = q.n; g.K = q.k_int; g.P = cnt;
       g.E.bias = q.bias; g.E.n_out = q.n;
       if (l + 1 < m.NC) { g.E.kind = EK_RELU; g.E.o1 = x.HC[l]; g.E.ld1 = m.Hc; }
       else { g.E.kind = m.c.col_squeeze_out ? EK_SIGMOID : EK_LINEAR_SIG; g.E.o1 = rgb + start * 3; g.E.ld1 = 3; }
