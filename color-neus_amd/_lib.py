@@ -102,7 +102,8 @@ EXPORTS = ["cnr_abi_version", "cnr_backend_name", "cnr_last_error", "cnr_param_c
            "cnr_nerf_param_count", "cnr_nerf_param_info", "cnr_outside_z", "cnr_outside_z_backward", "cnr_background_ctx_bytes",
            "cnr_background_bwd_scratch_bytes", "cnr_background_forward", "cnr_background_backward", "cnr_composite_background_scratch_bytes",
            "cnr_composite_background_forward", "cnr_composite_background_backward",
-           "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward"]
+           "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward",
+           "cnr_nn_scratch_bytes", "cnr_nn_search"]
 
 
 class RenderLibrary:
@@ -177,6 +178,9 @@ class RenderLibrary:
         L.cnr_mc_scratch_bytes.argtypes = [C.c_int32]
         L.cnr_mc_count.argtypes = [_FP, C.c_int32, C.c_float, _FP, C.c_size_t, _FP, _FP]
         L.cnr_mc_emit.argtypes = [_FP, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _FP, C.c_size_t, _FP, _FP, _FP]
+        L.cnr_nn_scratch_bytes.restype = C.c_size_t
+        L.cnr_nn_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.cnr_nn_search.argtypes = [_FP, C.c_int64, _FP, C.c_int64, _FP, _FP, _FP, C.c_size_t, _FP]
         L.cnr_timing_enable.argtypes = [C.c_int]
         L.cnr_timing_enable.restype = None
         L.cnr_timing_collect.argtypes = [C.POINTER(CnrKernelTiming), C.c_int]
@@ -196,7 +200,7 @@ class RenderLibrary:
         L.cnr_composite_background_forward.argtypes = [C.POINTER(CnrBgCompositeIn), C.POINTER(CnrOutputs), _FP, C.c_size_t, _FP]
         L.cnr_composite_background_backward.argtypes = [C.POINTER(CnrBgCompositeIn), C.POINTER(CnrOutputs), C.POINTER(CnrOutGrads),
                                                         C.POINTER(CnrBgCompositeGrads), _FP, C.c_size_t, _FP]
-        if L.cnr_abi_version() != 8:
+        if L.cnr_abi_version() != 9:
             raise RuntimeError("colorneus library ABI mismatch")
 
     @property

@@ -374,6 +374,23 @@ void be_mc_emit(const McVolume& m, const float* bmin, const float* bmax, float* 
   }
 }
 
+// twin of nn_search_kernel / nn_unpack_kernel: the same nn_dist2 / nn_update / nn_key on the whole target range, one query per iteration
+void be_nn_search(const NnSearch& p, cnr_stream) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < p.n; ++i) {
+    const float qx = p.query[i * 3], qy = p.query[i * 3 + 1], qz = p.query[i * 3 + 2];
+    float best = INFINITY;
+    int besti = -1;
+    for (long j = 0; j < p.m; ++j)
+      nn_update(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
+    if (besti < 0)
+      for (long j = 0; j < p.m; ++j)
+        nn_update_inf(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
+    p.keys[i] = nn_key(best, besti);
+    nn_unpack(p.keys[i], &p.dist2[i], &p.idx[i]);
+  }
+}
+
 void be_gen_rays(const GenRays& p, cnr_stream) {
   for (long i = 0; i < p.n; ++i) body_gen_rays(p, i);
 }

@@ -2455,6 +2455,27 @@ int cnr_mc_emit(const float* u, int32_t resolution, float threshold, const float
   return check_backend("mc_emit");
 }
 
+size_t cnr_nn_scratch_bytes(int64_t n_query, int64_t n_target) {
+  (void)n_target;
+  if (n_query <= 0) return 0;
+  return round_up_sz((size_t)n_query * sizeof(unsigned long long), 256);   // one 64-bit candidate key per query
+}
+
+int cnr_nn_search(const float* query, int64_t n_query, const float* target, int64_t n_target, float* dist2, int32_t* idx, void* scratch,
+                  size_t scratch_bytes, void* stream) {
+  if (n_query < 0) return fail("nn_search: n_query < 0");
+  if (n_query == 0) return 0;
+  if (n_target <= 0) return fail("nn_search: no target points (n_target = %lld)", (long long)n_target);
+  if (n_target >= (int64_t)1 << 31) return fail("nn_search: n_target must be below 2^31 (the index is an int32)");
+  if (!query || !target || !dist2 || !idx || !scratch) return fail("null argument");
+  if (scratch_bytes < cnr_nn_scratch_bytes(n_query, n_target)) return fail("nn_search scratch too small");
+  NnSearch p;
+  p.query = query; p.n = (long)n_query; p.target = target; p.m = (long)n_target; p.dist2 = dist2; p.idx = idx;
+  p.keys = static_cast<unsigned long long*>(scratch);
+  be_nn_search(p, (cnr_stream)stream);
+  return check_backend("nn_search");
+}
+
 
 size_t cnr_linear_scratch_bytes(int64_t n, int32_t k, int32_t n_out, int32_t backward) {
   LinearOp op;

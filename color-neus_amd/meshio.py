@@ -48,3 +48,68 @@ def read_ply(path):
     verts = np.stack([v["x"], v["y"], v["z"]], -1)
     cols = np.stack([v["red"], v["green"], v["blue"]], -1) if colored else None
     return verts, f["i"].copy(), cols
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply_vertices(path):
+    """Vertex positions of an ASCII or binary-little-endian PLY file as a float32 (V, 3) array, driven by the header: the ``vertex`` element may
+    carry any scalar properties of the standard types besides x / y / z (normals, colours, ... are skipped) and need not be followed by a face
+    element -- ground-truth clouds come from other writers than write_ply.  Elements in front of the vertex element must have scalar
+    properties only (their size is then known without parsing them)."""
+    with open(path, "rb") as fh:
+        if fh.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []          # elements: [name, count, [(property name, numpy type)]]
+        while True:
+            raw = fh.readline()
+            if not raw:
+                raise ValueError(f"{path}: PLY header without end_header")
+            tok = raw.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError(f"{path}: property in front of the first element")
+                if tok[1] == "list":
+                    elements[-1][2].append((tok[-1], None))
+                elif tok[1] in _PLY_TYPES:
+                    elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+                else:
+                    raise ValueError(f"{path}: unknown PLY property type '{tok[1]}'")
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError(f"{path}: PLY format '{fmt}' is not supported (ascii and binary_little_endian are)")
+        for name, count, props in elements:
+            if any(t is None for _, t in props):
+                raise ValueError(f"{path}: element '{name}' with a list property in front of / as the vertex element")
+            if name != "vertex":
+                if fmt == "ascii":        # one line per entry
+                    for _ in range(count):
+                        fh.readline()
+                else:
+                    fh.seek(count * sum(np.dtype(t).itemsize for _, t in props), 1)
+                continue
+            names = [n for n, _ in props]
+            if not all(c in names for c in "xyz"):
+                raise ValueError(f"{path}: the vertex element has no x / y / z")
+            if fmt == "ascii":
+                rows = [fh.readline().split() for _ in range(count)]
+                if any(len(r) < len(props) for r in rows):
+                    raise ValueError(f"{path}: short vertex line")
+                cols = [names.index(c) for c in "xyz"]
+                return np.array([[float(r[c]) for c in cols] for r in rows], dtype=np.float64).astype(np.float32).reshape(count, 3)
+            dt = np.dtype([(n, "<" + t) for n, t in props])
+            buf = fh.read(count * dt.itemsize)
+            if len(buf) != count * dt.itemsize:
+                raise ValueError(f"{path}: truncated vertex data")
+            v = np.frombuffer(buf, dtype=dt)
+            return np.stack([v["x"], v["y"], v["z"]], -1).astype(np.float32).reshape(count, 3)
+    raise ValueError(f"{path}: no vertex element")

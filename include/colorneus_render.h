@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CNR_ABI_VERSION 8
+#define CNR_ABI_VERSION 9
 
 typedef struct cnr_config {
   int32_t type;              /* 0 = NeuS (NeuS.py:68), 1 = Color_NeuS (Color_NeuS.py:10) */
@@ -336,6 +336,16 @@ size_t cnr_mc_scratch_bytes(int32_t resolution);
 int cnr_mc_count(const float* u, int32_t resolution, float threshold, void* scratch, size_t scratch_bytes, int32_t* totals, void* stream);
 int cnr_mc_emit(const float* u, int32_t resolution, float threshold, const float* bound_min /* host [3] */, const float* bound_max /* host [3] */,
                 void* scratch, size_t scratch_bytes, float* vertices /* [V][3] */, int32_t* triangles /* [F][3] */, void* stream);
+
+/* Exact nearest neighbour of every query point among the target points: the search behind the Chamfer distance / F-score of two meshes
+ * (lib/utils/mesh_tools.py:59-70 hands the vertices of two mesh files to pytorch3d.loss.chamfer_distance).  For query i,
+ *     d2(i, j) = (dx*dx + dy*dy) + dz*dz,  dx = query[i].x - target[j].x, ...   every operation one rounded fp32 operation, in this order,
+ * dist2[i] = min over j of d2(i, j), idx[i] = the lowest j that attains it.  A NaN d2 never wins; a query whose every d2 is NaN gets
+ * idx = -1 and a NaN dist2.  Brute force over all n_query * n_target pairs, exact; results are bitwise reproducible (integer-min reduction).
+ * n_query == 0 is a successful no-op; n_target must be in [1, 2^31).  scratch: cnr_nn_scratch_bytes, contents need not be initialised. */
+size_t cnr_nn_scratch_bytes(int64_t n_query, int64_t n_target);
+int cnr_nn_search(const float* query /* [n_query][3] */, int64_t n_query, const float* target /* [n_target][3] */, int64_t n_target,
+                  float* dist2 /* [n_query] */, int32_t* idx /* [n_query] */, void* scratch, size_t scratch_bytes, void* stream);
 
 /* extract_color: rgb = color_network(pts, g, -g, feat) per vertex (NeuS.py:44-64) */
 size_t cnr_vertex_color_scratch_bytes(const cnr_config* cfg, int64_t n_points);
