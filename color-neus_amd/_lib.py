@@ -75,6 +75,10 @@ class CnrInGrads(C.Structure):
     _fields_ = [("d_params", C.POINTER(_FP)), ("d_rays_o", _FP), ("d_rays_d", _FP), ("d_near", _FP), ("d_far", _FP)]
 
 
+class CnrCameraConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_cams", "pose_mode", "focal_order", "fx_only", "H", "W", "has_init_c2w")]
+
+
 _MODE = {"idr": 0, "no_view_dir": 1, "no_normal": 2}
 
 
@@ -103,7 +107,7 @@ EXPORTS = ["cnr_abi_version", "cnr_backend_name", "cnr_last_error", "cnr_param_c
            "cnr_background_bwd_scratch_bytes", "cnr_background_forward", "cnr_background_backward", "cnr_composite_background_scratch_bytes",
            "cnr_composite_background_forward", "cnr_composite_background_backward",
            "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward",
-           "cnr_nn_scratch_bytes", "cnr_nn_search"]
+           "cnr_nn_scratch_bytes", "cnr_nn_search", "cnr_camera_forward", "cnr_camera_backward"]
 
 
 class RenderLibrary:
@@ -181,6 +185,8 @@ class RenderLibrary:
         L.cnr_nn_scratch_bytes.restype = C.c_size_t
         L.cnr_nn_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
         L.cnr_nn_search.argtypes = [_FP, C.c_int64, _FP, C.c_int64, _FP, _FP, _FP, C.c_size_t, _FP]
+        L.cnr_camera_forward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP]
+        L.cnr_camera_backward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, _FP]
         L.cnr_timing_enable.argtypes = [C.c_int]
         L.cnr_timing_enable.restype = None
         L.cnr_timing_collect.argtypes = [C.POINTER(CnrKernelTiming), C.c_int]

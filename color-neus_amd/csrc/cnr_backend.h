@@ -438,6 +438,23 @@ struct GenRaysBwd {
 void be_gen_rays(const GenRays& p, cnr_stream s);
 void be_gen_rays_bwd(const GenRaysBwd& p, cnr_stream s);
 
+// ---- learnable cameras (camera_net.py:8-109): the producer of c2w / focal in front of the ray generator
+struct Camera {
+  const float* r; const float* t;       // [num_cams][6 or 3], [num_cams][3]; null: no pose part
+  const float* init_c2w;                // [num_cams][4][4] or null
+  const float* fx; const float* fy;     // [1] each; fy null with fx_only; fx null: no focal part
+  const long* cam_ids; long B;          // [B] or null: slot i is camera i (B == num_cams)
+  int num_cams, six_d, focal_order, fx_only, H, W;
+  float* c2w; float* focal;             // [B][4][4] (null: no pose part), [2] (null: no focal part)
+};
+struct CameraBwd {
+  Camera f;                             // the forward arguments (outputs unused)
+  const float* d_c2w; const float* d_focal;           // [B][4][4], [2]
+  float* d_r; float* d_t; float* d_fx; float* d_fy;   // dense [num_cams][6 or 3], [num_cams][3], [1], [1]; any may be null
+};
+void be_camera_fwd(const Camera& p, cnr_stream s);
+void be_camera_bwd(const CameraBwd& q, cnr_stream s);
+
 // ---- iso-surface extraction on the device-resident SDF lattice (replaces the CPU mcubes.marching_cubes call of extract_geometry,
 // NeuS.py:31-40): cell classification + edge ownership, two exclusive scans, vertex / triangle emission
 struct McVolume {

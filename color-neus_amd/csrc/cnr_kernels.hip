@@ -1794,6 +1794,12 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream s) {
   CNR_LAUNCH_CHECK("gen_rays_bwd");
 }
 
+// learnable cameras: one thread per slot (forward) / per camera (backward, which folds that camera's slots in slot order); one launch each
+CNR_PW_KERNEL(camera_fwd, Camera, body_camera_fwd)
+CNR_PW_KERNEL(camera_bwd, CameraBwd, body_camera_bwd)
+void be_camera_fwd(const Camera& p, cnr_stream s) { camera_fwd_launch(p, p.c2w && p.B > 1 ? p.B : 1, s); }
+void be_camera_bwd(const CameraBwd& q, cnr_stream s) { camera_bwd_launch(q, q.d_c2w && q.f.num_cams > 1 ? q.f.num_cams : 1, s); }
+
 // ------------------------------------------------------------------------------------------------
 // marching cubes on the device lattice: the 512^3 volume never leaves HBM between extract_fields and the mesh
 // ------------------------------------------------------------------------------------------------

@@ -413,6 +413,15 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
   }
 }
 
+void be_camera_fwd(const Camera& p, cnr_stream) {
+  const long n = p.c2w && p.B > 1 ? p.B : 1;
+  for (long i = 0; i < n; ++i) body_camera_fwd(p, i);
+}
+void be_camera_bwd(const CameraBwd& q, cnr_stream) {
+  const long n = q.d_c2w && q.f.num_cams > 1 ? q.f.num_cams : 1;
+  for (long cam = 0; cam < n; ++cam) body_camera_bwd(q, cam);
+}
+
 void be_clip_adam(const AdamArgs& a, cnr_stream) {
   for (int k = 0; k < a.count; ++k) {
     const AdamTensor& t = a.t[k];

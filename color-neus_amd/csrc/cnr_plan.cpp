@@ -2312,6 +2312,52 @@ int cnr_gen_rays_backward(const int64_t* pix_idx, int64_t n, const float* c2w, i
   return check_backend("gen_rays_backward");
 }
 
+static int camera_args(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w, const float* fx, const float* fy,
+                       const int64_t* cam_ids, int64_t B, bool pose, bool focal, Camera& c) {
+  if (!cfg) return fail("camera: null argument cfg");
+  if (!pose && !focal) return fail("camera: null argument: neither the pose nor the focal part is given");
+  c = Camera{};
+  c.num_cams = cfg->num_cams; c.H = cfg->H; c.W = cfg->W; c.focal_order = cfg->focal_order; c.fx_only = cfg->fx_only != 0;
+  if (pose) {
+    if (cfg->num_cams <= 0) return fail("camera: num_cams must be positive");
+    if (B <= 0) return fail("camera: B must be positive");
+    if (cfg->pose_mode != CNR_POSE_3D && cfg->pose_mode != CNR_POSE_6D) return fail("camera: unknown pose_mode %d", (int)cfg->pose_mode);
+    if (!r || !t) return fail("camera: null argument r / t");
+    if ((cfg->has_init_c2w != 0) != (init_c2w != nullptr)) return fail("camera: init_c2w must be given exactly when cfg->has_init_c2w is set");
+    if (!cam_ids && B != cfg->num_cams) return fail("camera: B must equal num_cams when cam_ids is null");
+    static_assert(sizeof(long) == sizeof(int64_t), "int64 camera ids");
+    c.r = r; c.t = t; c.init_c2w = init_c2w; c.cam_ids = reinterpret_cast<const long*>(cam_ids); c.B = B; c.six_d = cfg->pose_mode == CNR_POSE_6D;
+  }
+  if (focal) {
+    if (cfg->focal_order != 1 && cfg->focal_order != 2) return fail("camera: unknown focal_order %d", (int)cfg->focal_order);
+    if (cfg->H <= 0 || cfg->W <= 0) return fail("camera: H, W must be positive");
+    if (!fx || (!cfg->fx_only && !fy)) return fail("camera: null argument fx / fy");
+    c.fx = fx; c.fy = fy;
+  }
+  return 0;
+}
+
+int cnr_camera_forward(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w, const float* fx, const float* fy,
+                       const int64_t* cam_ids, int64_t B, float* c2w, float* focal, void* stream) {
+  Camera c;
+  if (camera_args(cfg, r, t, init_c2w, fx, fy, cam_ids, B, c2w != nullptr, focal != nullptr, c)) return -1;
+  c.c2w = c2w; c.focal = focal;
+  be_camera_fwd(c, (cnr_stream)stream);
+  return check_backend("camera_forward");
+}
+
+int cnr_camera_backward(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w, const float* fx, const float* fy,
+                        const int64_t* cam_ids, int64_t B, const float* d_c2w, const float* d_focal, float* d_r, float* d_t, float* d_fx,
+                        float* d_fy, void* stream) {
+  CameraBwd q;
+  if (camera_args(cfg, r, t, init_c2w, fx, fy, cam_ids, B, d_c2w != nullptr, d_focal != nullptr, q.f)) return -1;
+  if (d_c2w && !d_r && !d_t) return fail("camera_backward: null argument: d_c2w without d_r or d_t");
+  if (d_focal && !d_fx && !d_fy) return fail("camera_backward: null argument: d_focal without d_fx or d_fy");
+  q.d_c2w = d_c2w; q.d_focal = d_focal; q.d_r = d_r; q.d_t = d_t; q.d_fx = d_fx; q.d_fy = q.f.fx_only ? nullptr : d_fy;
+  be_camera_bwd(q, (cnr_stream)stream);
+  return check_backend("camera_backward");
+}
+
 size_t cnr_clip_adam_scratch_bytes(int32_t n_tensors, const int64_t* sizes) {
   if (!sizes || n_tensors <= 0) return 0;
   size_t chunks = 0;

@@ -4,7 +4,8 @@
 The reference builds directions and origins for ALL N*H*W pixels of the batch (about 184 MB per step at DTU size) and gathers
 n_rays of them.  Here the pixels are chosen first and one kernel (cnr_gen_rays) builds rays, colours and mask values only for
 those; ``rays_for_training`` also folds in what NeuS_Trainer.render does next (origin / radius normalisation, near / far).
-Learnable poses and focal lengths (config/Color_NeuS_iho.yml:18-20) get their gradients from cnr_gen_rays_backward.
+Learnable poses and focal lengths (config/Color_NeuS_iho.yml:18-20) get their gradients from cnr_gen_rays_backward; the parameters
+behind them (pose_net.r / .t, focal_net.fx / .fy) and the step from those gradients to theirs are in cameras.py.
 
 Pixel choice consumes the torch CPU generator exactly like the reference (same calls, same order), so a seeded run picks the same
 pixels: that is the only part left in torch -- it IS the reference's random stream."""

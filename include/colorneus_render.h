@@ -213,6 +213,41 @@ int cnr_gen_rays_backward(const int64_t* pix_idx, int64_t n, const float* c2w, i
                           int32_t normalize, int32_t opengl, const float* origin, float radius, const float* d_rays_o, const float* d_rays_d,
                           const float* d_near, const float* d_far, float* d_c2w, float* d_focal, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- learnable cameras, the producer in front of cnr_gen_rays: the reference's Focal_Net and Pose_Net (lib/models/tools/camera_net.py:8-109,
+ * called at the top of every training step, NeuS_Trainer.py:183-184) and their backward, one launch each.  All arithmetic fp32.
+ *   focal [2]: order 2: {(fx*fx)*W, (fy*fy)*H}; order 1: {fx*W, fy*H}; with fx_only both entries are the first one (fy is not read, may be NULL).
+ *   c2w [B][4][4]: slot i takes camera cam = cam_ids[i] (device int64; duplicates allowed, any order; NULL: camera i, B == num_cams):
+ *     c2w[i] = [[R, t[cam]], [0 0 0 1]] @ init_c2w[cam]   (the full 4x4 product), or without the product when init_c2w is NULL; R from r[cam]:
+ *       CNR_POSE_6D, r [num_cams][6] (Zhou et al. 2019): b1 = a1 / max(|a1|, 1e-12), b2' = a2 - (b1 . a2) b1, b2 = b2' / max(|b2'|, 1e-12),
+ *         b3 = b1 x b2 with a1 = r[0:3], a2 = r[3:6]; the ROWS of R are b1, b2, b3;
+ *       CNR_POSE_3D, r [num_cams][3] (axis-angle): R = I + A K + B K^2, K = [r]x, theta = |r|, A = sin(theta) / theta,
+ *         B = 2 sin^2(theta / 2) / theta^2; for theta^2 < 1e-4 the series A = 1 - theta^2 / 6, B = 1/2 - theta^2 / 24 (R = I and
+ *         dR/dr_k = [e_k]x at r = 0, the initial value).
+ *     A slot whose id is outside [0, num_cams) reads nothing: its c2w is NaN and it contributes nothing to the backward (the convention of
+ *     cnr_gen_rays for pixel indices).
+ * Either part may be left out: c2w == NULL (r, t, init_c2w, cam_ids, B, num_cams, pose_mode are then not used) or focal == NULL (fx, fy,
+ * focal_order, fx_only, H, W are not used), not both.
+ * cnr_camera_backward: from d_c2w [B][4][4] and d_focal [2] (either may be NULL like the output it belongs to) the DENSE gradients
+ * d_r [num_cams][6 or 3], d_t [num_cams][3] and d_fx [1], d_fy [1]; each is overwritten; one that is not wanted may be NULL (d_fy is not
+ * written with fx_only).  Rows of cameras no slot names are exactly 0; the slots of one camera are added in ascending slot order by one
+ * thread (no float atomics: bitwise reproducible).  No scratch. */
+#define CNR_POSE_3D 0
+#define CNR_POSE_6D 1
+typedef struct cnr_camera_config {
+  int32_t num_cams;
+  int32_t pose_mode;      /* CNR_POSE_3D / CNR_POSE_6D */
+  int32_t focal_order;    /* 1 or 2 */
+  int32_t fx_only;
+  int32_t H, W;
+  int32_t has_init_c2w;   /* must agree with init_c2w != NULL */
+} cnr_camera_config;
+int cnr_camera_forward(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w /* or NULL */, const float* fx,
+                       const float* fy /* NULL with fx_only */, const int64_t* cam_ids /* [B] or NULL */, int64_t B, float* c2w, float* focal,
+                       void* stream);
+int cnr_camera_backward(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w, const float* fx, const float* fy,
+                        const int64_t* cam_ids, int64_t B, const float* d_c2w, const float* d_focal, float* d_r, float* d_t, float* d_fx,
+                        float* d_fy, void* stream);
+
 /* ---- optimiser step of the training loop (the consumer after loss.backward(), train.py:72-77): per-parameter gradient clipping
  * (clip_gradient -> torch.nn.utils.clip_grad_norm_ on EACH parameter tensor, lib/utils/net_utils.py:174-184) followed by
  * torch.optim.Adam (net_utils.py:88: betas (0.9, 0.99), eps 1e-8, no weight decay) in ONE launch over all tensors.
