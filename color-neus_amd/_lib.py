@@ -107,7 +107,8 @@ EXPORTS = ["cnr_abi_version", "cnr_backend_name", "cnr_last_error", "cnr_param_c
            "cnr_background_bwd_scratch_bytes", "cnr_background_forward", "cnr_background_backward", "cnr_composite_background_scratch_bytes",
            "cnr_composite_background_forward", "cnr_composite_background_backward",
            "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward",
-           "cnr_nn_scratch_bytes", "cnr_nn_search", "cnr_camera_forward", "cnr_camera_backward"]
+           "cnr_nn_scratch_bytes", "cnr_nn_search", "cnr_camera_forward", "cnr_camera_backward",
+           "cnr_image_scratch_bytes", "cnr_image_metrics", "cnr_image_panel"]
 
 
 class RenderLibrary:
@@ -187,6 +188,10 @@ class RenderLibrary:
         L.cnr_nn_search.argtypes = [_FP, C.c_int64, _FP, C.c_int64, _FP, _FP, _FP, C.c_size_t, _FP]
         L.cnr_camera_forward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP]
         L.cnr_camera_backward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, _FP]
+        L.cnr_image_scratch_bytes.restype = C.c_size_t
+        L.cnr_image_scratch_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
+        L.cnr_image_metrics.argtypes = [_FP, _FP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.c_size_t, _FP]
+        L.cnr_image_panel.argtypes = [_FP, _FP, _FP, C.c_int, C.c_int, _FP, _FP, _FP, C.c_size_t, _FP]
         L.cnr_timing_enable.argtypes = [C.c_int]
         L.cnr_timing_enable.restype = None
         L.cnr_timing_collect.argtypes = [C.POINTER(CnrKernelTiming), C.c_int]
@@ -238,6 +243,27 @@ class RenderLibrary:
             self.check(self.lib.cnr_param_info(C.byref(ccfg), i, buf, 128, C.byref(r), C.byref(c)), "cnr_param_info")
             out.append((buf.value.decode(), r.value, c.value))
         return out
+
+
+def ptr(t):
+    """Device (or host) address of a tensor for a pointer argument; None gives NULL."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def stream_of(t):
+    """The current stream of a CUDA tensor's device as the ABI's stream argument (NULL for CPU tensors)."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else C.c_void_p(0)
+
+
+def library_for(library, dev, what):
+    """The library that serves tensors on ``dev``: CUDA tensors use the HIP library, CPU tensors only an explicitly passed CPU-emulation
+    ``library=``.  There is no CPU fallback: a mismatch raises.  ``what`` words the message ("points ... searched", "images ... evaluated")."""
+    lib = library if isinstance(library, RenderLibrary) else load_library(library)
+    if lib.backend.startswith("hip") != (dev.type == "cuda"):
+        raise RuntimeError(f"{what[0]} on '{dev}' cannot be {what[1]} by the '{lib.backend}' library: CUDA tensors use the HIP library, CPU tensors "
+                           "need an explicitly passed CPU-emulation library= (there is no CPU fallback)")
+    return lib
 
 
 def library_path() -> str:

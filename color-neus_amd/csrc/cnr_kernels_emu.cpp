@@ -391,6 +391,71 @@ void be_nn_search(const NnSearch& p, cnr_stream) {
   }
 }
 
+// twin of image_stats_kernel / image_stats_finish_kernel: the same img_* functions, one element per iteration, the row pass of the three
+// rows recomputed per element; float64 sums per image row, then the rows in index order (a fixed order, not the HIP build's: DESIGN 5)
+void be_image_stats(const ImageStats& p, cnr_stream) {
+  const int cs = p.cs;
+  const long rowlen = (long)p.W * cs, nrows = p.planes * p.H;
+  std::vector<double> part((size_t)nrows * 2);
+#pragma omp parallel for schedule(static)
+  for (long pr = 0; pr < nrows; ++pr) {
+    const long plane = pr / p.H;
+    const int r = (int)(pr - plane * p.H);
+    const float* px = p.x + plane * p.H * rowlen;
+    const float* py = p.y + plane * p.H * rowlen;
+    double sum_d = 0.0, sum_s = 0.0;
+    for (long g = 0; g < rowlen; ++g) {
+      const int pix = (int)(g / cs), ch = (int)(g - (long)pix * cs);
+      const long gl = (long)img_reflect(pix - 1, p.W) * cs + ch, gr = (long)img_reflect(pix + 1, p.W) * cs + ch;
+      float h[5][3];
+      for (int k = 0; k < 3; ++k) {
+        const long row = (long)img_reflect(r - 1 + k, p.H) * rowlen;
+        const float xl = px[row + gl], xc = px[row + g], xr = px[row + gr];
+        const float yl = py[row + gl], yc = py[row + g], yr = py[row + gr];
+        h[0][k] = img_tap3(xl, xc, xr);
+        h[1][k] = img_tap3(yl, yc, yr);
+        h[2][k] = img_tap3(xl * xl, xc * xc, xr * xr);
+        h[3][k] = img_tap3(yl * yl, yc * yc, yr * yr);
+        h[4][k] = img_tap3(xl * yl, xc * yc, xr * yr);
+      }
+      float m[5];
+      for (int q = 0; q < 5; ++q) m[q] = img_tap3(h[q][0], h[q][1], h[q][2]);
+      const float s = img_ssim(m[0], m[1], m[2], m[3], m[4]);
+      const long at = (long)r * rowlen + g;
+      if (p.map) p.map[plane * p.H * rowlen + at] = s;
+      sum_d += (double)img_sqerr(px[at], py[at]);
+      sum_s += (double)s;
+    }
+    part[2 * pr] = sum_d;
+    part[2 * pr + 1] = sum_s;
+  }
+  double a = 0.0, b = 0.0;
+  for (long pr = 0; pr < nrows; ++pr) { a += part[2 * pr]; b += part[2 * pr + 1]; }
+  p.sums[0] = a;
+  p.sums[1] = b;
+}
+
+// twin of depth_range_kernel / image_panel_kernel
+void be_image_panel(const ImagePanel& p, cnr_stream) {
+  p.keys[0] = p.keys[1] = 0xffffffffu;
+  for (long i = 0; i < (long)p.H * p.W; ++i) {
+    const float d = p.depth[i];
+    if (d == d) {
+      const unsigned k = img_depth_key(d);
+      p.keys[0] = std::min(p.keys[0], k);
+      p.keys[1] = std::min(p.keys[1], ~k);
+    }
+  }
+  float vmin, vmax;
+  img_depth_range(p.keys, &vmin, &vmax);
+  p.range[0] = vmin;
+  p.range[1] = vmax;
+  const int rowb = p.nsec * 3 * p.W;
+#pragma omp parallel for schedule(static)
+  for (int row = 0; row < p.H; ++row)
+    for (int col = 0; col < rowb; ++col) p.panel[(long)row * rowb + col] = img_panel_byte(p, row, col, vmin, vmax);
+}
+
 void be_gen_rays(const GenRays& p, cnr_stream) {
   for (long i = 0; i < p.n; ++i) body_gen_rays(p, i);
 }

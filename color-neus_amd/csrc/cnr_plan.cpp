@@ -2522,6 +2522,49 @@ int cnr_nn_search(const float* query, int64_t n_query, const float* target, int6
   return check_backend("nn_search");
 }
 
+// one {sum d*d, sum ssim} pair of doubles per tile of the [B][C][H][W] form (the channels-last form of the same image never has more tiles),
+// and 256 bytes for the two range keys of cnr_image_panel
+static long image_blocks(int64_t planes, int H, int W, int cs) { return (long)planes * img_tiles_y(H) * img_tiles_x(W, cs); }
+size_t cnr_image_scratch_bytes(int64_t n_images, int channels, int H, int W) {
+  if (n_images <= 0 || channels < 1 || H < 1 || W < 1) return 0;
+  return round_up_sz((size_t)image_blocks(n_images * channels, H, W, 1) * 2 * sizeof(double), 256) + 256;
+}
+
+int cnr_image_metrics(const float* img0, const float* img1, int64_t n_images, int channels, int H, int W, int channels_last, float* ssim_map,
+                      double* sums, void* scratch, size_t scratch_bytes, void* stream) {
+  if (n_images < 0) return fail("image_metrics: n_images < 0");
+  if (!sums) return fail("image_metrics: null argument (sums)");
+  ImageStats p;
+  p.x = img0; p.y = img1; p.planes = 0; p.H = H; p.W = W; p.cs = 1; p.map = ssim_map; p.partials = nullptr; p.nblocks = 0; p.sums = sums;
+  if (n_images > 0) {
+    if (channels < 1) return fail("image_metrics: channels must be at least 1 (got %d)", channels);
+    if (H < 2 || W < 2) return fail("image_metrics: H and W must be at least 2, the reflected border reads a neighbour (got %d x %d)", H, W);
+    if ((double)n_images * channels * H * W >= 2147483648.0) return fail("image_metrics: the element count must be below 2^31");
+    if (channels_last && channels > kImgMaxCs) return fail("image_metrics: the channels-last form takes at most %d channels (got %d)", kImgMaxCs, channels);
+    if (!img0 || !img1 || !scratch) return fail("image_metrics: null argument");
+    if (scratch_bytes < cnr_image_scratch_bytes(n_images, channels, H, W)) return fail("image_metrics scratch too small");
+    p.cs = channels_last ? channels : 1;
+    p.planes = channels_last ? (long)n_images : (long)n_images * channels;
+    p.nblocks = image_blocks(p.planes, H, W, p.cs);
+    p.partials = static_cast<double*>(scratch);
+  }
+  be_image_stats(p, (cnr_stream)stream);
+  return check_backend("image_metrics");
+}
+
+int cnr_image_panel(const float* gt, const float* render, const float* depth, int H, int W, uint8_t* panel, float* range, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (H < 1 || W < 1) return fail("image_panel: H and W must be at least 1 (got %d x %d)", H, W);
+  if ((double)H * W * 9.0 >= 2147483648.0) return fail("image_panel: the panel must have fewer than 2^31 bytes");
+  if (!depth || !panel || !range || !scratch || (gt == nullptr) != (render == nullptr)) return fail("image_panel: null argument");
+  if (scratch_bytes < 2 * sizeof(unsigned)) return fail("image_panel scratch too small");
+  ImagePanel p;
+  p.gt = gt; p.render = render; p.depth = depth; p.H = H; p.W = W; p.nsec = gt ? 3 : 1; p.panel = panel; p.range = range;
+  p.keys = static_cast<unsigned*>(scratch);
+  be_image_panel(p, (cnr_stream)stream);
+  return check_backend("image_panel");
+}
+
 
 size_t cnr_linear_scratch_bytes(int64_t n, int32_t k, int32_t n_out, int32_t backward) {
   LinearOp op;

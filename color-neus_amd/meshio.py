@@ -1,5 +1,8 @@
 """Mesh files of the evaluation path: what NeuS_Trainer.validate_mesh writes through trimesh (NeuS_Trainer.py:287-307) --
 binary little-endian PLY, vertices float32 x y z (+ uchar red green blue alpha when coloured), faces ``list uchar int vertex_indices``."""
+import struct
+import zlib
+
 import numpy as np
 
 
@@ -113,3 +116,23 @@ def read_ply_vertices(path):
             v = np.frombuffer(buf, dtype=dt)
             return np.stack([v["x"], v["y"], v["z"]], -1).astype(np.float32).reshape(count, 3)
     raise ValueError(f"{path}: no vertex element")
+
+
+def write_png(path, image_uint8):
+    """An 8-bit PNG of a ``[H, W, 3]`` (RGB, written as given) or ``[H, W]`` (grey) uint8 array or tensor: what the reference saves with
+    imageio (NeuS_Trainer.py:274), with zlib and struct from the standard library only.  Filter type 0 on every row, one IDAT chunk."""
+    if hasattr(image_uint8, "detach"):
+        image_uint8 = image_uint8.detach().cpu().numpy()
+    img = np.ascontiguousarray(image_uint8)
+    if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"write_png: expected a uint8 [H, W, 3] or [H, W] image, got {img.dtype} {img.shape}")
+    h, w = img.shape[0], img.shape[1]
+    rows = np.zeros((h, 1 + img[0].size), dtype=np.uint8)      # a filter-type byte (0: none) in front of every row
+    rows[:, 1:] = img.reshape(h, -1)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+
+    ihdr = struct.pack(">IIBBBBB", w, h, 8, 2 if img.ndim == 3 else 0, 0, 0, 0)
+    with open(path, "wb") as fh:
+        fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", ihdr) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))

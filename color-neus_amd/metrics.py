@@ -17,21 +17,11 @@ from . import _lib, meshio
 __all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance"]
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream_of(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else C.c_void_p(0)
+_ptr, _stream_of = _lib.ptr, _lib.stream_of
 
 
 def _library(library, dev):
-    lib = library if isinstance(library, _lib.RenderLibrary) else _lib.load_library(library)
-    hip = lib.backend.startswith("hip")
-    if hip != (dev.type == "cuda"):
-        raise RuntimeError(f"points on '{dev}' cannot be searched by the '{lib.backend}' library: CUDA tensors use the HIP library, CPU tensors "
-                           "need an explicitly passed CPU-emulation library= (there is no CPU fallback)")
-    return lib
+    return _lib.library_for(library, dev, ("points", "searched"))
 
 
 def _points(x, name):

@@ -382,6 +382,45 @@ size_t cnr_nn_scratch_bytes(int64_t n_query, int64_t n_target);
 int cnr_nn_search(const float* query /* [n_query][3] */, int64_t n_query, const float* target /* [n_target][3] */, int64_t n_target,
                   float* dist2 /* [n_query] */, int32_t* idx /* [n_query] */, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- image evaluation: what NeuS_Trainer.validate_image does behind its render loop (NeuS_Trainer.py:250-277), on the device.
+ * cnr_image_metrics: sums[0] = sum of the squared differences (PSNR, lib/metrics/similarity.py:24), sums[1] = sum of the SSIM map
+ * (kornia.metrics.ssim(img0, img1, 3), similarity.py:55) over all n_images * channels * H * W elements, and optionally the map.
+ * Every operation below is one rounded fp32 operation, in the order written (no FMA; `/` is the correctly rounded IEEE quotient):
+ *   window   the normalised 3-tap Gaussian of sigma 1.5 as float32 torch evaluates it: w1 = 0x1.3b3046p-2 (outer taps), w0 = 0x1.899f76p-2
+ *   border   reflection without repeating the edge: index -1 reads 1, index n reads n - 2 (hence H >= 2 and W >= 2)
+ *   filt(p)  separable, rows first: h[r][c] = (w1*p[r][c-1] + w0*p[r][c]) + w1*p[r][c+1], then (w1*h[r-1][c] + w0*h[r][c]) + w1*h[r+1][c]
+ *   per element, x = img0 and y = img1:
+ *            mu1 = filt(x), mu2 = filt(y), e11 = filt(x*x), e22 = filt(y*y), e12 = filt(x*y)
+ *            m11 = mu1*mu1, m22 = mu2*mu2, m12 = mu1*mu2, s1 = e11 - m11, s2 = e22 - m22, s12 = e12 - m12
+ *            num = (2*m12 + 1e-4f) * (2*s12 + 9e-4f),  den = ((m11 + m22) + 1e-4f) * ((s1 + s2) + 9e-4f),  ssim = num / (den + 1e-12f)
+ *            d = x - y, squared difference d*d
+ *   Every [H][W] plane is filtered on its own: nothing reaches across channels or images.
+ * This is kornia 0.6.9's ssim(img1, img2, window_size=3, max_val=1.0, eps=1e-12, padding="same") as its documentation states it.
+ * Layout: channels_last == 0: [n_images][channels][H][W]; != 0: [n_images][H][W][channels] (at most 32 channels); ssim_map (or NULL) has the
+ * inputs' layout.  The two sums are float64, added in a fixed order (per-block partials in scratch, then one block that adds those in index
+ * order; no floating-point atomics): two calls give the same bits.  The HIP build and the CPU emulation order the float64 additions
+ * differently; their totals agree to N * 2^-53 relative (N terms of magnitude <= 1).
+ * n_images == 0 is a successful no-op that writes sums = {0, 0}.  Errors: H < 2 or W < 2, channels < 1, a null required pointer, scratch
+ * too small, 2^31 or more elements.
+ *
+ * cnr_image_panel: the picture validate_image saves (NeuS_Trainer.py:250-263), uint8 [H][3W][3] = gt | render | depth, and
+ * range = {vmin, vmax} of the depth.  With gt == render == NULL only the depth map is written, [H][W][3].
+ *   colour   q = (uint8)(int)min(max(v * 255.0f, 0.0f), 255.0f): truncation, as rgb.mul(255.0).numpy().astype(np.uint8) (:252-256); NaN gives 0.
+ *            The clamp is a deviation: numpy wraps values outside [0, 256).
+ *   depth    viztools.cmap (lib/models/tools/viztools.py:145-162): vmin / vmax over the non-NaN depths ({0, 0} when there is none; exact and
+ *            order-independent), t = (d - vmin) / (vmax - vmin), v = (int)(t * 255.0f) clamped to [0, 255]; a range below 1e-10f or a NaN
+ *            depth gives v = 0.  Then the HOT ramp with u = v / 255.0f: r = clamp(2.5f*u), g = clamp(2.5f*u - 1.0f), b = clamp(5.0f*u - 4.0f),
+ *            clamp to [0, 1], each channel (uint8)(int)(255.0f*c + 0.5f), stored in cv2's order B, G, R (what the reference's cmap returns
+ *            and writes into its panel unswapped).  These are the three lines that OpenCV's 64-sample HOT table samples; cv2 interpolates its
+ *            256 entries from those samples, so its table can differ from this one by a level or two beside the knees at 0.4 and 0.8.
+ * scratch for either call: cnr_image_scratch_bytes (for the panel: of (1, 3, H, W)); contents need not be initialised. */
+size_t cnr_image_scratch_bytes(int64_t n_images, int channels, int H, int W);
+int cnr_image_metrics(const float* img0, const float* img1, int64_t n_images, int channels, int H, int W, int channels_last,
+                      float* ssim_map /* same layout as the inputs, or null */, double* sums /* [2] */,
+                      void* scratch, size_t scratch_bytes, void* stream);
+int cnr_image_panel(const float* gt /* [H][W][3] */, const float* render /* [H][W][3] */, const float* depth /* [H][W] */, int H, int W,
+                    uint8_t* panel /* [H][3W][3] */, float* range /* [2]: vmin, vmax */, void* scratch, size_t scratch_bytes, void* stream);
+
 /* extract_color: rgb = color_network(pts, g, -g, feat) per vertex (NeuS.py:44-64) */
 size_t cnr_vertex_color_scratch_bytes(const cnr_config* cfg, int64_t n_points);
 int cnr_vertex_color(const cnr_config* cfg, const float* const* params, const float* verts, int64_t n_points,
