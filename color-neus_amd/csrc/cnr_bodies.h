@@ -657,33 +657,18 @@ CNR_HD void body_bg_rays_bwd(const BgRaysBwd& p, long ray) {
 }
 
 // one foreground section of render_core (Color_NeuS.py:41-90 / NeuS.py:209-256)
-struct FgSample { float dist, inside, relax, gn, g[3]; AlphaOut a; };
-CNR_HD FgSample fg_sample(const CompositeBg& p, long ray, int j, float inv_s) {
-  FgSample q;
-  const float* z = p.z + ray * p.M;
-  const float* o = p.o + ray * 3;
-  const float* d = p.d + ray * 3;
-  q.dist = j + 1 < p.M ? z[j + 1] - z[j] : p.sample_dist;
-  const float mid = z[j] + q.dist * 0.5f;
-  const float x = o[0] + d[0] * mid, y = o[1] + d[1] * mid, w = o[2] + d[2] * mid;
-  const float pn = sqrtf(x * x + y * y + w * w);
-  q.inside = pn < 1.0f ? 1.0f : 0.0f;
-  q.relax = pn < 1.2f ? 1.0f : 0.0f;
-  const long pt = ray * p.M + j;
-  for (int c = 0; c < 3; ++c) q.g[c] = p.g[pt * 3 + c];
-  q.gn = sqrtf(q.g[0] * q.g[0] + q.g[1] * q.g[1] + q.g[2] * q.g[2]);
-  q.a = alpha_forward(p.sdf[pt], q.g, d, q.dist, inv_s, p.cos_anneal);
-  return q;
+CNR_HD RaySample fg_sample(const CompositeBg& p, long ray, int j, float inv_s) {
+  return ray_sample(p.z + ray * p.M, j, p.M, p.sample_dist, p.o + ray * 3, p.d + ray * 3, p.sdf, p.g, ray * p.M + j, inv_s, p.cos_anneal);
 }
 CNR_HD void body_composite_bg(const CompositeBg& p, long ray) {
   const int M = p.M, MF = p.MF;
-  const float inv_s = fminf(fmaxf(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]);
   float T = 1.0f, Tin = 1.0f, wsum = 0.f, wmax = -1.f, dep = 0.f, col[3] = {0.f, 0.f, 0.f}, gcl[3] = {0.f, 0.f, 0.f}, e0 = 0.f, e1 = 0.f;
   for (int j = 0; j < MF; ++j) {
     float alpha = p.bg_alpha[ray * MF + j];
     float c3[3] = {p.bg_color[(ray * MF + j) * 3], p.bg_color[(ray * MF + j) * 3 + 1], p.bg_color[(ray * MF + j) * 3 + 2]};
     if (j < M) {
-      const FgSample q = fg_sample(p, ray, j, inv_s);
+      const RaySample q = fg_sample(p, ray, j, inv_s);
       const long pt = ray * M + j;
       alpha = q.a.alpha * q.inside + alpha * (1.0f - q.inside);
       for (int k = 0; k < 3; ++k) c3[k] = p.color[pt * 3 + k] * q.inside + c3[k] * (1.0f - q.inside);
@@ -711,7 +696,7 @@ CNR_HD void body_composite_bg(const CompositeBg& p, long ray) {
 CNR_HD void body_composite_bg_bwd(const CompositeBgBwd& b, long ray) {
   const CompositeBg& p = b.f;
   const int M = p.M, MF = p.MF;
-  const float inv_s = fminf(fmaxf(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]);
   const float* d = p.d + ray * 3;
   const float* w = p.weights + ray * MF;
   // per-ray cotangents
@@ -733,7 +718,7 @@ CNR_HD void body_composite_bg_bwd(const CompositeBgBwd& b, long ray) {
     for (int j = 0; j < MF; ++j) {
       double alpha = p.bg_alpha[ray * MF + j];
       if (j < M) {
-        const FgSample q = fg_sample(p, ray, j, inv_s);
+        const RaySample q = fg_sample(p, ray, j, inv_s);
         const AlphaOutD ad = alpha_forward_d(p.sdf[ray * M + j], q.g, d, q.dist, inv_s, p.cos_anneal);
         const double a_in = fmin(fmax(ad.a_raw, 0.0), 1.0);
         alpha = a_in * q.inside + alpha * (1.0 - q.inside);
@@ -749,7 +734,7 @@ CNR_HD void body_composite_bg_bwd(const CompositeBgBwd& b, long ray) {
     const long fj = ray * MF + j;
     float bc[3] = {p.bg_color[fj * 3], p.bg_color[fj * 3 + 1], p.bg_color[fj * 3 + 2]};
     float c3[3] = {bc[0], bc[1], bc[2]};
-    FgSample q;
+    RaySample q;
     q.inside = 0.0f;
     if (j < M) {
       q = fg_sample(p, ray, j, inv_s);
@@ -802,5 +787,28 @@ CNR_HD void body_composite_bg_bwd(const CompositeBgBwd& b, long ray) {
   b.d_inv_s_partial[ray] = (float)dinvs;                              // (the clip of inv_s is applied by the variance reduction, be_variance_finish)
   for (int c = 0; c < 3; ++c) b.d_rays_d[ray * 3 + c] = drd[c];
 }
+
+// The point-wise kernels whose HIP form is the plain grid-stride loop over a body: X(name, parameter struct, body, element count of p).
+// The HIP file expands a row into kernel + launch + be_<name>, the emulation into an OpenMP loop.  (The row-staged embed_z / embed_pts /
+// fine_setup and the 16-lanes-per-point grad_finish / gbar_finish have HIP kernels of their own.)
+#define CNR_POINTWISE_KERNELS(X)                                                                          \
+  X(coltop_bwd, ColTopBwd, body_coltop_bwd, p.P)                                                          \
+  X(pbar_finish, PbarFinish, body_pbar_finish, p.P)                                                       \
+  X(query_in, QueryIn, body_query_in, p.P * 3)                                                            \
+  X(query_seed, QuerySeed, body_query_seed, p.P * (p.ldztop / 4) + (p.gbar ? p.P : 0))                    \
+  X(query_out, QueryOut, body_query_out, query_out_count(p))                                              \
+  X(gen_rays, GenRays, body_gen_rays, p.n)                                                                \
+  X(camera_fwd, Camera, body_camera_fwd, p.c2w && p.B > 1 ? p.B : 1)                                      \
+  X(camera_bwd, CameraBwd, body_camera_bwd, p.d_c2w && p.f.num_cams > 1 ? p.f.num_cams : 1)               \
+  X(outside_z, OutsideZ, body_outside_z, p.R)                                                             \
+  X(outside_z_bwd, OutsideZBwd, body_outside_z_bwd, p.R)                                                  \
+  X(bg_embed, BgEmbed, body_bg_embed, p.R * p.MF)                                                         \
+  X(bg_alpha, BgAlpha, body_bg_alpha, p.n)                                                                \
+  X(bg_heads_bwd, BgHeadsBwd, body_bg_heads_bwd, p.n)                                                     \
+  X(bg_join, BgJoin, body_bg_join, p.n * p.W)                                                             \
+  X(bg_embed_bwd, BgEmbedBwd, body_bg_embed_bwd, p.R * p.MF)                                              \
+  X(bg_rays_bwd, BgRaysBwd, body_bg_rays_bwd, p.R)                                                        \
+  X(composite_bg, CompositeBg, body_composite_bg, p.R)                                                    \
+  X(composite_bg_bwd, CompositeBgBwd, body_composite_bg_bwd, p.f.R)
 
 }  // namespace cnr

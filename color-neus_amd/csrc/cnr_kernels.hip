@@ -373,12 +373,14 @@ void be_strip_bwd(const StripBwd& p, cnr_stream s) {
 // ================================================================================================
 // point-wise kernels
 // ================================================================================================
-#define CNR_PW_KERNEL(NAME, PARAM, BODY)                                                    \
+// one row of CNR_POINTWISE_KERNELS (cnr_bodies.h): the grid-stride kernel over the body and be_<name>, which launches it on the row's element count
+#define CNR_PW_KERNEL(NAME, PARAM, BODY, COUNT)                                              \
   __global__ __launch_bounds__(256) void NAME##_kernel(const PARAM p, long n) {              \
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)   \
       BODY(p, i);                                                                            \
   }                                                                                          \
-  static void NAME##_launch(const PARAM& p, long n, cnr_stream s) {                          \
+  void be_##NAME(const PARAM& p, cnr_stream s) {                                             \
+    const long n = (COUNT);                                                                  \
     if (n <= 0) return;                                                                      \
     long blocks = (n + 255) / 256;                                                           \
     if (blocks > 8192) blocks = 8192;                                                        \
@@ -386,6 +388,7 @@ void be_strip_bwd(const StripBwd& p, cnr_stream s) {
     hipLaunchKernelGGL(NAME##_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, n);        \
     CNR_LAUNCH_CHECK(#NAME);                                                                 \
   }
+CNR_POINTWISE_KERNELS(CNR_PW_KERNEL)
 
 // Point-wise kernels that write kEmb / kAux-wide ROWS (192 B per point): a thread computes its point's rows into LDS (row stride 49 floats:
 // conflict-free), then the block stores the 128 rows -- one contiguous 24 KB piece of the output -- with fully coalesced accesses (a thread
@@ -417,48 +420,9 @@ static void staged_rows_launch(const char* name, const PARAM& p, long n, float* 
   TimingScope ts_(name, 2, 0, n, 0, 0, 0, s);
   hipLaunchKernelGGL((staged_rows_kernel<PARAM, ROWS>), dim3((unsigned)blocks), dim3(kRowsPerBlock), 0, s, p, n, E, AUX);
 }
-static void embed_z_launch(const EmbedZ& p, long n, cnr_stream s) { staged_rows_launch<EmbedZ, body_embed_z_rows>("embed_z", p, n, p.E, nullptr, s); CNR_LAUNCH_CHECK("embed_z"); }
-static void embed_pts_launch(const EmbedPts& p, long n, cnr_stream s) { staged_rows_launch<EmbedPts, body_embed_pts_rows>("embed_pts", p, n, p.E, p.AUX, s); CNR_LAUNCH_CHECK("embed_pts"); }
-static void fine_setup_launch(const FineSetup& p, long n, cnr_stream s) { staged_rows_launch<FineSetup, body_fine_setup_rows>("fine_setup", p, n, p.E, p.AUX, s); CNR_LAUNCH_CHECK("fine_setup"); }
-CNR_PW_KERNEL(coltop_bwd, ColTopBwd, body_coltop_bwd)
-// N_OUTSIDE > 0 (NeRF++ background): plain per-ray / per-point kernels
-CNR_PW_KERNEL(outside_z, OutsideZ, body_outside_z)
-CNR_PW_KERNEL(outside_z_bwd, OutsideZBwd, body_outside_z_bwd)
-CNR_PW_KERNEL(bg_embed, BgEmbed, body_bg_embed)
-CNR_PW_KERNEL(bg_alpha, BgAlpha, body_bg_alpha)
-CNR_PW_KERNEL(bg_heads_bwd, BgHeadsBwd, body_bg_heads_bwd)
-CNR_PW_KERNEL(bg_join, BgJoin, body_bg_join)
-CNR_PW_KERNEL(bg_embed_bwd, BgEmbedBwd, body_bg_embed_bwd)
-CNR_PW_KERNEL(bg_rays_bwd, BgRaysBwd, body_bg_rays_bwd)
-CNR_PW_KERNEL(composite_bg, CompositeBg, body_composite_bg)
-CNR_PW_KERNEL(composite_bg_bwd, CompositeBgBwd, body_composite_bg_bwd)
-void be_outside_z(const OutsideZ& p, cnr_stream s) { outside_z_launch(p, p.R, s); }
-void be_outside_z_bwd(const OutsideZBwd& p, cnr_stream s) { outside_z_bwd_launch(p, p.R, s); }
-void be_bg_embed(const BgEmbed& p, cnr_stream s) { bg_embed_launch(p, p.R * p.MF, s); }
-void be_bg_alpha(const BgAlpha& p, cnr_stream s) { bg_alpha_launch(p, p.n, s); }
-void be_bg_heads_bwd(const BgHeadsBwd& p, cnr_stream s) { bg_heads_bwd_launch(p, p.n, s); }
-void be_bg_join(const BgJoin& p, cnr_stream s) { bg_join_launch(p, p.n * p.W, s); }
-void be_bg_embed_bwd(const BgEmbedBwd& p, cnr_stream s) { bg_embed_bwd_launch(p, p.R * p.MF, s); }
-void be_bg_rays_bwd(const BgRaysBwd& p, cnr_stream s) { bg_rays_bwd_launch(p, p.R, s); }
-void be_composite_bg(const CompositeBg& p, cnr_stream s) { composite_bg_launch(p, p.R, s); }
-void be_composite_bg_bwd(const CompositeBgBwd& p, cnr_stream s) { composite_bg_bwd_launch(p, p.f.R, s); }
-CNR_PW_KERNEL(pbar_finish, PbarFinish, body_pbar_finish)
-CNR_PW_KERNEL(gen_rays, GenRays, body_gen_rays)
-
-void be_embed_z(const EmbedZ& p, cnr_stream s) { embed_z_launch(p, p.R * p.m, s); }
-void be_embed_pts(const EmbedPts& p, cnr_stream s) { embed_pts_launch(p, p.n, s); }
-void be_fine_setup(const FineSetup& p, cnr_stream s) { fine_setup_launch(p, p.R * p.M, s); }
-void be_coltop_bwd(const ColTopBwd& p, cnr_stream s) { coltop_bwd_launch(p, p.P, s); }
-void be_pbar_finish(const PbarFinish& p, cnr_stream s) { pbar_finish_launch(p, p.P, s); }
-
-// SDF point queries: the glue between the caller's dense rows and the padded rows of the render path's buffers
-CNR_PW_KERNEL(query_in, QueryIn, body_query_in)
-CNR_PW_KERNEL(query_seed, QuerySeed, body_query_seed)
-CNR_PW_KERNEL(query_out, QueryOut, body_query_out)
-void be_query_in(const QueryIn& p, cnr_stream s) { query_in_launch(p, p.P * 3, s); }
-void be_query_seed(const QuerySeed& p, cnr_stream s) { query_seed_launch(p, p.P * (p.ldztop / 4) + (p.gbar ? p.P : 0), s); }
-void be_query_out(const QueryOut& p, cnr_stream s) { query_out_launch(p, query_out_count(p), s); }
-
+void be_embed_z(const EmbedZ& p, cnr_stream s) { staged_rows_launch<EmbedZ, body_embed_z_rows>("embed_z", p, p.R * p.m, p.E, nullptr, s); CNR_LAUNCH_CHECK("embed_z"); }
+void be_embed_pts(const EmbedPts& p, cnr_stream s) { staged_rows_launch<EmbedPts, body_embed_pts_rows>("embed_pts", p, p.n, p.E, p.AUX, s); CNR_LAUNCH_CHECK("embed_pts"); }
+void be_fine_setup(const FineSetup& p, cnr_stream s) { staged_rows_launch<FineSetup, body_fine_setup_rows>("fine_setup", p, p.R * p.M, p.E, p.AUX, s); CNR_LAUNCH_CHECK("fine_setup"); }
 
 // ------------------------------------------------------------------------------------------------
 // PE-Jacobian kernels: 16 lanes per point, lane j owns the column triple [3j, 3j+3) of the 48-wide rows
@@ -1002,10 +966,7 @@ __global__ __launch_bounds__(256) void variance_finish_kernel(const VarianceFini
   float a = 0.0f;
   for (long r = threadIdx.x; r < p.R; r += 256) a += p.partial[r];
   a = block_sum_256(a, red);
-  if (threadIdx.x == 0) {
-    float raw = expf(p.variance[0] * 10.0f);
-    *p.d_variance = (raw >= 1e-6f && raw <= 1e6f) ? a * 10.0f * raw : 0.0f;
-  }
+  if (threadIdx.x == 0) *p.d_variance = inv_s_backward(p.variance[0], a);
 }
 void be_variance_finish(const VarianceFinish& p, cnr_stream s) {
   TimingScope ts_("variance_finish", 2, 0, p.R, 0, 0, 0, s);
@@ -1026,11 +987,62 @@ __device__ __forceinline__ float wave_scan_incl_mul(float x, int lane) {
   for (int d = 1; d < 64; d <<= 1) { float y = __shfl_up(x, d); if (lane >= d) x = y * x; }
   return x;
 }
+// exclusive product scan along a ray in chunks of 64: the product of f over the lanes below times the carry of the earlier chunks, which
+// then takes this chunk in
+__device__ __forceinline__ float wave_excl_cumprod(float f, int lane, float& carry) {
+  const float incl = wave_scan_incl_mul(f, lane);
+  float excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = 1.0f;
+  const float T = carry * excl;
+  carry = carry * __shfl(incl, 63);
+  return T;
+}
 // reverse inclusive scan: result[lane] = sum_{l >= lane} x[l]
 __device__ __forceinline__ float wave_scan_incl_add_rev(float x, int lane) {
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) { float y = __shfl_down(x, d); if (lane + d < 64) x = x + y; }
   return x;
+}
+
+// ---- building blocks of the sampler kernels (merge_kernel, upsample_kernel, sampler_step_kernel): one wavefront works on one ray's rows
+// in LDS.  None of them holds a barrier: every kernel places its own between the stages.
+// slope of the sdf along the ray in every section -> cs
+__device__ __forceinline__ void ray_section_slopes(const float* zs, const float* ss, int nsec, float* cs, int lane) {
+  for (int i = lane; i < nsec; i += 64) cs[i] = upsample_slope(ss[i], ss[i + 1], zs[i], zs[i + 1]);
+}
+// section alpha of up_sample from the slopes cs and the radii rs -> as
+__device__ __forceinline__ void ray_section_alphas(const float* zs, const float* ss, const float* cs, const float* rs, int nsec, float inv_s, float* as, int lane) {
+  for (int i = lane; i < nsec; i += 64) {
+    const float c = upsample_cos(i > 0 ? cs[i - 1] : 0.0f, cs[i], rs[i], rs[i + 1]);
+    as[i] = upsample_alpha(ss[i], ss[i + 1], zs[i], zs[i + 1], c, inv_s);
+  }
+}
+// as: section alphas -> weights = alpha * exclusive cumprod(1 - alpha + 1e-7), + 1e-5 (sample_pdf); given_w: as already holds the weights.
+// Returns their sum
+__device__ __forceinline__ float ray_pdf_weights(float* as, int nsec, bool given_w, int lane) {
+  float carry = 1.0f, part = 0.0f;
+  for (int base = 0; base < nsec; base += 64) {
+    const int i = base + lane;
+    const bool ok = i < nsec;
+    const float a = ok ? as[i] : 0.0f;
+    const float T = wave_excl_cumprod(ok ? 1.0f - a + 1e-7f : 1.0f, lane, carry);
+    const float w = (given_w ? a : a * T) + 1e-5f;
+    if (ok) { as[i] = w; part += w; }
+  }
+  return wave_sum(part);
+}
+// cdf of the weights as (nsec + 1 entries, cdf[0] = 0) -> cs
+__device__ __forceinline__ void ray_cdf(const float* as, float total, int nsec, float* cs, int lane) {
+  float csum = 0.0f;
+  for (int base = 0; base < nsec; base += 64) {
+    const int i = base + lane;
+    const bool ok = i < nsec;
+    const float pdf = ok ? as[i] / total : 0.0f;
+    const float incl = wave_scan_incl_add(pdf, lane);
+    if (ok) cs[i + 1] = csum + incl;
+    csum = csum + __shfl(incl, 63);
+  }
+  if (lane == 0) cs[0] = 0.0f;
 }
 
 __global__ __launch_bounds__(256) void upsample_kernel(const UpSample p) {
@@ -1052,63 +1064,21 @@ __global__ __launch_bounds__(256) void upsample_kernel(const UpSample p) {
       float z = p.z[ray * p.ldz + i];
       zs[i] = z;
       ss[i] = p.sdf[ray * p.lds + i];
-      float x = o[0] + d[0] * z, y = o[1] + d[1] * z, w = o[2] + d[2] * z;
-      rs[i] = sqrtf(x * x + y * y + w * w);
+      rs[i] = ray_radius(o, d, z);
     }
   }
   __syncthreads();
-  if (!given_w) for (int i = lane; i < nsec; i += 64) cs[i] = (ss[i + 1] - ss[i]) / (zs[i + 1] - zs[i] + 1e-5f);
+  if (!given_w) ray_section_slopes(zs, ss, nsec, cs, lane);
   __syncthreads();
-  if (!given_w)
-    for (int i = lane; i < nsec; i += 64) {
-      float prev = i > 0 ? cs[i - 1] : 0.0f;
-      float c = fminf(prev, cs[i]);
-      c = fminf(fmaxf(c, -1e3f), 0.0f);
-      const bool inside = rs[i] < 1.0f || rs[i + 1] < 1.0f;
-      c = inside ? c : c * 0.0f;
-      as[i] = upsample_alpha(ss[i], ss[i + 1], zs[i], zs[i + 1], c, p.inv_s);
-    }
+  if (!given_w) ray_section_alphas(zs, ss, cs, rs, nsec, p.inv_s, as, lane);
   __syncthreads();
-  // weights = alpha * exclusive cumprod(1 - alpha + 1e-7), + 1e-5 (sample_pdf), and their sum
-  float carry = 1.0f, part = 0.0f;
-  for (int base = 0; base < nsec; base += 64) {
-    const int i = base + lane;
-    const bool ok = i < nsec;
-    const float a = ok ? as[i] : 0.0f;
-    const float f = ok ? 1.0f - a + 1e-7f : 1.0f;
-    const float incl = wave_scan_incl_mul(f, lane);
-    float excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 1.0f;
-    const float w = (given_w ? a : a * (carry * excl)) + 1e-5f;
-    if (ok) { as[i] = w; part += w; }
-    carry = carry * __shfl(incl, 63);
-  }
-  const float total = wave_sum(part);
+  const float total = ray_pdf_weights(as, nsec, given_w, lane);
   __syncthreads();
-  // cdf (n entries, cdf[0] = 0) -> cs
-  float csum = 0.0f;
-  for (int base = 0; base < nsec; base += 64) {
-    const int i = base + lane;
-    const bool ok = i < nsec;
-    const float pdf = ok ? as[i] / total : 0.0f;
-    const float incl = wave_scan_incl_add(pdf, lane);
-    if (ok) cs[i + 1] = csum + incl;
-    csum = csum + __shfl(incl, 63);
-  }
-  if (lane == 0) cs[0] = 0.0f;
+  ray_cdf(as, total, nsec, cs, lane);
   __syncthreads();
   if (lane < p.m && active) {
     const float u = p.u_in ? p.u_in[ray * p.m + lane] : linspace_at(0.5f / (float)p.m, 1.0f - 0.5f / (float)p.m, p.m, lane);
-    int lo = 0, hi = n;
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (cs[mid] > u) hi = mid; else lo = mid + 1; }
-    const int below = lo - 1 > 0 ? lo - 1 : 0;
-    const int above = lo < n - 1 ? lo : n - 1;
-    const float c0 = cs[below], c1 = cs[above];
-    const float b0 = zs[below], b1 = zs[above];
-    float den = c1 - c0;
-    if (den < 1e-5f) den = 1.0f;
-    const float t = (u - c0) / den;
-    p.new_z[ray * p.m + lane] = b0 + t * (b1 - b0);
+    p.new_z[ray * p.m + lane] = invert_cdf(cs, zs, n, u);
   }
 }
 void be_upsample(const UpSample& p, cnr_stream s) {
@@ -1130,27 +1100,14 @@ __global__ __launch_bounds__(256) void merge_kernel(const MergeZ p) {
   for (int i = lane; i < p.n; i += 64) { zs[i] = p.z[ray * p.ldz + i]; ss[i] = with_sdf ? p.sdf_in[ray * p.lds_in + i] : 0.0f; }
   for (int j = lane; j < p.m; j += 64) { nz[j] = p.new_z[ray * p.m + j]; ns[j] = with_sdf ? p.new_sdf[ray * p.m + j] : 0.0f; }
   __syncthreads();
-  if (active) {
-    for (int i = lane; i < p.n; i += 64) {   // old sample i: stable position = i + #(new < z_i)
-      const float z = zs[i];
-      int cnt = 0;
-      for (int j = 0; j < p.m; ++j) cnt += nz[j] < z ? 1 : 0;
-      p.z[ray * p.ldz + i + cnt] = z;
-      if (with_sdf) p.sdf_out[ray * p.lds_out + i + cnt] = ss[i];
-    }
-    for (int j = lane; j < p.m; j += 64) {   // new sample j: position = j + #(old <= new_j), new samples keep their order
-      const float z = nz[j];
-      int lo = 0, hi = p.n;
-      while (lo < hi) { int mid = (lo + hi) >> 1; if (zs[mid] > z) hi = mid; else lo = mid + 1; }
-      int rank = 0;   // rank among the new samples (they are monotone in practice; this keeps the merge a bijection regardless)
-      for (int q2 = 0; q2 < p.m; ++q2) rank += (nz[q2] < z || (nz[q2] == z && q2 < j)) ? 1 : 0;
-      p.z[ray * p.ldz + lo + rank] = z;
-      if (with_sdf) p.sdf_out[ray * p.lds_out + lo + rank] = ns[j];
-    }
-  }
+  if (active)
+    merge_samples(zs, ss, p.n, nz, ns, p.m, lane, 64, [&](int at, float z, float s) {
+      p.z[ray * p.ldz + at] = z;
+      if (with_sdf) p.sdf_out[ray * p.lds_out + at] = s;
+    });
 }
-// merge (previous iteration) + up_sample + embedding of the new samples for one ray per wavefront: the arithmetic of merge_kernel,
-// upsample_kernel and the EmbedZ body, with the merged row handed over in LDS instead of through three launches
+// merge (previous iteration) + up_sample + embedding of the new samples for one ray per wavefront: the stages of merge_kernel and
+// upsample_kernel and the EmbedZ rows, with the merged row handed over in LDS instead of through three launches
 __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerStep p) {
   __shared__ float sh[4][7][kMaxRaySamples];
   __shared__ float shn[4][2][64];
@@ -1169,20 +1126,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerStep p) 
     for (int i = lane; i < g.n; i += 64) { zo[i] = g.z[ray * g.ldz + i]; so[i] = g.sdf_in[ray * g.lds_in + i]; }
     for (int j = lane; j < g.m; j += 64) { nz[j] = g.new_z[ray * g.m + j]; ns[j] = g.new_sdf[ray * g.m + j]; }
     __syncthreads();
-    for (int i = lane; i < g.n; i += 64) {   // old sample i: stable position = i + #(new < z_i)
-      const float z = zo[i];
-      int cnt = 0;
-      for (int j = 0; j < g.m; ++j) cnt += nz[j] < z ? 1 : 0;
-      zs[i + cnt] = z; ss[i + cnt] = so[i];
-    }
-    for (int j = lane; j < g.m; j += 64) {   // new sample j: position = j + #(old <= new_j), new samples keep their order
-      const float z = nz[j];
-      int lo = 0, hi = g.n;
-      while (lo < hi) { int mid = (lo + hi) >> 1; if (zo[mid] > z) hi = mid; else lo = mid + 1; }
-      int rank = 0;
-      for (int q2 = 0; q2 < g.m; ++q2) rank += (nz[q2] < z || (nz[q2] == z && q2 < j)) ? 1 : 0;
-      zs[lo + rank] = z; ss[lo + rank] = ns[j];
-    }
+    merge_samples(zo, so, g.n, nz, ns, g.m, lane, 64, [&](int at, float z, float s) { zs[at] = z; ss[at] = s; });
     __syncthreads();
     if (active)
       for (int i = lane; i < n; i += 64) { g.z[ray * g.ldz + i] = zs[i]; g.sdf_out[ray * g.lds_out + i] = ss[i]; }
@@ -1190,61 +1134,18 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const SamplerStep p) 
     for (int i = lane; i < n; i += 64) { zs[i] = u.z[ray * u.ldz + i]; ss[i] = u.sdf[ray * u.lds + i]; }
     __syncthreads();
   }
-  for (int i = lane; i < n; i += 64) {
-    const float z = zs[i];
-    const float x = o[0] + d[0] * z, y = o[1] + d[1] * z, w = o[2] + d[2] * z;
-    rs[i] = sqrtf(x * x + y * y + w * w);
-  }
+  for (int i = lane; i < n; i += 64) rs[i] = ray_radius(o, d, zs[i]);
   __syncthreads();
-  for (int i = lane; i < nsec; i += 64) cs[i] = (ss[i + 1] - ss[i]) / (zs[i + 1] - zs[i] + 1e-5f);
+  ray_section_slopes(zs, ss, nsec, cs, lane);
   __syncthreads();
-  for (int i = lane; i < nsec; i += 64) {
-    float prev = i > 0 ? cs[i - 1] : 0.0f;
-    float c = fminf(prev, cs[i]);
-    c = fminf(fmaxf(c, -1e3f), 0.0f);
-    const bool inside = rs[i] < 1.0f || rs[i + 1] < 1.0f;
-    c = inside ? c : c * 0.0f;
-    as[i] = upsample_alpha(ss[i], ss[i + 1], zs[i], zs[i + 1], c, u.inv_s);
-  }
+  ray_section_alphas(zs, ss, cs, rs, nsec, u.inv_s, as, lane);
   __syncthreads();
-  float carry = 1.0f, part = 0.0f;
-  for (int base = 0; base < nsec; base += 64) {
-    const int i = base + lane;
-    const bool ok = i < nsec;
-    const float a = ok ? as[i] : 0.0f;
-    const float f = ok ? 1.0f - a + 1e-7f : 1.0f;
-    const float incl = wave_scan_incl_mul(f, lane);
-    float excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 1.0f;
-    const float w = a * (carry * excl) + 1e-5f;
-    if (ok) { as[i] = w; part += w; }
-    carry = carry * __shfl(incl, 63);
-  }
-  const float total = wave_sum(part);
+  const float total = ray_pdf_weights(as, nsec, false, lane);
   __syncthreads();
-  float csum = 0.0f;
-  for (int base = 0; base < nsec; base += 64) {
-    const int i = base + lane;
-    const bool ok = i < nsec;
-    const float pdf = ok ? as[i] / total : 0.0f;
-    const float incl = wave_scan_incl_add(pdf, lane);
-    if (ok) cs[i + 1] = csum + incl;
-    csum = csum + __shfl(incl, 63);
-  }
-  if (lane == 0) cs[0] = 0.0f;
+  ray_cdf(as, total, nsec, cs, lane);
   __syncthreads();
   if (lane < u.m) {
-    const float uu = linspace_at(0.5f / (float)u.m, 1.0f - 0.5f / (float)u.m, u.m, lane);
-    int lo = 0, hi = n;
-    while (lo < hi) { int mid = (lo + hi) >> 1; if (cs[mid] > uu) hi = mid; else lo = mid + 1; }
-    const int below = lo - 1 > 0 ? lo - 1 : 0;
-    const int above = lo < n - 1 ? lo : n - 1;
-    const float c0 = cs[below], c1 = cs[above];
-    const float b0 = zs[below], b1 = zs[above];
-    float den = c1 - c0;
-    if (den < 1e-5f) den = 1.0f;
-    const float t = (uu - c0) / den;
-    const float znew = b0 + t * (b1 - b0);
+    const float znew = invert_cdf(cs, zs, n, linspace_at(0.5f / (float)u.m, 1.0f - 0.5f / (float)u.m, u.m, lane));
     nz[lane] = znew;
     if (active) u.new_z[ray * u.m + lane] = znew;
   }
@@ -1286,32 +1187,6 @@ void be_merge(const MergeZ& p, cnr_stream s) {
 
 constexpr int kRayChunks = kMaxRaySamples / 64;
 
-struct RaySample {   // forward quantities of one sample, recomputed identically in forward and backward
-  bool ok;
-  float z, dist, relax, inside, gn;
-  float g[3];
-  AlphaOut a;
-};
-
-__device__ __forceinline__ RaySample ray_sample(const float* zs, int j, int M, float sample_dist, const float o[3], const float d[3],
-                                                const float* sdf, const float* g, long pt, float inv_s, float r) {
-  RaySample q;
-  q.ok = j < M;
-  const int jj = q.ok ? j : M - 1;
-  q.z = zs[jj];
-  q.dist = jj + 1 < M ? zs[jj + 1] - q.z : sample_dist;
-  const float mid = q.z + q.dist * 0.5f;
-  const float x = o[0] + d[0] * mid, y = o[1] + d[1] * mid, w = o[2] + d[2] * mid;
-  const float pn = sqrtf(x * x + y * y + w * w);
-  q.inside = pn < 1.0f ? 1.0f : 0.0f;
-  q.relax = pn < 1.2f ? 1.0f : 0.0f;
-  const long p2 = q.ok ? pt : pt - (j - jj);
-  q.g[0] = g[p2 * 3]; q.g[1] = g[p2 * 3 + 1]; q.g[2] = g[p2 * 3 + 2];
-  q.gn = sqrtf(q.g[0] * q.g[0] + q.g[1] * q.g[1] + q.g[2] * q.g[2]);
-  q.a = alpha_forward(sdf[p2], q.g, d, q.dist, inv_s, r);
-  return q;
-}
-
 __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompositeFwd p) {
   __shared__ float shz[4][kMaxRaySamples];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1324,7 +1199,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompositeFwd p
   __syncthreads();
   float o[3], d[3];
   for (int c = 0; c < 3; ++c) { o[c] = p.o[ray * 3 + c]; d[c] = p.d[ray * 3 + c]; }
-  const float inv_s = fminf(fmaxf(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]);
 
   float carry = 1.0f;
   float wsum = 0.f, wmax = -1.f, dep = 0.f, col[3] = {0.f, 0.f, 0.f}, gcl[3] = {0.f, 0.f, 0.f}, e0 = 0.f, e1 = 0.f, drs = 0.f;
@@ -1335,12 +1210,8 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(const CompositeFwd p
       const long pt = ray * M + j;
       if (p.delta && j < M) drs += (p.delta[pt * 3] + p.delta[pt * 3 + 1]) + p.delta[pt * 3 + 2];
       RaySample q = ray_sample(zs, j, M, p.sample_dist, o, d, p.sdf, p.g, pt, inv_s, p.cos_anneal);
-      const float f = q.ok ? 1.0f - q.a.alpha + 1e-7f : 1.0f;
-      const float incl = wave_scan_incl_mul(f, lane);
-      float excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = 1.0f;
-      const float w = q.ok ? q.a.alpha * (carry * excl) : 0.0f;
-      carry = carry * __shfl(incl, 63);
+      const float T = wave_excl_cumprod(q.ok ? 1.0f - q.a.alpha + 1e-7f : 1.0f, lane, carry);
+      const float w = q.ok ? q.a.alpha * T : 0.0f;
       if (q.ok) {
         wsum += w; wmax = fmaxf(wmax, w); dep += w * q.z;
         if (p.color) for (int k = 0; k < 3; ++k) col[k] += w * p.color[pt * p.ldcolor + k];   // (null: the weights-only pass in front of the compaction)
@@ -1394,7 +1265,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwd p
   __syncthreads();
   float o[3], d[3];
   for (int c = 0; c < 3; ++c) { o[c] = p.o[ray * 3 + c]; d[c] = p.d[ray * 3 + c]; }
-  const float inv_s = fminf(fmaxf(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]);
 
   RaySample q[kRayChunks];
   float T[kRayChunks], w[kRayChunks];
@@ -1405,13 +1276,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwd p
     if (c * 64 < M) {
       const int j = c * 64 + lane;
       q[c] = ray_sample(zs, j, M, p.sample_dist, o, d, p.sdf, p.g, ray * M + j, inv_s, p.cos_anneal);
-      const float f = q[c].ok ? 1.0f - q[c].a.alpha + 1e-7f : 1.0f;
-      const float incl = wave_scan_incl_mul(f, lane);
-      float excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = 1.0f;
-      T[c] = carry * excl;
+      T[c] = wave_excl_cumprod(q[c].ok ? 1.0f - q[c].a.alpha + 1e-7f : 1.0f, lane, carry);
       w[c] = q[c].ok ? q[c].a.alpha * T[c] : 0.0f;
-      carry = carry * __shfl(incl, 63);
       wsum += w[c];
       if (q[c].ok) wmax = fmaxf(wmax, w[c]);
     }
@@ -1424,16 +1290,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwd p
     if (c * 64 < M && q[c].ok && w[c] == wmax && c * 64 + lane < amax) amax = c * 64 + lane;
   amax = wave_min_int(amax);
 
-  float dcol[3] = {0.f, 0.f, 0.f}, dglob[3] = {0.f, 0.f, 0.f};
-  if (p.d_color_fine) for (int k = 0; k < 3; ++k) dcol[k] = p.d_color_fine[ray * 3 + k];
-  if (p.d_global_color) for (int k = 0; k < 3; ++k) dglob[k] = p.d_global_color[ray * 3 + k];
-  float dws = p.d_weight_sum ? p.d_weight_sum[ray] : 0.0f;
-  if (p.background_rgb) for (int k = 0; k < 3; ++k) dws -= dcol[k] * p.background_rgb[k];
-  const float ddepth = p.d_depth ? p.d_depth[ray] : 0.0f;
-  const float dwmax = p.d_weight_max ? p.d_weight_max[ray] : 0.0f;
-  const float dge = p.d_gradient_error ? p.d_gradient_error[0] : 0.0f;
-  const float eik_den = p.eik_sums[1] + 1e-5f;
-  const float ddrel_ray = p.d_delta_relight_ray ? p.d_delta_relight_ray[ray] : 0.0f;
+  const RayUpstream up = ray_upstream(p, ray);
 
   // d loss / d w_j and the suffix sums S_j = sum_{k>j} wbar_k w_k (reverse scan, chunks from the back)
   float wbar[kRayChunks], S[kRayChunks];
@@ -1444,16 +1301,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwd p
     if (c * 64 < M) {
       const int j = c * 64 + lane;
       const long pt = ray * M + j;
-      float wb = 0.0f;
-      if (q[c].ok) {
-        for (int k = 0; k < 3; ++k) wb += dcol[k] * p.color[pt * p.ldcolor + k];
-        if (p.gcolor) for (int k = 0; k < 3; ++k) wb += dglob[k] * p.gcolor[pt * p.ldg + k];
-        wb += dws + ddepth * q[c].z;
-        if (p.d_weights) wb += p.d_weights[pt];
-        if (j == amax) wb += dwmax;
-      }
-      wbar[c] = wb;
-      const float x = wb * w[c];
+      wbar[c] = q[c].ok ? sample_wbar(p, up, pt, q[c].z, j == amax) : 0.0f;
+      const float x = wbar[c] * w[c];
       const float incl = wave_scan_incl_add_rev(x, lane);
       S[c] = rcarry + (incl - x);
       rcarry = rcarry + __shfl(incl, 0);
@@ -1466,48 +1315,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(const CompositeBwd p
     if (c * 64 < M) {
       const int j = c * 64 + lane;
       const long pt = ray * M + j;
-      if (q[c].ok) {
-        const float dalpha = wbar[c] * T[c] - S[c] / (1.0f - q[c].a.alpha + 1e-7f);
-        const AlphaGrad ag = alpha_backward(q[c].a, q[c].dist, inv_s, p.cos_anneal, dalpha, p.d_cdf ? p.d_cdf[pt] : 0.0f);
-        dinvs += ag.d_inv_s;
-        float gb[3];
-        const float ecoef = (q[c].relax > 0.0f && q[c].gn > 0.0f) ? dge / eik_den * 2.0f * (q[c].gn - 1.0f) / q[c].gn : 0.0f;
-        for (int k = 0; k < 3; ++k) {
-          gb[k] = ag.d_tc * d[k] + ecoef * q[c].g[k];
-          if (p.d_gradients) gb[k] += p.d_gradients[pt * 3 + k];
-          drd[k] += ag.d_tc * q[c].g[k];
-        }
-        if (active) {
-          if (p.d_z) { p.d_z[pt * 2] = ddepth * w[c]; p.d_z[pt * 2 + 1] = ag.d_dist; }
-          p.ztop[pt * p.ldztop + p.ztop_col] = (ag.d_sdf + (p.d_sdf_s ? p.d_sdf_s[pt] : 0.0f)) / p.sdf_scale;
-          for (int k = p.ztop_col + 1; k < p.ldztop; ++k) p.ztop[pt * p.ldztop + k] = 0.0f;   // (the pad columns behind it: one launch less than zeroing them apart)
-          for (int k = 0; k < 3; ++k) p.gbar[pt * 4 + k] = gb[k];
-          p.gbar[pt * 4 + 3] = 0.0f;
-          for (int k = 0; k < 3; ++k) {
-            const float cbar = dcol[k] * w[c] + (p.d_color_s ? p.d_color_s[pt * 3 + k] : 0.0f);   // cotangent of the composited (relit) colour sample
-            if (p.has_relight) {
-              const float relit = p.color[pt * p.ldcolor + k];
-              const float gc = p.gcolor[pt * p.ldg + k];
-              float tbar, gca = dglob[k] * w[c] + (p.d_gcolor_s ? p.d_gcolor_s[pt * 3 + k] : 0.0f);
-              if (p.inv_sigmoid) {
-                tbar = cbar * relit * (1.0f - relit);
-                gca += tbar * inverse_sigmoid_grad(gc);
-              } else {
-                const float pass = (relit > 0.0f && relit < 1.0f) ? 1.0f : 0.0f;   // clamp(rgb + sigmoid(h) - 0.5, 0, 1)
-                const float sg = relit - gc + 0.5f;                                 // = sigmoid(h) where the clamp is inactive
-                tbar = cbar * pass * sg * (1.0f - sg);
-                gca += cbar * pass;
-              }
-              p.dtop[pt * p.ldtop + k] = tbar + (p.d_delta_relight ? p.d_delta_relight[pt * 3 + k] : 0.0f) + ddrel_ray;
-              p.gc_a[pt * p.ldtop + k] = gca;
-            } else {
-              p.gc_a[pt * p.ldtop + k] = cbar;
-            }
-          }
-          if (p.has_relight) for (int k = 3; k < p.ldtop; ++k) p.dtop[pt * p.ldtop + k] = 0.0f;
-          for (int k = 3; k < p.ldtop; ++k) p.gc_a[pt * p.ldtop + k] = 0.0f;
-        }
-      }
+      if (q[c].ok) dinvs += sample_backward(p, up, q[c], d, pt, inv_s, T[c], w[c], wbar[c], S[c], active, drd);
     }
   }
   dinvs = wave_sum(dinvs);
@@ -1685,14 +1493,7 @@ __global__ __launch_bounds__(256) void rays_grad_finish_kernel(const RaysGradFin
   if (lane == 0) {
     if (p.d_o && p.d_d)
       for (int k = 0; k < 3; ++k) {
-        const float dk = dr[k];
-        float acc = sd[k] + p.d_rays_d_alpha[ray * 3 + k] + spe[k];
-        float f = 1.0f;
-        for (int m = 0; m < p.multires_view; ++m) {
-          acc += f * (cosf(dk * f) * spe[3 + 6 * m + k] - sinf(dk * f) * spe[6 + 6 * m + k]);
-          f *= 2.0f;
-        }
-        p.d_d[ray * 3 + k] = acc;
+        p.d_d[ray * 3 + k] = rays_d_grad(dr[k], sd[k], p.d_rays_d_alpha[ray * 3 + k], spe, k, p.multires_view);
         p.d_o[ray * 3 + k] = so[k];
       }
     if (p.dz_parts && p.d_near && p.d_far) { p.d_near[ray] = snear; p.d_far[ray] = sfar; }
@@ -1759,7 +1560,6 @@ void be_clip_adam(const AdamArgs& a, cnr_stream s) {
   CNR_LAUNCH_CHECK("clip_adam");
 }
 
-void be_gen_rays(const GenRays& p, cnr_stream s) { gen_rays_launch(p, p.n, s); }
 
 // backward of the ray generator: one workgroup per camera folds the contributions of that camera's rays (thread-strided partial
 // sums, then a fixed-order tree: bitwise deterministic, no float atomics); the focal gradient is summed over the cameras in order.
@@ -1795,10 +1595,6 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream s) {
 }
 
 // learnable cameras: one thread per slot (forward) / per camera (backward, which folds that camera's slots in slot order); one launch each
-CNR_PW_KERNEL(camera_fwd, Camera, body_camera_fwd)
-CNR_PW_KERNEL(camera_bwd, CameraBwd, body_camera_bwd)
-void be_camera_fwd(const Camera& p, cnr_stream s) { camera_fwd_launch(p, p.c2w && p.B > 1 ? p.B : 1, s); }
-void be_camera_bwd(const CameraBwd& q, cnr_stream s) { camera_bwd_launch(q, q.d_c2w && q.f.num_cams > 1 ? q.f.num_cams : 1, s); }
 
 // ------------------------------------------------------------------------------------------------
 // marching cubes on the device lattice: the 512^3 volume never leaves HBM between extract_fields and the mesh

@@ -131,30 +131,17 @@ void be_dw_gemm(const DwGemm& g, cnr_stream) {
 }
 
 #define CNR_PW(NAME, PARAM, BODY, COUNT)                \
-  void NAME(const PARAM& p, cnr_stream) {               \
+  void be_##NAME(const PARAM& p, cnr_stream) {          \
     const long n_ = (COUNT);                            \
     _Pragma("omp parallel for") for (long i = 0; i < n_; ++i) BODY(p, i); \
   }
-CNR_PW(be_embed_z, EmbedZ, body_embed_z, p.R* p.m)
-CNR_PW(be_embed_pts, EmbedPts, body_embed_pts, p.n)
-CNR_PW(be_fine_setup, FineSetup, body_fine_setup, p.R* p.M)
-CNR_PW(be_grad_finish, GradFinish, body_grad_finish, p.P)
-CNR_PW(be_coltop_bwd, ColTopBwd, body_coltop_bwd, p.P)
-CNR_PW(be_gbar_finish, GbarFinish, body_gbar_finish, p.P)
-CNR_PW(be_pbar_finish, PbarFinish, body_pbar_finish, p.P)
-CNR_PW(be_query_in, QueryIn, body_query_in, p.P * 3)
-CNR_PW(be_query_seed, QuerySeed, body_query_seed, p.P * (p.ldztop / 4) + (p.gbar ? p.P : 0))
-CNR_PW(be_query_out, QueryOut, body_query_out, query_out_count(p))
-CNR_PW(be_outside_z, OutsideZ, body_outside_z, p.R)
-CNR_PW(be_outside_z_bwd, OutsideZBwd, body_outside_z_bwd, p.R)
-CNR_PW(be_bg_embed, BgEmbed, body_bg_embed, p.R* p.MF)
-CNR_PW(be_bg_alpha, BgAlpha, body_bg_alpha, p.n)
-CNR_PW(be_bg_heads_bwd, BgHeadsBwd, body_bg_heads_bwd, p.n)
-CNR_PW(be_bg_join, BgJoin, body_bg_join, p.n* p.W)
-CNR_PW(be_bg_embed_bwd, BgEmbedBwd, body_bg_embed_bwd, p.R* p.MF)
-CNR_PW(be_bg_rays_bwd, BgRaysBwd, body_bg_rays_bwd, p.R)
-CNR_PW(be_composite_bg, CompositeBg, body_composite_bg, p.R)
-CNR_PW(be_composite_bg_bwd, CompositeBgBwd, body_composite_bg_bwd, p.f.R)
+CNR_POINTWISE_KERNELS(CNR_PW)
+// the kernels outside that table: their HIP forms stage rows in LDS or spread a point over 16 lanes
+CNR_PW(embed_z, EmbedZ, body_embed_z, p.R* p.m)
+CNR_PW(embed_pts, EmbedPts, body_embed_pts, p.n)
+CNR_PW(fine_setup, FineSetup, body_fine_setup, p.R* p.M)
+CNR_PW(grad_finish, GradFinish, body_grad_finish, p.P)
+CNR_PW(gbar_finish, GbarFinish, body_gbar_finish, p.P)
 
 void be_head_bwd(const HeadBwd& p, cnr_stream) {
   const long per = round_up((int)((p.P + p.nslots - 1) / p.nslots), 64);
@@ -323,8 +310,7 @@ void be_reduce_eik(const ReduceEik& p, cnr_stream) {
 void be_variance_finish(const VarianceFinish& p, cnr_stream) {
   float a = 0.0f;
   for (long r = 0; r < p.R; ++r) a += p.partial[r];
-  float raw = expf(p.variance[0] * 10.0f);
-  *p.d_variance = (raw >= 1e-6f && raw <= 1e6f) ? a * 10.0f * raw : 0.0f;
+  *p.d_variance = inv_s_backward(p.variance[0], a);
 }
 
 void be_mc_count(const McVolume& m, cnr_stream) {
@@ -456,9 +442,6 @@ void be_image_panel(const ImagePanel& p, cnr_stream) {
     for (int col = 0; col < rowb; ++col) p.panel[(long)row * rowb + col] = img_panel_byte(p, row, col, vmin, vmax);
 }
 
-void be_gen_rays(const GenRays& p, cnr_stream) {
-  for (long i = 0; i < p.n; ++i) body_gen_rays(p, i);
-}
 void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
   for (int cam = 0; cam < q.f.n_cams; ++cam) {
     double acc[14] = {0};   // (the HIP kernel sums in float in a fixed tree order; the tests compare both with autograd)
@@ -476,15 +459,6 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
     for (int c = 0; c < q.f.n_cams; ++c) s += q.d_focal_partial[c * 2 + j];
     q.d_focal[j] = s;
   }
-}
-
-void be_camera_fwd(const Camera& p, cnr_stream) {
-  const long n = p.c2w && p.B > 1 ? p.B : 1;
-  for (long i = 0; i < n; ++i) body_camera_fwd(p, i);
-}
-void be_camera_bwd(const CameraBwd& q, cnr_stream) {
-  const long n = q.d_c2w && q.f.num_cams > 1 ? q.f.num_cams : 1;
-  for (long cam = 0; cam < n; ++cam) body_camera_bwd(q, cam);
 }
 
 void be_clip_adam(const AdamArgs& a, cnr_stream) {
@@ -528,16 +502,10 @@ void be_upsample(const UpSample& p, cnr_stream) {
     if (p.w_in) {
       for (int i = 0; i < nsec; ++i) { w[i] = p.w_in[ray * nsec + i] + 1e-5f; total += w[i]; }
     } else {
-    for (int i = 0; i < n; ++i) {
-      float x = p.o[ray * 3] + p.d[ray * 3] * z[i], y = p.o[ray * 3 + 1] + p.d[ray * 3 + 1] * z[i], q = p.o[ray * 3 + 2] + p.d[ray * 3 + 2] * z[i];
-      rad[i] = sqrtf(x * x + y * y + q * q);
-    }
-    for (int i = 0; i < nsec; ++i) cs[i] = (s[i + 1] - s[i]) / (z[i + 1] - z[i] + 1e-5f);
+    for (int i = 0; i < n; ++i) rad[i] = ray_radius(p.o + ray * 3, p.d + ray * 3, z[i]);
+    for (int i = 0; i < nsec; ++i) cs[i] = upsample_slope(s[i], s[i + 1], z[i], z[i + 1]);
     for (int i = 0; i < nsec; ++i) {
-      float prev = i > 0 ? cs[i - 1] : 0.0f;
-      float c = std::min(prev, cs[i]);
-      c = std::min(std::max(c, -1e3f), 0.0f);
-      if (!(rad[i] < 1.0f || rad[i + 1] < 1.0f)) c = c * 0.0f;
+      float c = upsample_cos(i > 0 ? cs[i - 1] : 0.0f, cs[i], rad[i], rad[i + 1]);
       float a = upsample_alpha(s[i], s[i + 1], z[i], z[i + 1], c, p.inv_s);
       w[i] = a * T + 1e-5f;
       T = T * (1.0f - a + 1e-7f);
@@ -549,12 +517,7 @@ void be_upsample(const UpSample& p, cnr_stream) {
     for (int i = 0; i < nsec; ++i) { run += w[i] / total; cdf[i + 1] = run; }
     for (int k = 0; k < p.m; ++k) {
       float u = p.u_in ? p.u_in[ray * p.m + k] : linspace_at(0.5f / (float)p.m, 1.0f - 0.5f / (float)p.m, p.m, k);
-      int idx = (int)(std::upper_bound(cdf.begin(), cdf.end(), u) - cdf.begin());
-      int below = std::max(idx - 1, 0), above = std::min(idx, n - 1);
-      float den = cdf[above] - cdf[below];
-      if (den < 1e-5f) den = 1.0f;
-      float t = (u - cdf[below]) / den;
-      p.new_z[ray * p.m + k] = z[below] + t * (z[above] - z[below]);
+      p.new_z[ray * p.m + k] = invert_cdf(cdf.data(), z, n, u);
     }
   }
 }
@@ -565,44 +528,16 @@ void be_merge(const MergeZ& p, cnr_stream) {
     std::vector<float> z(p.z + ray * p.ldz, p.z + ray * p.ldz + p.n), s(p.n, 0.0f);
     if (p.new_sdf) s.assign(p.sdf_in + ray * p.lds_in, p.sdf_in + ray * p.lds_in + p.n);
     const float* nz = p.new_z + ray * p.m;
-    for (int i = 0; i < p.n; ++i) {
-      int cnt = 0;
-      for (int j = 0; j < p.m; ++j) cnt += nz[j] < z[i] ? 1 : 0;
-      p.z[ray * p.ldz + i + cnt] = z[i];
-      if (p.new_sdf) p.sdf_out[ray * p.lds_out + i + cnt] = s[i];
-    }
-    for (int j = 0; j < p.m; ++j) {
-      int lo = (int)(std::upper_bound(z.begin(), z.end(), nz[j]) - z.begin());
-      int rank = 0;
-      for (int q = 0; q < p.m; ++q) rank += (nz[q] < nz[j] || (nz[q] == nz[j] && q < j)) ? 1 : 0;
-      p.z[ray * p.ldz + lo + rank] = nz[j];
-      if (p.new_sdf) p.sdf_out[ray * p.lds_out + lo + rank] = p.new_sdf[ray * p.m + j];
-    }
+    const float* ns = p.new_sdf ? p.new_sdf + ray * p.m : nz;   // (without new_sdf the values go nowhere)
+    merge_samples(z.data(), s.data(), p.n, nz, ns, p.m, 0, 1, [&](int at, float zv, float sv) {
+      p.z[ray * p.ldz + at] = zv;
+      if (p.new_sdf) p.sdf_out[ray * p.lds_out + at] = sv;
+    });
   }
 }
 
-struct SampleF {
-  float z, dist, relax, inside, gn, g[3];
-  AlphaOut a;
-};
-static SampleF sample_fwd(const float* z, int j, int M, float sample_dist, const float* o, const float* d, const float* sdf,
-                          const float* g, long pt, float inv_s, float r) {
-  SampleF q;
-  q.z = z[j];
-  q.dist = j + 1 < M ? z[j + 1] - q.z : sample_dist;
-  float mid = q.z + q.dist * 0.5f;
-  float x = o[0] + d[0] * mid, y = o[1] + d[1] * mid, w = o[2] + d[2] * mid;
-  float pn = sqrtf(x * x + y * y + w * w);
-  q.inside = pn < 1.0f ? 1.0f : 0.0f;
-  q.relax = pn < 1.2f ? 1.0f : 0.0f;
-  for (int k = 0; k < 3; ++k) q.g[k] = g[pt * 3 + k];
-  q.gn = sqrtf(q.g[0] * q.g[0] + q.g[1] * q.g[1] + q.g[2] * q.g[2]);
-  q.a = alpha_forward(sdf[pt], q.g, d, q.dist, inv_s, r);
-  return q;
-}
-
 void be_composite_fwd(const CompositeFwd& p, cnr_stream) {
-  const float inv_s = std::min(std::max(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
+  const float inv_s = inv_s_of(p.variance[0]);
 #pragma omp parallel for
   for (long ray = 0; ray < p.R; ++ray) {
     const int M = p.M;
@@ -610,7 +545,7 @@ void be_composite_fwd(const CompositeFwd& p, cnr_stream) {
     float T = 1.0f, wsum = 0.f, wmax = -1.f, dep = 0.f, col[3] = {0, 0, 0}, gcl[3] = {0, 0, 0}, e0 = 0.f, e1 = 0.f;
     for (int j = 0; j < M; ++j) {
       long pt = ray * M + j;
-      SampleF q = sample_fwd(z, j, M, p.sample_dist, p.o + ray * 3, p.d + ray * 3, p.sdf, p.g, pt, inv_s, p.cos_anneal);
+      RaySample q = ray_sample(z, j, M, p.sample_dist, p.o + ray * 3, p.d + ray * 3, p.sdf, p.g, pt, inv_s, p.cos_anneal);
       float w = q.a.alpha * T;
       T = T * (1.0f - q.a.alpha + 1e-7f);
       wsum += w; wmax = std::max(wmax, w); dep += w * q.z;
@@ -639,81 +574,27 @@ void be_composite_fwd(const CompositeFwd& p, cnr_stream) {
 }
 
 void be_composite_bwd(const CompositeBwd& p, cnr_stream) {
-  const float inv_s = std::min(std::max(expf(p.variance[0] * 10.0f), 1e-6f), 1e6f);
-  const float dge = p.d_gradient_error ? p.d_gradient_error[0] : 0.0f;
-  const float eik_den = p.eik_sums[1] + 1e-5f;
+  const float inv_s = inv_s_of(p.variance[0]);
 #pragma omp parallel for
   for (long ray = 0; ray < p.R; ++ray) {
     const int M = p.M;
     const float* z = p.z + ray * M;
     const float* d = p.d + ray * 3;
-    std::vector<SampleF> q(M);
+    std::vector<RaySample> q(M);
     std::vector<float> T(M), w(M), wbar(M), S(M);
     float t = 1.0f, wmax = -1.0f;
     int amax = 0;
     for (int j = 0; j < M; ++j) {
-      q[j] = sample_fwd(z, j, M, p.sample_dist, p.o + ray * 3, d, p.sdf, p.g, ray * M + j, inv_s, p.cos_anneal);
+      q[j] = ray_sample(z, j, M, p.sample_dist, p.o + ray * 3, d, p.sdf, p.g, ray * M + j, inv_s, p.cos_anneal);
       T[j] = t; w[j] = q[j].a.alpha * t; t = t * (1.0f - q[j].a.alpha + 1e-7f);
       if (w[j] > wmax) { wmax = w[j]; amax = j; }
     }
-    float dcol[3] = {0, 0, 0}, dglob[3] = {0, 0, 0};
-    if (p.d_color_fine) for (int k = 0; k < 3; ++k) dcol[k] = p.d_color_fine[ray * 3 + k];
-    if (p.d_global_color) for (int k = 0; k < 3; ++k) dglob[k] = p.d_global_color[ray * 3 + k];
-    float dws = p.d_weight_sum ? p.d_weight_sum[ray] : 0.0f;
-    if (p.background_rgb) for (int k = 0; k < 3; ++k) dws -= dcol[k] * p.background_rgb[k];
-    const float ddepth = p.d_depth ? p.d_depth[ray] : 0.0f, dwmax = p.d_weight_max ? p.d_weight_max[ray] : 0.0f;
-    for (int j = 0; j < M; ++j) {
-      long pt = ray * M + j;
-      float wb = 0.0f;
-      for (int k = 0; k < 3; ++k) wb += dcol[k] * p.color[pt * p.ldcolor + k];
-      if (p.gcolor) for (int k = 0; k < 3; ++k) wb += dglob[k] * p.gcolor[pt * p.ldg + k];
-      wb += dws + ddepth * q[j].z;
-      if (p.d_weights) wb += p.d_weights[pt];
-      if (j == amax) wb += dwmax;
-      wbar[j] = wb;
-    }
+    const RayUpstream up = ray_upstream(p, ray);
+    for (int j = 0; j < M; ++j) wbar[j] = sample_wbar(p, up, ray * M + j, q[j].z, j == amax);
     float run = 0.0f;
     for (int j = M - 1; j >= 0; --j) { S[j] = run; run += wbar[j] * w[j]; }
     float dinvs = 0.0f, drd[3] = {0, 0, 0};
-    for (int j = 0; j < M; ++j) {
-      long pt = ray * M + j;
-      float dalpha = wbar[j] * T[j] - S[j] / (1.0f - q[j].a.alpha + 1e-7f);
-      AlphaGrad ag = alpha_backward(q[j].a, q[j].dist, inv_s, p.cos_anneal, dalpha, p.d_cdf ? p.d_cdf[pt] : 0.0f);
-      dinvs += ag.d_inv_s;
-      float ecoef = (q[j].relax > 0.0f && q[j].gn > 0.0f) ? dge / eik_den * 2.0f * (q[j].gn - 1.0f) / q[j].gn : 0.0f;
-      for (int k = 0; k < 3; ++k) {
-        float gb = ag.d_tc * d[k] + ecoef * q[j].g[k];
-        if (p.d_gradients) gb += p.d_gradients[pt * 3 + k];
-        p.gbar[pt * 4 + k] = gb;
-        drd[k] += ag.d_tc * q[j].g[k];
-      }
-      p.gbar[pt * 4 + 3] = 0.0f;
-      if (p.d_z) { p.d_z[pt * 2] = ddepth * w[j]; p.d_z[pt * 2 + 1] = ag.d_dist; }
-      p.ztop[pt * p.ldztop + p.ztop_col] = (ag.d_sdf + (p.d_sdf_s ? p.d_sdf_s[pt] : 0.0f)) / p.sdf_scale;
-          for (int k = p.ztop_col + 1; k < p.ldztop; ++k) p.ztop[pt * p.ldztop + k] = 0.0f;   // (the pad columns behind it: one launch less than zeroing them apart)
-      for (int k = 0; k < 3; ++k) {
-        float cbar = dcol[k] * w[j] + (p.d_color_s ? p.d_color_s[pt * 3 + k] : 0.0f);
-        if (p.has_relight) {
-          float relit = p.color[pt * p.ldcolor + k], gc = p.gcolor[pt * p.ldg + k];
-          float tbar, gca = dglob[k] * w[j] + (p.d_gcolor_s ? p.d_gcolor_s[pt * 3 + k] : 0.0f);
-          if (p.inv_sigmoid) {
-            tbar = cbar * relit * (1.0f - relit);
-            gca += tbar * inverse_sigmoid_grad(gc);
-          } else {
-            float pass = (relit > 0.0f && relit < 1.0f) ? 1.0f : 0.0f;
-            float sg = relit - gc + 0.5f;
-            tbar = cbar * pass * sg * (1.0f - sg);
-            gca += cbar * pass;
-          }
-          p.dtop[pt * p.ldtop + k] = tbar + (p.d_delta_relight ? p.d_delta_relight[pt * 3 + k] : 0.0f) + (p.d_delta_relight_ray ? p.d_delta_relight_ray[ray] : 0.0f);
-          p.gc_a[pt * p.ldtop + k] = gca;
-        } else {
-          p.gc_a[pt * p.ldtop + k] = cbar;
-        }
-      }
-      if (p.has_relight) for (int k = 3; k < p.ldtop; ++k) p.dtop[pt * p.ldtop + k] = 0.0f;
-      for (int k = 3; k < p.ldtop; ++k) p.gc_a[pt * p.ldtop + k] = 0.0f;
-    }
+    for (int j = 0; j < M; ++j) dinvs += sample_backward(p, up, q[j], d, ray * M + j, inv_s, T[j], w[j], wbar[j], S[j], true, drd);
     if (p.d_s_val) dinvs += -p.d_s_val[ray] / (inv_s * inv_s);
     p.dinvs_partial[ray] = dinvs;
     if (p.d_rays_d) for (int k = 0; k < 3; ++k) p.d_rays_d[ray * 3 + k] = drd[k];
@@ -754,14 +635,7 @@ void be_rays_grad_finish(const RaysGradFinish& p, cnr_stream) {
     }
     if (!(p.d_o && p.d_d)) continue;
     for (int k = 0; k < 3; ++k) {
-      float dk = dr[k];
-      float acc = sd[k] + p.d_rays_d_alpha[ray * 3 + k] + spe[k];
-      float f = 1.0f;
-      for (int m = 0; m < p.multires_view; ++m) {
-        acc += f * (cosf(dk * f) * spe[3 + 6 * m + k] - sinf(dk * f) * spe[6 + 6 * m + k]);
-        f *= 2.0f;
-      }
-      p.d_d[ray * 3 + k] = acc;
+      p.d_d[ray * 3 + k] = rays_d_grad(dr[k], sd[k], p.d_rays_d_alpha[ray * 3 + k], spe, k, p.multires_view);
       p.d_o[ray * 3 + k] = so[k];
     }
   }

@@ -33,6 +33,8 @@ def _config(cfg_name):
         c = O.dtu_config()
         c.sdf.multires = 4
         return c
+    if cfg_name == "dtu_256":   # 96 + 160 samples per ray: four 64-sample chunks, and exactly the row length of the per-ray kernels
+        return O.dtu_config(96, 160)
     return O.tiny_config()
 
 
@@ -118,6 +120,17 @@ def test_narrow_embedding_hip(R):
     """SDF MULTIRES 4 (27 embedding columns, K padded to 32) at DTU widths: the narrow-input kernels (cnr_sweep0.hip, cnr_narrow_bwd.hip) then run
     with one of their three k16 blocks empty -- its LDS columns must read as zeros whatever earlier kernels left there."""
     _check(R, None, torch.device("cuda:0"), "dtu_pe4")
+
+
+def test_four_chunk_rays_emu():
+    """256 samples per ray at 5 rays (one full workgroup of four rays and one wavefront of the next): the chunk carry of the compositor's scans,
+    forward and reverse, crosses three chunk boundaries.  Same gates as above."""
+    _check(5, N.EMU_LIB, torch.device("cpu"), "dtu_256")
+
+
+@pytest.mark.gpu
+def test_four_chunk_rays_hip():
+    _check(5, None, torch.device("cuda:0"), "dtu_256")
 
 
 _CHILD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_edge_child.py")

@@ -705,3 +705,44 @@ def test_fused_sampler_step_is_bit_identical(tmp_path):
     assert set(res["fused"]) == set(res["separate"]) and any(k.endswith("out:z_vals") for k in res["fused"])
     for k in sorted(res["fused"]):
         assert np.array_equal(res["fused"][k], res["separate"][k], equal_nan=True), k
+
+
+_SAMPLER_RAGGED_CHILD = r"""
+import sys, os
+root, out = sys.argv[1], sys.argv[2]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+import numpy as np, torch
+import _native as N
+import test_edge_batches as T
+import color_neus_amd as cn
+from oracle import colorneus_oracle as O
+dev = torch.device("cuda:0")
+ocfg = T._config("dtu_256")
+r = N.make_renderer(ocfg, O.init_params(ocfg, seed=5, trained_like=True), None, dev)
+o, d, near, far, t_rand, gt, mask = T._batch(5, 105)
+torch.manual_seed(7)   # the jitter draw of the coarse samples (CPU generator): the same in both processes
+o_ = r(o.to(dev), d.to(dev), near.to(dev), far.to(dev))
+loss, _ = cn.compute_loss(o_, gt.to(dev), mask.to(dev))
+loss.backward()
+res = {"out:" + k: v.detach().cpu().numpy() for k, v in o_.items() if torch.is_tensor(v)}
+res.update({"g:" + k: p.grad.detach().cpu().numpy() for k, p in r.named_parameters() if p.grad is not None})
+np.savez(out, **res)
+"""
+
+
+def test_fused_sampler_step_is_bit_identical_ragged_four_chunks(tmp_path):
+    """The same comparison where the fixtures do not reach: 5 rays (the second workgroup has one active wavefront and three that recompute
+    the last ray and store nothing) of 96 + 160 samples, so the row grows 96 -> 136 -> 176 -> 216 -> 256 and the merges and scans cross the
+    128 and 192 chunk boundaries with a ragged last chunk.  The library draws its own z_vals; they, every output and every gradient agree to
+    the bit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = {}
+    for tag, extra in (("fused", {}), ("separate", {"CNR_NO_SAMPLER_FUSE": "1"})):
+        path = str(tmp_path / (tag + ".npz"))
+        r = subprocess.run([sys.executable, "-c", _SAMPLER_RAGGED_CHILD, root, path], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        res[tag] = dict(np.load(path))
+    assert set(res["fused"]) == set(res["separate"])
+    assert res["fused"]["out:z_vals"].shape == (5, 256)
+    for k in sorted(res["fused"]):
+        assert np.array_equal(res["fused"][k], res["separate"][k], equal_nan=True), k

@@ -75,6 +75,61 @@ def _crafted_rows(library, device):
         assert float((got - ref).abs().max()) < 2e-5, m
 
 
+def _multi_chunk_rays():
+    g = torch.Generator().manual_seed(11)
+    o = torch.nn.functional.normalize(torch.randn(5, 3, generator=g), dim=-1) * 2.7
+    d = torch.nn.functional.normalize(torch.randn(5, 3, generator=g) * 0.3 - o, dim=-1)
+    return o, d
+
+
+def _sample_pdf_multi_chunk(library, device):
+    """Rows longer than one 64-entry chunk (130: two chunks and two entries; 256: the row length of the kernel) at 5 rays, which leaves three
+    wavefronts of the second workgroup without a ray: the chunk carries of the weight and cdf scans.  Weights in [0.5, 1.5] keep every cdf
+    step three orders above the 1e-5 switch, so the comparison with the oracle is one of round-off (measured 1.4e-6 on the emulation; the oracle's
+    own float32-to-float64 distance is 3.5e-7)."""
+    from oracle import colorneus_oracle as O
+    g = torch.Generator().manual_seed(12)
+    for n in (130, 256):
+        bins = torch.linspace(1.0, 3.0, n).repeat(5, 1)
+        w = torch.rand(5, n - 1, generator=g) + 0.5
+        for m in (64, 7):
+            got = cn.sample_pdf(bins.to(device), w.to(device), m, det=True, library=library).cpu()
+            err = float((got - O.sample_pdf_det(bins, w, m)).abs().max())
+            print("sample_pdf n=%d m=%d: %.2e" % (n, m, err))
+            assert err < 2e-5, (n, m, err)
+
+
+def _up_sample_multi_chunk(library, device):
+    """up_sample on rows of 160 and 250 samples (three and four chunks, the last ragged) at 5 rays, on a bumpy sphere: measured 6.9e-6 (emulation) from the
+    float32 oracle, whose own float32-to-float64 distance is 9.7e-7."""
+    from oracle import colorneus_oracle as O
+    r = N.make_renderer(O.tiny_config(), G.prefixed(G.load("functions"), "tinyw:"), library, device)
+    o, d = _multi_chunk_rays()
+    near, far = O.near_far_from_sphere(o, d)
+    for n in (160, 250):
+        z = near[:, None] + (far - near)[:, None] * torch.linspace(0.0, 1.0, n)[None, :]
+        pts = o[:, None, :] + d[:, None, :] * z[..., None]
+        sdf = pts.norm(dim=-1) - 0.6 + 0.05 * torch.sin(7.0 * pts[..., 0])
+        for inv_s in (64.0, 512.0):
+            for m in (64, 20):
+                got = r.up_sample(o.to(device), d.to(device), z.to(device), sdf.to(device), m, inv_s).cpu()
+                err = float((got - O.up_sample(o, d, z, sdf, m, inv_s)).abs().max())
+                print("up_sample n=%d inv_s=%g m=%d: %.2e" % (n, inv_s, m, err))
+                assert err < 1e-4, (n, inv_s, m, err)
+
+
+@pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
+def test_multi_chunk_rows_emu():
+    _sample_pdf_multi_chunk(N.EMU_LIB, "cpu")
+    _up_sample_multi_chunk(N.EMU_LIB, "cpu")
+
+
+@pytest.mark.gpu
+def test_multi_chunk_rows_hip():
+    _sample_pdf_multi_chunk(None, "cuda:0")
+    _up_sample_multi_chunk(None, "cuda:0")
+
+
 @pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
 def test_sample_pdf_emu():
     _sample_pdf(N.EMU_LIB, "cpu")
