@@ -5,6 +5,8 @@ The product library is ``libcolorneus_hip.so`` next to this file (built by ``__g
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -97,18 +99,97 @@ def c_config(cfg) -> CnrConfig:
                      rel_include_grad=int(cfg.rel_include_grad), rel_inv_sigmoid=int(cfg.rel_inv_sigmoid))
 
 
-EXPORTS = ["cnr_abi_version", "cnr_backend_name", "cnr_last_error", "cnr_param_count", "cnr_param_info", "cnr_ctx_bytes",
-           "cnr_bwd_scratch_bytes", "cnr_render_forward", "cnr_render_backward", "cnr_infer_scratch_bytes", "cnr_render_forward_only", "cnr_sdf_eval_scratch_bytes", "cnr_sdf_eval",
-           "cnr_sdf_grid_scratch_bytes", "cnr_sdf_grid", "cnr_sdf_grid_slab_scratch_bytes", "cnr_sdf_grid_slab", "cnr_vertex_color_scratch_bytes", "cnr_vertex_color",
-           "cnr_timing_enable", "cnr_timing_collect", "cnr_loss_scratch_bytes", "cnr_loss_sums", "cnr_loss_sums_ray", "cnr_loss_grads", "cnr_loss_combine", "cnr_loss_coef", "cnr_loss_forward", "cnr_loss_backward", "cnr_loss_shard_stats", "cnr_loss_shard_combine",
-           "cnr_sample_pdf", "cnr_sample_pdf_u", "cnr_up_sample", "cnr_clip_adam_step", "cnr_clip_adam_scratch_bytes", "cnr_gen_rays", "cnr_gen_rays_backward", "cnr_sample_z", "cnr_mc_scratch_bytes", "cnr_mc_count", "cnr_mc_emit",
-           "cnr_linear_scratch_bytes", "cnr_linear_forward", "cnr_linear_backward",
-           "cnr_nerf_param_count", "cnr_nerf_param_info", "cnr_outside_z", "cnr_outside_z_backward", "cnr_background_ctx_bytes",
-           "cnr_background_bwd_scratch_bytes", "cnr_background_forward", "cnr_background_backward", "cnr_composite_background_scratch_bytes",
-           "cnr_composite_background_forward", "cnr_composite_background_backward",
-           "cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes", "cnr_sdf_query_forward", "cnr_sdf_query_backward",
-           "cnr_nn_scratch_bytes", "cnr_nn_search", "cnr_camera_forward", "cnr_camera_backward",
-           "cnr_image_scratch_bytes", "cnr_image_metrics", "cnr_image_panel"]
+_int, _i32, _i64, _f32, _size = C.c_int, C.c_int32, C.c_int64, C.c_float, C.c_size_t
+_PP = C.POINTER(_FP)              # const float* const* params / float* const* d_params
+_F3 = C.POINTER(C.c_float)        # host float[3] bounds
+_cfg, _ncfg, _lcfg = C.POINTER(CnrConfig), C.POINTER(CnrNerfConfig), C.POINTER(CnrLossConfig)
+_in, _out, _gout = C.POINTER(CnrInputs), C.POINTER(CnrOutputs), C.POINTER(CnrOutGrads)
+_bgin = C.POINTER(CnrBgCompositeIn)
+_info = [_int, C.c_char_p, _int, C.POINTER(_int), C.POINTER(_int)]   # index, name, name_len, rows, cols
+
+# Every export of include/colorneus_render.h, in the header's order: name -> (restype, argtypes).  tests/test_binding.py holds the arity of
+# each entry against the header's prototype.
+SIGNATURES = {
+    # per-launch timing
+    "cnr_timing_enable": (None, [_int]),
+    "cnr_timing_collect": (_int, [C.POINTER(CnrKernelTiming), _int]),
+    # loss of the training step
+    "cnr_loss_scratch_bytes": (_size, [_i64]),
+    "cnr_loss_sums": (_int, [_lcfg, _FP, _FP, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _size, _FP]),
+    "cnr_loss_sums_ray": (_int, [_lcfg, _FP, _FP, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _size, _FP]),
+    "cnr_loss_grads": (_int, [_lcfg, _FP, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _FP, _FP, _FP]),
+    "cnr_loss_combine": (_int, [_lcfg, _FP, _FP, _f32, _i32, _i32, _i32, _FP, _FP]),
+    "cnr_loss_coef": (_int, [_lcfg, _FP, _FP, _f32, _i32, _i32, _i32, _FP, _FP]),
+    "cnr_loss_forward": (_int, [_lcfg, _FP, _FP, _FP, _i32, _FP, _FP, _FP, _i64, _i32, _f32, _i32, _i32, _FP, _FP, _FP, _size, _FP]),
+    "cnr_loss_backward": (_int, [_lcfg, _FP, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _FP, _f32, _i32, _i32, _FP, _FP, _FP, _FP, _FP]),
+    "cnr_loss_shard_stats": (_int, [_lcfg, _FP, _FP, _FP, _i32, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _size, _FP]),
+    "cnr_loss_shard_combine": (_int, [_lcfg, _FP, _f32, _i32, _i32, _i32, _FP, _FP]),
+    # ray generation, learnable cameras
+    "cnr_gen_rays": (_int, [_FP, _i64, _FP, _i32, _FP, _i32, _i32, _i32, _i32, _FP, _FP, _FP, _f32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "cnr_gen_rays_backward": (_int, [_FP, _i64, _FP, _i32, _FP, _i32, _i32, _i32, _i32, _FP, _f32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _size, _FP]),
+    "cnr_camera_forward": (_int, [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, _i64, _FP, _FP, _FP]),
+    "cnr_camera_backward": (_int, [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, _i64, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    # optimiser step
+    "cnr_clip_adam_scratch_bytes": (_size, [_i32, C.POINTER(_i64)]),
+    "cnr_clip_adam_step": (_int, [C.POINTER(CnrAdamConfig), _i32, C.POINTER(_i64), _PP, _PP, _FP, _FP, _FP, _size, _FP]),
+    # identification, parameter inventory
+    "cnr_abi_version": (_int, []),
+    "cnr_backend_name": (C.c_char_p, []),
+    "cnr_last_error": (C.c_char_p, []),
+    "cnr_param_count": (_int, [_cfg]),
+    "cnr_param_info": (_int, [_cfg] + _info),
+    # the render path
+    "cnr_ctx_bytes": (_size, [_cfg, _i64]),
+    "cnr_bwd_scratch_bytes": (_size, [_cfg, _i64]),
+    "cnr_render_forward": (_int, [_cfg, _PP, _in, _out, _FP, _size, _FP]),
+    "cnr_infer_scratch_bytes": (_size, [_cfg, _i64]),
+    "cnr_render_forward_only": (_int, [_cfg, _PP, _in, _out, _FP, _size, _FP]),
+    "cnr_sample_z": (_int, [_cfg, _PP, _in, _FP, _FP, _size, _FP]),
+    "cnr_render_backward": (_int, [_cfg, _PP, _in, _out, _FP, _size, _gout, C.POINTER(CnrInGrads), _FP, _size, _FP]),
+    "cnr_sample_pdf": (_int, [_FP, _FP, _i64, _i32, _i32, _FP, _FP]),
+    "cnr_sample_pdf_u": (_int, [_FP, _FP, _FP, _i64, _i32, _i32, _FP, _FP]),
+    "cnr_up_sample": (_int, [_FP, _FP, _FP, _FP, _i64, _i32, _i32, _f32, _FP, _FP]),
+    # SDF evaluation, point queries, lattice, iso-surface
+    "cnr_sdf_eval_scratch_bytes": (_size, [_cfg, _i64]),
+    "cnr_sdf_eval": (_int, [_cfg, _PP, _FP, _i64, _f32, _FP, _FP, _size, _FP]),
+    "cnr_sdf_query_ctx_bytes": (_size, [_cfg, _i64, _i32]),
+    "cnr_sdf_query_bwd_scratch_bytes": (_size, [_cfg, _i64, _i32]),
+    "cnr_sdf_query_forward": (_int, [_cfg, _PP, _FP, _i64, _i32, _FP, _FP, _FP, _FP, _size, _FP]),
+    "cnr_sdf_query_backward": (_int, [_cfg, _PP, _FP, _i64, _i32, _FP, _FP, _FP, _FP, _size, _PP, _FP, _FP, _size, _FP]),
+    "cnr_sdf_grid_scratch_bytes": (_size, [_cfg, _i32]),
+    "cnr_sdf_grid": (_int, [_cfg, _PP, _F3, _F3, _i32, _FP, _FP, _size, _FP]),
+    "cnr_sdf_grid_slab_scratch_bytes": (_size, [_cfg, _i32, _i32, _i32]),
+    "cnr_sdf_grid_slab": (_int, [_cfg, _PP, _F3, _F3, _i32, _i32, _i32, _FP, _FP, _size, _FP]),
+    "cnr_mc_scratch_bytes": (_size, [_i32]),
+    "cnr_mc_count": (_int, [_FP, _i32, _f32, _FP, _size, _FP, _FP]),
+    "cnr_mc_emit": (_int, [_FP, _i32, _f32, _F3, _F3, _FP, _size, _FP, _FP, _FP]),
+    # nearest neighbours, image evaluation, vertex colours
+    "cnr_nn_scratch_bytes": (_size, [_i64, _i64]),
+    "cnr_nn_search": (_int, [_FP, _i64, _FP, _i64, _FP, _FP, _FP, _size, _FP]),
+    "cnr_image_scratch_bytes": (_size, [_i64, _int, _int, _int]),
+    "cnr_image_metrics": (_int, [_FP, _FP, _i64, _int, _int, _int, _int, _FP, _FP, _FP, _size, _FP]),
+    "cnr_image_panel": (_int, [_FP, _FP, _FP, _int, _int, _FP, _FP, _FP, _size, _FP]),
+    "cnr_vertex_color_scratch_bytes": (_size, [_cfg, _i64]),
+    "cnr_vertex_color": (_int, [_cfg, _PP, _FP, _i64, _FP, _FP, _size, _FP]),
+    # one plain fully-connected layer
+    "cnr_linear_scratch_bytes": (_size, [_i64, _i32, _i32, _i32]),
+    "cnr_linear_forward": (_int, [_FP, _i64, _i32, _FP, _FP, _i32, _i32, _FP, _FP, _size, _FP]),
+    "cnr_linear_backward": (_int, [_FP, _FP, _FP, _i64, _i32, _FP, _i32, _i32, _FP, _FP, _FP, _FP, _size, _FP]),
+    # N_OUTSIDE > 0: the NeRF++ background
+    "cnr_nerf_param_count": (_int, [_ncfg]),
+    "cnr_nerf_param_info": (_int, [_ncfg] + _info),
+    "cnr_outside_z": (_int, [_FP, _FP, _FP, _i64, _i32, _i32, _i32, _FP, _FP, _FP]),
+    "cnr_outside_z_backward": (_int, [_FP, _FP, _FP, _i64, _i32, _i32, _i32, _FP, _FP, _FP]),
+    "cnr_background_ctx_bytes": (_size, [_ncfg, _i64, _i32]),
+    "cnr_background_bwd_scratch_bytes": (_size, [_ncfg, _i64, _i32]),
+    "cnr_background_forward": (_int, [_ncfg, _PP, _FP, _FP, _FP, _i64, _i32, _f32, _FP, _FP, _FP, _size, _FP]),
+    "cnr_background_backward": (_int, [_ncfg, _PP, _FP, _FP, _FP, _i64, _i32, _f32, _FP, _size, _FP, _FP, _FP, _PP, _FP, _FP, _FP, _FP, _size, _FP]),
+    "cnr_composite_background_scratch_bytes": (_size, [_i64]),
+    "cnr_composite_background_forward": (_int, [_bgin, _out, _FP, _size, _FP]),
+    "cnr_composite_background_backward": (_int, [_bgin, _out, _gout, C.POINTER(CnrBgCompositeGrads), _FP, _size, _FP]),
+}
+EXPORTS = list(SIGNATURES)
+ABI_VERSION = 9
 
 
 class RenderLibrary:
@@ -119,99 +200,10 @@ class RenderLibrary:
                 "or `make -C color-neus_amd/csrc hip`. There is no CPU/PyTorch fallback for the render path.")
         self.path = path
         self.lib = C.CDLL(path)
-        L = self.lib
-        L.cnr_abi_version.restype = C.c_int
-        L.cnr_backend_name.restype = C.c_char_p
-        L.cnr_last_error.restype = C.c_char_p
-        L.cnr_param_count.argtypes = [C.POINTER(CnrConfig)]
-        L.cnr_param_info.argtypes = [C.POINTER(CnrConfig), C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        for f in ("cnr_ctx_bytes", "cnr_bwd_scratch_bytes", "cnr_infer_scratch_bytes", "cnr_sdf_eval_scratch_bytes", "cnr_vertex_color_scratch_bytes"):
-            getattr(L, f).restype = C.c_size_t
-            getattr(L, f).argtypes = [C.POINTER(CnrConfig), C.c_int64]
-        L.cnr_sdf_grid_scratch_bytes.restype = C.c_size_t
-        L.cnr_sdf_grid_scratch_bytes.argtypes = [C.POINTER(CnrConfig), C.c_int32]
-        L.cnr_render_forward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(CnrInputs), C.POINTER(CnrOutputs),
-                                         _FP, C.c_size_t, _FP]
-        L.cnr_render_forward_only.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(CnrInputs), C.POINTER(CnrOutputs),
-                                              _FP, C.c_size_t, _FP]
-        L.cnr_render_backward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(CnrInputs), C.POINTER(CnrOutputs),
-                                          _FP, C.c_size_t, C.POINTER(CnrOutGrads), C.POINTER(CnrInGrads), _FP, C.c_size_t, _FP]
-        L.cnr_sdf_eval.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, C.c_float, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_sdf_grid.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32,
-                                   _FP, _FP, C.c_size_t, _FP]
-        L.cnr_sdf_grid_slab_scratch_bytes.restype = C.c_size_t
-        L.cnr_sdf_grid_slab_scratch_bytes.argtypes = [C.POINTER(CnrConfig), C.c_int32, C.c_int32, C.c_int32]
-        L.cnr_sdf_grid_slab.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32,
-                                        _FP, _FP, C.c_size_t, _FP]
-        L.cnr_linear_scratch_bytes.restype = C.c_size_t
-        L.cnr_linear_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
-        L.cnr_linear_forward.argtypes = [_FP, C.c_int64, C.c_int32, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_linear_backward.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_vertex_color.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, _FP, _FP, C.c_size_t, _FP]
-        for f in ("cnr_sdf_query_ctx_bytes", "cnr_sdf_query_bwd_scratch_bytes"):
-            getattr(L, f).restype = C.c_size_t
-            getattr(L, f).argtypes = [C.POINTER(CnrConfig), C.c_int64, C.c_int32]
-        L.cnr_sdf_query_forward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_sdf_query_backward.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_size_t,
-                                             C.POINTER(_FP), _FP, _FP, C.c_size_t, _FP]
-        L.cnr_loss_scratch_bytes.restype = C.c_size_t
-        L.cnr_loss_scratch_bytes.argtypes = [C.c_int64]
-        L.cnr_loss_sums.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_loss_sums_ray.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_loss_grads.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, _FP]
-        L.cnr_loss_combine.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, C.c_float, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]
-        L.cnr_loss_coef.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, C.c_float, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]
-        L.cnr_loss_forward.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, C.c_int32, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_int32,
-                                       _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_loss_backward.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, C.c_float, C.c_int32, C.c_int32,
-                                        _FP, _FP, _FP, _FP, _FP]
-        L.cnr_loss_shard_stats.argtypes = [C.POINTER(CnrLossConfig), _FP, _FP, _FP, C.c_int32, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_loss_shard_combine.argtypes = [C.POINTER(CnrLossConfig), _FP, C.c_float, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]
-        L.cnr_sample_pdf.argtypes = [_FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP]
-        L.cnr_sample_pdf_u.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP]
-        L.cnr_up_sample.argtypes = [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_float, _FP, _FP]
-        L.cnr_clip_adam_step.argtypes = [C.POINTER(CnrAdamConfig), C.c_int32, C.POINTER(C.c_int64), C.POINTER(_FP), C.POINTER(_FP), _FP, _FP, _FP,
-                                         C.c_size_t, _FP]
-        L.cnr_clip_adam_scratch_bytes.restype = C.c_size_t
-        L.cnr_clip_adam_scratch_bytes.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
-        L.cnr_gen_rays.argtypes = [_FP, C.c_int64, _FP, C.c_int32, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, C.c_float,
-                                   _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]
-        L.cnr_gen_rays_backward.argtypes = [_FP, C.c_int64, _FP, C.c_int32, _FP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, C.c_float,
-                                            _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_sample_z.argtypes = [C.POINTER(CnrConfig), C.POINTER(_FP), C.POINTER(CnrInputs), _FP, _FP, C.c_size_t, _FP]
-        L.cnr_mc_scratch_bytes.restype = C.c_size_t
-        L.cnr_mc_scratch_bytes.argtypes = [C.c_int32]
-        L.cnr_mc_count.argtypes = [_FP, C.c_int32, C.c_float, _FP, C.c_size_t, _FP, _FP]
-        L.cnr_mc_emit.argtypes = [_FP, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _FP, C.c_size_t, _FP, _FP, _FP]
-        L.cnr_nn_scratch_bytes.restype = C.c_size_t
-        L.cnr_nn_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
-        L.cnr_nn_search.argtypes = [_FP, C.c_int64, _FP, C.c_int64, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_camera_forward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP]
-        L.cnr_camera_backward.argtypes = [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, _FP, _FP, _FP]
-        L.cnr_image_scratch_bytes.restype = C.c_size_t
-        L.cnr_image_scratch_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int]
-        L.cnr_image_metrics.argtypes = [_FP, _FP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_image_panel.argtypes = [_FP, _FP, _FP, C.c_int, C.c_int, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_timing_enable.argtypes = [C.c_int]
-        L.cnr_timing_enable.restype = None
-        L.cnr_timing_collect.argtypes = [C.POINTER(CnrKernelTiming), C.c_int]
-        L.cnr_nerf_param_count.argtypes = [C.POINTER(CnrNerfConfig)]
-        L.cnr_nerf_param_info.argtypes = [C.POINTER(CnrNerfConfig), C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.cnr_outside_z.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP]
-        L.cnr_outside_z_backward.argtypes = [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP]
-        for f in ("cnr_background_ctx_bytes", "cnr_background_bwd_scratch_bytes"):
-            getattr(L, f).restype = C.c_size_t
-            getattr(L, f).argtypes = [C.POINTER(CnrNerfConfig), C.c_int64, C.c_int32]
-        L.cnr_background_forward.argtypes = [C.POINTER(CnrNerfConfig), C.POINTER(_FP), _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_float, _FP, _FP, _FP,
-                                             C.c_size_t, _FP]
-        L.cnr_background_backward.argtypes = [C.POINTER(CnrNerfConfig), C.POINTER(_FP), _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_float, _FP, C.c_size_t,
-                                              _FP, _FP, _FP, C.POINTER(_FP), _FP, _FP, _FP, _FP, C.c_size_t, _FP]
-        L.cnr_composite_background_scratch_bytes.restype = C.c_size_t
-        L.cnr_composite_background_scratch_bytes.argtypes = [C.c_int64]
-        L.cnr_composite_background_forward.argtypes = [C.POINTER(CnrBgCompositeIn), C.POINTER(CnrOutputs), _FP, C.c_size_t, _FP]
-        L.cnr_composite_background_backward.argtypes = [C.POINTER(CnrBgCompositeIn), C.POINTER(CnrOutputs), C.POINTER(CnrOutGrads),
-                                                        C.POINTER(CnrBgCompositeGrads), _FP, C.c_size_t, _FP]
-        if L.cnr_abi_version() != 9:
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(self.lib, name)      # (CDLL keeps the function object as an attribute of self.lib from here on)
+            fn.restype, fn.argtypes = restype, argtypes
+        if self.lib.cnr_abi_version() != ABI_VERSION:
             raise RuntimeError("colorneus library ABI mismatch")
 
     @property
@@ -221,6 +213,17 @@ class RenderLibrary:
     def check(self, rc, what):
         if rc != 0:
             raise RuntimeError(f"{what} failed: {self.lib.cnr_last_error().decode()}")
+
+    def call(self, name, *args):
+        """Call the status-returning entry point ``name``; a non-zero status raises with that name and cnr_last_error()."""
+        if getattr(self.lib, name)(*args) != 0:
+            raise RuntimeError(f"{name} failed: {self.lib.cnr_last_error().decode()}")
+
+    def scratch(self, bytes_fn, device, *args, at_least=0):
+        """(uninitialised uint8 tensor on ``device``, nbytes) for the size function ``bytes_fn(*args)``; the tensor holds at least
+        ``at_least`` bytes (a valid pointer where the size can be 0), nbytes is what the size function said."""
+        nb = getattr(self.lib, bytes_fn)(*args)
+        return torch.empty(max(nb, at_least), dtype=torch.uint8, device=device), nb
 
     def timing_enable(self, on: bool):
         self.lib.cnr_timing_enable(1 if on else 0)
@@ -232,15 +235,17 @@ class RenderLibrary:
         return [(buf[i].name.decode(), buf[i].kind, buf[i].nt, buf[i].P, buf[i].N, buf[i].K, buf[i].pairs, buf[i].ms, buf[i].bytes)
                 for i in range(min(n, max_records))]
 
-    def param_inventory(self, ccfg):
-        n = self.lib.cnr_param_count(C.byref(ccfg))
+    def param_inventory(self, ccfg, count="cnr_param_count", info="cnr_param_info"):
+        """[(name, rows, cols)] of a configuration in the library's canonical order; ``count`` / ``info`` name the pair of entry points
+        (the renderer's by default, cnr_nerf_param_* for the background network's CnrNerfConfig)."""
+        n = getattr(self.lib, count)(C.byref(ccfg))
         if n < 0:
             raise RuntimeError(f"unsupported renderer configuration: {self.lib.cnr_last_error().decode()}")
         out = []
         buf = C.create_string_buffer(128)
         r, c = C.c_int(), C.c_int()
         for i in range(n):
-            self.check(self.lib.cnr_param_info(C.byref(ccfg), i, buf, 128, C.byref(r), C.byref(c)), "cnr_param_info")
+            self.call(info, C.byref(ccfg), i, buf, 128, C.byref(r), C.byref(c))
             out.append((buf.value.decode(), r.value, c.value))
         return out
 
@@ -250,16 +255,63 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def stream_of(t):
-    """The current stream of a CUDA tensor's device as the ABI's stream argument (NULL for CPU tensors)."""
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else C.c_void_p(0)
+def stream_of(x):
+    """The current stream of a tensor's device, or of a torch.device, as the ABI's stream argument (NULL on the CPU)."""
+    dev = x if isinstance(x, torch.device) else x.device
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
+
+
+def param_array(tensors, n=None):
+    """The addresses of ``tensors`` as a ``void*[n]`` (n: len(tensors) unless given); a None entry and every slot past the list are NULL."""
+    return (C.c_void_p * (len(tensors) if n is None else n))(*[t.data_ptr() if t is not None else None for t in tensors])
+
+
+def flat_grads(plist, device, n=None):
+    """Gradients of the parameters ``plist`` as views into ONE flat float32 buffer (in this order): a ray-sharded run all-reduces it as is
+    and the fused optimiser step (optim.ClipAdam, optim.flat_view_of_grads) streams it -- no torch.cat, no copy back.  Returns
+    (flat, views, param_array(views, n)).
+
+    A backward pass must hand the views over WITHOUT keeping a second reference (``del views, flat`` before it returns): autograd then
+    installs them as p.grad as they are (it clones a gradient that something else still references), so p.grad aliases the flat buffer."""
+    sizes = [p.numel() for p in plist]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+    views, off = [], 0
+    for p, size in zip(plist, sizes):
+        views.append(flat[off:off + size].view(p.shape))
+        off += size
+    return flat, views, param_array(views, n)
+
+
+def float3(v):
+    """A host ``float[3]`` (bound_min / bound_max arguments)."""
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def ordered_names(inventory, named, exempt_prefix=None):
+    """The names of a library inventory [(name, rows, cols)] in its order, checked against a module's ``dict(named_parameters())``: every
+    entry exists with rows * cols elements, and the module has no parameter beyond them other than those under ``exempt_prefix``."""
+    order = []
+    for name, rows, cols in inventory:
+        if name not in named:
+            raise RuntimeError(f"library expects parameter {name!r} which this module does not have")
+        if named[name].numel() != rows * cols:
+            raise RuntimeError(f"parameter {name}: expected {rows}x{cols}, have {tuple(named[name].shape)}")
+        order.append(name)
+    extra = [k for k in named if k not in order and not (exempt_prefix and k.startswith(exempt_prefix))]
+    if extra:
+        raise RuntimeError(f"parameter inventory mismatch between module and library: {extra[:3]}")
+    return order
+
+
+def resolve_library(library=None):
+    """``library`` as a RenderLibrary: the object itself, the build at a path, or (None) the HIP library next to this file."""
+    return library if isinstance(library, RenderLibrary) else load_library(library)
 
 
 def library_for(library, dev, what):
     """The library that serves tensors on ``dev``: CUDA tensors use the HIP library, CPU tensors only an explicitly passed CPU-emulation
     ``library=``.  There is no CPU fallback: a mismatch raises.  ``what`` words the message ("points ... searched", "images ... evaluated")."""
-    lib = library if isinstance(library, RenderLibrary) else load_library(library)
+    lib = resolve_library(library)
     if lib.backend.startswith("hip") != (dev.type == "cuda"):
         raise RuntimeError(f"{what[0]} on '{dev}' cannot be {what[1]} by the '{lib.backend}' library: CUDA tensors use the HIP library, CPU tensors "
                            "need an explicitly passed CPU-emulation library= (there is no CPU fallback)")

@@ -16,14 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream_of(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else C.c_void_p(0)
+from ._lib import param_array, ptr, stream_of
 
 
 class NeRF(nn.Module):
@@ -51,23 +44,8 @@ class NeRF(nn.Module):
     def ordered_params(self, lib):
         """Parameters in the library's canonical order (cnr_nerf_param_info), checked against this module's own names and shapes."""
         if self._order is None:
-            cfg = self.config()
-            named = dict(self.named_parameters())
-            n = lib.lib.cnr_nerf_param_count(C.byref(cfg))
-            if n < 0:
-                lib.check(n, "cnr_nerf_param_count")
-            order = []
-            for i in range(n):
-                buf = C.create_string_buffer(128)
-                rows, cols = C.c_int(), C.c_int()
-                lib.check(lib.lib.cnr_nerf_param_info(C.byref(cfg), i, buf, 128, C.byref(rows), C.byref(cols)), "cnr_nerf_param_info")
-                name = buf.value.decode()
-                if name not in named or named[name].numel() != rows.value * cols.value:
-                    raise RuntimeError(f"background parameter inventory mismatch at {name}")
-                order.append(name)
-            if set(order) != set(named):
-                raise RuntimeError("background parameter inventory mismatch between module and library")
-            self._order = order
+            inv = lib.param_inventory(self.config(), "cnr_nerf_param_count", "cnr_nerf_param_info")
+            self._order = _lib.ordered_names(inv, dict(self.named_parameters()))
         named = dict(self.named_parameters())
         return [named[k] for k in self._order]
 
@@ -87,8 +65,7 @@ class OutsideZ(torch.autograd.Function):
         t_c = t_rand.detach().to(dev).contiguous().float() if t_rand is not None else None
         z_feed = torch.empty(R, M + n_outside, dtype=torch.float32, device=dev)
         src = torch.empty(R, M + n_outside, dtype=torch.int32, device=dev)
-        lib.check(lib.lib.cnr_outside_z(_ptr(far_c), _ptr(t_c), _ptr(z_c), R, M, n_outside, n_samples, _ptr(z_feed), _ptr(src), _stream_of(z_c)),
-                  "cnr_outside_z")
+        lib.call("cnr_outside_z", ptr(far_c), ptr(t_c), ptr(z_c), R, M, n_outside, n_samples, ptr(z_feed), ptr(src), stream_of(z_c))
         ctx.lib, ctx.meta = lib, (R, M, n_samples, n_outside, far.shape, t_c is not None)
         ctx.save_for_backward(src, t_c if t_c is not None else torch.empty(0, device=dev))
         ctx.mark_non_differentiable(src)
@@ -102,8 +79,8 @@ class OutsideZ(torch.autograd.Function):
         dz = d_z_feed.contiguous().float()
         d_far = torch.empty(R, dtype=torch.float32, device=dz.device)
         d_z = torch.empty(R, M, dtype=torch.float32, device=dz.device) if ctx.needs_input_grad[3] else None
-        lib.check(lib.lib.cnr_outside_z_backward(_ptr(t_c if has_t else None), _ptr(src), _ptr(dz), R, M, n_outside, n_samples, _ptr(d_far), _ptr(d_z),
-                                                 _stream_of(dz)), "cnr_outside_z_backward")
+        lib.call("cnr_outside_z_backward", ptr(t_c if has_t else None), ptr(src), ptr(dz), R, M, n_outside, n_samples, ptr(d_far), ptr(d_z),
+                 stream_of(dz))
         return None, d_far.reshape(far_shape), None, d_z, None, None
 
 
@@ -116,13 +93,11 @@ class Background(torch.autograd.Function):
         dev = z_feed.device
         o, d, zf = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float(), z_feed.detach().contiguous().float()
         plist = [p.detach().contiguous().float() for p in params]
-        parr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
         alpha = torch.empty(R, MF, dtype=torch.float32, device=dev)
         color = torch.empty(R, MF, 3, dtype=torch.float32, device=dev)
-        nb = lib.lib.cnr_background_ctx_bytes(C.byref(ncfg), R, MF)
-        buf = torch.empty(nb, dtype=torch.uint8, device=dev)
-        lib.check(lib.lib.cnr_background_forward(C.byref(ncfg), parr, _ptr(o), _ptr(d), _ptr(zf), R, MF, float(sample_dist), _ptr(alpha), _ptr(color),
-                                                 _ptr(buf), nb, _stream_of(zf)), "cnr_background_forward")
+        buf, nb = lib.scratch("cnr_background_ctx_bytes", dev, C.byref(ncfg), R, MF)
+        lib.call("cnr_background_forward", C.byref(ncfg), param_array(plist), ptr(o), ptr(d), ptr(zf), R, MF, float(sample_dist), ptr(alpha),
+                 ptr(color), ptr(buf), nb, stream_of(zf))
         ctx.lib, ctx.ncfg, ctx.meta = lib, ncfg, (R, MF, float(sample_dist), len(plist))
         ctx.save_for_backward(o, d, zf, color, buf, *plist)
         ctx.set_materialize_grads(False)
@@ -138,21 +113,15 @@ class Background(torch.autograd.Function):
         dev = zf.device
         da = d_alpha.contiguous().float() if d_alpha is not None else None
         dc = d_color.contiguous().float() if d_color is not None else None
-        parr = (C.c_void_p * npar)(*[p.data_ptr() for p in plist])
-        flat = torch.empty(sum(p.numel() for p in plist), dtype=torch.float32, device=dev)
-        gviews, off = [], 0
-        for p in plist:
-            gviews.append(flat[off:off + p.numel()].view_as(p))
-            off += p.numel()
-        garr = (C.c_void_p * npar)(*[g.data_ptr() for g in gviews])
+        flat, gviews, garr = _lib.flat_grads(plist, dev)
         d_o, d_d = torch.empty(R, 3, dtype=torch.float32, device=dev), torch.empty(R, 3, dtype=torch.float32, device=dev)
         d_zf = torch.empty(R, MF, dtype=torch.float32, device=dev)
-        nb = lib.lib.cnr_background_bwd_scratch_bytes(C.byref(ncfg), R, MF)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        lib.check(lib.lib.cnr_background_backward(C.byref(ncfg), parr, _ptr(o), _ptr(d), _ptr(zf), R, MF, sample_dist, _ptr(buf), buf.numel(), _ptr(color),
-                                                  _ptr(da), _ptr(dc), garr, _ptr(d_o), _ptr(d_d), _ptr(d_zf), _ptr(scratch), nb, _stream_of(zf)),
-                  "cnr_background_backward")
-        return (None, None, None, d_o, d_d, d_zf, *gviews)
+        scratch, nb = lib.scratch("cnr_background_bwd_scratch_bytes", dev, C.byref(ncfg), R, MF)
+        lib.call("cnr_background_backward", C.byref(ncfg), param_array(plist), ptr(o), ptr(d), ptr(zf), R, MF, sample_dist, ptr(buf), buf.numel(),
+                 ptr(color), ptr(da), ptr(dc), garr, ptr(d_o), ptr(d_d), ptr(d_zf), ptr(scratch), nb, stream_of(zf))
+        res = (None, None, None, d_o, d_d, d_zf, *gviews)
+        del gviews, flat   # (_lib.flat_grads: the views go to autograd without a second reference)
+        return res
 
 
 _COMP_OUT = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "weights", "gradient_error", "depth", "global_color"]
@@ -176,10 +145,9 @@ class CompositeBg(torch.autograd.Function):
                    inside_sphere=torch.empty(R, M, **f32), depth=torch.empty(R, **f32), global_color=torch.empty(R, 3, **f32) if gcolor is not None else None,
                    eik_sums=torch.empty(2, **f32))
         cin = CompositeBg._cin(t, R, M, MF, sample_dist, cos_anneal_ratio)
-        cout = _lib.CnrOutputs(**{k: _ptr(out.get(k)) for k in _lib.OUTPUT_FIELDS})
-        nb = lib.lib.cnr_composite_background_scratch_bytes(R)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        lib.check(lib.lib.cnr_composite_background_forward(C.byref(cin), C.byref(cout), _ptr(scratch), nb, _stream_of(t["z_vals"])), "cnr_composite_background_forward")
+        cout = _lib.CnrOutputs(**{k: ptr(out.get(k)) for k in _lib.OUTPUT_FIELDS})
+        scratch, nb = lib.scratch("cnr_composite_background_scratch_bytes", dev, R)
+        lib.call("cnr_composite_background_forward", C.byref(cin), C.byref(cout), ptr(scratch), nb, stream_of(t["z_vals"]))
         ctx.lib, ctx.meta = lib, (R, M, MF, float(sample_dist), float(cos_anneal_ratio), gcolor is not None, background_rgb is not None, variance.shape)
         ctx.save_for_backward(*[t[k] if t[k] is not None else torch.empty(0, **f32) for k in
                                 ("rays_o", "rays_d", "z_vals", "z_feed", "sdf", "grads", "color", "gcolor", "bg_alpha", "bg_color", "variance", "bg")],
@@ -192,11 +160,11 @@ class CompositeBg(torch.autograd.Function):
 
     @staticmethod
     def _cin(t, R, M, MF, sample_dist, cos_anneal_ratio):
-        return _lib.CnrBgCompositeIn(rays_o=_ptr(t["rays_o"]), rays_d=_ptr(t["rays_d"]), z_vals=_ptr(t["z_vals"]), z_feed=_ptr(t["z_feed"]), n_rays=R, n_z=M,
-                                     n_feed=MF, sample_dist=float(sample_dist), sdf_samples=_ptr(t["sdf"]), gradients=_ptr(t["grads"]),
-                                     color_samples=_ptr(t["color"]), global_color_samples=_ptr(t["gcolor"]), bg_alpha=_ptr(t["bg_alpha"]),
-                                     bg_color=_ptr(t["bg_color"]), variance=_ptr(t["variance"]), cos_anneal_ratio=float(cos_anneal_ratio),
-                                     background_rgb=_ptr(t["bg"]))
+        return _lib.CnrBgCompositeIn(rays_o=ptr(t["rays_o"]), rays_d=ptr(t["rays_d"]), z_vals=ptr(t["z_vals"]), z_feed=ptr(t["z_feed"]), n_rays=R, n_z=M,
+                                     n_feed=MF, sample_dist=float(sample_dist), sdf_samples=ptr(t["sdf"]), gradients=ptr(t["grads"]),
+                                     color_samples=ptr(t["color"]), global_color_samples=ptr(t["gcolor"]), bg_alpha=ptr(t["bg_alpha"]),
+                                     bg_color=ptr(t["bg_color"]), variance=ptr(t["variance"]), cos_anneal_ratio=float(cos_anneal_ratio),
+                                     background_rgb=ptr(t["bg"]))
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -210,22 +178,20 @@ class CompositeBg(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         names = [k for k in _COMP_OUT if has_gc or k != "global_color"]
         g = {k: (v.contiguous().float() if v is not None else None) for k, v in zip(names, gouts[:len(names)])}
-        go = _lib.CnrOutGrads(**{k: _ptr(g.get(k)) for k in _lib.OUT_GRAD_FIELDS})
+        go = _lib.CnrOutGrads(**{k: ptr(g.get(k)) for k in _lib.OUT_GRAD_FIELDS})
         cin = CompositeBg._cin(t, R, M, MF, sample_dist, car)
-        cout = _lib.CnrOutputs(**{k: _ptr({"weights": weights, "eik_sums": eik_sums}.get(k)) for k in _lib.OUTPUT_FIELDS})
+        cout = _lib.CnrOutputs(**{k: ptr({"weights": weights, "eik_sums": eik_sums}.get(k)) for k in _lib.OUTPUT_FIELDS})
         # (composite_bg_args checks the forward output pointers: the backward only reads weights and eik_sums, the rest may be any valid buffers)
         dummyR = torch.empty(R, max(M, 3), **f32)
         for k in ("color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "inside_sphere", "depth", "gradient_error", "global_color"):
-            setattr(cout, k, _ptr(dummyR))
+            setattr(cout, k, ptr(dummyR))
         d = dict(d_sdf_samples=torch.empty(R, M, **f32), d_gradients=torch.empty(R, M, 3, **f32), d_color_samples=torch.empty(R, M, 3, **f32),
                  d_global_color_samples=torch.empty(R, M, 3, **f32) if has_gc else None, d_bg_alpha=torch.empty(R, MF, **f32),
                  d_bg_color=torch.empty(R, MF, 3, **f32), d_variance=torch.empty(1, **f32), d_rays_d=torch.empty(R, 3, **f32),
                  d_z_vals=torch.zeros(R, M, **f32), d_z_feed=torch.empty(R, MF, **f32))
-        gi = _lib.CnrBgCompositeGrads(**{k: _ptr(v) for k, v in d.items()})
-        nb = lib.lib.cnr_composite_background_scratch_bytes(R)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        lib.check(lib.lib.cnr_composite_background_backward(C.byref(cin), C.byref(cout), C.byref(go), C.byref(gi), _ptr(scratch), nb, _stream_of(weights)),
-                  "cnr_composite_background_backward")
+        gi = _lib.CnrBgCompositeGrads(**{k: ptr(v) for k, v in d.items()})
+        scratch, nb = lib.scratch("cnr_composite_background_scratch_bytes", dev, R)
+        lib.call("cnr_composite_background_backward", C.byref(cin), C.byref(cout), C.byref(go), C.byref(gi), ptr(scratch), nb, stream_of(weights))
         need = ctx.needs_input_grad
         return (None, None, None, None, None, d["d_rays_d"] if need[5] else None, d["d_z_vals"] if need[6] else None, d["d_z_feed"] if need[7] else None,
                 d["d_sdf_samples"], d["d_gradients"], d["d_color_samples"], d["d_global_color_samples"], d["d_bg_alpha"], d["d_bg_color"],

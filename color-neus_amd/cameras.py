@@ -23,27 +23,15 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._lib import ptr, stream_of
 
 __all__ = ["FocalNet", "PoseNet", "Cameras", "cameras_from_state_dict"]
 
 _POSE_MODE = {"3d": 0, "6d": 1}
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream_of(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
-
-
 def _library(library, dev):
-    lib = library if isinstance(library, _lib.RenderLibrary) else _lib.load_library(library)
-    hip = lib.backend.startswith("hip")
-    if hip != (dev.type == "cuda"):
-        raise RuntimeError(f"camera parameters on '{dev}' cannot be evaluated by the '{lib.backend}' library: CUDA tensors use the HIP library, "
-                           "CPU tensors need an explicitly passed CPU-emulation library= (there is no CPU fallback)")
-    return lib
+    return _lib.library_for(library, dev, ("camera parameters", "evaluated"))
 
 
 def _f32(t):
@@ -70,9 +58,8 @@ class _CameraFunction(torch.autograd.Function):
                                    has_init_c2w=int(ic is not None))
         if B > 0 or focal is not None:
             pose = B > 0
-            lib.check(lib.lib.cnr_camera_forward(C.byref(cfg), _ptr(rc if pose else None), _ptr(tc if pose else None), _ptr(ic if pose else None),
-                                                 _ptr(fxc), _ptr(fyc), _ptr(ids if pose else None), B, _ptr(c2w if pose else None), _ptr(focal),
-                                                 _stream_of(dev)), "cnr_camera_forward")
+            lib.call("cnr_camera_forward", C.byref(cfg), ptr(rc if pose else None), ptr(tc if pose else None), ptr(ic if pose else None),
+                     ptr(fxc), ptr(fyc), ptr(ids if pose else None), B, ptr(c2w if pose else None), ptr(focal), stream_of(dev))
         ctx.lib, ctx.cfg, ctx.B = lib, cfg, B
         ctx.shapes = (fx.shape if fx is not None else None, fy.shape if fy is not None else None)
         saved = (ids, rc, tc, ic, fxc, fyc)
@@ -102,10 +89,9 @@ class _CameraFunction(torch.autograd.Function):
         if pose or focal:
             g_c = _f32(d_c2w) if pose else None
             g_f = _f32(d_focal) if focal else None
-            ctx.lib.check(ctx.lib.lib.cnr_camera_backward(C.byref(ctx.cfg), _ptr(rc if pose else None), _ptr(tc if pose else None),
-                                                          _ptr(ic if pose else None), _ptr(fxc if focal else None), _ptr(fyc if focal else None),
-                                                          _ptr(ids if pose else None), B, _ptr(g_c), _ptr(g_f), _ptr(d_r), _ptr(d_t), _ptr(d_fx),
-                                                          _ptr(d_fy), _stream_of(dev)), "cnr_camera_backward")
+            ctx.lib.call("cnr_camera_backward", C.byref(ctx.cfg), ptr(rc if pose else None), ptr(tc if pose else None),
+                         ptr(ic if pose else None), ptr(fxc if focal else None), ptr(fyc if focal else None), ptr(ids if pose else None), B,
+                         ptr(g_c), ptr(g_f), ptr(d_r), ptr(d_t), ptr(d_fx), ptr(d_fy), stream_of(dev))
         sx, sy = ctx.shapes
         return (None, None, None, d_r, d_t, None, d_fx.reshape(sx) if d_fx is not None else None, d_fy.reshape(sy) if d_fy is not None else None)
 

@@ -10,16 +10,12 @@ are not dependencies of this package.
 Inputs of any float dtype and any strides are detached and converted to contiguous float32 on their own device, and the work goes to the
 current stream.  CUDA tensors go through the HIP library; CPU tensors only with an explicitly passed emulation ``library=`` (there is no CPU
 fallback).  NOTHING HERE IS DIFFERENTIABLE."""
-import ctypes as C
-
 import torch
 
 from . import _lib, meshio, parallel, rays
+from ._lib import ptr, stream_of
 
 __all__ = ["image_metrics", "psnr", "ssim", "mse2psnr", "PSNR", "SSIM", "AverageMeter", "cmap", "panel", "validate_image"]
-
-
-_ptr, _stream_of = _lib.ptr, _lib.stream_of
 
 
 def _library(library, dev):
@@ -78,10 +74,8 @@ def image_metrics(img0, img1, return_map=False, library=None):
     n = b * c * h * w
     sums = torch.empty(2, dtype=torch.float64, device=x.device)
     smap = torch.empty_like(x) if return_map else None      # empty_like keeps the memory format
-    nb = lib.lib.cnr_image_scratch_bytes(b, c, h, w)
-    scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
-    lib.check(lib.lib.cnr_image_metrics(_ptr(x), _ptr(y), b, c, h, w, int(cl), _ptr(smap), _ptr(sums), _ptr(scratch), nb, _stream_of(x)),
-              "cnr_image_metrics")
+    scratch, nb = lib.scratch("cnr_image_scratch_bytes", x.device, b, c, h, w, at_least=1)
+    lib.call("cnr_image_metrics", ptr(x), ptr(y), b, c, h, w, int(cl), ptr(smap), ptr(sums), ptr(scratch), nb, stream_of(x))
     means = sums / torch.full((), float(n), dtype=torch.float64, device=x.device)      # tensor / tensor: a true float64 division on either device
     mse, mean_ssim = means[0], means[1]
     out = {"mse": mse, "psnr": -10.0 * torch.log10(mse), "ssim": mean_ssim}
@@ -186,10 +180,9 @@ def _panel(gt, render, depth, library):
         colour.append(t.contiguous())
     out = torch.empty(h, (3 if colour else 1) * w, 3, dtype=torch.uint8, device=d.device)
     rng = torch.empty(2, dtype=torch.float32, device=d.device)
-    nb = lib.lib.cnr_image_scratch_bytes(1, 3, h, w)
-    scratch = torch.empty(nb, dtype=torch.uint8, device=d.device)
-    lib.check(lib.lib.cnr_image_panel(_ptr(colour[0] if colour else None), _ptr(colour[1] if colour else None), _ptr(d), h, w, _ptr(out), _ptr(rng),
-                                      _ptr(scratch), nb, _stream_of(d)), "cnr_image_panel")
+    scratch, nb = lib.scratch("cnr_image_scratch_bytes", d.device, 1, 3, h, w)
+    lib.call("cnr_image_panel", ptr(colour[0] if colour else None), ptr(colour[1] if colour else None), ptr(d), h, w, ptr(out), ptr(rng),
+             ptr(scratch), nb, stream_of(d))
     return out
 
 

@@ -39,14 +39,7 @@ def compute_loss(render_dict, rgb_gt, mask=None, lambda_fine=1.0, lambda_eikonal
 # ---------------------------------------------------------------------------------------------------------------------
 import ctypes as _C
 
-
-def _p(t):
-    return _C.c_void_p(t.data_ptr()) if t is not None else _C.c_void_p(0)
-
-
-def _stream(t):
-    return _C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else _C.c_void_p(0)
-
+from ._lib import CnrLossConfig, ptr, resolve_library, stream_of
 
 _SCRATCH = {}   # (library path, device, stream) -> the loss scratch of that stream
 
@@ -87,20 +80,19 @@ class _FusedLoss(torch.autograd.Function):
             # single process: the two reduction phases and the scalar tail of the objective in ONE launch (cnr_loss_forward)
             sums, out8 = torch.empty(4, **f32), torch.empty(8, **f32)
             gerr_c = gerr.detach().reshape(-1).to(**f32).contiguous()
-            lib.check(lib.lib.cnr_loss_forward(_C.byref(lcfg), _p(color_c), _p(wsum_c), _p(drel_c), int(per_ray), _p(gt_c), _p(mask_c), _p(gerr_c), R, int(M), Rg,
-                                               int(use_mask), int(use_rel), _p(sums), _p(out8), _p(scratch), nb, _stream(color_c)), "cnr_loss_forward")
+            lib.call("cnr_loss_forward", _C.byref(lcfg), ptr(color_c), ptr(wsum_c), ptr(drel_c), int(per_ray), ptr(gt_c), ptr(mask_c), ptr(gerr_c), R, int(M),
+                     Rg, int(use_mask), int(use_rel), ptr(sums), ptr(out8), ptr(scratch), nb, stream_of(color_c))
             eik_factor = None
         else:
             # ray-sharded: this rank's statistics (one launch), ONE 5-float all-reduce, the scalar tail on the reduced statistics (one launch);
             # no torch arithmetic in between (include/colorneus_render.h, cnr_loss_shard_*)
             stats, out8 = torch.empty(8, **f32), torch.empty(8, **f32)
             eik_c = eik_sums.detach().reshape(-1).to(**f32).contiguous()
-            lib.check(lib.lib.cnr_loss_shard_stats(_C.byref(lcfg), _p(color_c), _p(wsum_c), _p(drel_c), int(per_ray), _p(gt_c), _p(mask_c), _p(eik_c), R, int(M),
-                                                   _p(stats), _p(scratch), nb, _stream(color_c)), "cnr_loss_shard_stats")
+            lib.call("cnr_loss_shard_stats", _C.byref(lcfg), ptr(color_c), ptr(wsum_c), ptr(drel_c), int(per_ray), ptr(gt_c), ptr(mask_c), ptr(eik_c), R,
+                     int(M), ptr(stats), ptr(scratch), nb, stream_of(color_c))
             if world > 1:
                 dist.all_reduce(stats[:5], op=dist.ReduceOp.SUM, group=group)
-            lib.check(lib.lib.cnr_loss_shard_combine(_C.byref(lcfg), _p(stats), Rg, int(M), int(use_mask), int(use_rel), _p(out8), _stream(color_c)),
-                      "cnr_loss_shard_combine")
+            lib.call("cnr_loss_shard_combine", _C.byref(lcfg), ptr(stats), Rg, int(M), int(use_mask), int(use_rel), ptr(out8), stream_of(color_c))
             eik_factor = out8[6]
         loss, rgb_loss, eik, mask_out, rel_out, mean_rel = out8[:6].unbind(0)
         ctx.lib, ctx.lcfg, ctx.Rg, ctx.M = lib, lcfg, Rg, M
@@ -134,9 +126,9 @@ class _FusedLoss(torch.autograd.Function):
         want_drel = has_rel and ctx.shapes[2] is not None
         # d mean(delta_relight * mask)^2 / d delta_relight[r, j, c] = 2 mean / n * mask[r]: one value per ray, written by the same launch
         per_ray = torch.empty(R, dtype=torch.float32, device=dev) if want_drel else None
-        lib.check(lib.lib.cnr_loss_backward(_C.byref(lcfg), _p(color_c), _p(wsum_c), _p(gt_c), _p(mask_g), R, int(M), _p(g.reshape(-1).contiguous()),
-                                            _p(mean_rel), _p(eik_factor if has_factor else None), Rg, int(has_mask), int(has_rel), _p(coef), _p(d_color),
-                                            _p(d_wsum), _p(per_ray), _stream(color_c)), "cnr_loss_backward")
+        lib.call("cnr_loss_backward", _C.byref(lcfg), ptr(color_c), ptr(wsum_c), ptr(gt_c), ptr(mask_g), R, int(M), ptr(g.reshape(-1).contiguous()),
+                 ptr(mean_rel), ptr(eik_factor if has_factor else None), Rg, int(has_mask), int(has_rel), ptr(coef), ptr(d_color), ptr(d_wsum),
+                 ptr(per_ray), stream_of(color_c))
         d_drel = None
         if want_drel:
             # handed to the renderer's backward as an expanded (stride-0) view -- its compositor backward takes the per-ray vector, no
@@ -151,8 +143,7 @@ def compute_loss_fused(render_dict, rgb_gt, mask=None, lambda_fine=1.0, lambda_e
     """Same objective and return convention as compute_loss, evaluated by the render library's loss kernels.  With
     ``n_rays_global`` (ray-sharded data parallel) the returned loss is the GLOBAL value on every rank and its backward yields the
     rank-local gradients whose sum over ranks is the single-GPU gradient."""
-    from ._lib import CnrLossConfig, load_library
-    lib = library if library is not None else load_library()
+    lib = resolve_library(library)
     lcfg = CnrLossConfig(lambda_fine, lambda_eikonal, lambda_mask, lambda_relight, 0 if rgb_loss_type == "mse" else 1, 1 if include_mask else 0)
     drel = render_dict.get("delta_relight") if lambda_relight != 0 else None
     n_samples = 0

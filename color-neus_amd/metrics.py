@@ -8,16 +8,12 @@ calls in float64.
 Every function takes ``(N, 3)`` tensors of any float dtype and any strides, converts them to contiguous float32 on their own device and runs on
 the current stream.  CUDA tensors go through the HIP library; CPU tensors only with an explicitly passed emulation ``library=`` (there is no
 CPU fallback).  NOTHING HERE IS DIFFERENTIABLE: inputs are detached and results carry no graph."""
-import ctypes as C
-
 import torch
 
 from . import _lib, meshio
+from ._lib import ptr, stream_of
 
 __all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance"]
-
-
-_ptr, _stream_of = _lib.ptr, _lib.stream_of
 
 
 def _library(library, dev):
@@ -41,9 +37,8 @@ def _search(q, t, lib):
     idx = torch.empty(n, dtype=torch.int32, device=q.device)
     if n == 0:
         return dist2, idx
-    nb = lib.lib.cnr_nn_scratch_bytes(n, m)
-    scratch = torch.empty(nb, dtype=torch.uint8, device=q.device)
-    lib.check(lib.lib.cnr_nn_search(_ptr(q), n, _ptr(t), m, _ptr(dist2), _ptr(idx), _ptr(scratch), nb, _stream_of(q)), "cnr_nn_search")
+    scratch, nb = lib.scratch("cnr_nn_scratch_bytes", q.device, n, m)
+    lib.call("cnr_nn_search", ptr(q), n, ptr(t), m, ptr(dist2), ptr(idx), ptr(scratch), nb, stream_of(q))
     return dist2, idx
 
 

@@ -16,6 +16,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import param_array, ptr, stream_of
 
 
 def flat_view_of_grads(params):
@@ -23,11 +24,11 @@ def flat_view_of_grads(params):
     grads = [p.grad for p in params]
     if not grads or any(g is None or not g.is_contiguous() or g.dtype != torch.float32 for g in grads):
         return None
-    ptr = grads[0].data_ptr()
+    addr = grads[0].data_ptr()
     for g in grads:
-        if g.data_ptr() != ptr:
+        if g.data_ptr() != addr:
             return None
-        ptr += g.numel() * 4
+        addr += g.numel() * 4
     g0 = grads[0]
     total = sum(g.numel() for g in grads)
     st = g0.untyped_storage()
@@ -58,8 +59,7 @@ class ClipAdam(torch.optim.Optimizer):
     @property
     def _lib(self):
         if self._lib_obj is None:
-            lib = self._library
-            self._lib_obj = lib if isinstance(lib, _lib.RenderLibrary) else _lib.load_library(lib)
+            self._lib_obj = _lib.resolve_library(self._library)
         return self._lib_obj
 
     def _group_state(self, gi, group):
@@ -129,7 +129,7 @@ class ClipAdam(torch.optim.Optimizer):
                 raise RuntimeError("ClipAdam: the parameter list of a group changed after the first step")
             b1, b2 = group["betas"]
             mn = group.get("max_norm")
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
+            stream = stream_of(dev)
             offs = [0]
             for z in sizes_all:
                 offs.append(offs[-1] + z)
@@ -152,15 +152,12 @@ class ClipAdam(torch.optim.Optimizer):
                 grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
                 n = len(ps)
                 sz = (C.c_int64 * n)(*sizes_all[i:j + 1])
-                pw = (C.c_void_p * n)(*[p.data_ptr() for p in ps])
-                pg = (C.c_void_p * n)(*[g.data_ptr() for g in grads])
+                pw, pg = param_array(ps), param_array(grads)
                 nb = self._lib.lib.cnr_clip_adam_scratch_bytes(n, sz)
                 key = (gi, str(dev))
                 if key not in self._scratch or self._scratch[key].numel() < nb:   # scratch is not optimiser state: kept out of state_dict
                     self._scratch[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
-                rc = self._lib.lib.cnr_clip_adam_step(C.byref(cfg), n, sz, pw, pg, C.c_void_p(st["exp_avg"].data_ptr() + 4 * offs[i]),
-                                                      C.c_void_p(st["exp_avg_sq"].data_ptr() + 4 * offs[i]),
-                                                      C.c_void_p(self._scratch[key].data_ptr()), nb, stream)
-                self._lib.check(rc, "cnr_clip_adam_step")
+                self._lib.call("cnr_clip_adam_step", C.byref(cfg), n, sz, pw, pg, C.c_void_p(st["exp_avg"].data_ptr() + 4 * offs[i]),
+                               C.c_void_p(st["exp_avg_sq"].data_ptr() + 4 * offs[i]), ptr(self._scratch[key]), nb, stream)
                 i = j + 1
         return loss

@@ -15,19 +15,8 @@ import warnings
 
 import torch
 
-from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream_of(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else C.c_void_p(0)
-
-
-def _library(library):
-    return library if isinstance(library, _lib.RenderLibrary) else _lib.load_library(library)
+from ._lib import ptr, stream_of
+from ._lib import resolve_library as _library
 
 
 def choose_pixels(n_rays, pixels_per_image, device, mask=None, mask_rate=0.9):
@@ -118,10 +107,9 @@ class _GenRays(torch.autograd.Function):
         msel = torch.empty(n, **f32) if msk is not None else None
         near = torch.empty(n, **f32) if want_nearfar else None
         far = torch.empty(n, **f32) if want_nearfar else None
-        rc = lib.lib.cnr_gen_rays(_ptr(idx), n, _ptr(c2w_c), c2w_c.shape[0], _ptr(focal_c), H, W, int(normalize), int(opengl), _ptr(img), _ptr(msk),
-                                  _ptr(org), float(radius), _ptr(rays_o), _ptr(rays_d), _ptr(rgb), _ptr(msel), _ptr(near), _ptr(far),
-                                  _ptr(_bad_counter(dev)) if idx is not None else C.c_void_p(0), _stream_of(c2w_c))
-        lib.check(rc, "cnr_gen_rays")
+        lib.call("cnr_gen_rays", ptr(idx), n, ptr(c2w_c), c2w_c.shape[0], ptr(focal_c), H, W, int(normalize), int(opengl), ptr(img), ptr(msk),
+                 ptr(org), float(radius), ptr(rays_o), ptr(rays_d), ptr(rgb), ptr(msel), ptr(near), ptr(far),
+                 ptr(_bad_counter(dev)) if idx is not None else C.c_void_p(0), stream_of(c2w_c))
         ctx.lib, ctx.meta = lib, (n, H, W, int(normalize), int(opengl), float(radius), c2w.shape, focal.shape)
         ctx.save_for_backward(idx if idx is not None else torch.empty(0, dtype=torch.int64, device=dev), c2w_c, focal_c,
                               org if org is not None else torch.empty(0, device=dev))
@@ -148,10 +136,9 @@ class _GenRays(torch.autograd.Function):
         d_c2w = torch.empty_like(c2w_c)
         d_focal = torch.empty(2, dtype=torch.float32, device=dev)
         scratch = torch.empty(c2w_c.shape[0] * 2, dtype=torch.float32, device=dev)
-        rc = ctx.lib.lib.cnr_gen_rays_backward(_ptr(idx if idx.numel() else None), n, _ptr(c2w_c), c2w_c.shape[0], _ptr(focal_c), H, W, normalize, opengl,
-                                               _ptr(org if org.numel() else None), radius, _ptr(d_o), _ptr(d_d), _ptr(d_near), _ptr(d_far),
-                                               _ptr(d_c2w), _ptr(d_focal), _ptr(scratch), scratch.numel() * 4, _stream_of(c2w_c))
-        ctx.lib.check(rc, "cnr_gen_rays_backward")
+        ctx.lib.call("cnr_gen_rays_backward", ptr(idx if idx.numel() else None), n, ptr(c2w_c), c2w_c.shape[0], ptr(focal_c), H, W, normalize, opengl,
+                     ptr(org if org.numel() else None), radius, ptr(d_o), ptr(d_d), ptr(d_near), ptr(d_far), ptr(d_c2w), ptr(d_focal),
+                     ptr(scratch), scratch.numel() * 4, stream_of(c2w_c))
         return (None, None, None, d_c2w.reshape(c2w_shape) if need[3] else None, d_focal.reshape(focal_shape) if need[4] else None,
                 None, None, None, None, None, None, None, None, None)
 

@@ -13,21 +13,63 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._lib import param_array, ptr, stream_of
 from .config import RenderConfig, config_from_node
 
 _OUT_DIFF = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error", "depth",
              "global_color", "delta_relight"]
 _SAMPLE_OUT = ["sdf_samples", "color_samples", "global_color_samples"]   # per-sample network outputs (only with want_samples)
+_RETURN_KEYS = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error", "inside_sphere",
+                "depth", "global_color", "delta_relight_ray_sum", "delta_relight", "z_vals", "eik_sums"]   # of NeuSRenderer.forward's dict
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+def _alloc_outputs(cfg, R, device, mode):
+    """The output tensors of one render call, keyed by _lib.OUTPUT_FIELDS' names (None: not produced, passed as NULL).  ``mode``:
+    "saving" (the training dict), "loss_only" (what compute_loss needs: no [R][M][3] tensors, the relight term as per-ray sums),
+    "with_samples" (the dict plus the per-sample network outputs for the N_OUTSIDE mixing) or "forward_only" (same entries as "saving")."""
+    M, color = cfg.n_total, cfg.type == "Color_NeuS"
+    loss_only, samples = mode == "loss_only", mode == "with_samples"
+    f32 = dict(dtype=torch.float32, device=device)
+    return dict(color_fine=torch.empty(R, 3, **f32), s_val=torch.empty(R, 1, **f32), cdf_fine=torch.empty(R, M, **f32),
+                weight_sum=torch.empty(R, 1, **f32), weight_max=torch.empty(R, 1, **f32),
+                gradients=None if loss_only else torch.empty(R, M, 3, **f32), weights=torch.empty(R, M, **f32),
+                gradient_error=torch.empty((), **f32), inside_sphere=torch.empty(R, M, **f32), depth=torch.empty(R, **f32),
+                global_color=torch.empty(R, 3, **f32) if color else None,
+                delta_relight=torch.empty(R, M, 3, **f32) if (color and not loss_only) else None,
+                delta_relight_ray_sum=torch.empty(R, **f32) if (color and loss_only) else None,
+                z_vals=torch.empty(R, M, **f32), eik_sums=torch.empty(2, **f32),
+                sdf_samples=torch.empty(R, M, **f32) if samples else None,
+                color_samples=torch.empty(R, M, 3, **f32) if samples else None,
+                global_color_samples=torch.empty(R, M, 3, **f32) if (samples and color) else None)
 
 
-def _stream_of(t):
-    if t.is_cuda:
-        return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-    return C.c_void_p(0)
+def _rays_f32(rays_o, rays_d, near, far):
+    """The four ray inputs as the contiguous float32 tensors the library reads (near / far flattened)."""
+    return (rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float(),
+            near.detach().reshape(-1).contiguous().float(), far.detach().reshape(-1).contiguous().float())
+
+
+def _inputs(rays_o, rays_d, near, far, t_rand=None, z_override=None, background_rgb=None, cos_anneal_ratio=0.0, prune_eps=0.0):
+    """CnrInputs of contiguous float32 tensors (``z_override``: the z_vals output buffer that already holds the given positions, or None)."""
+    return _lib.CnrInputs(rays_o=ptr(rays_o), rays_d=ptr(rays_d), near_=ptr(near), far_=ptr(far), t_rand=ptr(t_rand),
+                          z_vals_override=ptr(z_override) if z_override is not None else None, background_rgb=ptr(background_rgb),
+                          n_rays=rays_o.shape[0], cos_anneal_ratio=float(cos_anneal_ratio), prune_eps=float(prune_eps))
+
+
+def _forward_call(owner, entry, bytes_fn, mode, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio, prune_eps, params):
+    """What cnr_render_forward and cnr_render_forward_only share: (outputs, float32 ray inputs, detached parameters, context / scratch buffer)."""
+    lib, ccfg, cfg = owner._lib, owner._ccfg, owner.rcfg
+    R = rays_o.shape[0]
+    rays = _rays_f32(rays_o, rays_d, near, far)
+    out = _alloc_outputs(cfg, R, rays_o.device, mode)
+    if z_override is not None:
+        out["z_vals"].copy_(z_override.detach().reshape(R, cfg.n_total))
+    plist = [p.detach().contiguous() for p in params]
+    cin = _inputs(*rays, t_rand, out["z_vals"] if z_override is not None else None, background_rgb, cos_anneal_ratio, prune_eps)
+    cout = _lib.CnrOutputs(**{k: ptr(out[k]) for k in _lib.OUTPUT_FIELDS})
+    buf, nbytes = lib.scratch(bytes_fn, rays_o.device, C.byref(ccfg), R)
+    lib.call(entry, C.byref(ccfg), param_array(plist), C.byref(cin), C.byref(cout), ptr(buf), nbytes, stream_of(rays_o))
+    return out, rays, plist, buf
 
 
 class _RenderFunction(torch.autograd.Function):
@@ -35,47 +77,20 @@ class _RenderFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, owner, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio, prune_eps, want_samples, *params):
-        lib, ccfg, cfg = owner._lib, owner._ccfg, owner.rcfg
-        dev = rays_o.device
-        R, M = rays_o.shape[0], cfg.n_total
-        f32 = dict(dtype=torch.float32, device=dev)
-        rays_o_c, rays_d_c = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
-        near_c, far_c = near.detach().reshape(-1).contiguous().float(), far.detach().reshape(-1).contiguous().float()
-        color = cfg.type == "Color_NeuS"
+        cfg = owner.rcfg
         # want_samples: False / True (per-sample network outputs for the N_OUTSIDE mixing) / "loss_only" (the training outputs compute_loss
         # needs: no [R][M][3] dict tensors, the relight term as per-ray sums)
-        loss_only = want_samples == "loss_only"
-        want_samples = want_samples is True
-        out = dict(color_fine=torch.empty(R, 3, **f32), s_val=torch.empty(R, 1, **f32), cdf_fine=torch.empty(R, M, **f32),
-                   weight_sum=torch.empty(R, 1, **f32), weight_max=torch.empty(R, 1, **f32),
-                   gradients=None if loss_only else torch.empty(R, M, 3, **f32), weights=torch.empty(R, M, **f32),
-                   gradient_error=torch.empty((), **f32), inside_sphere=torch.empty(R, M, **f32), depth=torch.empty(R, **f32),
-                   global_color=torch.empty(R, 3, **f32) if color else None,
-                   delta_relight=torch.empty(R, M, 3, **f32) if (color and not loss_only) else None,
-                   delta_relight_ray_sum=torch.empty(R, **f32) if (color and loss_only) else None,
-                   z_vals=torch.empty(R, M, **f32), eik_sums=torch.empty(2, **f32),
-                   sdf_samples=torch.empty(R, M, **f32) if want_samples else None,
-                   color_samples=torch.empty(R, M, 3, **f32) if want_samples else None,
-                   global_color_samples=torch.empty(R, M, 3, **f32) if (want_samples and color) else None)
-        if z_override is not None:
-            out["z_vals"].copy_(z_override.detach().reshape(R, M))
-        plist = [p.detach().contiguous() for p in params]
-        parr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
-        cin = _lib.CnrInputs(rays_o=_ptr(rays_o_c), rays_d=_ptr(rays_d_c), near_=_ptr(near_c), far_=_ptr(far_c),
-                             t_rand=_ptr(t_rand), z_vals_override=_ptr(out["z_vals"]) if z_override is not None else None,
-                             background_rgb=_ptr(background_rgb), n_rays=R, cos_anneal_ratio=float(cos_anneal_ratio),
-                             prune_eps=float(prune_eps))
-        cout = _lib.CnrOutputs(**{k: _ptr(out[k]) for k in _lib.OUTPUT_FIELDS})
-        nbytes = lib.lib.cnr_ctx_bytes(C.byref(ccfg), R)
-        ctx_buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rc = lib.lib.cnr_render_forward(C.byref(ccfg), parr, C.byref(cin), C.byref(cout), _ptr(ctx_buf), nbytes, _stream_of(rays_o))
-        lib.check(rc, "cnr_render_forward")
+        mode = "loss_only" if want_samples == "loss_only" else "with_samples" if want_samples is True else "saving"
+        out, (rays_o_c, rays_d_c, near_c, far_c), plist, ctx_buf = _forward_call(
+            owner, "cnr_render_forward", "cnr_ctx_bytes", mode, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio,
+            prune_eps, params)
         ctx.owner = owner
         # tensors go through save_for_backward (outputs held in a plain attribute would form an uncollectable
         # tensor -> grad_fn -> ctx -> tensor cycle and leak the multi-GB context buffer every step)
         ctx.cfg_aux = (float(cos_anneal_ratio), z_override is not None, t_rand is not None, background_rgb is not None, len(plist),
                        float(prune_eps))
-        saved = [rays_o_c, rays_d_c, near_c, far_c, out["z_vals"], out["gradients"] if out["gradients"] is not None else torch.empty(0, **f32), ctx_buf]
+        saved = [rays_o_c, rays_d_c, near_c, far_c, out["z_vals"],
+                 out["gradients"] if out["gradients"] is not None else torch.empty(0, dtype=torch.float32, device=rays_o.device), ctx_buf]
         if t_rand is not None:
             saved.append(t_rand)
         if background_rgb is not None:
@@ -96,7 +111,7 @@ class _RenderFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gouts):
         owner = ctx.owner
-        lib, ccfg, cfg = owner._lib, owner._ccfg, owner.rcfg
+        lib, ccfg = owner._lib, owner._ccfg
         car, had_override, has_trand, has_bg, nparams, prune_eps = ctx.cfg_aux
         if prune_eps > 0:
             raise RuntimeError("prune_eps > 0 is inference-only (early-termination compaction); call under torch.no_grad()")
@@ -109,7 +124,6 @@ class _RenderFunction(torch.autograd.Function):
         pos += 1 if has_bg else 0
         plist = sv[pos:pos + nparams]
         R = rays_o.shape[0]
-        color = cfg.type == "Color_NeuS"
         names = ctx.diff_names + ctx.sample_names
         gmap = {}
         for k, g in zip(names, gouts[:len(names)]):
@@ -123,76 +137,38 @@ class _RenderFunction(torch.autograd.Function):
                 gmap["delta_relight_per_ray"] = g[:, 0, 0].contiguous().float()
                 continue
             gmap[k] = g.contiguous().float() if g is not None else None
-        cg = _lib.CnrOutGrads(**{k: _ptr(gmap.get(k)) for k in _lib.OUT_GRAD_FIELDS})
-        # every parameter gradient is a view into ONE flat buffer (canonical parameter order): a ray-sharded run all-reduces it as is and
-        # the fused optimiser step (optim.ClipAdam) streams it -- no torch.cat, no copy back
-        flat = torch.empty(sum(p.numel() for p in plist), dtype=torch.float32, device=rays_o.device)
-        dparams, off = [], 0
-        for p in plist:
-            dparams.append(flat[off:off + p.numel()].view(p.shape))
-            off += p.numel()
-        darr = (C.c_void_p * len(dparams))(*[p.data_ptr() for p in dparams])
+        cg = _lib.CnrOutGrads(**{k: ptr(gmap.get(k)) for k in _lib.OUT_GRAD_FIELDS})
+        flat, dparams, darr = _lib.flat_grads(plist, rays_o.device)
         d_o = torch.empty_like(rays_o) if ctx.rays_need_grad else None
         d_d = torch.empty_like(rays_d) if ctx.rays_need_grad else None
         d_near = torch.empty_like(near) if ctx.nearfar_need_grad else None
         d_far = torch.empty_like(far) if ctx.nearfar_need_grad else None
-        gin = _lib.CnrInGrads(d_params=C.cast(darr, C.POINTER(C.c_void_p)), d_rays_o=_ptr(d_o), d_rays_d=_ptr(d_d),
-                              d_near=_ptr(d_near), d_far=_ptr(d_far))
-        parr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
-        cin = _lib.CnrInputs(rays_o=_ptr(rays_o), rays_d=_ptr(rays_d), near_=_ptr(near), far_=_ptr(far), t_rand=_ptr(t_rand),
-                             z_vals_override=_ptr(z_vals) if had_override else None,
-                             background_rgb=_ptr(background_rgb), n_rays=R, cos_anneal_ratio=car)
-        cout = _lib.CnrOutputs(z_vals=_ptr(z_vals), gradients=_ptr(gradients) if gradients.numel() else None)   # the only forward outputs backward reads (gradients: NULL = kept in the context buffer)
-        nbytes = lib.lib.cnr_bwd_scratch_bytes(C.byref(ccfg), R)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=rays_o.device)
-        rc = lib.lib.cnr_render_backward(C.byref(ccfg), parr, C.byref(cin), C.byref(cout), _ptr(ctx_buf), ctx_buf.numel(),
-                                         C.byref(cg), C.byref(gin), _ptr(scratch), nbytes, _stream_of(rays_o))
-        lib.check(rc, "cnr_render_backward")
+        gin = _lib.CnrInGrads(d_params=C.cast(darr, C.POINTER(C.c_void_p)), d_rays_o=ptr(d_o), d_rays_d=ptr(d_d),
+                              d_near=ptr(d_near), d_far=ptr(d_far))
+        cin = _inputs(rays_o, rays_d, near, far, t_rand, z_vals if had_override else None, background_rgb, car)
+        cout = _lib.CnrOutputs(z_vals=ptr(z_vals), gradients=ptr(gradients) if gradients.numel() else None)   # the only forward outputs backward reads (gradients: NULL = kept in the context buffer)
+        scratch, nbytes = lib.scratch("cnr_bwd_scratch_bytes", rays_o.device, C.byref(ccfg), R)
+        lib.call("cnr_render_backward", C.byref(ccfg), param_array(plist), C.byref(cin), C.byref(cout), ptr(ctx_buf), ctx_buf.numel(),
+                 C.byref(cg), C.byref(gin), ptr(scratch), nbytes, stream_of(rays_o))
         if d_near is not None:
             d_near, d_far = d_near.reshape(ctx.nearfar_shapes[0]), d_far.reshape(ctx.nearfar_shapes[1])
-        # hand the views over without keeping a second reference: autograd then installs them as p.grad as they are (it clones a
-        # gradient that something else still references), so p.grad aliases the flat buffer
         res = (None, d_o, d_d, d_near, d_far, None, None, None, None, None, None) + tuple(dparams)
-        del dparams, flat
+        del dparams, flat   # (_lib.flat_grads: the views go to autograd without a second reference)
         return res
 
 
 def _render_forward_only(owner, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio, prune_eps, params):
     """cnr_render_forward_only: the inference use of the path (NeuS_Trainer.validate_image, NeuS_Trainer.py:236-245; evaluation.py).  Same
     outputs, bit-identical values; nothing is kept for a backward pass and the scratch buffer is about half of the training context (14.1 GB against 29.7 GB at 8192 rays)."""
-    lib, ccfg, cfg = owner._lib, owner._ccfg, owner.rcfg
-    dev = rays_o.device
-    R, M = rays_o.shape[0], cfg.n_total
-    f32 = dict(dtype=torch.float32, device=dev)
-    rays_o_c, rays_d_c = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
-    near_c, far_c = near.detach().reshape(-1).contiguous().float(), far.detach().reshape(-1).contiguous().float()
-    color = cfg.type == "Color_NeuS"
-    out = dict(color_fine=torch.empty(R, 3, **f32), s_val=torch.empty(R, 1, **f32), cdf_fine=torch.empty(R, M, **f32),
-               weight_sum=torch.empty(R, 1, **f32), weight_max=torch.empty(R, 1, **f32), gradients=torch.empty(R, M, 3, **f32),
-               weights=torch.empty(R, M, **f32), gradient_error=torch.empty((), **f32), inside_sphere=torch.empty(R, M, **f32),
-               depth=torch.empty(R, **f32), global_color=torch.empty(R, 3, **f32) if color else None,
-               delta_relight=torch.empty(R, M, 3, **f32) if color else None, delta_relight_ray_sum=None,
-               z_vals=torch.empty(R, M, **f32), eik_sums=torch.empty(2, **f32), sdf_samples=None, color_samples=None, global_color_samples=None)
-    if z_override is not None:
-        out["z_vals"].copy_(z_override.detach().reshape(R, M))
-    plist = [p.detach().contiguous() for p in params]
-    parr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
-    cin = _lib.CnrInputs(rays_o=_ptr(rays_o_c), rays_d=_ptr(rays_d_c), near_=_ptr(near_c), far_=_ptr(far_c),
-                         t_rand=_ptr(t_rand), z_vals_override=_ptr(out["z_vals"]) if z_override is not None else None,
-                         background_rgb=_ptr(background_rgb), n_rays=R, cos_anneal_ratio=float(cos_anneal_ratio), prune_eps=float(prune_eps))
-    cout = _lib.CnrOutputs(**{k: _ptr(out[k]) for k in _lib.OUTPUT_FIELDS})
-    nbytes = lib.lib.cnr_infer_scratch_bytes(C.byref(ccfg), R)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rc = lib.lib.cnr_render_forward_only(C.byref(ccfg), parr, C.byref(cin), C.byref(cout), _ptr(scratch), nbytes, _stream_of(rays_o))
-    lib.check(rc, "cnr_render_forward_only")
-    return out
+    return _forward_call(owner, "cnr_render_forward_only", "cnr_infer_scratch_bytes", "forward_only", rays_o, rays_d, near, far, t_rand,
+                         z_override, background_rgb, cos_anneal_ratio, prune_eps, params)[0]
 
 
 def sample_pdf(bins, weights, n_samples, det=False, library=None):
     """ray_utils.sample_pdf(bins, weights, n_samples, det=False) (lib/models/tools/ray_utils.py:121-154; same default as the reference) on the
     device: the hierarchical sampler's own kernel (cnr_sample_pdf; NeuS.up_sample passes det=True, NeuS.py:180).  det=False: the uniform draws come
     from torch.rand on the CPU generator with the reference's shape and call order (ray_utils.py:135-136), the inversion runs in the same kernel."""
-    lib = library if isinstance(library, _lib.RenderLibrary) else _lib.load_library(library)
+    lib = _lib.resolve_library(library)
     bins = bins.detach().contiguous().float()
     weights = weights.detach().contiguous().float()
     n = bins.shape[-1]
@@ -200,11 +176,10 @@ def sample_pdf(bins, weights, n_samples, det=False, library=None):
     R = bins.numel() // n
     out = torch.empty(*bins.shape[:-1], n_samples, dtype=torch.float32, device=bins.device)
     if det:
-        rc = lib.lib.cnr_sample_pdf(_ptr(bins), _ptr(weights), R, n, int(n_samples), _ptr(out), _stream_of(bins))
+        lib.call("cnr_sample_pdf", ptr(bins), ptr(weights), R, n, int(n_samples), ptr(out), stream_of(bins))
     else:
         u = torch.rand(list(bins.shape[:-1]) + [int(n_samples)]).to(bins.device).contiguous()
-        rc = lib.lib.cnr_sample_pdf_u(_ptr(bins), _ptr(weights), _ptr(u), R, n, int(n_samples), _ptr(out), _stream_of(bins))
-    lib.check(rc, "cnr_sample_pdf")
+        lib.call("cnr_sample_pdf_u", ptr(bins), ptr(weights), ptr(u), R, n, int(n_samples), ptr(out), stream_of(bins))
     return out
 
 
@@ -266,8 +241,7 @@ class _SdfQueryBinding:
     @property
     def lib(self):
         if self._lib_obj is None:
-            lib = self._library_arg
-            self._lib_obj = lib if isinstance(lib, _lib.RenderLibrary) else _lib.load_library(lib)
+            self._lib_obj = _lib.resolve_library(self._library_arg)
         return self._lib_obj
 
     def names(self):
@@ -291,11 +265,7 @@ class _SdfQueryBinding:
 
     def param_array(self, tensors):
         """The canonical inventory as a pointer array: the sdf_network entries (the leading ones) from ``tensors``, NULL for the others."""
-        nall, names = self.names()
-        ptrs = [None] * nall
-        for i, t in enumerate(tensors):
-            ptrs[i] = t.data_ptr() if t is not None else None
-        return (C.c_void_p * nall)(*ptrs)
+        return param_array(tensors, self.names()[0])
 
     def forward(self, x, params, want_grad, want_feat, keep_ctx):
         """cnr_sdf_query_forward on the float32 [n, 3] points x (0 < n): (sdf [n, 1], feat [n, F] or None, grad [n, 3] or None, ctx or None)."""
@@ -304,11 +274,9 @@ class _SdfQueryBinding:
         sdf = torch.empty(n, 1, **f32)
         feat = torch.empty(n, self.d_out - 1, **f32) if want_feat else None
         grad = torch.empty(n, 3, **f32) if want_grad else None
-        nb = L.lib.cnr_sdf_query_ctx_bytes(C.byref(self.ccfg), n, int(want_grad))
-        cbuf = torch.empty(nb, dtype=torch.uint8, device=dev)
-        rc = L.lib.cnr_sdf_query_forward(C.byref(self.ccfg), self.param_array(params), _ptr(x), n, int(want_grad), _ptr(sdf), _ptr(feat),
-                                         _ptr(grad), _ptr(cbuf), nb, _stream_of(x))
-        L.check(rc, "cnr_sdf_query_forward")
+        cbuf, nb = L.scratch("cnr_sdf_query_ctx_bytes", dev, C.byref(self.ccfg), n, int(want_grad))
+        L.call("cnr_sdf_query_forward", C.byref(self.ccfg), self.param_array(params), ptr(x), n, int(want_grad), ptr(sdf), ptr(feat),
+               ptr(grad), ptr(cbuf), nb, stream_of(x))
         return sdf, feat, grad, (cbuf if keep_ctx else None)
 
 
@@ -346,21 +314,14 @@ class _SdfQueryFunction(torch.autograd.Function):
             # one buffer; when the step also renders, this backward runs first (its node is newer), autograd adopts these views as the sdf
             # .grad tensors and adds the render's sdf gradients into them, while the colour / relight gradients stay in the render's buffer:
             # flat_view_of_grads over all parameters is then None and the all-reduce takes its gathered-copy path (same values, one copy)
-            flat = torch.empty(sum(p.numel() for p in plist), dtype=torch.float32, device=dev)
-            off = 0
-            for i, p in enumerate(plist):
-                dparams[i] = flat[off:off + p.numel()].view(p.shape)
-                off += p.numel()
-            darr = C.cast(binding.param_array(dparams), C.POINTER(C.c_void_p))
+            flat, dparams, darr = _lib.flat_grads(plist, dev, binding.names()[0])
         if need_x or need_p:
             wg = int(ctx.want_grad)
-            nb = L.lib.cnr_sdf_query_bwd_scratch_bytes(C.byref(binding.ccfg), n, wg)
-            scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-            rc = L.lib.cnr_sdf_query_backward(C.byref(binding.ccfg), binding.param_array(plist), _ptr(x), n, wg, _ptr(d_sdf), _ptr(d_feat),
-                                              _ptr(d_grad), _ptr(cbuf), cbuf.numel(), darr, _ptr(d_x), _ptr(scratch), nb, _stream_of(x))
-            L.check(rc, "cnr_sdf_query_backward")
+            scratch, nb = L.scratch("cnr_sdf_query_bwd_scratch_bytes", dev, C.byref(binding.ccfg), n, wg)
+            L.call("cnr_sdf_query_backward", C.byref(binding.ccfg), binding.param_array(plist), ptr(x), n, wg, ptr(d_sdf), ptr(d_feat),
+                   ptr(d_grad), ptr(cbuf), cbuf.numel(), darr, ptr(d_x), ptr(scratch), nb, stream_of(x))
         res = (None, None, None, d_x) + tuple(d if need else None for d, need in zip(dparams, ctx.needs_input_grad[4:]))
-        del dparams, flat
+        del dparams, flat   # (_lib.flat_grads: the views go to autograd without a second reference)
         return res
 
 
@@ -460,10 +421,8 @@ class _SDFNet(nn.Module):
         L = q.lib
         params = [p.detach().contiguous() for p in self._query_params()]
         out = torch.empty(n, 1, dtype=torch.float32, device=x.device)
-        nb = L.lib.cnr_sdf_eval_scratch_bytes(C.byref(q.ccfg), n)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=x.device)
-        rc = L.lib.cnr_sdf_eval(C.byref(q.ccfg), q.param_array(params), _ptr(x), n, 1.0, _ptr(out), _ptr(scratch), nb, _stream_of(x))
-        L.check(rc, "cnr_sdf_eval")
+        scratch, nb = L.scratch("cnr_sdf_eval_scratch_bytes", x.device, C.byref(q.ccfg), n)
+        L.call("cnr_sdf_eval", C.byref(q.ccfg), q.param_array(params), ptr(x), n, 1.0, ptr(out), ptr(scratch), nb, stream_of(x))
         return out
 
 
@@ -537,26 +496,14 @@ class NeuSRenderer(nn.Module):
     @property
     def _lib(self):
         if self._lib_obj is None:
-            lib = self._library_arg
-            self._lib_obj = lib if isinstance(lib, _lib.RenderLibrary) else _lib.load_library(lib)
+            self._lib_obj = _lib.resolve_library(self._library_arg)
         return self._lib_obj
 
     def _ordered_params(self):
         """Parameters in the library's canonical order (names = reference state_dict names)."""
         if self._order is None:
-            inv = self._lib.param_inventory(self._ccfg)
-            named = dict(self.named_parameters())
-            order = []
-            for name, rows, cols in inv:
-                if name not in named:
-                    raise RuntimeError(f"library expects parameter {name!r} which this module does not have")
-                if named[name].numel() != rows * cols:
-                    raise RuntimeError(f"parameter {name}: expected {rows}x{cols}, have {tuple(named[name].shape)}")
-                order.append(name)
-            extra = [k for k in named if k not in order and not k.startswith("nerf.")]   # nerf.*: the background network has its own inventory (cnr_nerf_param_info)
-            if extra:
-                raise RuntimeError(f"parameter inventory mismatch between module and library: {extra[:3]}")
-            self._order = order
+            # nerf.*: the background network has its own inventory (cnr_nerf_param_info)
+            self._order = _lib.ordered_names(self._lib.param_inventory(self._ccfg), dict(self.named_parameters()), exempt_prefix="nerf.")
         named = dict(self.named_parameters())
         return [named[k] for k in self._order]
 
@@ -629,30 +576,17 @@ class NeuSRenderer(nn.Module):
             if loss_only:
                 raise ValueError("training_outputs='loss_only' belongs to the training step, not to a forward-only call")
             out = _render_forward_only(self, rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps, params)
-            ret = {k: out[k] for k in ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights",
-                                       "gradient_error", "inside_sphere", "depth"]}
-            if self.rcfg.type == "Color_NeuS":
-                ret["global_color"], ret["delta_relight"] = out["global_color"], out["delta_relight"]
-            ret["z_vals"], ret["eik_sums"] = out["z_vals"], out["eik_sums"]
-            return ret
-        res = _RenderFunction.apply(self, rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps,
-                                    "loss_only" if loss_only else False, *params)
-        color = self.rcfg.type == "Color_NeuS"
-        names = [k for k in _OUT_DIFF if not (k in ("global_color", "delta_relight") and not color) and not (loss_only and k in ("gradients", "delta_relight"))]
-        if loss_only and color:
-            names.append("delta_relight_ray_sum")
-        out = dict(zip(names + ["inside_sphere", "z_vals", "eik_sums"], res))
-        ret = {k: out[k] for k in ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights",
-                                   "gradient_error", "inside_sphere", "depth"] if k in out}
-        if color:
-            ret["global_color"] = out["global_color"]
-            if loss_only:
-                ret["delta_relight_ray_sum"] = out["delta_relight_ray_sum"]
-            else:
-                ret["delta_relight"] = out["delta_relight"]
-        ret["z_vals"] = out["z_vals"]       # extra keys (not in the reference dict)
-        ret["eik_sums"] = out["eik_sums"]   # {sum relax*(|g|-1)^2, sum relax}: needed by ray-sharded training
-        return ret
+        else:
+            res = _RenderFunction.apply(self, rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps,
+                                        "loss_only" if loss_only else False, *params)
+            color = self.rcfg.type == "Color_NeuS"
+            names = [k for k in _OUT_DIFF if not (k in ("global_color", "delta_relight") and not color) and not (loss_only and k in ("gradients", "delta_relight"))]
+            if loss_only and color:
+                names.append("delta_relight_ray_sum")
+            out = dict(zip(names + ["inside_sphere", "z_vals", "eik_sums"], res))
+        # the reference's dict in its key order, then the extra keys (not in the reference dict): z_vals, and eik_sums =
+        # {sum relax*(|g|-1)^2, sum relax}, needed by ray-sharded training
+        return {k: out[k] for k in _RETURN_KEYS if out.get(k) is not None}
 
     def _empty_batch(self, dev, background_rgb, cos_anneal_ratio):
         """No rays (the reference runs its torch ops on empty tensors): the C ABI takes n_rays > 0, so one dummy ray is rendered without
@@ -669,10 +603,8 @@ class NeuSRenderer(nn.Module):
         z = z_vals.detach().contiguous().float()
         R, n = z.shape
         out = torch.empty(R, int(n_importance), dtype=torch.float32, device=z.device)
-        rc = self._lib.lib.cnr_up_sample(_ptr(rays_o.detach().contiguous().float()), _ptr(rays_d.detach().contiguous().float()), _ptr(z),
-                                         _ptr(sdf.detach().reshape(R, n).contiguous().float()), R, n, int(n_importance), float(inv_s),
-                                         _ptr(out), _stream_of(z))
-        self._lib.check(rc, "cnr_up_sample")
+        self._lib.call("cnr_up_sample", ptr(rays_o.detach().contiguous().float()), ptr(rays_d.detach().contiguous().float()), ptr(z),
+                       ptr(sdf.detach().reshape(R, n).contiguous().float()), R, n, int(n_importance), float(inv_s), ptr(out), stream_of(z))
         return out
 
     # -- N_OUTSIDE > 0 (NeuS.py:313-369): four library calls chained by autograd (background.py); no tensor arithmetic here ------------
@@ -713,21 +645,18 @@ class NeuSRenderer(nn.Module):
         """The hierarchical sampler on its own (cnr_sample_z): final z_vals [R, M], no gradient (NeuS.py:343)."""
         rc, dev = self.rcfg, rays_o.device
         R = len(rays_o)
-        o, d = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float()
-        nr, fr = near.detach().reshape(-1).contiguous().float(), far.detach().reshape(-1).contiguous().float()
+        rays = _rays_f32(rays_o, rays_d, near, far)
         z = torch.empty(R, rc.n_total, dtype=torch.float32, device=dev)
         plist, parr = self._param_array()
-        cin = _lib.CnrInputs(rays_o=_ptr(o), rays_d=_ptr(d), near_=_ptr(nr), far_=_ptr(fr), t_rand=_ptr(t_rand), n_rays=R)
-        nb = self._lib.lib.cnr_ctx_bytes(C.byref(self._ccfg), R)
-        buf = torch.empty(nb, dtype=torch.uint8, device=dev)
-        rcode = self._lib.lib.cnr_sample_z(C.byref(self._ccfg), parr, C.byref(cin), _ptr(z), _ptr(buf), nb, _stream_of(o))
-        self._lib.check(rcode, "cnr_sample_z")
+        cin = _inputs(*rays, t_rand)
+        buf, nb = self._lib.scratch("cnr_ctx_bytes", dev, C.byref(self._ccfg), R)
+        self._lib.call("cnr_sample_z", C.byref(self._ccfg), parr, C.byref(cin), ptr(z), ptr(buf), nb, stream_of(rays[0]))
         return z
 
     # -- evaluation paths (NeuS.py:14-64, 410-420) ---------------------------------------------------------------------
     def _param_array(self):
         plist = [p.detach().contiguous() for p in self._ordered_params()]
-        return plist, (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
+        return plist, param_array(plist)
 
     def sdf(self, pts, sign=1.0):
         """sdf_network.sdf(pts) (fields.py:99) on the device, any number of points."""
@@ -737,37 +666,28 @@ class NeuSRenderer(nn.Module):
         if n == 0:   # (the C ABI takes n_points > 0)
             return out
         plist, parr = self._param_array()
-        nb = self._lib.lib.cnr_sdf_eval_scratch_bytes(C.byref(self._ccfg), n)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=pts.device)
-        rc = self._lib.lib.cnr_sdf_eval(C.byref(self._ccfg), parr, _ptr(pts), n, float(sign), _ptr(out), _ptr(scratch), nb,
-                                        _stream_of(pts))
-        self._lib.check(rc, "cnr_sdf_eval")
+        scratch, nb = self._lib.scratch("cnr_sdf_eval_scratch_bytes", pts.device, C.byref(self._ccfg), n)
+        self._lib.call("cnr_sdf_eval", C.byref(self._ccfg), parr, ptr(pts), n, float(sign), ptr(out), ptr(scratch), nb, stream_of(pts))
         return out
 
     def extract_fields(self, bound_min, bound_max, device, resolution):
         """u = -sdf on linspace(bound_min, bound_max, resolution)^3 (NeuS.py:14-28); stays on the device, one D2H at the end."""
-        bmin = (C.c_float * 3)(*[float(x) for x in bound_min])
-        bmax = (C.c_float * 3)(*[float(x) for x in bound_max])
+        bmin, bmax = _lib.float3(bound_min), _lib.float3(bound_max)
         dev = torch.device(device)
         u = torch.empty(resolution, resolution, resolution, dtype=torch.float32, device=dev)
         plist, parr = self._param_array()
-        nb = self._lib.lib.cnr_sdf_grid_scratch_bytes(C.byref(self._ccfg), resolution)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        rc = self._lib.lib.cnr_sdf_grid(C.byref(self._ccfg), parr, bmin, bmax, resolution, _ptr(u), _ptr(scratch), nb, _stream_of(u))
-        self._lib.check(rc, "cnr_sdf_grid")
+        scratch, nb = self._lib.scratch("cnr_sdf_grid_scratch_bytes", dev, C.byref(self._ccfg), resolution)
+        self._lib.call("cnr_sdf_grid", C.byref(self._ccfg), parr, bmin, bmax, resolution, ptr(u), ptr(scratch), nb, stream_of(u))
         return u
 
     def extract_fields_slab(self, bound_min, bound_max, device, resolution, x_begin, x_end):
         """Rows x in [x_begin, x_end) of extract_fields' lattice (same values): the unit of the sharded evaluation (parallel.sharded_extract_fields)."""
-        bmin = (C.c_float * 3)(*[float(x) for x in bound_min])
-        bmax = (C.c_float * 3)(*[float(x) for x in bound_max])
+        bmin, bmax = _lib.float3(bound_min), _lib.float3(bound_max)
         dev = torch.device(device)
         u = torch.empty(x_end - x_begin, resolution, resolution, dtype=torch.float32, device=dev)
         plist, parr = self._param_array()
-        nb = self._lib.lib.cnr_sdf_grid_slab_scratch_bytes(C.byref(self._ccfg), resolution, x_begin, x_end)
-        scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
-        rc = self._lib.lib.cnr_sdf_grid_slab(C.byref(self._ccfg), parr, bmin, bmax, resolution, x_begin, x_end, _ptr(u), _ptr(scratch), nb, _stream_of(u))
-        self._lib.check(rc, "cnr_sdf_grid_slab")
+        scratch, nb = self._lib.scratch("cnr_sdf_grid_slab_scratch_bytes", dev, C.byref(self._ccfg), resolution, x_begin, x_end, at_least=1)
+        self._lib.call("cnr_sdf_grid_slab", C.byref(self._ccfg), parr, bmin, bmax, resolution, x_begin, x_end, ptr(u), ptr(scratch), nb, stream_of(u))
         return u
 
     def marching_cubes(self, u, bound_min, bound_max, threshold=0.0):
@@ -777,16 +697,14 @@ class NeuSRenderer(nn.Module):
         res = u.shape[0]
         assert u.shape == (res, res, res)
         lib = self._lib
-        nb = lib.lib.cnr_mc_scratch_bytes(res)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=u.device)
+        scratch, nb = lib.scratch("cnr_mc_scratch_bytes", u.device, res)
         totals = torch.empty(2, dtype=torch.int32, device=u.device)
-        lib.check(lib.lib.cnr_mc_count(_ptr(u), res, float(threshold), _ptr(scratch), nb, _ptr(totals), _stream_of(u)), "cnr_mc_count")
+        lib.call("cnr_mc_count", ptr(u), res, float(threshold), ptr(scratch), nb, ptr(totals), stream_of(u))
         nv, nt = (int(x) for x in totals.tolist())     # the one host round trip: the caller owns the output buffers
         verts = torch.empty(max(nv, 1), 3, dtype=torch.float32, device=u.device)
         tris = torch.empty(max(nt, 1), 3, dtype=torch.int32, device=u.device)
-        bmin = (C.c_float * 3)(*[float(x) for x in bound_min])
-        bmax = (C.c_float * 3)(*[float(x) for x in bound_max])
-        lib.check(lib.lib.cnr_mc_emit(_ptr(u), res, float(threshold), bmin, bmax, _ptr(scratch), nb, _ptr(verts), _ptr(tris), _stream_of(u)), "cnr_mc_emit")
+        bmin, bmax = _lib.float3(bound_min), _lib.float3(bound_max)
+        lib.call("cnr_mc_emit", ptr(u), res, float(threshold), bmin, bmax, ptr(scratch), nb, ptr(verts), ptr(tris), stream_of(u))
         return verts[:nv], tris[:nt]
 
     def extract_geometry(self, bound_min, bound_max, device, resolution, threshold=0.0):
@@ -804,10 +722,8 @@ class NeuSRenderer(nn.Module):
         if n == 0:
             return rgb.cpu().numpy()
         plist, parr = self._param_array()
-        nb = self._lib.lib.cnr_vertex_color_scratch_bytes(C.byref(self._ccfg), n)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=pts.device)
-        rc = self._lib.lib.cnr_vertex_color(C.byref(self._ccfg), parr, _ptr(pts), n, _ptr(rgb), _ptr(scratch), nb, _stream_of(pts))
-        self._lib.check(rc, "cnr_vertex_color")
+        scratch, nb = self._lib.scratch("cnr_vertex_color_scratch_bytes", pts.device, C.byref(self._ccfg), n)
+        self._lib.call("cnr_vertex_color", C.byref(self._ccfg), parr, ptr(pts), n, ptr(rgb), ptr(scratch), nb, stream_of(pts))
         return rgb.cpu().numpy()
 
 
