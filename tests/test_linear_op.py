@@ -61,6 +61,12 @@ def _embed(x, multires):
 
 # (k, n_out, relu): pts_linears[0], pts_linears[i], the skip layer, alpha / feature heads, the view branch, the rgb head (NeRF(), fields.py:228-248)
 SHAPES = [(84, 256, True), (256, 256, True), (340, 256, True), (256, 1, False), (256, 256, False), (283, 128, True), (128, 3, False), (5, 7, True)]
+# widths between the tested 64 and 256 (tests/test_width_lattice.py runs whole networks of them; these isolate one forward, one backward and one
+# weight-gradient launch per shape): the weight-stationary kernel with 128 / 96 weight rows and 8 / 7 k16 blocks, K = 240 (the boundary of its
+# stream form) and K = 272 beyond it, an output one column either side of its 96-column threshold, an 80-wide output (3-tile general kernel),
+# and outputs of exactly 32 and 33 columns (the row-tail boundary of the weight-gradient tiles)
+SHAPES += [(128, 128, True), (112, 96, True), (240, 256, True), (48, 160, False), (272, 224, True), (256, 95, True), (256, 97, False), (80, 80, True),
+           (256, 32, False), (256, 33, False)]
 
 
 def _check(library, device, sizes):
@@ -69,9 +75,21 @@ def _check(library, device, sizes):
     g = torch.Generator().manual_seed(0)
     for n in sizes:
         for k, n_out, relu in SHAPES:
-            x = torch.randn(n, k, generator=g).to(device).requires_grad_(True)
-            w = (torch.randn(n_out, k, generator=g) / k ** 0.5).to(device).requires_grad_(True)
-            b = (torch.randn(n_out, generator=g) * 0.1).to(device).requires_grad_(True)
+            x = torch.randn(n, k, generator=g)
+            w = torch.randn(n_out, k, generator=g) / k ** 0.5
+            b = torch.randn(n_out, generator=g) * 0.1
+            if relu:
+                # The derivative of ReLU is discontinuous at 0: a pre-activation closer to 0 than the tolerance on y may be gated the other way
+                # by a y that passes, which moves its whole row of dx and dW by O(1) (met on the first draw of (1280, 272, 224): one unit at 4.1e-7,
+                # y = 0 -- a wrong row in dx and dW at 7e-2).  Rows holding such a pre-activation (about 2 % of them) are drawn again, so every gate is decided by y's check.
+                for _ in range(16):
+                    z = torch.nn.functional.linear(x.double(), w.double(), b.double())
+                    near = (z.abs() < 2e-5 * float(z.max())).any(dim=1)
+                    if not bool(near.any()):
+                        break
+                    x[near] = torch.randn(int(near.sum()), k, generator=g)
+                assert not bool(near.any()), (n, k, n_out)
+            x, w, b = x.to(device).requires_grad_(True), w.to(device).requires_grad_(True), b.to(device).requires_grad_(True)
             dy = torch.randn(n, n_out, generator=g).to(device)
             ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
             if relu:
