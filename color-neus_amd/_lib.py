@@ -124,9 +124,12 @@ SIGNATURES = {
     "cnr_loss_backward": (_int, [_lcfg, _FP, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _FP, _f32, _i32, _i32, _FP, _FP, _FP, _FP, _FP]),
     "cnr_loss_shard_stats": (_int, [_lcfg, _FP, _FP, _FP, _i32, _FP, _FP, _FP, _i64, _i32, _FP, _FP, _size, _FP]),
     "cnr_loss_shard_combine": (_int, [_lcfg, _FP, _f32, _i32, _i32, _i32, _FP, _FP]),
-    # ray generation, learnable cameras
+    # ray generation, on-device pixel choice, learnable cameras
     "cnr_gen_rays": (_int, [_FP, _i64, _FP, _i32, _FP, _i32, _i32, _i32, _i32, _FP, _FP, _FP, _f32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     "cnr_gen_rays_backward": (_int, [_FP, _i64, _FP, _i32, _FP, _i32, _i32, _i32, _i32, _FP, _f32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _size, _FP]),
+    "cnr_pixel_table_scratch_bytes": (_size, [_i32, _i64]),
+    "cnr_pixel_table_build": (_int, [_FP, _i32, _i64, _FP, _FP, _FP, _FP, _size, _FP]),
+    "cnr_choose_pixels": (_int, [_FP, _i64, _i32, _FP, _FP, _i32, _i32, _i64, _FP, _FP, _FP, _i64, _FP, _FP, _FP, _FP, _FP]),
     "cnr_camera_forward": (_int, [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, _i64, _FP, _FP, _FP]),
     "cnr_camera_backward": (_int, [C.POINTER(CnrCameraConfig), _FP, _FP, _FP, _FP, _FP, _FP, _i64, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     # optimiser step

@@ -438,6 +438,28 @@ struct GenRaysBwd {
 void be_gen_rays(const GenRays& p, cnr_stream s);
 void be_gen_rays_bwd(const GenRaysBwd& p, cnr_stream s);
 
+// ---- on-device pixel choice (cnr_pixel_table_build / cnr_choose_pixels; specified in include/colorneus_render.h): the sampling semantics of
+// get_rays_multicam's pixel choice (ray_utils.py:57-76) on a Philox stream keyed by a device {seed, step}.  The arithmetic (pix_* in cnr_bodies.h)
+// is shared by the HIP kernels and the emulation; all of it is integer arithmetic.
+constexpr int kPixTile = 4096;            // pixels of one image that one workgroup counts / scatters (16 wave-chunks of 256: 64 lanes x one 16-byte load)
+constexpr int kPixMaxSlots = 1024;        // images per draw: the slot prefixes live in LDS
+struct PixelTable {
+  const float* masks; int n_images; long hw;   // [n_images][hw]
+  int* order;                             // [n_images][hw]: foreground pixels ascending, then background pixels ascending
+  int* fg_count; int* bg_count;           // [n_images]
+  int* tile_counts; long tiles;           // [n_images][tiles][2] scratch: per-tile {fg, bg} counts -> exclusive offsets within the image
+};
+void be_pixel_table(const PixelTable& t, cnr_stream s);
+struct PixelDraw {
+  long* state;                            // device {seed, step}; the step is advanced behind the draw
+  long n; int want_fg; const int* want_fg_dev;
+  const int* cam_ids; int B, n_images; long hw;
+  const int* order; const int* fg_count; const int* bg_count;   // all null: draws with replacement over [0, span)
+  unsigned long long span;
+  long* idx; int* cams_out; int* counts_out; float* t_rand;
+};
+void be_choose_pixels(const PixelDraw& p, cnr_stream s);
+
 // ---- learnable cameras (camera_net.py:8-109): the producer of c2w / focal in front of the ray generator
 struct Camera {
   const float* r; const float* t;       // [num_cams][6 or 3], [num_cams][3]; null: no pose part

@@ -461,6 +461,46 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
   }
 }
 
+void be_pixel_table(const PixelTable& t, cnr_stream) {
+#pragma omp parallel for schedule(static)
+  for (int n = 0; n < t.n_images; ++n) {
+    const float* m = t.masks + (long)n * t.hw;
+    int* row = t.order + (long)n * t.hw;
+    int f = 0, g = 0;
+    for (long i = 0; i < t.hw; ++i) f += pix_class(m[i]) == 1;
+    for (long i = 0, a = 0; i < t.hw; ++i) {
+      const int c = pix_class(m[i]);
+      if (c == 1) row[a++] = (int)i;
+      else if (c == 2) row[f + g++] = (int)i;
+    }
+    t.fg_count[n] = f; t.bg_count[n] = g;
+  }
+}
+
+void be_choose_pixels(const PixelDraw& p, cnr_stream) {
+  const PixKey k = pix_key(p.state[0], p.state[1]);
+  std::vector<unsigned> pf(p.B), pb(p.B);
+  std::vector<int> cams(p.B);
+  unsigned F = 0, G = 0;
+  for (int b = 0; b < p.B; ++b) {
+    unsigned f, g;
+    cams[b] = pix_slot_image(p, k, b);
+    pix_slot_counts(p, cams[b], &f, &g);
+    pf[b] = F += f; pb[b] = G += g;
+    if (p.cams_out) p.cams_out[b] = cams[b];
+  }
+  const unsigned want = (unsigned)pix_want_fg(p), kfg = want < F ? want : F;
+  const unsigned long long m = (unsigned long long)p.n - kfg;
+  if (p.counts_out) { p.counts_out[0] = p.order ? (int)kfg : 0; p.counts_out[1] = p.order ? (int)(m < G ? m : G) : 0; }
+#pragma omp parallel for schedule(static)
+  for (long j = 0; j < p.n; ++j) {
+    if (p.order) pix_draw_masked(p, k, j, pf.data(), pb.data(), cams.data(), kfg);
+    else p.idx[j] = pix_draw_replace(p, k, j);
+    if (p.t_rand) p.t_rand[j] = pix_jitter(k, j);
+  }
+  p.state[1] = (long)((unsigned long long)p.state[1] + 1ull);
+}
+
 void be_clip_adam(const AdamArgs& a, cnr_stream) {
   for (int k = 0; k < a.count; ++k) {
     const AdamTensor& t = a.t[k];

@@ -2312,6 +2312,57 @@ int cnr_gen_rays_backward(const int64_t* pix_idx, int64_t n, const float* c2w, i
   return check_backend("gen_rays_backward");
 }
 
+// ---- on-device pixel choice
+static long pixel_tiles(int64_t hw) { return (long)((hw + kPixTile - 1) / kPixTile); }
+static int pixel_table_dims(const char* who, int32_t n_images, int64_t hw) {
+  if (n_images <= 0 || hw <= 0) return fail("%s: n_images and pixels_per_image must be positive", who);
+  if (hw >= (int64_t)1 << 31) return fail("%s: pixels_per_image must be below 2^31 (pixel indices are int32)", who);
+  if ((double)n_images * (double)hw >= 4294967296.0) return fail("%s: n_images * pixels_per_image must be below 2^32", who);
+  return 0;
+}
+size_t cnr_pixel_table_scratch_bytes(int32_t n_images, int64_t pixels_per_image) {
+  if (n_images <= 0 || pixels_per_image <= 0) return 0;
+  return round_up_sz((size_t)n_images * (size_t)pixel_tiles(pixels_per_image) * 2 * sizeof(int), 256);
+}
+
+int cnr_pixel_table_build(const float* masks, int32_t n_images, int64_t pixels_per_image, int32_t* order, int32_t* fg_count, int32_t* bg_count,
+                          void* scratch, size_t scratch_bytes, void* stream) {
+  if (pixel_table_dims("pixel_table_build", n_images, pixels_per_image)) return -1;
+  if (!masks || !order || !fg_count || !bg_count || !scratch) return fail("pixel_table_build: null argument");
+  if (scratch_bytes < cnr_pixel_table_scratch_bytes(n_images, pixels_per_image)) return fail("pixel_table_build scratch too small");
+  PixelTable t;
+  t.masks = masks; t.n_images = n_images; t.hw = (long)pixels_per_image; t.order = order; t.fg_count = fg_count; t.bg_count = bg_count;
+  t.tile_counts = static_cast<int*>(scratch); t.tiles = pixel_tiles(pixels_per_image);
+  if ((double)n_images * (double)t.tiles >= 2147483648.0) return fail("pixel_table_build: too many tiles (n_images * ceil(pixels_per_image / %d) must be below 2^31)", kPixTile);
+  be_pixel_table(t, (cnr_stream)stream);
+  return check_backend("pixel_table_build");
+}
+
+int cnr_choose_pixels(int64_t* state, int64_t n, int32_t want_fg, const int32_t* want_fg_dev, const int32_t* cam_ids, int32_t images_per_step,
+                      int32_t n_images, int64_t pixels_per_image, const int32_t* order, const int32_t* fg_count, const int32_t* bg_count, int64_t span,
+                      int64_t* idx, int32_t* cams_out, int32_t* counts_out, float* t_rand, void* stream) {
+  if (n <= 0) return fail("choose_pixels: n must be positive");
+  if (n >= (int64_t)1 << 31) return fail("choose_pixels: n must be below 2^31");
+  if (pixel_table_dims("choose_pixels", n_images, pixels_per_image)) return -1;
+  if (images_per_step <= 0) return fail("choose_pixels: images_per_step must be positive");
+  if (images_per_step > kPixMaxSlots) return fail("choose_pixels: at most %d images per step (got %d)", kPixMaxSlots, (int)images_per_step);
+  if (images_per_step > n_images) return fail("choose_pixels: images_per_step %d exceeds the table's %d images", (int)images_per_step, (int)n_images);
+  if (!state || !idx) return fail("choose_pixels: null argument");
+  const bool table = order && fg_count && bg_count;
+  if (!table && (order || fg_count || bg_count)) return fail("choose_pixels: order, fg_count and bg_count must be given together");
+  if (!table && (want_fg > 0 || want_fg_dev)) return fail("choose_pixels: foreground draws need the pixel table (order, fg_count, bg_count)");
+  if (want_fg < 0 || want_fg > n) return fail("choose_pixels: want_fg must be in [0, n]");
+  if (span < 0 || (double)span > (double)n_images * (double)pixels_per_image) return fail("choose_pixels: span must be in [0, n_images * pixels_per_image]");
+  static_assert(sizeof(long) == sizeof(int64_t), "int64 state and indices");
+  PixelDraw p;
+  p.state = reinterpret_cast<long*>(state); p.n = (long)n; p.want_fg = want_fg; p.want_fg_dev = want_fg_dev; p.cam_ids = cam_ids; p.B = images_per_step;
+  p.n_images = n_images; p.hw = (long)pixels_per_image; p.order = table ? order : nullptr; p.fg_count = fg_count; p.bg_count = bg_count;
+  p.span = (unsigned long long)(span ? span : pixels_per_image);
+  p.idx = reinterpret_cast<long*>(idx); p.cams_out = cams_out; p.counts_out = counts_out; p.t_rand = t_rand;
+  be_choose_pixels(p, (cnr_stream)stream);
+  return check_backend("choose_pixels");
+}
+
 static int camera_args(const cnr_camera_config* cfg, const float* r, const float* t, const float* init_c2w, const float* fx, const float* fy,
                        const int64_t* cam_ids, int64_t B, bool pose, bool focal, Camera& c) {
   if (!cfg) return fail("camera: null argument cfg");

@@ -7,15 +7,20 @@ those; ``rays_for_training`` also folds in what NeuS_Trainer.render does next (o
 Learnable poses and focal lengths (config/Color_NeuS_iho.yml:18-20) get their gradients from cnr_gen_rays_backward; the parameters
 behind them (pose_net.r / .t, focal_net.fx / .fy) and the step from those gradients to theirs are in cameras.py.
 
-Pixel choice consumes the torch CPU generator exactly like the reference (same calls, same order), so a seeded run picks the same
-pixels: that is the only part left in torch -- it IS the reference's random stream."""
+Pixel choice has two sources.  The default (``choose_pixels``) consumes the torch CPU generator exactly like the reference (same calls, same
+order), so a seeded run picks the same pixels: that part stays in torch -- it IS the reference's random stream -- and it costs what the
+reference's costs: two nonzero over the whole mask stack and permutations of all its pixels on the host, every step.  The opt-in source
+(``PixelSampler``, passed as ``sampler=``) keeps the sampling semantics (a share of the batch from the foreground, the rest from the background,
+both without replacement, shuffled) on a counter-based stream of its own on the device (cnr_pixel_table_build / cnr_choose_pixels): no host
+synchronisation, no per-step allocation, capturable in a HIP graph, and a function of (seed, step) alone, so the ranks of a ray-sharded run
+draw the same batch without talking.  It does NOT reproduce the reference's pixels."""
 import ctypes as C
 import os
 import warnings
 
 import torch
 
-from ._lib import ptr, stream_of
+from ._lib import library_for, ptr, stream_of
 from ._lib import resolve_library as _library
 
 
@@ -38,6 +43,116 @@ def choose_pixels(n_rays, pixels_per_image, device, mask=None, mask_rate=0.9):
     bg_order = torch.randperm(bg.shape[0])
     chosen = torch.cat([fg[fg_order[:want_fg]], bg[bg_order[:n_rays - want_fg]]], dim=-1)
     return chosen[torch.randperm(chosen.shape[0])]
+
+
+class PixelSampler:
+    """Pixel choice on the device: the pixel table of a mask stack and a {seed, step} random state (include/colorneus_render.h, "on-device
+    pixel choice").  Not the reference's random stream -- the same sampling semantics on a Philox stream of its own.
+
+    ``masks``: the DEVICE mask stack [N, H, W] (or [N, H * W]) the batches are drawn from -- a resident dataset's, built once; callers that
+    upload a fresh batch stack per step call ``rebuild``.  Without masks (``n_images`` and ``pixels_per_image`` given) the draws are uniform
+    with replacement, like the reference's unmasked route.  The sampler owns its state and its output buffers; the buffers are sized on first
+    use and keep their addresses, and a draw neither allocates nor touches the host, so it may run inside graph.GraphedStep.  What ``draw``
+    returns ARE those buffers: the next draw of the same size overwrites them (clone what must outlive it; a backward pass through the rays of a
+    batch runs before the next draw).
+    """
+
+    def __init__(self, masks=None, *, n_images=None, pixels_per_image=None, seed=0, library=None, device=None):
+        if masks is not None:
+            if masks.dim() not in (2, 3):
+                raise ValueError("masks [N, H, W] (or [N, H * W]) expected")
+            device = masks.device
+            n_images, pixels_per_image = masks.shape[0], masks[0].numel()
+        elif n_images is None or pixels_per_image is None:
+            raise ValueError("PixelSampler needs a mask stack, or n_images and pixels_per_image")
+        if device is None:
+            device = "cuda" if _library(library).backend.startswith("hip") else "cpu"
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = library_for(library, self.device, ("pixels", "chosen"))
+        self.n_images, self.pixels_per_image = int(n_images), int(pixels_per_image)
+        self.mask_shape = None
+        self.state = torch.zeros(2, dtype=torch.int64, device=self.device)           # {seed, step}
+        self.want_fg_buffer = torch.zeros(1, dtype=torch.int32, device=self.device)  # draw(mask_rate=None) reads the foreground count here
+        self.order = self.fg_count = self.bg_count = self._scratch = None
+        self._out, self._cams = {}, {}
+        self._counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self.last_cams = self.last_idx = self.last_t_rand = None    # device views of the last draw: its images, indices, jitter
+        self.seed(seed)
+        if masks is not None:
+            self.rebuild(masks)
+
+    def seed(self, s, step=0):
+        """Set the state: the same (seed, step) draws the same batch on every rank.  (A host-to-device copy: not inside a captured step.)"""
+        wrap = lambda v: ((int(v) + (1 << 63)) % (1 << 64)) - (1 << 63)
+        self.state.copy_(torch.tensor([wrap(s), wrap(step)], dtype=torch.int64))
+
+    @property
+    def last_counts(self):
+        """Device int32 [2] of the last masked draw: foreground draws made, background draws served."""
+        return self._counts
+
+    def rebuild(self, masks):
+        """Build the pixel table of ``masks`` (same shape as before) into the sampler's buffers: three launches, no allocation after the first."""
+        if masks.device != self.device:
+            raise ValueError(f"masks are on {masks.device} but the sampler is on {self.device}")
+        if masks.shape[0] != self.n_images or masks[0].numel() != self.pixels_per_image or (self.mask_shape not in (None, tuple(masks.shape))):
+            raise ValueError(f"mask stack {tuple(masks.shape)} does not match the sampler's "
+                             f"{self.mask_shape or (self.n_images, self.pixels_per_image)}")
+        m = masks.detach().contiguous().float()
+        if self.order is None:
+            n = self.n_images
+            self.order = torch.empty(n, self.pixels_per_image, dtype=torch.int32, device=self.device)
+            self.fg_count, self.bg_count = (torch.zeros(n, dtype=torch.int32, device=self.device) for _ in range(2))
+            self._scratch = self.lib.scratch("cnr_pixel_table_scratch_bytes", self.device, n, self.pixels_per_image, at_least=256)
+        self.lib.call("cnr_pixel_table_build", ptr(m), self.n_images, self.pixels_per_image, ptr(self.order), ptr(self.fg_count), ptr(self.bg_count),
+                      ptr(self._scratch[0]), self._scratch[1], stream_of(self.device))
+        self.mask_shape = tuple(masks.shape)
+
+    def check_stacks(self, image, mask=None):
+        """The image [N, H, W, 3] / mask [N, H, W] stacks that go to the ray kernel with this sampler's (global) indices must be the stacks it
+        was built on: same number of images, same H x W."""
+        for name, t in (("image", image), ("mask", mask)):
+            if t is None:
+                continue
+            hw = tuple(t.shape[1:3])
+            ok = t.shape[0] == self.n_images and hw[0] * hw[1] == self.pixels_per_image
+            if ok and self.mask_shape is not None and len(self.mask_shape) == 3:
+                ok = hw == self.mask_shape[1:]
+            if not ok:
+                raise ValueError(f"{name} stack {tuple(t.shape)} is not the stack the sampler was built on: "
+                                 f"{self.mask_shape or (self.n_images, self.pixels_per_image)}")
+
+    def draw(self, n_rays, mask_rate=0.9, images=None, images_per_step=None, jitter=False, span=None):
+        """One batch: int64 [n_rays] global pixel indices (image * H * W + pixel; -1 where the background cannot serve a draw), and with
+        ``jitter`` the renderer's ``t_rand`` [n_rays, 1] as well (it is drawn either way: ``last_t_rand``).  Advances the step by one.
+
+        ``mask_rate``: the foreground share, want_fg = int(mask_rate * n_rays) as the reference forms it; None: want_fg is read from
+        ``want_fg_buffer`` on the device (a captured step following the MASK_RATE schedule).  ``images``: int32 device tensor of the images
+        of this step, or ``images_per_step`` = B for B images chosen by the stream (default: all).  ``span`` (unmasked draws only): the
+        index range, default one image's pixels as in the reference."""
+        n = int(n_rays)
+        cam_ids = None
+        if images is not None:
+            cam_ids = torch.as_tensor(images, dtype=torch.int32, device=self.device).contiguous()
+            B = cam_ids.numel()
+        else:
+            B = self.n_images if images_per_step is None else int(images_per_step)
+        table = self.order is not None
+        out = self._out.get(n)
+        if out is None:
+            out = self._out[n] = (torch.empty(max(n, 0), dtype=torch.int64, device=self.device), torch.empty(max(n, 0), 1, dtype=torch.float32, device=self.device))
+        cams = self._cams.get(B)
+        if cams is None:
+            cams = self._cams[B] = torch.empty(max(B, 1), dtype=torch.int32, device=self.device)
+        want_dev = self.want_fg_buffer if (table and mask_rate is None) else None
+        want_fg = int(mask_rate * n) if (table and mask_rate is not None) else 0
+        self.lib.call("cnr_choose_pixels", ptr(self.state), n, want_fg, ptr(want_dev), ptr(cam_ids), B, self.n_images, self.pixels_per_image,
+                      ptr(self.order), ptr(self.fg_count), ptr(self.bg_count), int(span or 0), ptr(out[0]), ptr(cams), ptr(self._counts),
+                      ptr(out[1]), stream_of(self.device))
+        self.last_cams, self.last_idx, self.last_t_rand = cams[:B], out[0], out[1]
+        return (out[0], out[1]) if jitter else out[0]
 
 
 _CHECK_INDICES = os.environ.get("CNR_CHECK_INDICES", "0") not in ("", "0")
@@ -148,11 +263,21 @@ def _generate(lib, pix_idx, n, c2w, focal, H, W, normalize, opengl, image=None, 
     return o, d, (rgb if image is not None else None), (msel if mask is not None else None), (near if want_nearfar else None), (far if want_nearfar else None)
 
 
-def get_rays_multicam(c2w, focal, image, n_rays, normalize=False, mask=None, mask_rate=0.9, return_mask=False, opengl=False, library=None):
-    """Random n rays in world space from N cameras: the reference's signature and return values (ray_utils.py:16-87)."""
+def _pixels(sampler, n_rays, H, W, device, image, mask, mask_rate):
+    """The batch's pixel indices: the reference's CPU stream, or the draw of a PixelSampler built on these very stacks."""
+    if sampler is None:
+        return choose_pixels(n_rays, H * W, device, mask, mask_rate)
+    sampler.check_stacks(image, mask)
+    return sampler.draw(n_rays, mask_rate)
+
+
+def get_rays_multicam(c2w, focal, image, n_rays, normalize=False, mask=None, mask_rate=0.9, return_mask=False, opengl=False, library=None,
+                      sampler=None):
+    """Random n rays in world space from N cameras: the reference's signature and return values (ray_utils.py:16-87).  ``sampler``: a
+    PixelSampler built on the ``mask`` stack (image / mask must be the stacks it was built on) draws the pixels on the device instead."""
     assert c2w.dim() == 3 and image.dim() == 4, "c2w [N,4,4] and image [N,H,W,3] expected (multi-camera form)"
     H, W = image.shape[1], image.shape[2]
-    idx = choose_pixels(n_rays, H * W, c2w.device, mask, mask_rate)
+    idx = _pixels(sampler, n_rays, H, W, c2w.device, image, mask, mask_rate)
     if return_mask:
         assert mask is not None
     o, d, rgb, msel, _, _ = _generate(_library(library), idx, idx.shape[0], c2w, focal, H, W, normalize, opengl, image=image,
@@ -168,13 +293,14 @@ def get_rays_at(c2w, focal, H, W, normalize=False, opengl=False, library=None):
 
 
 def rays_for_training(c2w, focal, image, n_rays, origin, radius, normalize=False, mask=None, mask_rate=0.9, return_mask=False, opengl=False,
-                      library=None):
+                      library=None, sampler=None):
     """What NeuS_Trainer.render does in front of the renderer call (NeuS_Trainer.py:104-120) in one launch: pixel choice, rays,
     (rays_o - origin) / radius, near / far from the unit sphere, colours and mask values of the chosen pixels.
-    Returns rays_o, rays_d, near, far, rgb_gt, mask_select (None unless return_mask)."""
+    Returns rays_o, rays_d, near, far, rgb_gt, mask_select (None unless return_mask).  ``sampler``: as in get_rays_multicam; a draw the
+    background could not serve is a NaN ray that bad_index_count() counts."""
     assert c2w.dim() == 3 and image.dim() == 4
     H, W = image.shape[1], image.shape[2]
-    idx = choose_pixels(n_rays, H * W, c2w.device, mask, mask_rate)
+    idx = _pixels(sampler, n_rays, H, W, c2w.device, image, mask, mask_rate)
     o, d, rgb, msel, near, far = _generate(_library(library), idx, idx.shape[0], c2w, focal, H, W, normalize, opengl, image=image,
                                            mask=mask if return_mask else None, origin=torch.as_tensor(origin, dtype=torch.float32), radius=float(radius),
                                            want_nearfar=True)

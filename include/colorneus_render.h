@@ -213,6 +213,68 @@ int cnr_gen_rays_backward(const int64_t* pix_idx, int64_t n, const float* c2w, i
                           int32_t normalize, int32_t opengl, const float* origin, float radius, const float* d_rays_o, const float* d_rays_d,
                           const float* d_near, const float* d_far, float* d_c2w, float* d_focal, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- on-device pixel choice, the producer in front of cnr_gen_rays: the sampling SEMANTICS of get_rays_multicam's pixel choice
+ * (lib/models/tools/ray_utils.py:57-76: a share of the batch from the foreground pixels and the rest from the background, both without
+ * replacement, the result shuffled) on a counter-based random stream of its own -- NOT torch's CPU stream (that route stays in the host
+ * layer and stays the default).  No host synchronisation, no allocation, capturable in a HIP graph, and a pure function of
+ * (seed, step, table, arguments): every rank of a ray-sharded run draws the same batch without communicating.  Everything below is
+ * integer-exact (the jitter is an exact dyadic float), so the specification can be restated and compared bitwise.
+ *
+ * Random primitive: Philox4x32-10 (Salmon et al. 2011).  Counter (c0, c1, c2, c3), key (k0, k1), all uint32; ten times
+ *     (c0, c1, c2, c3) <- (hi(0xCD9E8D57 * c2) ^ c1 ^ k0,  lo(0xCD9E8D57 * c2),  hi(0xD2511F53 * c0) ^ c3 ^ k1,  lo(0xD2511F53 * c0))
+ *   (hi / lo: the halves of the 64-bit product), with (k0, k1) += (0x9E3779B9, 0xBB67AE85) between rounds (nine times).  Known answers:
+ *     counter 0,0,0,0 key 0,0                                                 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     counter and key all ffffffff                                            -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     counter 243f6a88 85a308d3 13198a2e 03707344 key a4093822 299f31d0       -> d16cfe09 94fdcceb 5001e420 24126ea1
+ * State: device int64 state[2] = {seed, step}.  Key = (seed & 0xffffffff, (seed >> 32) & 0xffffffff); counter word 3 = step & 0xffffffff;
+ *   counter word 2 = the stream id: 0 image choice, 1 foreground, 2 background, 3 shuffle, 4 draws with replacement, 5 jitter.
+ *   philox(a, b, s) below is Philox4x32-10 of the counter (a, b, s, step & 0xffffffff) under that key; [i] is its output word i.
+ * Keyed bijection perm(j, D, s) of [0, D), D < 2^32, j < D:  D <= 1: 0.  Otherwise bits = bit_length(D - 1), h = (bits + 1) / 2 (integer
+ *   division), m = 2^h - 1, x = j; repeat { L = x >> h, R = x & m; for r = 0 .. 7: (L, R) <- (R, L ^ (philox(R, r, s)[0] & m)); x = (L << h) | R }
+ *   until x < D (cycle walking on an 8-round Feistel network over 2h bits: the network permutes [0, 2^2h) and 2^2h < 4 D, so the walk ends
+ *   and takes fewer than 4 rounds of the loop on average).  A bijection and not rejection of repeated draws: every draw is a function of its
+ *   own index alone -- O(1) work per draw whatever the share of the domain that is drawn (want_fg >= F returns every foreground pixel), no
+ *   shared state between the threads of the launch, no dependence on the launch shape.  (Four Feistel rounds are measurably non-uniform on small domains: the joint table of perm on D = 5
+ *   / D = 7 over 3000 steps had chi^2 126 / 174 at 16 / 36 degrees of freedom; eight rounds 19.8 / 47.6.)
+ *
+ * Pixel table (cnr_pixel_table_build) of a mask stack masks [n_images][pixels_per_image] (float32): per image, order [n_images][pixels_per_image]
+ *   (int32) holds the pixel indices with mask > 0 in ascending order, then those with mask == 0 in ascending order; fg_count / bg_count
+ *   [n_images] their numbers.  A pixel that is neither (negative, NaN) is in neither list; the tail of its image's row of `order` is not
+ *   written.  Three launches: per-tile counts (wavefront ballot + popcount), a per-image exclusive scan of the tile counts, a stable scatter;
+ *   the mask is read twice, nothing is allocated.  scratch: cnr_pixel_table_scratch_bytes, contents need not be initialised.
+ *   n_images * pixels_per_image < 2^32, pixels_per_image < 2^31.
+ *
+ * Draw (cnr_choose_pixels): n pixel indices idx [n] (int64), GLOBAL over the table's images: cam * pixels_per_image + pixel -- they pair with
+ *   cnr_gen_rays given the c2w / image / mask stacks of all n_images.
+ *   images    B = images_per_step slots, 1 <= B <= min(n_images, 1024).  cam_ids (device int32 [B]) names the image of each slot; with
+ *             cam_ids == NULL slot b is image perm(b, n_images, 0) (B == n_images: a permutation of all images).  A cam_ids entry outside
+ *             [0, n_images) makes an empty slot.
+ *   want_fg   the number of foreground draws wanted: the host value, or, when want_fg_dev != NULL, the device int32 it points at (as
+ *             cnr_adam_config.hyper_dev: a captured launch follows a schedule); clamped to [0, n] on the device.
+ *   With a table (order, fg_count, bg_count given): F / G = the sums of fg_count / bg_count over the B slots in slot order, k = min(want_fg, F),
+ *             m = n - k.  Foreground draw j < k has rank perm(j, F, 1); the rank maps to (slot, offset) by upper bound in the slot-order
+ *             inclusive prefix of fg_count (the first slot whose prefix exceeds the rank; offset = rank - the prefix before that slot); its
+ *             pixel is order[cam][offset].  Background draw j < min(m, G): rank perm(j, G, 2), prefix of bg_count, pixel
+ *             order[cam][fg_count[cam] + offset].  A draw that cannot be served (j >= G) is -1: cnr_gen_rays makes that ray NaN and counts it.
+ *             The list (foreground draws, then background draws) is written shuffled: idx[perm(j, n, 3)] = list[j].
+ *             counts_out [2] = {k, min(m, G)}.
+ *   Without a table (all three NULL; want_fg must be 0 and want_fg_dev NULL): n draws WITH replacement, idx[j] = the upper 64 bits of the
+ *             128-bit product ((w[0] << 32) | w[1]) * span, w = philox(j, 0, 4); span = the argument, or pixels_per_image when it is 0 (the
+ *             reference's unmasked draws never leave camera 0, ray_utils.py:58), at most n_images * pixels_per_image.  counts_out = {0, 0}.
+ *   cams_out  [B] (or NULL): the image of every slot.
+ *   t_rand    [n] (or NULL): the renderer's per-ray jitter draw, t_rand[j] = (philox(j, 0, 5)[0] >> 8) * 2^-24, in [0, 1).
+ *   state     after the draw state[1] (the step, all 64 bits) is advanced by one, by the same launch behind a workgroup barrier: stream-ordered and part
+ *             of whatever graph captured the call.  One launch of one workgroup: O(n + B) work. */
+size_t cnr_pixel_table_scratch_bytes(int32_t n_images, int64_t pixels_per_image);
+int cnr_pixel_table_build(const float* masks /* [n_images][pixels_per_image] */, int32_t n_images, int64_t pixels_per_image,
+                          int32_t* order /* [n_images][pixels_per_image] */, int32_t* fg_count /* [n_images] */, int32_t* bg_count /* [n_images] */,
+                          void* scratch, size_t scratch_bytes, void* stream);
+int cnr_choose_pixels(int64_t* state /* device [2] */, int64_t n, int32_t want_fg, const int32_t* want_fg_dev /* device [1] or NULL */,
+                      const int32_t* cam_ids /* device [B] or NULL */, int32_t images_per_step, int32_t n_images, int64_t pixels_per_image,
+                      const int32_t* order, const int32_t* fg_count, const int32_t* bg_count, int64_t span /* 0: pixels_per_image */,
+                      int64_t* idx /* [n] */, int32_t* cams_out /* [B] or NULL */, int32_t* counts_out /* [2] or NULL */,
+                      float* t_rand /* [n] or NULL */, void* stream);
+
 /* ---- learnable cameras, the producer in front of cnr_gen_rays: the reference's Focal_Net and Pose_Net (lib/models/tools/camera_net.py:8-109,
  * called at the top of every training step, NeuS_Trainer.py:183-184) and their backward, one launch each.  All arithmetic fp32.
  *   focal [2]: order 2: {(fx*fx)*W, (fy*fy)*H}; order 1: {fx*W, fy*H}; with fx_only both entries are the first one (fy is not read, may be NULL).

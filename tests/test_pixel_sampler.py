@@ -1,0 +1,419 @@
+"""On-device pixel choice (color_neus_amd.rays.PixelSampler on cnr_pixel_table_build / cnr_choose_pixels).
+
+Every case runs on the CPU-emulation library (device cpu) and, marked gpu, on the HIP library (cuda:0).  All outputs are integers or exact dyadic
+floats, so every comparison is BITWISE.  The yardstick is a numpy restatement of the specification in include/colorneus_render.h written
+here; it uses nothing from the library and first checks itself against the three published Philox4x32-10 known answers.  The pixel table is
+compared with torch.nonzero.  The uniformity of the specification is tested on the restatement (the library equals it bitwise)."""
+import functools
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import color_neus_amd as cn
+from color_neus_amd import parallel, rays
+import _native as N
+
+BACKENDS = ["emu", pytest.param("hip", marks=pytest.mark.gpu)]
+U = np.uint64
+M32 = U(0xffffffff)
+PM0, PM1, PW0, PW1 = U(0xD2511F53), U(0xCD9E8D57), U(0x9E3779B9), U(0xBB67AE85)
+S32 = U(32)
+
+
+def _lib_and_dev(backend):
+    if backend == "emu":
+        assert os.path.isfile(N.EMU_LIB), "emulation library not built"
+        return N.EMU_LIB, "cpu"
+    assert torch.cuda.is_available(), "needs a GPU"
+    return None, "cuda:0"
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------------------------
+def philox(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on broadcast uint64 arrays holding 32-bit words."""
+    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(*[np.asarray(v, dtype=U) & M32 for v in (c0, c1, c2, c3, k0, k1)])
+    for _ in range(10):
+        p0, p1 = PM0 * c0, PM1 * c2
+        c0, c1, c2, c3 = (p1 >> S32) ^ c1 ^ k0, p1 & M32, (p0 >> S32) ^ c3 ^ k1, p0 & M32
+        k0, k1 = (k0 + PW0) & M32, (k1 + PW1) & M32
+    return c0, c1, c2, c3
+
+
+def _key(seed):
+    s = int(seed) % (1 << 64)
+    return U(s & 0xffffffff), U(s >> 32)
+
+
+def perm(j, D, stream, seed, step, rounds=8):
+    """perm(j, D, stream) for arrays of j and / or step."""
+    j, step = np.broadcast_arrays(np.asarray(j, dtype=U), np.asarray(np.asarray(step, dtype=np.int64) & 0xffffffff, dtype=U))
+    x = j.copy().reshape(-1)
+    step = step.reshape(-1)
+    if D <= 1:
+        return np.zeros(j.shape, dtype=np.int64)
+    assert (x < D).all()
+    h = ((int(D) - 1).bit_length() + 1) // 2
+    m, hh = U((1 << h) - 1), U(h)
+    k0, k1 = _key(seed)
+    todo = np.arange(x.size)
+    while todo.size:
+        L, R = x[todo] >> hh, x[todo] & m
+        for r in range(rounds):
+            L, R = R, L ^ (philox(R, U(r), U(stream), step[todo], k0, k1)[0] & m)
+        x[todo] = (L << hh) | R
+        todo = todo[x[todo] >= U(D)]
+    return x.astype(np.int64).reshape(j.shape)
+
+
+def ref_table(masks):
+    """[(fg pixels, bg pixels)] per image by torch.nonzero."""
+    flat = masks.detach().cpu().reshape(masks.shape[0], -1)
+    return [(torch.nonzero(r > 0, as_tuple=True)[0].numpy(), torch.nonzero(r == 0, as_tuple=True)[0].numpy()) for r in flat]
+
+
+def ref_draw(seed, step, n, N_, hw, table=None, want_fg=0, cam_ids=None, B=None, span=None):
+    """idx [n], cams [B], counts [2], t_rand [n] of one draw."""
+    k0, k1 = _key(seed)
+    st = U(int(step) & 0xffffffff)
+    B = len(cam_ids) if cam_ids is not None else (N_ if B is None else B)
+    cams = np.asarray(cam_ids, dtype=np.int64) if cam_ids is not None else perm(np.arange(B), N_, 0, seed, step)
+    j = np.arange(n, dtype=U)
+    t_rand = ((philox(j, 0, 5, st, k0, k1)[0] >> U(8)).astype(np.float64) * 2.0 ** -24).astype(np.float32)
+    if table is None:
+        w = philox(j, 0, 4, st, k0, k1)
+        sp = hw if not span else span
+        idx = np.array([(((int(a) << 32) | int(b)) * sp) >> 64 for a, b in zip(w[0], w[1])], dtype=np.int64)
+        return idx, cams, np.array([0, 0]), t_rand
+    lists = []
+    for which, stream, count in ((0, 1, None), (1, 2, None)):
+        sizes = np.array([len(table[c][which]) for c in cams])
+        pre = np.cumsum(sizes)
+        D = int(pre[-1])
+        cnt = min(want_fg, D) if which == 0 else min(n - len(lists[0]), D)
+        ranks = perm(np.arange(cnt), D, stream, seed, step)
+        slot = np.searchsorted(pre, ranks, side="right")
+        off = ranks - (pre[slot] - sizes[slot])
+        lists.append(np.array([cams[s] * hw + table[cams[s]][which][o] for s, o in zip(slot, off)], dtype=np.int64))
+    k, served = len(lists[0]), len(lists[1])
+    full = np.concatenate([lists[0], lists[1], np.full(n - k - served, -1, dtype=np.int64)])
+    idx = np.empty(n, dtype=np.int64)
+    idx[perm(np.arange(n), n, 3, seed, step)] = full
+    return idx, cams, np.array([k, served]), t_rand
+
+
+def test_restatement_reproduces_the_philox_known_answers():
+    kat = [((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
+           ((0xffffffff,) * 4, (0xffffffff,) * 2, "408f276d 41c83b0e a20bc7c6 6d5451fd"),
+           ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0), "d16cfe09 94fdcceb 5001e420 24126ea1")]
+    for c, k, want in kat:
+        got = " ".join("%08x" % int(w) for w in philox(*c, *k))
+        assert got == want, (c, k, got)
+    for D in (1, 2, 3, 5, 64, 100, 257):      # perm is a bijection of [0, D)
+        assert sorted(perm(np.arange(D), D, 1, 12345, 7).tolist()) == list(range(D))
+
+
+# ---- inputs (computed once, never modified) -------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _masks(H, W, special=False):
+    """N = 3: all foreground, all background, random at 30 %; with `special` a few negative and NaN values in every image."""
+    g = torch.Generator().manual_seed(H * 1000 + W)
+    m = torch.stack([torch.ones(H, W), torch.zeros(H, W), (torch.rand(H, W, generator=g) < 0.3).float()])
+    if special:
+        flat = m.reshape(3, -1)
+        for n in range(3):
+            at = torch.randperm(H * W, generator=g)[:7]
+            flat[n, at[:4]] = torch.tensor([-1.0, -0.0, -1e-30, -float("inf")])[: len(at[:4])]
+            flat[n, at[4:]] = float("nan")
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def _scene():
+    """N = 5 images of 8 x 16 at 30 % foreground, with cameras and colours for the ray kernel."""
+    g = torch.Generator().manual_seed(11)
+    n, H, W = 5, 8, 16
+    masks = (torch.rand(n, H, W, generator=g) < 0.3).float()
+    image = torch.rand(n, H, W, 3, generator=g)
+    c2w = torch.eye(4).repeat(n, 1, 1)
+    c2w[:, :3, :3] = torch.linalg.qr(torch.randn(n, 3, 3, generator=g))[0]
+    c2w[:, :3, 3] = torch.randn(n, 3, generator=g)
+    return masks, image, c2w, torch.tensor([20.0, 21.0]), ref_table(masks)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _f32bits(a):
+    return np.asarray(a, dtype=np.float32).view(np.int32)
+
+
+# ---- 1. the table ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("backend", BACKENDS)
+@pytest.mark.parametrize("H,W,special", [(1, 1, False), (67, 129, False), (97, 131, False), (67, 129, True)])   # 97 * 131 = 3.1 tiles of 4096 pixels
+def test_table_against_nonzero(backend, H, W, special):
+    library, dev = _lib_and_dev(backend)
+    masks = _masks(H, W, special)
+    s = cn.PixelSampler(masks.to(dev), library=library)
+    want = ref_table(masks)
+    order, fg, bg = _np(s.order), _np(s.fg_count), _np(s.bg_count)
+    assert order.dtype == np.int32 and order.shape == (3, H * W)
+    for n, (wf, wb) in enumerate(want):
+        assert (fg[n], bg[n]) == (len(wf), len(wb)), n
+        assert np.array_equal(order[n, :fg[n]], wf) and np.array_equal(order[n, fg[n]:fg[n] + bg[n]], wb), n
+    if special:
+        assert all(fg[n] + bg[n] < H * W for n in range(3))     # the negative and NaN pixels are in neither list (-0.0 is background)
+    else:
+        assert fg.tolist()[:2] == [H * W, 0] and bg.tolist()[:2] == [0, H * W]
+    before = order.copy()
+    s.rebuild(masks.to(dev))                                    # the same buffers, the same table
+    again = _np(s.order)
+    assert np.array_equal(_np(s.fg_count), fg) and all(np.array_equal(again[n, :fg[n] + bg[n]], before[n, :fg[n] + bg[n]]) for n in range(3))
+
+
+# ---- 2. the draw against the restatement ------------------------------------------------------------------------------------------------------
+def _compare(s, got, want, jitter=True):
+    idx, cams, counts, t = want
+    gi, gt = got if jitter else (got, None)
+    assert gi.dtype == torch.int64 and np.array_equal(_np(gi), idx)
+    assert np.array_equal(_np(s.last_cams), cams) and np.array_equal(_np(s.last_counts), counts)
+    if jitter:
+        assert tuple(gt.shape) == (len(idx), 1) and np.array_equal(_f32bits(_np(gt).reshape(-1)), _f32bits(t))
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_draw_against_the_restatement(backend):
+    library, dev = _lib_and_dev(backend)
+    masks, _, _, _, table = _scene()
+    n, hw = 64, 8 * 16
+    s = cn.PixelSampler(masks.to(dev), seed=3, library=library)
+    cam_ids = [4, 0, 2]
+    _compare(s, s.draw(n, 0.5, images=torch.tensor(cam_ids, dtype=torch.int32, device=dev), jitter=True),
+             ref_draw(3, 0, n, 5, hw, table, want_fg=32, cam_ids=cam_ids))
+    _compare(s, s.draw(n, 0.8, images_per_step=2, jitter=True), ref_draw(3, 1, n, 5, hw, table, want_fg=int(0.8 * 64), B=2))
+    _compare(s, s.draw(n, 0.9, images_per_step=5, jitter=True), ref_draw(3, 2, n, 5, hw, table, want_fg=int(0.9 * 64), B=5))
+    _compare(s, s.draw(n, 0.9, jitter=False), ref_draw(3, 3, n, 5, hw, table, want_fg=int(0.9 * 64), B=5), jitter=False)
+    assert _np(s.state).tolist() == [3, 4]
+    for seed in (0x1234567800000005, -7):      # want_fg through the device scalar, three consecutive steps; both key words, a step above 2^32
+        s.seed(seed, step=(1 << 32) + 10)
+        for i, want_fg in enumerate((0, 17, 64)):
+            s.want_fg_buffer.fill_(want_fg)
+            _compare(s, s.draw(n, None, images_per_step=3, jitter=True), ref_draw(seed, (1 << 32) + 10 + i, n, 5, hw, table, want_fg=want_fg, B=3))
+        assert _np(s.state).tolist() == [seed, (1 << 32) + 13]
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_unmasked_draws_against_the_restatement(backend):
+    library, dev = _lib_and_dev(backend)
+    n, N_, hw = 64, 5, 8 * 16
+    s = cn.PixelSampler(n_images=N_, pixels_per_image=hw, seed=9, library=library, device=dev)
+    want = ref_draw(9, 0, n, N_, hw)
+    _compare(s, s.draw(n, jitter=True), want)
+    assert want[0].min() >= 0 and want[0].max() < hw                      # the reference's quirk: camera 0 only
+    want = ref_draw(9, 1, n, N_, hw, B=3, span=3 * hw)
+    _compare(s, s.draw(n, images_per_step=3, jitter=True, span=3 * hw), want)
+    assert want[0].max() >= hw and want[0].max() < 3 * hw
+
+
+# ---- 3. properties, independent of the restatement ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_draw_properties(backend):
+    library, dev = _lib_and_dev(backend)
+    masks, image, c2w, focal, _ = _scene()
+    n, hw = 64, 8 * 16
+    flat = masks.reshape(-1)
+    s = cn.PixelSampler(masks.to(dev), seed=5, library=library)
+    for B, rate in ((5, 0.9), (2, 0.5), (1, 0.25)):
+        idx = _np(s.draw(n, rate, images_per_step=B)).copy()
+        cams = set(_np(s.last_cams).tolist())
+        F = int(sum(masks[c].sum() for c in cams))
+        assert len(set(idx.tolist())) == n and idx.min() >= 0                        # distinct
+        assert set((idx // hw).tolist()) <= cams and len(cams) == B                  # in the chosen images
+        k = min(int(rate * n), F)
+        assert int((flat[idx] > 0).sum()) == k and int((flat[idx] == 0).sum()) == n - k
+        assert _np(s.last_counts).tolist() == [k, n - k]
+    # want_fg >= F returns every foreground pixel exactly once
+    sparse = torch.zeros(2, 8, 16)
+    sparse[0, 1, 3:9] = 1.0
+    sparse[1, 6, 2:11] = 1.0
+    s2 = cn.PixelSampler(sparse.to(dev), seed=1, library=library)
+    idx = _np(s2.draw(n, 1.0)).copy()
+    fg_all = torch.nonzero(sparse.reshape(-1) > 0, as_tuple=True)[0].tolist()
+    assert sorted(i for i in idx.tolist() if sparse.reshape(-1)[i] > 0) == fg_all and len(set(idx.tolist())) == n
+    assert _np(s2.last_counts).tolist() == [len(fg_all), n - len(fg_all)]
+    # a background shortfall of s gives exactly s indices of -1, which the ray kernel counts
+    crowded = torch.ones(2, 8, 16)
+    crowded[0, 0, :2] = 0.0
+    crowded[1, 7, 5] = 0.0
+    s3 = cn.PixelSampler(crowded.to(dev), seed=2, library=library)
+    rays.bad_index_count()
+    out = rays.rays_for_training(c2w[:2].to(dev), focal.to(dev), image[:2].to(dev), n, torch.zeros(3), 1.0, mask=crowded.to(dev), mask_rate=0.5,
+                                 return_mask=True, library=library, sampler=s3)
+    idx = _np(s3.last_idx)
+    short = n - 32 - 3
+    assert int((idx == -1).sum()) == short and len(set(idx[idx >= 0].tolist())) == n - short
+    assert _np(s3.last_counts).tolist() == [32, 3]
+    assert rays.bad_index_count() == short and int(torch.isnan(out[0]).any(dim=1).sum()) == short
+    # the same (seed, step) reproduces; the step advances by one per draw; two samplers with equal state draw the same batch
+    a, b = cn.PixelSampler(masks.to(dev), seed=77, library=library), cn.PixelSampler(masks.to(dev), seed=77, library=library)
+    first = [_np(a.draw(n, 0.9)).copy() for _ in range(3)]
+    assert _np(a.state).tolist() == [77, 3] and not np.array_equal(first[0], first[1]) and not np.array_equal(first[1], first[2])
+    a.seed(77, step=1)
+    assert np.array_equal(_np(a.draw(n, 0.9)), first[1])
+    world = 4
+    for step in range(3):                                       # the ranks of a ray-sharded run: every rank draws, each keeps its slice
+        full = _np(b.draw(n, 0.9)).copy()
+        assert np.array_equal(full, first[step])
+        parts = []
+        for rank in range(world):
+            r = cn.PixelSampler(masks.to(dev), seed=77, library=library)
+            r.seed(77, step=step)
+            parts.append(_np(r.draw(n, 0.9))[parallel.shard_slice(n, rank, world)].copy())
+        assert np.array_equal(np.concatenate(parts), full)
+
+
+# ---- 4. uniformity of the specification (on the restatement) ----------------------------------------------------------------------------------------
+def _chi2_quantile(df, p=1e-6):
+    """Upper p quantile of chi^2 with df degrees of freedom by Wilson-Hilferty."""
+    z = math.sqrt(2.0) * _erfinv(1.0 - 2.0 * p)
+    return df * (1.0 - 2.0 / (9.0 * df) + z * math.sqrt(2.0 / (9.0 * df))) ** 3
+
+
+def _erfinv(y):
+    lo, hi = 0.0, 6.0           # bisection on math.erf: exact enough for a quantile
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if math.erf(mid) < y else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def test_uniformity_of_the_specification():
+    """Bounds: the upper 1e-6 quantile of chi^2 by Wilson-Hilferty, computed here: 308.8 at 199 degrees of freedom, 131.7 at 63, 59.2 at 16,
+    92.0 at 36.  The inclusion statistic is also held below 304, the (slightly lower) figure the feature request quotes for 199."""
+    assert 308.0 < _chi2_quantile(199) < 309.5
+    seed, steps, D, k, n = 2024, 4000, 200, 20, 64
+    st = np.arange(steps)[:, None]
+    drawn = perm(np.arange(k)[None, :], D, 1, seed, st)                   # [steps][k] foreground ranks
+    assert all(len(set(r.tolist())) == k for r in drawn[:50])
+    counts = np.bincount(drawn.reshape(-1), minlength=D).astype(np.float64)
+    e = steps * k / D
+    chi_incl = ((counts - e) ** 2 / e).sum() / (1.0 - k / D)               # inclusion counts: hypergeometric variance
+    print("inclusion chi2 / (1 - k/D) = %.1f (199 dof, bound %.1f)" % (chi_incl, _chi2_quantile(199)))
+    assert chi_incl < min(_chi2_quantile(199), 304.0)
+    inv = np.argsort(perm(np.arange(n)[None, :], n, 3, seed, st), axis=1)  # out[perm(j)] = list[j]: out position 0 holds list element inv[0]
+    first = np.bincount(inv[:, 0], minlength=n).astype(np.float64)
+    e = steps / n
+    chi_first = ((first - e) ** 2 / e).sum()
+    print("first shuffled element chi2 = %.1f (63 dof, bound %.1f)" % (chi_first, _chi2_quantile(63)))
+    assert chi_first < _chi2_quantile(63)
+    for D, dof in ((5, 16), (7, 36)):                                     # joint table of (j, perm(j)): (D - 1)^2 degrees of freedom
+        steps = 3000
+        p = perm(np.arange(D)[None, :], D, 1, seed, np.arange(steps)[:, None])
+        tab = np.zeros((D, D))
+        for j in range(D):
+            tab[j] = np.bincount(p[:, j], minlength=D)
+        e = steps / D
+        chi = ((tab - e) ** 2 / e).sum()
+        print("joint table D = %d: chi2 = %.1f (%d dof, bound %.1f)" % (D, chi, dof, _chi2_quantile(dof)))
+        assert chi < _chi2_quantile(dof)
+
+
+# ---- 5. integration ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_rays_for_training_with_a_sampler(backend):
+    library, dev = _lib_and_dev(backend)
+    masks, image, c2w, focal, table = _scene()
+    n, H, W = 64, 8, 16
+    md, im, cw, fo = masks.to(dev), image.to(dev), c2w.to(dev), focal.to(dev)
+    origin, radius = torch.tensor([0.1, -0.2, 0.05]), 1.7
+    s = cn.PixelSampler(md, seed=21, library=library)
+    got = rays.rays_for_training(cw, fo, im, n, origin, radius, normalize=True, mask=md, mask_rate=0.7, return_mask=True, library=library, sampler=s)
+    want_idx = torch.from_numpy(ref_draw(21, 0, n, 5, H * W, table, want_fg=int(0.7 * n))[0]).to(dev)
+    o, d, rgb, msel, near, far = rays._generate(rays._library(library), want_idx, n, cw, fo, H, W, True, False, image=im, mask=md, origin=origin,
+                                                radius=radius, want_nearfar=True)
+    for a, b in zip(got, (o, d, near, far, rgb, msel)):
+        assert np.array_equal(_f32bits(_np(a)), _f32bits(_np(b)))
+    got = rays.get_rays_multicam(cw, fo, im, n, normalize=True, mask=md, mask_rate=0.7, return_mask=True, library=library, sampler=s)
+    want_idx = torch.from_numpy(ref_draw(21, 1, n, 5, H * W, table, want_fg=int(0.7 * n))[0]).to(dev)
+    o, d, rgb, msel, _, _ = rays._generate(rays._library(library), want_idx, n, cw, fo, H, W, True, False, image=im, mask=md)
+    for a, b in zip(got, (o, d, rgb, msel)):
+        assert np.array_equal(_f32bits(_np(a)), _f32bits(_np(b)))
+    # sampler=None: the reference's stream, call for call
+    torch.manual_seed(5)
+    a = rays.rays_for_training(cw, fo, im, n, origin, radius, normalize=True, mask=md, mask_rate=0.7, return_mask=True, library=library)
+    state_a = torch.get_rng_state()
+    torch.manual_seed(5)
+    idx = rays.choose_pixels(n, H * W, torch.device(dev), md, 0.7)
+    state_b = torch.get_rng_state()
+    b = rays._generate(rays._library(library), idx, n, cw, fo, H, W, True, False, image=im, mask=md, origin=origin, radius=radius, want_nearfar=True)
+    assert torch.equal(state_a, state_b)
+    for x, y in zip(a, (b[0], b[1], b[4], b[5], b[2], b[3])):
+        assert np.array_equal(_f32bits(_np(x)), _f32bits(_np(y)))
+
+
+# ---- 6. graph capture (a linear chain: no parallel branches) --------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_captured_draw_replays_without_the_host():
+    _, dev = _lib_and_dev("hip")
+    g = torch.Generator().manual_seed(4)
+    nimg, H, W, R = 3, 64, 64, 256
+    masks = (torch.rand(nimg, H, W, generator=g) < 0.3).float().to(dev)
+    c2w = torch.eye(4).repeat(nimg, 1, 1)
+    c2w[:, :3, 3] = torch.randn(nimg, 3, generator=g)
+    c2w, focal = c2w.to(dev), torch.tensor([70.0, 71.0], device=dev)
+    lib = rays._library(None)
+    eager = cn.PixelSampler(masks, seed=31)
+    eager.seed(31, step=6)
+    want = []
+    for _ in range(3):
+        idx, t = eager.draw(R, 0.9, jitter=True)
+        o = rays._generate(lib, idx, R, c2w, focal, H, W, True, False)[0]
+        want.append((idx.clone(), t.clone(), o.clone()))
+    s = cn.PixelSampler(masks, seed=31)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):                                # first use sizes the buffers
+        s.draw(R, 0.9, jitter=True)
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize()
+    s.seed(31, step=6)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        idx, t = s.draw(R, 0.9, jitter=True)
+        o = rays._generate(lib, idx, R, c2w, focal, H, W, True, False)[0]
+    assert s.state.tolist() == [31, 6]                           # the capture ran nothing
+    got = []
+    for _ in range(3):
+        graph.replay()
+        got.append((idx.clone(), t.clone(), o.clone()))
+    torch.cuda.synchronize()
+    assert s.state.tolist() == [31, 9]
+    for (gi, gt, go), (wi, wt, wo) in zip(got, want):
+        assert torch.equal(gi, wi) and torch.equal(gt.view(torch.int32), wt.view(torch.int32)) and torch.equal(go.view(torch.int32), wo.view(torch.int32))
+    assert not torch.equal(got[0][0], got[1][0]) and not torch.equal(got[1][0], got[2][0]) and not torch.equal(got[0][1], got[1][1])
+
+
+# ---- 7. argument errors ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_argument_errors(backend):
+    library, dev = _lib_and_dev(backend)
+    masks, image, c2w, focal, _ = _scene()
+    s = cn.PixelSampler(masks.to(dev), library=library)
+    with pytest.raises(RuntimeError, match=r"cnr_choose_pixels failed: choose_pixels: images_per_step 6 exceeds the table's 5 images"):
+        s.draw(64, 0.9, images_per_step=6)
+    big = cn.PixelSampler(n_images=2000, pixels_per_image=4, library=library, device=dev)
+    with pytest.raises(RuntimeError, match=r"cnr_choose_pixels failed: choose_pixels: at most 1024 images per step \(got 1025\)"):
+        big.draw(64, images_per_step=1025)
+    assert big.draw(64, images_per_step=1024).shape == (64,)
+    assert _np(s.state).tolist() == [0, 0]                      # a refused call draws nothing
+    other = torch.zeros(5, 16, 8)
+    with pytest.raises(ValueError, match="not the stack the sampler was built on"):
+        rays.rays_for_training(c2w.to(dev), focal.to(dev), image.to(dev), 64, torch.zeros(3), 1.0, mask=other.to(dev), library=library, sampler=s)
+    with pytest.raises(ValueError, match="not the stack the sampler was built on"):
+        rays.get_rays_multicam(c2w[:4].to(dev), focal.to(dev), image[:4].to(dev), 64, mask=masks[:4].to(dev), library=library, sampler=s)
+    with pytest.raises(ValueError, match="does not match the sampler's"):
+        s.rebuild(other.to(dev))
