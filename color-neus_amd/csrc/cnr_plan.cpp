@@ -118,20 +118,30 @@ static void identity_seg(Lin& l) {
   l.seg[0] = {0, 0, l.k_ref};
 }
 
-static int add_linear_params(Model& m, Lin& l, const std::string& prefix, bool wn) {
+// Parameter registration.  The order is part of the ABI (checkpoints, cnr_param_info): bias, then weight_g / weight_v (or weight) for the
+// SDF and colour stacks (add_linear_params); weight, then bias for the plain layers of the relight and background networks (add_weight_bias).
+static void add_linear_params(std::vector<ParamInfo>& params, Lin& l, const std::string& prefix, bool wn) {
   l.name = prefix;
   l.wn = wn;
-  l.p_b = (int)m.params.size();
-  m.params.push_back({prefix + ".bias", l.n, 1});
+  l.p_b = (int)params.size();
+  params.push_back({prefix + ".bias", l.n, 1});
   if (wn) {
-    l.p_g = (int)m.params.size();
-    m.params.push_back({prefix + ".weight_g", l.n, 1});
-    l.p_v = (int)m.params.size();
-    m.params.push_back({prefix + ".weight_v", l.n, l.k_ref});
-  } else {
-    l.p_v = (int)m.params.size();
-    m.params.push_back({prefix + ".weight", l.n, l.k_ref});
+    l.p_g = (int)params.size();
+    params.push_back({prefix + ".weight_g", l.n, 1});
   }
+  l.p_v = (int)params.size();
+  params.push_back({prefix + (wn ? ".weight_v" : ".weight"), l.n, l.k_ref});
+}
+static void add_weight_bias(std::vector<ParamInfo>& params, Lin& l, const std::string& name) {
+  l.name = name; l.wn = false;
+  l.p_v = (int)params.size(); params.push_back({name + ".weight", l.n, l.k_ref});
+  l.p_b = (int)params.size(); params.push_back({name + ".bias", l.n, 1});
+}
+static int param_info(const std::vector<ParamInfo>& params, int index, char* name, int name_len, int* rows, int* cols) {
+  if (index < 0 || index >= (int)params.size()) return fail("parameter index out of range");
+  if (name && name_len > 0) snprintf(name, name_len, "%s", params[index].name.c_str());
+  if (rows) *rows = params[index].rows;
+  if (cols) *cols = params[index].cols;
   return 0;
 }
 
@@ -183,7 +193,7 @@ static int build_model(const cnr_config* cfg, Model& m) {
     // the layer below a skip connection: its launches also write the embedding into the columns behind its own (tail fill); zero weight rows
     // under those columns let every 32-column block of the launch run the same code (the stream form of the layer kernel)
     if (l < m.L && m.skip(l + 1) && round_up(q.n + m.emb, 32) <= 256) q.wpad = round_up(q.n + m.emb, 32);
-    add_linear_params(m, q, "sdf_network.lin" + std::to_string(l), c.sdf_weight_norm != 0);
+    add_linear_params(m.params, q, "sdf_network.lin" + std::to_string(l), c.sdf_weight_norm != 0);
     prev = out;
   }
   m.p_variance = (int)m.params.size();
@@ -210,7 +220,7 @@ static int build_model(const cnr_config* cfg, Model& m) {
       identity_seg(q);
     }
     q.finish_dims();
-    add_linear_params(m, q, "color_network.lin" + std::to_string(l), c.col_weight_norm != 0);
+    add_linear_params(m.params, q, "color_network.lin" + std::to_string(l), c.col_weight_norm != 0);
   }
   // ---- relight layers (fields.py:305-325)
   if (m.has_relight) {
@@ -227,9 +237,7 @@ static int build_model(const cnr_config* cfg, Model& m) {
       if (ig) q.seg[q.nseg++] = {3, 3 + m.nv, 3};
       q.seg[q.nseg++] = {6, 3, m.nv};
       q.finish_dims();
-      q.name = "relight_network.in_layer"; q.wn = false;
-      q.p_v = (int)m.params.size(); m.params.push_back({q.name + ".weight", q.n, q.k_ref});
-      q.p_b = (int)m.params.size(); m.params.push_back({q.name + ".bias", q.n, 1});
+      add_weight_bias(m.params, q, "relight_network.in_layer");
     }
     for (int i = 0; i < m.NR; ++i) {
       Lin& q = m.rel[1 + i];
@@ -242,9 +250,7 @@ static int build_model(const cnr_config* cfg, Model& m) {
         q.k_ref = m.Hr; identity_seg(q);
       }
       q.finish_dims();
-      q.name = "relight_network.rl_mlp." + std::to_string(i); q.wn = false;
-      q.p_v = (int)m.params.size(); m.params.push_back({q.name + ".weight", q.n, q.k_ref});
-      q.p_b = (int)m.params.size(); m.params.push_back({q.name + ".bias", q.n, 1});
+      add_weight_bias(m.params, q, "relight_network.rl_mlp." + std::to_string(i));
     }
   } else {
     m.Hr = 0; m.NR = 0;
@@ -491,14 +497,65 @@ static void layout_ctx(Model& m, long R, Arena& a, Ctx& x) {
   place_slack(a);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The pool of weight-gradient partial sums, shared by every backward entry point.  A layer's region is [slots][npad][ldw] partial sums +
+// [slots][npad] column sums (the bias gradient); every layer keeps its own until one batched reduction at the end.  A layout sums
+// region_floats over its layers and places the pool; the launch code takes the regions in its own order, and take refuses to leave the
+// pool.  Several launches may fill consecutive slot groups of one region (SDF layers: value pair | gradient-chain pair, each either fused
+// into its layer launch or a separate GEMM); finish queues the one reduction over all of them.  Only the group at slot 0 carries column
+// sums.  How many slots a layer gets is the caller's policy (region_slots, dw_chunks).
+// ------------------------------------------------------------------------------------------------
+struct DwRegion { float* part = nullptr; float* csum = nullptr; };   // (part == nullptr: refused by DwPool::take)
+struct DwPool {
+  float* base = nullptr;
+  size_t floats = 0, off = 0;
+  std::vector<FinishWeight> pending;   // reductions queued by finish, issued as one launch by flush
+
+  static size_t csum_floats(const Lin& q, int slots) { return round_up_sz((size_t)slots * q.npad, 64); }
+  static size_t region_floats(const Lin& q, int slots) { return round_up_sz((size_t)slots * q.npad * q.ldw, 64) + csum_floats(q, slots); }
+  void place(Arena& a, size_t n) {
+    floats = n; off = 0;
+    base = a.f(n);
+    pending.clear();
+  }
+  // the next region; past the end of the pool: an error (cnr_last_error) and a null region, into which the caller launches nothing
+  DwRegion take(const Lin& q, int slots) {
+    DwRegion r;
+    const size_t need = region_floats(q, slots);
+    if (!base) return r;   // (a dry-run layout: there is nothing to hand out, and nothing to overrun)
+    if (need > floats - off) {
+      fail("weight-gradient pool: %d slots of layer %s need %zu floats, %zu of %zu are left", slots, q.name.c_str(), need, floats - off, floats);
+      return r;
+    }
+    r.part = base + off;
+    off += need;
+    r.csum = base + off - csum_floats(q, slots);
+    return r;
+  }
+  // THE place where a Lin becomes a FinishWeight: the reduction over the first nslots slots of r (column sums over the first ncolsum)
+  void finish(const Lin& q, const DwRegion& r, int nslots, int ncolsum, const float* const* params, float* const* dparams) {
+    FinishWeight f;
+    f.partial = r.part; f.nchunk = nslots; f.npad = q.npad; f.ldk = q.ldw; f.colsum = ncolsum > 0 ? r.csum : nullptr; f.ncolsum = ncolsum;
+    f.g = q.p_g >= 0 ? params[q.p_g] : nullptr; f.v = params[q.p_v];
+    f.n = q.n; f.k_ref = q.k_ref; f.nseg = q.nseg;
+    for (int i = 0; i < q.nseg; ++i) f.seg[i] = q.seg[i];
+    f.dg = q.p_g >= 0 ? dparams[q.p_g] : nullptr; f.dv = dparams[q.p_v]; f.db = dparams[q.p_b]; f.row_rot = q.row_rot;
+    pending.push_back(f);
+  }
+  // the columns >= 256 of the layer queued last were filled by be_strip_bwd, over nslots slots
+  void strip_columns_of_last_finish(int nslots) { pending.back().col_hi = 256; pending.back().nchunk_hi = nslots; }
+  void flush(cnr_stream s) {   // all queued reductions (+ weight-norm backward) in one launch
+    if (!pending.empty()) be_finish_weights(pending.data(), (int)pending.size(), s);
+    pending.clear();
+  }
+};
+
 struct Bwd {   // backward scratch
   float *ZTOP, *gbar_a, *dtop, *gc_a, *gc_b, *dctop, *dinvs, *drd_alpha, *dAUXc, *dAUXr, *gbar_t, *cbar, *ebar0, *ebars, *pbar, *dzparts;
   std::vector<float*> D, DC, VB, Z2;
   std::vector<float*> rsX0, rsY1;   // row scales of the SDF cotangents z-bar_l (value pair) and q-bar_l (gradient-chain pair)
   float* rsD;                       // row scales of the colour / relight cotangent consumed right after its layer GEMM
-  float* partial;                     // pool of per-layer weight-gradient partial sums
-  size_t partial_floats, partial_off;
-  std::vector<FinishWeight> pending;  // reductions queued by run_dw, issued as one launch by flush_dw
+  DwPool dw;                          // per-layer weight-gradient partial sums
   int nchunk; long chunk_pts;
   int fslots;                         // slots (point ranges) of a fused layer + weight-gradient launch (cnr_gemm_fdw.hip)
   int cap_slots;                      // slots reserved per layer in the pool: fslots + max(nchunk, fslots)
@@ -561,17 +618,13 @@ static void place_sdf_sweeps(const Model& m, long P, bool grad_path, Arena& a, B
   b.VB.assign(m.L, nullptr); b.Z2.resize(m.L);
   for (int l = 0; l < m.L; ++l) { if (grad_path) b.VB[l] = a.f((size_t)P * m.Hs); b.Z2[l] = a.f((size_t)P * m.Hs); }
 }
-// the slot counts over P points and the partial-sum pool: every layer keeps its own [slots][npad][ldw] partial sums (+ bias column sums)
-// until one batched reduction at the end
+// the slot counts over P points and the partial-sum pool: region_slots slots for every layer of the stacks
 static void place_dw_pool(std::initializer_list<const std::vector<Lin>*> stacks, long P, Arena& a, Bwd& b) {
   bwd_slots(P, b);
   size_t tot = 0;
   for (auto* st : stacks)
-    for (auto& q : *st) { const int cap = region_slots(q, b); tot += round_up_sz((size_t)cap * q.npad * q.ldw, 64) + round_up_sz((size_t)cap * q.npad, 64); }
-  b.partial_floats = tot;
-  b.partial = a.f(tot);
-  b.partial_off = 0;
-  b.pending.clear();
+    for (auto& q : *st) tot += DwPool::region_floats(q, region_slots(q, b));
+  b.dw.place(a, tot);
 }
 // row scales of the SDF cotangents z-bar_l (value pairs) and, with the gradient path, q-bar_l (gradient-chain pairs)
 static void place_sdf_bwd_row_scales(const Model& m, long P, bool grad_path, Arena& a, Bwd& b) {
@@ -616,29 +669,38 @@ static void layout_bwd(const Model& m, long R, const Ctx& x, Arena& a, Bwd& b) {
 
 // ------------------------------------------------------------------------------------------------
 // sdf_only: the SDF layers alone (point queries: the other entries of params may be null)
-static void prep_all(Model& m, const float* const* params, cnr_stream s, bool sdf_only = false) {
+// THE place where a Lin becomes a PrepWeight (g only with weight norm) and the two SplitJobs of its f16 planes (W and W^T)
+static PrepWeight prep_desc(const Lin& q, const float* const* params) {
+  PrepWeight p;
+  p.g = q.p_g >= 0 ? params[q.p_g] : nullptr;
+  p.v = params[q.p_v];
+  p.b = params[q.p_b];
+  p.n = q.n; p.k_ref = q.k_ref;
+  p.nseg = q.nseg;
+  for (int i = 0; i < q.nseg; ++i) p.seg[i] = q.seg[i];
+  p.W = q.W; p.ldw = q.ldw; p.npad = q.wpad;
+  p.Wt = q.Wt; p.ldwt = q.ldwt; p.kpad = q.kpad;
+  p.bias = q.bias; p.row_rot = q.row_rot;
+  return p;
+}
+static void add_split_jobs(const Lin& q, std::vector<SplitJob>& sj) {
+  sj.push_back(SplitJob{q.W, q.wpad, q.ldw, q.Wp, q.Wps});
+  sj.push_back(SplitJob{q.Wt, q.kpad, q.ldwt, q.Wtp, q.Wtps});
+}
+// effective weights of the layers (one launch) and their f16 planes (one launch)
+static void prep_layers(const std::vector<Lin*>& layers, const float* const* params, cnr_stream s) {
   std::vector<PrepWeight> pw;
   std::vector<SplitJob> sj;
-  auto prep = [&](Lin& q) {
-    PrepWeight p;
-    p.g = q.p_g >= 0 ? params[q.p_g] : nullptr;
-    p.v = params[q.p_v];
-    p.b = params[q.p_b];
-    p.n = q.n; p.k_ref = q.k_ref;
-    p.nseg = q.nseg;
-    for (int i = 0; i < q.nseg; ++i) p.seg[i] = q.seg[i];
-    p.W = q.W; p.ldw = q.ldw; p.npad = q.wpad;
-    p.Wt = q.Wt; p.ldwt = q.ldwt; p.kpad = q.kpad;
-    p.bias = q.bias; p.row_rot = q.row_rot;
-    pw.push_back(p);
-    sj.push_back(SplitJob{q.W, q.wpad, q.ldw, q.Wp, q.Wps});
-    sj.push_back(SplitJob{q.Wt, q.kpad, q.ldwt, q.Wtp, q.Wtps});
-  };
-  for (auto& q : m.sdf) prep(q);
-  if (!sdf_only) for (auto& q : m.col) prep(q);
-  if (!sdf_only) for (auto& q : m.rel) prep(q);
-  be_prep_weights(pw.data(), (int)pw.size(), s);            // effective weights of every layer: one launch
-  be_split_planes_many(sj.data(), (int)sj.size(), s);       // their f16 planes (W and W^T): one launch
+  for (const Lin* q : layers) { pw.push_back(prep_desc(*q, params)); add_split_jobs(*q, sj); }
+  be_prep_weights(pw.data(), (int)pw.size(), s);
+  be_split_planes_many(sj.data(), (int)sj.size(), s);
+}
+static void prep_all(Model& m, const float* const* params, cnr_stream s, bool sdf_only = false) {
+  std::vector<Lin*> layers;
+  for (auto& q : m.sdf) layers.push_back(&q);
+  if (!sdf_only) for (auto& q : m.col) layers.push_back(&q);
+  if (!sdf_only) for (auto& q : m.rel) layers.push_back(&q);
+  prep_layers(layers, params, s);
   std::vector<PackJob> pj;
   for (auto& q : m.sdf) if (q.Wf) pj.push_back(PackJob{q.Wp, (long)q.wpad * q.ldw, q.wpad, q.ldw, q.Wf});
   // the hidden layers of the ReLU stacks (chain-fused forward, cnr_chain_fwd.hip); their 3-wide heads stay fp32
@@ -1113,28 +1175,6 @@ static int render_forward(const cnr_config* cfg, const float* const* params, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// A layer's region of the partial-sum pool: [slots][npad][ldw] + [slots][npad] column sums.  Several launches may fill consecutive slot
-// groups of one region (SDF layers: value pair | gradient-chain pair, each either fused into its layer launch or a separate GEMM);
-// finish_region queues the one reduction over all of them.  Only the group at slot 0 carries bias column sums.
-struct DwRegion { float* part = nullptr; float* csum = nullptr; };
-static DwRegion take_region(const Lin& q, Bwd& b) {
-  DwRegion r;
-  const int cap = region_slots(q, b);
-  r.part = b.partial + b.partial_off;
-  b.partial_off += round_up_sz((size_t)cap * q.npad * q.ldw, 64);
-  r.csum = b.partial + b.partial_off;
-  b.partial_off += round_up_sz((size_t)cap * q.npad, 64);
-  return r;
-}
-static void finish_region(const Lin& q, const DwRegion& r, int nslots, int ncolsum, Bwd& b, const float* const* params, float* const* dparams) {
-  FinishWeight f;
-  f.partial = r.part; f.nchunk = nslots; f.npad = q.npad; f.ldk = q.ldw; f.colsum = ncolsum > 0 ? r.csum : nullptr; f.ncolsum = ncolsum;
-  f.g = q.p_g >= 0 ? params[q.p_g] : nullptr; f.v = params[q.p_v];
-  f.n = q.n; f.k_ref = q.k_ref; f.nseg = q.nseg;
-  for (int i = 0; i < q.nseg; ++i) f.seg[i] = q.seg[i];
-  f.dg = q.p_g >= 0 ? dparams[q.p_g] : nullptr; f.dv = dparams[q.p_v]; f.db = dparams[q.p_b]; f.row_rot = q.row_rot;
-  b.pending.push_back(f);
-}
 // separate weight-gradient GEMM into slots [slot0, slot0 + nchunk) of a region (bias column sums only for a group at slot 0)
 static void dw_into_region(const Lin& q, DwGemm& g, const DwRegion& r, int slot0, int nchunk, long P, bool with_bias, cnr_stream s, int kmain = 0) {
   with_bias = with_bias && slot0 == 0;
@@ -1176,7 +1216,7 @@ static bool strip_bwd_ok(const Lin& q, const LayerGemm& g, const DwGemm& d) {
          (g.E.kind == EK_RELU_MASK || g.E.kind == EK_SPLIT) && g.E.split == 256 && g.E.bias == nullptr &&
          d.Y[0].kind == VK_DIRECT && d.Y[0].scale == 1.0f && d.npairs == 1;
 }
-// narrows g to its 256 main columns and returns the strip launch (to be issued after the main launches; finish with finish_strip_region)
+// narrows g to its 256 main columns and returns the strip launch (to be issued after the main launches; then DwPool::strip_columns_of_last_finish)
 static StripBwd take_strips(const Lin& q, LayerGemm& g, const DwGemm& d, const DwRegion& r, const Bwd& b) {
   StripBwd sb;
   sb.dout = g.A.a; sb.ldo = g.A.lda; sb.P = g.P; sb.nt = q.k_int - 256; sb.Wt = q.Wt; sb.ldwt = q.ldwt;
@@ -1187,33 +1227,33 @@ static StripBwd take_strips(const Lin& q, LayerGemm& g, const DwGemm& d, const D
   g.N = 256; g.E.n_out = 256; g.E.o2 = nullptr;
   return sb;
 }
-static void strip_columns_of_last_finish(Bwd& b) { b.pending.back().col_hi = 256; b.pending.back().nchunk_hi = b.nchunk; }
 
 // backward of a narrow head (<= 4 outputs on a <= 256-wide ReLU layer) in one streaming launch: cotangent of the layer below + weight / bias gradient
 static bool head_bwd_ok(const Lin& q, const LayerGemm& g) {
   return head_bwd_static_ok(q, g.E.ldaux) && (g.E.ld1 & 3) == 0 && g.A.kind == VK_DIRECT && (g.A.lda & 3) == 0 && g.E.kind == EK_RELU_MASK &&
          g.E.split >= q.k_int && g.E.aux != nullptr && g.E.o1 != nullptr;
 }
-static void run_head_bwd(const Lin& q, const LayerGemm& g, Bwd& b, const float* const* params, float* const* dparams, cnr_stream s) {
-  const DwRegion r = take_region(q, b);
+static int run_head_bwd(const Lin& q, const LayerGemm& g, Bwd& b, const float* const* params, float* const* dparams, cnr_stream s) {
+  const DwRegion r = b.dw.take(q, region_slots(q, b));
+  if (!r.part) return -1;
   HeadBwd h;
   h.dtop = g.A.a; h.ldt = g.A.lda; h.aux = g.E.aux; h.ldaux = g.E.ldaux; h.W = q.W; h.ldw = q.ldw; h.n = q.n; h.K = q.k_int; h.P = g.P;
   h.dout = g.E.o1; h.ldo = g.E.ld1; h.partial = r.part; h.colsum = r.csum; h.npad = q.npad; h.ldk = q.ldw; h.nslots = b.nchunk;
   be_head_bwd(h, s);
-  finish_region(q, r, b.nchunk, b.nchunk, b, params, dparams);
+  b.dw.finish(q, r, b.nchunk, b.nchunk, params, dparams);
+  return 0;
 }
 
-static void run_dw(const Model& m, const Lin& q, DwGemm& g, Bwd& b, const float* const* params, float* const* dparams,
-                   bool with_bias, cnr_stream s) {
-  const DwRegion r = take_region(q, b);
-  dw_into_region(q, g, r, 0, b.nchunk, g.P, with_bias, s);
-  finish_region(q, r, b.nchunk, with_bias ? b.nchunk : 0, b, params, dparams);
-  (void)m;
+// THE plain weight gradient of a layer: a region of cap slots, one GEMM of g's operand pairs over its first nchunk slots, the reduction queued
+static int plain_dw(DwPool& pool, const Lin& q, DwGemm& g, int cap, int nchunk, const float* const* params, float* const* dparams, cnr_stream s) {
+  const DwRegion r = pool.take(q, cap);
+  if (!r.part) return -1;
+  dw_into_region(q, g, r, 0, nchunk, g.P, true, s);
+  pool.finish(q, r, nchunk, nchunk, params, dparams);
+  return 0;
 }
-
-static void flush_dw(Bwd& b, cnr_stream s) {
-  if (!b.pending.empty()) be_finish_weights(b.pending.data(), (int)b.pending.size(), s);
-  b.pending.clear();
+static int run_dw(const Lin& q, DwGemm& g, Bwd& b, const float* const* params, float* const* dparams, cnr_stream s) {
+  return plain_dw(b.dw, q, g, region_slots(q, b), b.nchunk, params, dparams, s);
 }
 
 // Backward of one layer of a ReLU stack (relight rl_mlp, colour): g = the launch that forms the cotangent of the layer's input, d = its
@@ -1224,9 +1264,10 @@ static void flush_dw(Bwd& b, cnr_stream s) {
 // stack alternates).  head: the stack's top layer, whose cotangent rows are packed (b.ldtop != kTop) only for the head kernel.
 static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* rs_in, int rev, bool head, Bwd& b, const float* const* params,
                            float* const* dP, cnr_stream s) {
-  if (head_bwd_ok(q, g)) { run_head_bwd(q, g, b, params, dP, s); return 0; }
+  if (head_bwd_ok(q, g)) return run_head_bwd(q, g, b, params, dP, s);
   if (head && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");   // (layout_bwd decides both from the same predicate)
-  const DwRegion r = take_region(q, b);
+  const DwRegion r = b.dw.take(q, region_slots(q, b));
+  if (!r.part) return -1;
   const bool strips = strip_bwd_ok(q, g, d);
   StripBwd sb;
   if (strips) sb = take_strips(q, g, d, r, b);
@@ -1243,8 +1284,8 @@ static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* r
   }
   if (strips) be_strip_bwd(sb, s);
   const int nslots = fused ? b.fslots : b.nchunk;
-  finish_region(q, r, nslots, nslots, b, params, dP);
-  if (strips) strip_columns_of_last_finish(b);
+  b.dw.finish(q, r, nslots, nslots, params, dP);
+  if (strips) b.dw.strip_columns_of_last_finish(b.nchunk);
   return 0;
 }
 
@@ -1252,12 +1293,13 @@ static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* r
 // by render_backward and cnr_sdf_query_backward (the render path issues the same launches with the same arguments in the same order as
 // before this was a function of its own).  Seeds: b.ZTOP (cotangent of the top layer's outputs [feat | sdf / scale | 0]) and b.gbar_a
 // (cotangent of grad_x sdf).  Entered inside an open range (be_range_push), which it closes after the weight-gradient reductions.
+// Every region of the partial-sum pool is taken before the first launch that writes into one; -1 when the pool refuses.
 struct SdfBwdArgs {
   const float* daux_c = nullptr; const float* daux_r = nullptr;   // cotangents of the colour / relight aux rows [p g ..] (render) or null (query)
   bool grad_path = true;    // false: no cotangent on grad_x sdf -- no gbar / second-order sweep (Z2 starts from zero), value pairs only
   bool pts_grad = false;    // form ebar0 / ebars and the total point cotangent b.pbar (camera refinement, point queries)
 };
-static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const float* const* params, float* const* dP /* null: no weight gradients */,
+static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const float* const* params, float* const* dP /* null: no weight gradients */,
                          const SdfBwdArgs& sa, cnr_stream s) {
   const float scale = m.c.sdf_scale;
   const bool fdw = be_fdw_enabled() && dP != nullptr;   // (the fused layer + weight-gradient launches only where weight gradients are wanted)
@@ -1325,7 +1367,8 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
   std::vector<char> fuse_v(m.L + 1, 0), fuse_g(m.L + 1, 0);
   for (int l = 0; l <= m.L; ++l) {
     const Lin& q = m.sdf[l];
-    sreg[l] = take_region(q, b);
+    sreg[l] = b.dw.take(q, region_slots(q, b));
+    if (!sreg[l].part) { be_range_pop(); return -1; }
     const bool sq = q.npad >= 224 && q.npad <= 256 && q.ldw == 256;
     auto ok = [&](const LayerGemm& g) { return fdw_shape_ok(g); };
     if (fdw && sq && l >= 1 && l < m.L && x.rsY[l] && ok(vback_gemm(l))) fuse_v[l] = 1;
@@ -1434,9 +1477,9 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
       grad_pair(l, d, 0);
       dw_into_region(q, d, r, value_slots(l), grad_slots(l), P, false, s);
     }
-    finish_region(q, r, value_slots(l) + grad_slots(l), value_slots(l), b, params, dP);
+    b.dw.finish(q, r, value_slots(l) + grad_slots(l), value_slots(l), params, dP);
   }
-  flush_dw(b, s);   // all partial-sum reductions + weight-norm backward in one launch
+  b.dw.flush(s);   // all partial-sum reductions + weight-norm backward in one launch
   be_range_pop();
   // ---- 8 (first part). total cotangent of the points
   if (rays_grad) {
@@ -1446,6 +1489,7 @@ static void sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const flo
     pf.multires = m.c.sdf_multires; pf.pbar = b.pbar;
     be_pbar_finish(pf, s);
   }
+  return 0;
 }
 
 static int render_backward(const cnr_config* cfg, const float* const* params, const cnr_render_inputs* in,
@@ -1525,19 +1569,20 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
       nb.X = b.D[0]; nb.ldx = m.Hr; nb.Y = x.AUX; nb.ldy = kAux; nb.ky = q.k_int; nb.P = P;
       narrow_bwd_weights(nb, q);
       nb.dx = b.dAUXr; nb.lddx = kAux; nb.ndx = q.k_int; nb.ldk = q.ldw;
-      nb.partial = b.partial;   // (placeholder for the shape test; the region is taken below)
+      nb.partial = b.dw.base;   // (placeholder for the shape test; the region is taken below)
       if (be_fdw_enabled() && q.n == 256 && q.npad == 256 && m.Hr == 256 && be_narrow_bwd_ok(nb) && be_narrow_bwd_slots(P) <= region_slots(q, b)) {
-        const DwRegion r = take_region(q, b);
+        const DwRegion r = b.dw.take(q, region_slots(q, b));
+        if (!r.part) return -1;
         nb.partial = r.part; nb.colsum = r.csum;
         be_narrow_bwd(nb, s);
-        finish_region(q, r, be_narrow_bwd_slots(P), be_narrow_bwd_slots(P), b, params, dP);
+        b.dw.finish(q, r, be_narrow_bwd_slots(P), be_narrow_bwd_slots(P), params, dP);
       } else {   // ... or a narrow layer launch + a weight-gradient launch
         be_layer_gemm(g, s);
         DwGemm d;
         d.npairs = 1; d.P = P;
         d.X[0] = g.A;
         d.Y[0] = relight_input_view(m, -1, x);
-        run_dw(m, q, d, b, params, dP, true, s);
+        if (run_dw(q, d, b, params, dP, s)) return -1;
       }
     }
   }
@@ -1569,7 +1614,7 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
   be_range_pop(); be_range_push("sdf second-order sweep");
   SdfBwdArgs args;
   args.daux_c = b.dAUXc; args.daux_r = m.has_relight ? b.dAUXr : nullptr; args.grad_path = true; args.pts_grad = rays_grad;
-  sdf_backward(m, P, x, b, params, dP, args, s);
+  if (sdf_backward(m, P, x, b, params, dP, args, s)) return -1;
   // ---- 8. d rays (camera refinement configs)
   if (rays_grad) {
     RaysGradFinish rg;
@@ -1751,7 +1796,7 @@ static int sdf_query_backward(const cnr_config* cfg, const float* const* params,
   be_range_push("sdf second-order sweep");
   SdfBwdArgs args;
   args.grad_path = grad_path; args.pts_grad = d_pts != nullptr;
-  sdf_backward(m, P, q.x, b, params, d_params, args, s);
+  if (sdf_backward(m, P, q.x, b, params, d_params, args, s)) return -1;
   if (d_pts) {
     QueryOut qo;
     qo.n = n; qo.F = m.F; qo.ldf = 0; qo.ldg = 4;
@@ -1766,7 +1811,7 @@ static int sdf_query_backward(const cnr_config* cfg, const float* const* params,
 // one plain fully-connected layer y = act(x W^T + b) and its backward on the layer / weight-gradient kernels of the render path:
 // the NeRF++ background stack (fields.py:192-274) is a chain of these (color-neus_amd/background.py)
 // ------------------------------------------------------------------------------------------------
-struct LinearOp { Lin q; int ldx = 0, ldy = 0; float *xp = nullptr, *yp = nullptr, *gp = nullptr, *dxp = nullptr; float* part = nullptr; int nchunk = 1; };
+struct LinearOp { Lin q; int ldx = 0, ldy = 0; float *xp = nullptr, *yp = nullptr, *gp = nullptr, *dxp = nullptr; DwPool dw; int nchunk = 1; };
 
 static int linear_check(long n, int k, int n_out) {
   if (n <= 0 || k < 1 || n_out < 1 || k > 4096 || n_out > 4096) return fail("linear: need n > 0, 1 <= k, n_out <= 4096");
@@ -1775,6 +1820,7 @@ static int linear_check(long n, int k, int n_out) {
 static void layout_linear(long n, int k, int n_out, bool backward, Arena& a, LinearOp& op) {
   Lin& q = op.q;
   q.n = n_out; q.k_ref = k; identity_seg(q); q.finish_dims(); q.wn = false;
+  q.name = "linear"; q.p_v = 0; q.p_b = 1;   // (the op's two-entry parameter lists: {W, b} and {dW, db})
   place_lin(q, a);
   op.ldx = round_up(k, 16); op.ldy = round_up(n_out, 16);
   op.xp = a.f((size_t)n * op.ldx);
@@ -1783,20 +1829,14 @@ static void layout_linear(long n, int k, int n_out, bool backward, Arena& a, Lin
     op.gp = a.f((size_t)n * op.ldy);
     op.dxp = a.f((size_t)n * op.ldx);
     op.nchunk = dw_chunks(n);
-    op.part = a.f(round_up_sz((size_t)op.nchunk * q.npad * q.ldw, 64) + round_up_sz((size_t)op.nchunk * q.npad, 64));
+    op.dw.place(a, DwPool::region_floats(q, op.nchunk));
   }
   place_slack(a);
 }
 
 static void linear_prep(LinearOp& op, const float* W, const float* b, cnr_stream s) {
-  Lin& q = op.q;
-  PrepWeight p;
-  p.g = nullptr; p.v = W; p.b = b; p.n = q.n; p.k_ref = q.k_ref; p.nseg = q.nseg;
-  for (int i = 0; i < q.nseg; ++i) p.seg[i] = q.seg[i];
-  p.W = q.W; p.ldw = q.ldw; p.npad = q.wpad; p.Wt = q.Wt; p.ldwt = q.ldwt; p.kpad = q.kpad; p.bias = q.bias; p.row_rot = 0;
-  be_prep_weights(&p, 1, s);
-  SplitJob sj[2] = {SplitJob{q.W, q.wpad, q.ldw, q.Wp, q.Wps}, SplitJob{q.Wt, q.kpad, q.ldwt, q.Wtp, q.Wtps}};
-  be_split_planes_many(sj, 2, s);
+  const float* params[2] = {W, b};
+  prep_layers({&op.q}, params, s);
 }
 
 // compact [n][c] -> padded [n][ld] with zero pad columns
@@ -1822,12 +1862,6 @@ struct NerfModel {
   std::vector<ParamInfo> params;
   int skip_at = -1;                   // the layer AFTER which [e | h] is concatenated (input of layer skip_at + 1), -1: none
 };
-static int nerf_add(NerfModel& m, Lin& q, const std::string& name) {
-  q.name = name; q.wn = false;
-  q.p_v = (int)m.params.size(); m.params.push_back({name + ".weight", q.n, q.k_ref});
-  q.p_b = (int)m.params.size(); m.params.push_back({name + ".bias", q.n, 1});
-  return 0;
-}
 static int build_nerf(const cnr_nerf_config* cfg, NerfModel& m) {
   if (!cfg) return fail("null nerf config");
   m.c = *cfg;
@@ -1848,13 +1882,13 @@ static int build_nerf(const cnr_nerf_config* cfg, NerfModel& m) {
       q.seg[0] = {0, m.ne, m.W}; q.seg[1] = {m.W, 0, m.ne};
     } else { q.k_ref = m.W; identity_seg(q); }
     q.finish_dims();
-    nerf_add(m, q, "pts_linears." + std::to_string(i));
+    add_weight_bias(m.params, q, "pts_linears." + std::to_string(i));
   }
   // nn.Module registration order of NeRF.__init__ (fields.py:215-231): pts_linears, views_linears, feature_linear, alpha_linear, rgb_linear
-  m.view.n = m.W / 2; m.view.k_ref = m.W + m.nv; identity_seg(m.view); m.view.finish_dims(); nerf_add(m, m.view, "views_linears.0");
-  m.feat.n = m.W; m.feat.k_ref = m.W; identity_seg(m.feat); m.feat.finish_dims(); nerf_add(m, m.feat, "feature_linear");
-  m.alpha.n = 1; m.alpha.k_ref = m.W; identity_seg(m.alpha); m.alpha.finish_dims(); nerf_add(m, m.alpha, "alpha_linear");
-  m.rgb.n = 3; m.rgb.k_ref = m.W / 2; identity_seg(m.rgb); m.rgb.finish_dims(); nerf_add(m, m.rgb, "rgb_linear");
+  m.view.n = m.W / 2; m.view.k_ref = m.W + m.nv; identity_seg(m.view); m.view.finish_dims(); add_weight_bias(m.params, m.view, "views_linears.0");
+  m.feat.n = m.W; m.feat.k_ref = m.W; identity_seg(m.feat); m.feat.finish_dims(); add_weight_bias(m.params, m.feat, "feature_linear");
+  m.alpha.n = 1; m.alpha.k_ref = m.W; identity_seg(m.alpha); m.alpha.finish_dims(); add_weight_bias(m.params, m.alpha, "alpha_linear");
+  m.rgb.n = 3; m.rgb.k_ref = m.W / 2; identity_seg(m.rgb); m.rgb.finish_dims(); add_weight_bias(m.params, m.rgb, "rgb_linear");
   return 0;
 }
 struct NerfCtx {       // forward-saved state of one background call
@@ -1887,20 +1921,7 @@ static int nerf_h_ld(const NerfModel& m, const NerfCtx& x, int i) { return i == 
 static void nerf_prep(NerfModel& m, const float* const* params, cnr_stream s) {
   std::vector<Lin*> all;
   nerf_layers(m, all);
-  std::vector<PrepWeight> pw;
-  std::vector<SplitJob> sj;
-  for (Lin* qp : all) {
-    Lin& q = *qp;
-    PrepWeight p;
-    p.g = nullptr; p.v = params[q.p_v]; p.b = params[q.p_b]; p.n = q.n; p.k_ref = q.k_ref; p.nseg = q.nseg;
-    for (int i = 0; i < q.nseg; ++i) p.seg[i] = q.seg[i];
-    p.W = q.W; p.ldw = q.ldw; p.npad = q.wpad; p.Wt = q.Wt; p.ldwt = q.ldwt; p.kpad = q.kpad; p.bias = q.bias; p.row_rot = 0;
-    pw.push_back(p);
-    sj.push_back(SplitJob{q.W, q.wpad, q.ldw, q.Wp, q.Wps});
-    sj.push_back(SplitJob{q.Wt, q.kpad, q.ldwt, q.Wtp, q.Wtps});
-  }
-  be_prep_weights(pw.data(), (int)pw.size(), s);
-  be_split_planes_many(sj.data(), (int)sj.size(), s);
+  prep_layers(all, params, s);
 }
 static int background_forward(const cnr_nerf_config* cfg, const float* const* params, const float* rays_o, const float* rays_d, const float* z_feed,
                               long R, int MF, float sample_dist, float* alpha, float* color, void* ctx, size_t ctx_bytes, cnr_stream s) {
@@ -1948,7 +1969,7 @@ static int background_forward(const cnr_nerf_config* cfg, const float* const* pa
   be_bg_alpha(ba, s);
   return check_backend("background_forward");
 }
-struct NerfBwd { float *dRGB, *dDens, *dDist, *DHV, *dF, *dVE, *T, *dEs, *dE0, *dp; std::vector<float*> DZ; float* part; size_t part_floats; int nchunk; };
+struct NerfBwd { float *dRGB, *dDens, *dDist, *DHV, *dF, *dVE, *T, *dEs, *dE0, *dp; std::vector<float*> DZ; DwPool dw; int nchunk; };
 static void layout_nerf_bwd(NerfModel& m, const NerfCtx& x, long n, Arena& a, NerfBwd& b) {
   b.dRGB = a.f((size_t)n * 16); b.dDens = a.f((size_t)n * 16); b.dDist = a.f(n);
   b.DHV = a.f((size_t)n * (m.W / 2)); b.dF = a.f((size_t)n * m.W); b.dVE = a.f((size_t)n * 32);
@@ -1959,26 +1980,17 @@ static void layout_nerf_bwd(NerfModel& m, const NerfCtx& x, long n, Arena& a, Ne
   std::vector<Lin*> all;
   nerf_layers(m, all);
   size_t tot = 0;
-  for (Lin* q : all) tot += round_up_sz((size_t)b.nchunk * q->npad * q->ldw, 64) + round_up_sz((size_t)b.nchunk * q->npad, 64);
-  b.part_floats = tot; b.part = a.f(tot);
+  for (Lin* q : all) tot += DwPool::region_floats(*q, b.nchunk);
+  b.dw.place(a, tot);
   place_slack(a);
 }
 // weight + bias gradient of one background layer: dW = sum_pt X (x) Y, db = column sums of X; queued for one batched finish
-static void nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int ldy, long n, NerfBwd& b, size_t& off, const float* const* params,
-                    float* const* dP, std::vector<FinishWeight>& pend, cnr_stream s) {
-  float* part = b.part + off; off += round_up_sz((size_t)b.nchunk * q.npad * q.ldw, 64);
-  float* csum = b.part + off; off += round_up_sz((size_t)b.nchunk * q.npad, 64);
+// (no row scales: dw_into_region keeps the tiles off the split-f16 form)
+static int nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int ldy, long n, NerfBwd& b, const float* const* params,
+                   float* const* dP, cnr_stream s) {
   DwGemm d;
   d.npairs = 1; d.P = n; d.X[0] = direct_view(X, ldx); d.Y[0] = direct_view(Y, ldy);
-  d.N = q.n; d.K = q.k_int; d.nchunk = b.nchunk; d.chunk_pts = round_up((int)((n + b.nchunk - 1) / b.nchunk), 16);
-  d.partial = part; d.Npad = q.npad; d.ldk = q.ldw; d.colsum = csum; d.split_f16 = false;
-  be_dw_gemm(d, s);
-  FinishWeight f;
-  f.partial = part; f.nchunk = b.nchunk; f.npad = q.npad; f.ldk = q.ldw; f.colsum = csum; f.ncolsum = b.nchunk;
-  f.g = nullptr; f.v = params[q.p_v]; f.n = q.n; f.k_ref = q.k_ref; f.nseg = q.nseg;
-  for (int i = 0; i < q.nseg; ++i) f.seg[i] = q.seg[i];
-  f.dg = nullptr; f.dv = dP[q.p_v]; f.db = dP[q.p_b]; f.row_rot = 0;
-  pend.push_back(f);
+  return plain_dw(b.dw, q, d, b.nchunk, b.nchunk, params, dP, s);
 }
 static int background_backward(const cnr_nerf_config* cfg, const float* const* params, const float* rays_o, const float* rays_d, const float* z_feed,
                                long R, int MF, float sample_dist, const void* ctx, size_t ctx_bytes, const float* color, const float* d_alpha,
@@ -1992,8 +2004,6 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   NerfBwd b;
   if (layout_checked("background context", const_cast<void*>(ctx), ctx_bytes, [&](Arena& a) { layout_nerf(m, n, a, x); })) return -1;
   if (layout_checked("background scratch", scratch, scratch_bytes, [&](Arena& a) { layout_nerf_bwd(m, x, n, a, b); })) return -1;
-  std::vector<FinishWeight> pend;
-  size_t off = 0;
   BgHeadsBwd hb;
   hb.n = n; hb.density = x.dens; hb.dist = x.dist; hb.rgb = color; hb.d_alpha = d_alpha; hb.d_rgb = d_color;
   hb.d_density = b.dDens; hb.ldd = 16; hb.d_rgb_pre = b.dRGB; hb.ldr = 16; hb.d_dist = b.dDist;
@@ -2001,7 +2011,7 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   const float* hl = x.H[m.D - 1];
   const int ldh = nerf_h_ld(m, x, m.D - 1);
   // rgb head: dW, cotangent of the view layer's pre-activation (ReLU mask)
-  nerf_dw(m.rgb, b.dRGB, 16, x.HV, m.W / 2, n, b, off, params, dP, pend, s);
+  if (nerf_dw(m.rgb, b.dRGB, 16, x.HV, m.W / 2, n, b, params, dP, s)) return -1;
   {
     LayerGemm g = bwd_gemm(m.rgb, n);
     g.A = direct_view(b.dRGB, 16); g.Wp = nullptr;
@@ -2009,7 +2019,7 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
     be_layer_gemm(g, s);
   }
   // view layer: dW, cotangent of [feature | PE(view)]
-  nerf_dw(m.view, b.DHV, m.W / 2, x.FV, x.ldfv, n, b, off, params, dP, pend, s);
+  if (nerf_dw(m.view, b.DHV, m.W / 2, x.FV, x.ldfv, n, b, params, dP, s)) return -1;
   {
     LayerGemm g = bwd_gemm(m.view, n);
     g.A = direct_view(b.DHV, m.W / 2);
@@ -2018,8 +2028,8 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   }
   be_zero_cols(b.dVE, 32, m.nv, 32, n, s);
   // feature layer and density head: both read the last hidden activation
-  nerf_dw(m.feat, b.dF, m.W, hl, ldh, n, b, off, params, dP, pend, s);
-  nerf_dw(m.alpha, b.dDens, 16, hl, ldh, n, b, off, params, dP, pend, s);
+  if (nerf_dw(m.feat, b.dF, m.W, hl, ldh, n, b, params, dP, s)) return -1;
+  if (nerf_dw(m.alpha, b.dDens, 16, hl, ldh, n, b, params, dP, s)) return -1;
   {
     LayerGemm g = bwd_gemm(m.feat, n);
     g.A = direct_view(b.dF, m.W);
@@ -2034,7 +2044,7 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
     const Lin& q = m.pts[i];
     const float* in = i == 0 ? x.E : x.H[i - 1];
     const int ld_in = i == 0 ? x.lde : nerf_h_ld(m, x, i - 1);
-    nerf_dw(q, b.DZ[i], m.W, in, ld_in, n, b, off, params, dP, pend, s);
+    if (nerf_dw(q, b.DZ[i], m.W, in, ld_in, n, b, params, dP, s)) return -1;
     LayerGemm g = bwd_gemm(q, n);
     g.A = direct_view(b.DZ[i], m.W); g.E.n_out = q.k_int;
     if (i == 0) { g.E.kind = EK_STORE; g.E.o1 = b.dE0; g.E.ld1 = x.lde; }
@@ -2045,7 +2055,7 @@ static int background_backward(const cnr_nerf_config* cfg, const float* const* p
   }
   be_zero_cols(b.dE0, x.lde, m.ne, x.lde, n, s);
   if (b.dEs) be_zero_cols(b.dEs, x.lde, m.ne, x.lde, n, s);
-  be_finish_weights(pend.data(), (int)pend.size(), s);
+  b.dw.flush(s);
   BgEmbedBwd eb;
   eb.o = rays_o; eb.d = rays_d; eb.z_feed = z_feed; eb.R = R; eb.MF = MF; eb.sample_dist = sample_dist; eb.multires = cfg->multires; eb.multires_view = cfg->multires_view;
   eb.dE0 = b.dE0; eb.lde0 = x.lde; eb.dE1 = b.dEs; eb.lde1 = x.lde; eb.dVE = b.dVE; eb.ldve = 32; eb.dp = b.dp;
@@ -2081,12 +2091,7 @@ int cnr_param_count(const cnr_config* cfg) {
 
 int cnr_param_info(const cnr_config* cfg, int index, char* name, int name_len, int* rows, int* cols) {
   Model m;
-  if (build_model(cfg, m)) return -1;
-  if (index < 0 || index >= (int)m.params.size()) return fail("parameter index out of range");
-  if (name && name_len > 0) snprintf(name, name_len, "%s", m.params[index].name.c_str());
-  if (rows) *rows = m.params[index].rows;
-  if (cols) *cols = m.params[index].cols;
-  return 0;
+  return build_model(cfg, m) ? -1 : param_info(m.params, index, name, name_len, rows, cols);
 }
 
 size_t cnr_ctx_bytes(const cnr_config* cfg, int64_t n_rays) {
@@ -2649,12 +2654,7 @@ int cnr_nerf_param_count(const cnr_nerf_config* cfg) {
 }
 int cnr_nerf_param_info(const cnr_nerf_config* cfg, int index, char* name, int name_len, int* rows, int* cols) {
   NerfModel m;
-  if (build_nerf(cfg, m)) return -1;
-  if (index < 0 || index >= (int)m.params.size()) return fail("parameter index out of range");
-  if (name && name_len > 0) snprintf(name, name_len, "%s", m.params[index].name.c_str());
-  if (rows) *rows = m.params[index].rows;
-  if (cols) *cols = m.params[index].cols;
-  return 0;
+  return build_nerf(cfg, m) ? -1 : param_info(m.params, index, name, name_len, rows, cols);
 }
 int cnr_outside_z(const float* far_, const float* t_rand, const float* z_vals, int64_t n_rays, int32_t n_z, int32_t n_outside, int32_t n_samples,
                   float* z_feed, int32_t* src, void* stream) {
@@ -2767,19 +2767,16 @@ int cnr_linear_backward(const float* x, const float* y, const float* dy, int64_t
   View dz = direct_view(op.gp, op.ldy);    // cotangent of the pre-activation: dy gated by the ReLU output
   if (relu) { pad_in(op.yp, op.ldy, y, n_out, n, s); dz.kind = VK_RELUGATE; dz.b = op.yp; dz.ldb = op.ldy; }
   // weight and bias gradients: dW[n_out][k] = sum_pt dz (x) x, db = column sums of dz
+  // (the GEMM forms the column sums whether or not the caller wants db; the reduction reads them only for a db)
+  const float* params[2] = {W, nullptr};
+  float* dparams[2] = {dW, db};
+  const DwRegion r = op.dw.take(q, op.nchunk);
+  if (!r.part) return -1;
   DwGemm d;
   d.npairs = 1; d.P = n; d.X[0] = dz; d.Y[0] = direct_view(op.xp, op.ldx);
-  d.N = q.n; d.K = q.k_int; d.nchunk = op.nchunk; d.chunk_pts = round_up((int)((n + op.nchunk - 1) / op.nchunk), 16);
-  d.partial = op.part; d.Npad = q.npad; d.ldk = q.ldw;
-  float* csum = op.part + round_up_sz((size_t)op.nchunk * q.npad * q.ldw, 64);
-  d.colsum = csum; d.split_f16 = false;
-  be_dw_gemm(d, s);
-  FinishWeight f;
-  f.partial = op.part; f.nchunk = op.nchunk; f.npad = q.npad; f.ldk = q.ldw; f.colsum = db ? csum : nullptr; f.ncolsum = op.nchunk;
-  f.g = nullptr; f.v = W; f.n = q.n; f.k_ref = q.k_ref; f.nseg = q.nseg;
-  for (int i = 0; i < q.nseg; ++i) f.seg[i] = q.seg[i];
-  f.dg = nullptr; f.dv = dW; f.db = db; f.row_rot = 0;
-  be_finish_weights(&f, 1, s);
+  dw_into_region(q, d, r, 0, op.nchunk, n, true, s);
+  op.dw.finish(q, r, op.nchunk, db ? op.nchunk : 0, params, dparams);
+  op.dw.flush(s);   // (before the dx launch)
   if (dx) {
     LayerGemm g = bwd_gemm(q, n);
     g.A = dz;

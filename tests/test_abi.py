@@ -1,5 +1,6 @@
 """CPU: the C-ABI library loads without a GPU and exports every symbol that include/colorneus_render.h declares;
 the host-side module mirrors the reference interface; the product path has no fallback."""
+import contextlib
 import ctypes
 import os
 import re
@@ -121,3 +122,149 @@ def test_register_into_reference_style_registry():
     reg = Reg()
     cn.register_into(reg)
     assert reg.d == {"NeuS": cn.NeuSRenderer, "Color_NeuS": cn.ColorNeuSRenderer}
+
+
+# ---- every *_bytes query against the entry point it sizes -----------------------------------------------------------------------------------
+def _tiny(name, lib, dev, n=5):
+    """(renderer, rays_o, rays_d, near, far) of a golden fixture's first n rays."""
+    import _golden as G
+    import _native as N
+    fx = G.load(name)
+    ocfg, P = G.weights_of(name, fx)
+    t = lambda k: torch.from_numpy(fx[k][:n].copy()).to(dev)
+    return N.make_renderer(ocfg, P, lib, dev), t("rays_o"), t("rays_d"), t("jit:near"), t("jit:far")
+
+
+def _points(dev):
+    return (torch.rand(7, 3, generator=torch.Generator().manual_seed(3)) - 0.5).to(dev)
+
+
+def _render_forward(lib, dev):
+    r, *rays = _tiny("tiny_sharp", lib, dev)
+    return lambda: r(*rays, perturb_overwrite=0, forward_only=False)
+
+
+def _render_backward(lib, dev):
+    out = _render_forward(lib, dev)()["color_fine"]
+    return lambda: torch.autograd.backward([out], [torch.ones_like(out)])
+
+
+def _forward_only(lib, dev):
+    r, *rays = _tiny("tiny_sharp", lib, dev)
+    return lambda: r(*rays, perturb_overwrite=0, forward_only=True)
+
+
+def _query_forward(lib, dev):
+    r = _tiny("tiny_sharp", lib, dev)[0]
+    x = _points(dev)
+    return lambda: r.sdf_network.gradient(x)
+
+
+def _query_backward(lib, dev):
+    g = _query_forward(lib, dev)()
+    return lambda: torch.autograd.backward([g], [torch.ones_like(g)])
+
+
+def _background_forward(lib, dev):
+    from color_neus_amd import background as B
+    r, o, d, near, far = _tiny("tiny_outside", lib, dev)
+    n_feed = r.rcfg.n_total + r.n_outside
+    z_feed = torch.sort(torch.rand(5, n_feed, generator=torch.Generator().manual_seed(4)) * 3.0 + 0.5, dim=-1).values.to(dev)
+    return lambda: B.Background.apply(lib, r.nerf.config(), 2.0 / r.n_samples, o, d, z_feed, *r.nerf.ordered_params(lib))
+
+
+def _background_backward(lib, dev):
+    alpha, color = _background_forward(lib, dev)()
+    return lambda: torch.autograd.backward([alpha, color], [torch.ones_like(alpha), torch.ones_like(color)])
+
+
+def _linear(backward):
+    def prepare(lib, dev):
+        n, k, n_out = 37, 43, 33
+        g = torch.Generator().manual_seed(5)
+        x, w, b, y, dy = (torch.randn(*shape, generator=g).to(dev) for shape in ((n, k), (n_out, k), (n_out,), (n, n_out), (n, n_out)))
+        dx, dW, db = torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+        ptr, stream = _lib.ptr, _lib.stream_of(x)
+
+        def go():
+            buf, nb = lib.scratch("cnr_linear_scratch_bytes", x.device, n, k, n_out, int(backward))
+            if backward:
+                lib.call("cnr_linear_backward", ptr(x), ptr(y), ptr(dy), n, k, ptr(w), n_out, 1, ptr(dx), ptr(dW), ptr(db), ptr(buf), nb, stream)
+            else:
+                lib.call("cnr_linear_forward", ptr(x), n, k, ptr(w), ptr(b), n_out, 1, ptr(y), ptr(buf), nb, stream)
+        return go
+    return prepare
+
+
+def _vertex_color(lib, dev):
+    r = _tiny("tiny_sharp", lib, dev)[0]
+    verts = _points("cpu").numpy()
+    return lambda: r.extract_color(verts, dev)
+
+
+# entry point -> (its size query, prepare(lib, device) -> the call; what the call needs beforehand, a forward pass say, runs inside prepare)
+SIZED_ENTRY_POINTS = {
+    "cnr_render_forward": ("cnr_ctx_bytes", _render_forward),
+    "cnr_render_backward": ("cnr_bwd_scratch_bytes", _render_backward),
+    "cnr_render_forward_only": ("cnr_infer_scratch_bytes", _forward_only),
+    "cnr_sdf_query_forward": ("cnr_sdf_query_ctx_bytes", _query_forward),
+    "cnr_sdf_query_backward": ("cnr_sdf_query_bwd_scratch_bytes", _query_backward),
+    "cnr_background_forward": ("cnr_background_ctx_bytes", _background_forward),
+    "cnr_background_backward": ("cnr_background_bwd_scratch_bytes", _background_backward),
+    "cnr_linear_forward": ("cnr_linear_scratch_bytes", _linear(False)),
+    "cnr_linear_backward": ("cnr_linear_scratch_bytes", _linear(True)),
+    "cnr_vertex_color": ("cnr_vertex_color_scratch_bytes", _vertex_color),
+}
+
+
+@contextlib.contextmanager
+def _sized(lib, query, entry, short):
+    """While active, the buffer that ``query`` sizes is handed to ``entry`` as ``short`` bytes smaller than it is (the allocation keeps its
+    full size: a library that failed to refuse would still stay inside it).  Yields the list of sizes that reached ``entry``."""
+    seen, pending = [], []
+    scratch, call = lib.scratch, lib.call
+
+    def scratch_(bytes_fn, device, *args, **kw):
+        buf, nb = scratch(bytes_fn, device, *args, **kw)
+        if bytes_fn != query:
+            return buf, nb
+        assert nb > short and nb % 256 == 0 and buf.numel() == nb, (bytes_fn, nb)
+        pending.append(nb - short)
+        return buf, nb - short
+
+    def call_(name, *args):
+        if name == entry:
+            assert pending and pending[-1] in args, (name, pending)
+            seen.append(pending[-1])
+        return call(name, *args)
+
+    lib.scratch, lib.call = scratch_, call_
+    try:
+        yield seen
+    finally:
+        del lib.scratch, lib.call
+
+
+@pytest.mark.parametrize("entry", list(SIZED_ENTRY_POINTS))
+@pytest.mark.parametrize("backend", ["emu", pytest.param("hip", marks=pytest.mark.gpu)])
+def test_every_scratch_query_is_exact(backend, entry):
+    """A *_bytes query cannot disagree with the entry point it sizes (both run the same layout function, and the partial-sum pool inside the
+    backward layouts is sized and handed out by one owner): a buffer of exactly the queried size is accepted, one arena rounding (256 bytes)
+    smaller is refused with the layout's message, and nothing is launched after the refusal.  Shapes: 5 rays of the tiny fixtures, 7 query
+    points, the 37 x 43 -> 33 layer.  Nothing is asserted about the outputs (the parity tests do that)."""
+    lib = cn.load_library(os.path.join(ROOT, "tests", "_build", "libcolorneus_emu.so") if backend == "emu" else None)
+    dev = "cpu" if backend == "emu" else "cuda:0"
+    query, prepare = SIZED_ENTRY_POINTS[entry]
+    go = prepare(lib, dev)
+    with _sized(lib, query, entry, 0) as seen:
+        go()
+    assert len(seen) == 1, seen
+    go = prepare(lib, dev)
+    lib.timing_enable(True)
+    try:
+        lib.timing_collect()
+        with _sized(lib, query, entry, 256) as seen, pytest.raises(RuntimeError, match="too small"):
+            go()
+        assert len(seen) == 1 and lib.timing_collect() == [], seen
+    finally:
+        lib.timing_enable(False)

@@ -9,7 +9,9 @@ checkout (it imports the package it lies next to) and compare the two directorie
 Calls: a training step (render, fused loss, backward, ClipAdam) with the full dict and with training_outputs="loss_only"; a forward-only call
 without and with prune_eps; sdf, extract_fields / _slab at resolution 8, marching_cubes, extract_color; sample_pdf and up_sample; a point query
 forward and backward with want_grad; the N_OUTSIDE path forward and backward; get_rays_at and rays_for_training backward; the camera forward
-and backward; image_metrics and panel; nearest_neighbors."""
+and backward; image_metrics and panel; nearest_neighbors; one plain layer (37 x 43 -> 33) forward and backward; every *_bytes query of a
+caller-provided buffer at 5 and 4096 rays / points."""
+import ctypes as C
 import filecmp
 import os
 import sys
@@ -170,6 +172,33 @@ def main(out_dir):
     d2, idx = cn.metrics.nearest_neighbors(torch.rand(9, 3, generator=g), torch.rand(11, 3, generator=g), library=lib)
     save("nn.dist2", d2)
     save("nn.idx", idx)
+
+    # -- one plain layer: ragged in all three dimensions, with ReLU and without, with db and without ----------------------------------------
+    n, k, n_out = 37, 43, 33
+    L, ptr, null = lib.lib, cn._lib.ptr, cn._lib.ptr(None)
+    xl, wl, bl, dyl = (torch.randn(*shape, generator=g) for shape in ((n, k), (n_out, k), (n_out,), (n, n_out)))
+    for relu in (0, 1):
+        y = torch.empty(n, n_out)
+        buf, nb = lib.scratch("cnr_linear_scratch_bytes", "cpu", n, k, n_out, 0)
+        lib.call("cnr_linear_forward", ptr(xl), n, k, ptr(wl), ptr(bl), n_out, relu, ptr(y), ptr(buf), nb, null)
+        save(f"linear.relu{relu}.y", y)
+        for with_db in (0, 1):
+            dx, dW, db = torch.empty(n, k), torch.empty(n_out, k), torch.empty(n_out) if with_db else None
+            buf, nb = lib.scratch("cnr_linear_scratch_bytes", "cpu", n, k, n_out, 1)
+            lib.call("cnr_linear_backward", ptr(xl), ptr(y), ptr(dyl), n, k, ptr(wl), n_out, relu, ptr(dx), ptr(dW), ptr(db), ptr(buf), nb, null)
+            save_dict(f"linear.relu{relu}.db{with_db}", dict(dx=dx, dW=dW, db=db))
+
+    # -- every *_bytes query of the caller-provided buffers, at the configurations built above ------------------------------------------------
+    sizes = []
+    for n in (5, 4096):
+        for ren in (r, r0, rb):
+            c = C.byref(ren._ccfg)
+            sizes += [L.cnr_ctx_bytes(c, n), L.cnr_bwd_scratch_bytes(c, n), L.cnr_infer_scratch_bytes(c, n), L.cnr_vertex_color_scratch_bytes(c, n)]
+            sizes += [fn(c, n, wg) for wg in (0, 1) for fn in (L.cnr_sdf_query_ctx_bytes, L.cnr_sdf_query_bwd_scratch_bytes)]
+        ncfg, n_feed = rb.nerf.config(), rb.rcfg.n_total + rb.n_outside
+        sizes += [L.cnr_background_ctx_bytes(C.byref(ncfg), n, n_feed), L.cnr_background_bwd_scratch_bytes(C.byref(ncfg), n, n_feed)]
+        sizes += [L.cnr_linear_scratch_bytes(n, k, n_out, backward) for backward in (0, 1)]
+    save("scratch_bytes", np.asarray(sizes, dtype=np.int64))
     print(f"{count[0]} arrays written to {out_dir}")
 
 
