@@ -138,22 +138,12 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
       const f4 v = sc4 < kEmb ? erows[pass] : z4;
       float mx = ws_absmax4(v);
       mx = cnr_max16(mx);
-      const float sc = chain_row_scale(mx);
-      if (sc4 < kEmb) {
-        f16x4 h1, h2;
-        float x;
-        x = v.x * sc; h1[0] = (_Float16)x; h2[0] = (_Float16)(x - (float)h1[0]);
-        x = v.y * sc; h1[1] = (_Float16)x; h2[1] = (_Float16)(x - (float)h1[1]);
-        x = v.z * sc; h1[2] = (_Float16)x; h2[2] = (_Float16)(x - (float)h1[2]);
-        x = v.w * sc; h1[3] = (_Float16)x; h2[3] = (_Float16)(x - (float)h1[3]);
-        unsigned char* dst = smem + row_l * CH_ALD + sc4 * 2;
-        *reinterpret_cast<f16x4*>(dst) = h1;
-        *reinterpret_cast<f16x4*>(dst + APLANE) = h2;
-      }
+      const float sc = split_row_scale(mx);
+      if (sc4 < kEmb) split_put4(v, sc, smem + row_l * CH_ALD + sc4 * 2, APLANE);
       if ((tid & 15) == 0) rs[row_l] = cnr_pow2_rcp(sc);
     }
     }
-    lds_barrier();
+    cnr_lds_barrier();
 
     for (int l = 0; l < c.nl; ++l) {
       VC_LANE_INDICES
@@ -259,7 +249,7 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
           if (half == 0) pm[(rt * 32 + pt) * 8 + wave] = both;
         }
       }
-      lds_barrier();   // partial maxima visible; every wave is done reading the planes of this layer's input
+      cnr_lds_barrier();   // partial maxima visible; every wave is done reading the planes of this layer's input
       if (!last) {
         if (tid < 128) *reinterpret_cast<f4*>(cwb + ((l + 1) & 1) * 512 + tid * 4) = cw_next;
 #pragma unroll
@@ -268,9 +258,9 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
           float mx = pm[row_l * 8];
 #pragma unroll
           for (int w = 1; w < WAVES; ++w) mx = fmaxf(mx, pm[row_l * 8 + w]);
-          const float sc = chain_row_scale(mx);
+          const float sc = split_row_scale(mx);
 #pragma unroll
-          for (int j = 0; j < CB; ++j) chain_put16(acc[j][rt], sc, smem + row_l * CH_ALD + (cbase + 32 * j) * 2, APLANE);
+          for (int j = 0; j < CB; ++j) split_put16(acc[j][rt], sc, smem + row_l * CH_ALD + (cbase + 32 * j) * 2, APLANE);
           if (wave == 0 && half == 0) rs[row_l] = cnr_pow2_rcp(sc);
         }
       } else {
@@ -283,7 +273,7 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
           if (grow < c.P) c.sdf_out[grow] = (sum + c.btop[0]) * c.top_scale;
         }
       }
-      lds_barrier();
+      cnr_lds_barrier();
     }
   }
 }

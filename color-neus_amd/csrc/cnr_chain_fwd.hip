@@ -37,10 +37,6 @@ namespace cnr {
 // every tile streams from L2: +0.85 ... 1.0 % of the step against plain stores, same bits (profiles/r06_ab_nt_saved_activations.txt)
 #define CH_SAVE_STORE(p_, v_) __builtin_nontemporal_store((v_), reinterpret_cast<f4*>(p_))
 
-
-// the scale a row's consumers get (LayerGemm::rs_out convention): 0 for an all-zero row, NaN for a non-finite one
-__device__ __forceinline__ float chain_rs_value(float mx, float sc) { return (mx > 0.0f && mx < 3.0e38f) ? sc : (mx == 0.0f ? 0.0f : __builtin_nanf("")); }
-
 template <int RT>
 __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainFwd c) {
   constexpr int T = 32 * RT;
@@ -119,18 +115,18 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
           const int row_l = pass * 32 + (tid >> 4);
           float mx = fmaxf(fmaxf(fmaxf(ws_absmax4(v0[pass]), ws_absmax4(v1[pass])), fmaxf(ws_absmax4(v2[pass]), ws_absmax4(v3[pass]))), ws_absmax4(vx[pass]));
           mx = cnr_max16(mx);
-          const float sc = chain_row_scale(mx);
+          const float sc = split_row_scale(mx);
           unsigned char* dst = smem + row_l * CH_ALD + sc4 * 2;
-          if (sc4 < ncol) chain_put4(v0[pass], sc, dst, APLANE);
-          if (64 + sc4 < ncol) chain_put4(v1[pass], sc, dst + 128, APLANE);
-          if (128 + sc4 < ncol) chain_put4(v2[pass], sc, dst + 256, APLANE);
-          if (192 + sc4 < ncol) chain_put4(v3[pass], sc, dst + 384, APLANE);
+          if (sc4 < ncol) split_put4(v0[pass], sc, dst, APLANE);
+          if (64 + sc4 < ncol) split_put4(v1[pass], sc, dst + 128, APLANE);
+          if (128 + sc4 < ncol) split_put4(v2[pass], sc, dst + 256, APLANE);
+          if (192 + sc4 < ncol) split_put4(v3[pass], sc, dst + 384, APLANE);
           if ((tid & 15) == 0) {
             rs[row_l] = cnr_pow2_rcp(sc); rsf[row_l] = sc;
-            if (S.rs_in != nullptr && row_l < rows_left) S.rs_in[tile0 + row_l] = chain_rs_value(mx, sc);
+            if (S.rs_in != nullptr && row_l < rows_left) S.rs_in[tile0 + row_l] = split_rs_value(mx, sc);
           }
         }
-        lds_barrier();
+        cnr_lds_barrier();
       }
 
       f32x16 acc1[1][RT];
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
       if (S.nkb_x > 0) {
         // ---- the extra input columns, staged over the main ones with the SAME row scale
         chain_wprime<1>(wr1, wr2, wlane, S.nkb_w, S.nkb_main, S.nkb_x);
-        lds_barrier();                                        // every wave is done reading the main segment
+        cnr_lds_barrier();                                        // every wave is done reading the main segment
 #pragma unroll
         for (int pass = 0; pass < RT; ++pass) {
           const int row_l = pass * 32 + (tid >> 4), sc4 = (tid & 15) * 4;
@@ -162,10 +158,10 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
             } else if (sc4 == 0) {
               v = *reinterpret_cast<const f4*>(rgbs + row_l * 4);
             }
-            chain_put4(v, rsf[row_l], smem + row_l * CH_ALD + sc4 * 2, APLANE);
+            split_put4(v, rsf[row_l], smem + row_l * CH_ALD + sc4 * 2, APLANE);
           }
         }
-        lds_barrier();
+        cnr_lds_barrier();
         if (!(CNR_ABLATION(c.dbg) & 2)) {
           if (S.nkb_x == 3) chain_mfma_blocks<RT, 1, 3>(acc1, wr1, wr2, Ab, APLANE, wlane, S.nkb_w, S.nkb_main);
           else if (S.nkb_x == 2) chain_mfma_blocks<RT, 1, 2>(acc1, wr1, wr2, Ab, APLANE, wlane, S.nkb_w, S.nkb_main);
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
           }
         }
       }
-      lds_barrier();   // partial maxima visible; every wave is done reading the planes of this step's input
+      cnr_lds_barrier();   // partial maxima visible; every wave is done reading the planes of this step's input
       if (tid < 128) *reinterpret_cast<f4*>(cwb + ((last_step ? 0 : s + 1) & 1) * 512 + tid * 4) = cw_next;
       if (!chain_end) {
         // ---- the next step's input planes (its extra segment, if it comes from the colour head, shares the row scale)
@@ -218,12 +214,12 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
 #pragma unroll
           for (int w = 1; w < 8; ++w) mx = fmaxf(mx, pm[row_l * 8 + w]);
           if (with_rgb) { const f4 g = *reinterpret_cast<const f4*>(rgbs + row_l * 4); mx = fmaxf(mx, ws_absmax4(g)); }
-          const float sc = chain_row_scale(mx);
-          chain_put16(acc[rt], sc, smem + row_l * CH_ALD + cbase * 2, APLANE);
+          const float sc = split_row_scale(mx);
+          split_put16(acc[rt], sc, smem + row_l * CH_ALD + cbase * 2, APLANE);
           if (wave == 0 && half == 0) {
             rs[row_l] = cnr_pow2_rcp(sc); rsf[row_l] = sc;
             const long grow = tile * T + row_l;
-            if (Sn.rs_in != nullptr && grow < P) Sn.rs_in[grow] = chain_rs_value(mx, sc);
+            if (Sn.rs_in != nullptr && grow < P) Sn.rs_in[grow] = split_rs_value(mx, sc);
           }
         }
       }
@@ -283,7 +279,7 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
       }
       if (chain_end) {
         const ChainFwdHead& H = S.head == 1 ? c.col_head : c.rel_head;
-        lds_barrier();
+        cnr_lds_barrier();
         if (tid < T) {
           const int row_l = tid;
           const long grow = tile * T + row_l;
@@ -326,7 +322,7 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
           }
         }
       }
-      lds_barrier();
+      cnr_lds_barrier();
     }
   }
 }
@@ -421,11 +417,11 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
         const int row_l = pass * 32 + (tid >> 4);
         float mx = ws_absmax4(x[pass]);
         mx = cnr_max16(mx);
-        const float sc = chain_row_scale(mx);
-        if (sc4 < kEmb) chain_put4(x[pass], sc, smem + row_l * CH_ALD + sc4 * 2, APLANE);
+        const float sc = split_row_scale(mx);
+        if (sc4 < kEmb) split_put4(x[pass], sc, smem + row_l * CH_ALD + sc4 * 2, APLANE);
         if ((tid & 15) == 0) rs[row_l] = cnr_pow2_rcp(sc);
       }
-      lds_barrier();
+      cnr_lds_barrier();
     }
     for (int l = 0; l < nsteps; ++l) {
       int tid = tid0;
@@ -526,7 +522,7 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
           if (last_hidden) { const float od = cnr_pair32_sum(rdot[rt]); if (half == 0) pd[(rt * 32 + pt) * 8 + wave] = od; }
         }
       }
-      lds_barrier();   // partial maxima / dots visible; every wave is done reading the planes of this step's input
+      cnr_lds_barrier();   // partial maxima / dots visible; every wave is done reading the planes of this step's input
       if (tid < 128) *reinterpret_cast<f4*>(cwb + tid * 4) = cw_next;
       if (!is_top) {
         float* rso = c.rs[l + 1];
@@ -536,11 +532,11 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
           float mx = pm[row_l * 8];
 #pragma unroll
           for (int w = 1; w < 8; ++w) mx = fmaxf(mx, pm[row_l * 8 + w]);
-          const float sc = chain_row_scale(mx);
-          chain_put16(acc[rt], sc, smem + row_l * CH_ALD + cbase * 2, APLANE);
+          const float sc = split_row_scale(mx);
+          split_put16(acc[rt], sc, smem + row_l * CH_ALD + cbase * 2, APLANE);
           if (wave == 0 && half == 0) {
             rs[row_l] = cnr_pow2_rcp(sc);
-            if (rso != nullptr && row_l < rows_left) rso[tile0 + row_l] = chain_rs_value(mx, sc);
+            if (rso != nullptr && row_l < rows_left) rso[tile0 + row_l] = split_rs_value(mx, sc);
           }
         }
         if (last_hidden && tid < T) {
@@ -551,7 +547,7 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
           if (tid < rows_left) v.sdf_out[tile0 + tid] = (sum + v.btop[0]) * v.top_scale;
         }
       }
-      lds_barrier();
+      cnr_lds_barrier();
     }
   }
 }

@@ -17,6 +17,7 @@
 #include "cnr_hip_util.h"
 #include "cnr_gemm_int.h"
 #include "cnr_gemm_fp32.h"
+#include "cnr_split.h"
 
 namespace cnr {
 
@@ -44,7 +45,7 @@ static void dispatch_layer_gemm(const LayerGemm& g, int nt, cnr_stream s) {
 }
 
 // Row scales for a launch that does not go through the weight-stationary kernel (debug switches, unusual shapes): same
-// definition as WS_PUT_TILE, one thread per row.  Slow path, kept only so that LayerGemm::rs_out is always honoured.
+// definition as the staging of the weight-stationary kernel (cnr_split.h), one thread per row.  Slow path, kept only so that LayerGemm::rs_out is always honoured.
 __global__ void row_scale_kernel(const LayerGemm g) {
   const long row = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long Pn = g.P_dev ? (long)*g.P_dev : g.P;
@@ -52,9 +53,7 @@ __global__ void row_scale_kernel(const LayerGemm g) {
   const int kpad = ((g.K + 15) >> 4) * 16;
   float mx = 0.0f;
   for (int c = 0; c < kpad; c += 4) mx = fmaxf(mx, ws_absmax4(view_eval4(g.A, row, c)));
-  float sc = mx == 0.0f ? 0.0f : __builtin_nanf("");   // 0: all-zero row, NaN: non-finite row
-  if (mx > 0.0f && mx < 3.0e38f) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sc = ldexpf(1.0f, 14 - e_); }
-  g.rs_out[row] = sc;
+  g.rs_out[row] = split_rs_value(mx, split_row_scale(mx));
 }
 
 void be_layer_gemm(const LayerGemm& g, cnr_stream s) {

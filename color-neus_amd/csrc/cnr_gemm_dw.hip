@@ -6,6 +6,7 @@
 #include "cnr_backend.h"
 #include "cnr_hip_util.h"
 #include "cnr_gemm_int.h"
+#include "cnr_split.h"
 
 namespace cnr {
 
@@ -400,14 +401,6 @@ static void launch_dw_bx(const DwGemm& g, int n0, int k0, cnr_stream s) {
 constexpr int DH_OPER = 2 * DX_PLANE;
 constexpr int DH_BUF = 2 * DH_OPER;
 
-// 2^G / sx for a power-of-two sx > 0 by exponent arithmetic (0 stays 0, NaN stays NaN, underflow flushes to 0)
-__device__ __forceinline__ float dh_yscale(float sx, int G) {
-  const unsigned bits = __float_as_uint(sx);
-  const int field = G - (int)((bits >> 23) & 0xff) + 254;      // biased exponent of 2^(G - log2 sx)
-  const float r = __uint_as_float((unsigned)(field < 1 ? 0 : (field > 254 ? 254 : field)) << 23);
-  return sx > 0.0f ? (field < 1 ? 0.0f : r) : sx;
-}
-
 template <int XK0, int YK0, int XK1, int YK1>
 __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, int n0, int k0) {
   DwGemm g = g_in;
@@ -425,15 +418,15 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
   const int nslab = nslab_pair * g.npairs;
   // exponent of this workgroup's slice of the point range: G = 1 + min log2(sx * sy) over its own points (both pairs, all-zero rows
   // excluded): no separate reduction launch, and a slice of small-magnitude points keeps its own dynamic range
-  int G = 0x7f7f7f7f;
+  int G = SPLIT_GBIG;
   {
     const int npts = nslab_pair * 16;
     auto scan = [&](const float* sxp, const float* syp) {   // (no run-time index into g: the struct must stay in registers)
       for (int i = tid; i < npts; i += 512) {
         const long pt = ((long)(i >> 4) * g.nchunk + chunk) * 16 + (i & 15);
         if (pt < p_end) {
-          const float a = sxp[pt], b = syp[pt];   // powers of two (or 0 / NaN): exponent = biased exponent field - 127
-          const int e = (int)((__float_as_uint(a) >> 23) & 0xff) + (int)((__float_as_uint(b) >> 23) & 0xff) - 254 + 1;
+          const float a = sxp[pt], b = syp[pt];   // powers of two (or 0 / NaN)
+          const int e = split_exp2_of_product(a, b) + 1;
           if (a > 0.0f && b > 0.0f && e < G) G = e;
         }
       }
@@ -449,7 +442,7 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
     for (int w = 0; w < 8; ++w) { const int o = red[w]; G = o < G ? o : G; }
     cnr_lds_barrier();
     G = __builtin_amdgcn_readfirstlane(G);                // (uniform: keep it in a scalar register)
-    if (G > 250 || G < -250) G = 0;                       // no point with two non-zero rows: everything is zero anyway
+    if (G >= SPLIT_GBIG) G = 0;                           // no point with two non-zero rows: everything is zero anyway
   }
 
   f32x16 acc[2][4];
@@ -508,15 +501,13 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
     }                                                                                      \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                        \
       float f_ = rsx[i];                                                                   \
-      if (is_y) f_ = dh_yscale(f_, G);                                                      \
+      if (is_y) f_ = split_yscale(f_, G);                                                    \
       v_[i].x *= f_; v_[i].y *= f_; v_[i].z *= f_; v_[i].w *= f_;                          \
     }                                                                                      \
     unsigned char* d_ = sdst + (buf_) * DH_BUF;                                            \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                        \
-      f16x4 h1, h2;                                                                        \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) { const float x_ = v_[i][j]; h1[i] = (_Float16)x_; h2[i] = (_Float16)(x_ - (float)h1[i]); } \
-      *reinterpret_cast<f16x4*>(d_ + j * DX_JREG) = h1;                                    \
-      *reinterpret_cast<f16x4*>(d_ + DX_PLANE + j * DX_JREG) = h2;                         \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {   /* column j of the 4 points */       \
+      const f4 c_ = {v_[0][j], v_[1][j], v_[2][j], v_[3][j]};                              \
+      split_store4(c_, d_ + j * DX_JREG, DX_PLANE);                                        \
     }                                                                                      \
   }
 
@@ -566,7 +557,8 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
 #undef DH_FINISH_
 
   // undo 2^G in two exact steps (G can exceed the fp32 exponent range of a single factor)
-  const float u1 = ldexpf(1.0f, -(G / 2)), u2 = ldexpf(1.0f, -(G - G / 2));
+  const SplitPow2 un = split_pow2(-G);
+  const float u1 = un.u1, u2 = un.u2;
   float* out = g.partial + chunk * (long)g.Npad * g.ldk;
 #pragma unroll
   for (int i = 0; i < 2; ++i)

@@ -45,7 +45,6 @@ constexpr int FD_OFF_T = FD_OFF_Y + 2 * FD_YBUF;
 constexpr int FD_OFF_INFO = FD_OFF_T + 4 * FD_TBYTES;   // [3 tiles][4 D waves] min log2(ss * se) of the rows a wave staged
 constexpr int FD_LDS = FD_OFF_INFO + 64;
 static_assert(FD_LDS <= 160 * 1024, "LDS budget of one CU");
-constexpr int FD_GBIG = 0x3f000000;              // "no point with two non-zero rows yet"
 
 // Round 6: BOTH operands of the weight-gradient MFMAs come out of row-major [point][column] f16 planes by the LDS transpose read
 // (ds_read_b64_tr_b16: a 16-lane group reads a [4 points][16 columns] block, 8 contiguous bytes per lane, and every lane receives one column of
@@ -55,13 +54,6 @@ constexpr int FD_GBIG = 0x3f000000;              // "no point with two non-zero 
 // stores removed).  The four rows of a block are points 4 apart: both row strides (528 B, 272 B) are 4 banks mod 64, so rows 4 points apart
 // sit 16 banks apart and the 2 x 4 x 4 eight-byte pieces of a 32-lane half cover the 64 banks exactly once.  Position q = 4 h + r of k group
 // kg in k16 block kb therefore holds point 16 kb + 4 r + 2 kg + h -- in both operands, which is all the MFMA needs.
-// 2^G / sx for a power-of-two sx > 0 by exponent arithmetic (0 stays 0, NaN stays NaN, underflow flushes to 0)
-__device__ __forceinline__ float fd_yscale(float sx, int G) {
-  const unsigned bits = __float_as_uint(sx);
-  const int field = G - (int)((bits >> 23) & 0xff) + 254;
-  const float r = __uint_as_float((unsigned)(field < 1 ? 0 : (field > 254 ? 254 : field)) << 23);
-  return sx > 0.0f ? (field < 1 ? 0.0f : r) : sx;
-}
 
 // the epilogue-side operand of 4 columns from the epilogue's side inputs (see DwFuse in cnr_views.h)
 template <int EK>
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     const f4 wsc = *reinterpret_cast<const f4*>(g.wscale + ecol);
     const f4 bias4 = epi_bias4(g.E, ecol);
     float* T = reinterpret_cast<float*>(smem + FD_OFF_T + wave * FD_TBYTES);
-    int G = FD_GBIG;
+    SplitBlockExp ge;   // the P waves follow the block exponent of the D waves one tile ahead (nothing accumulated here)
     f4 wr1 = {0.f, 0.f, 0.f, 0.f}, xacc = {0.f, 0.f, 0.f, 0.f};   // XR: column 256 of this lane's 4 weight rows; the extra row's sums
     float xb = 0.0f;
     if constexpr (XR == 2) {
@@ -161,7 +153,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
       {
         const int* qi = info + ab * 4;
         int m = qi[0]; m = qi[1] < m ? qi[1] : m; m = qi[2] < m ? qi[2] : m; m = qi[3] < m ? qi[3] : m;
-        if (m < FD_GBIG && m + 1 < G) G = m + 1;
+        ge.fold(m);
       }
       float zq[4] = {0.f, 0.f, 0.f, 0.f};                // XR == 2: A[row][256] of this lane's 4 rows (requested before the product, used after it)
       if constexpr (XR == 2) {
@@ -235,17 +227,10 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         }
         epi_finish4_sel<EK, GENF>(g.E, row, ecol, v, bias4, ern[q]);
         ern[q] = fetch_side(tn * FD_TP + rr, ecol);
-        const float ys = fd_yscale(ssr[rr], G);
+        const float ys = split_yscale(ssr[rr], ge.G);
         ep.x *= ys; ep.y *= ys; ep.z *= ys; ep.w *= ys;
         unsigned char* yrow = Yb + rr * FD_YLD + (wave * 32 + cc) * 2;
-        if (!(dbg & 2)) {
-          ws_f16x4 h1, h2;
-          h1[0] = (_Float16)ep.x; h1[1] = (_Float16)ep.y; h1[2] = (_Float16)ep.z; h1[3] = (_Float16)ep.w;
-          h2[0] = (_Float16)(ep.x - (float)h1[0]); h2[1] = (_Float16)(ep.y - (float)h1[1]);
-          h2[2] = (_Float16)(ep.z - (float)h1[2]); h2[3] = (_Float16)(ep.w - (float)h1[3]);
-          *reinterpret_cast<ws_f16x4*>(yrow) = h1;
-          *reinterpret_cast<ws_f16x4*>(yrow + FD_YPLANE) = h2;
-        }
+        if (!(dbg & 2)) split_store4(ep, yrow, FD_YPLANE);
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -330,7 +315,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     auto d_put = [&](int i, int ab, const RawTile& rt) {
       unsigned char* B = smem + ab * FD_ABUF;
       float* rs = reinterpret_cast<float*>(B + 2 * FD_APLANE);
-      int qmin = FD_GBIG;
+      int qmin = SPLIT_GBIG;
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         f4 v[4];
@@ -341,26 +326,24 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         }
         float mx = fmaxf(fmaxf(ws_absmax4(v[0]), ws_absmax4(v[1])), fmaxf(ws_absmax4(v[2]), ws_absmax4(v[3])));
         mx = cnr_max16(mx);
-        const bool valid = mx > 0.0f && mx < 3.0e38f;
-        float sc = 1.0f;
-        if (valid) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sc = ldexpf(1.0f, 14 - e_); }
+        const float sc = split_row_scale(mx);
         const int row_l = srow + 16 * p;
         unsigned char* dst = B + row_l * FD_ALD + scol * 2;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) ws_put4(v[q], sc, dst + 128 * q, FD_APLANE);
+        for (int q = 0; q < 4; ++q) split_put4(v[q], sc, dst + 128 * q, FD_APLANE);
         if (want_cs) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) { cs[q].x += v[q].x; cs[q].y += v[q].y; cs[q].z += v[q].z; cs[q].w += v[q].w; }
         }
-        const float ssv = valid ? sc : (mx == 0.0f ? 0.0f : __builtin_nanf(""));
+        const float ssv = split_rs_value(mx, sc);
         if ((dt & 15) == 0) {
           rs[row_l] = cnr_pow2_rcp(sc);
           rs[32 + row_l] = ssv;
           if (g.rs_out && half == 0) g.rs_out[FD_TILE(i) * FD_TP + row_l] = ssv;
         }
         const float se = rt.se[p];
-        if (valid && se > 0.0f) {
-          const int e = (int)((__float_as_uint(sc) >> 23) & 0xff) + (int)((__float_as_uint(se) >> 23) & 0xff) - 254;
+        if (split_row_valid(mx) && se > 0.0f) {
+          const int e = split_exp2_of_product(sc, se);
           qmin = e < qmin ? e : qmin;
         }
       }
@@ -395,25 +378,13 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         }
       }
     };
-    int Gd = FD_GBIG;
+    SplitBlockExp gd;
     // weight-gradient contribution of tile i (buffer abp): fold the tile's exponent into the running one first
     auto d_acc = [&](int i, int abp) {
       const int* qi = info + abp * 4;
       int mq = qi[0]; mq = qi[1] < mq ? qi[1] : mq; mq = qi[2] < mq ? qi[2] : mq; mq = qi[3] < mq ? qi[3] : mq;
       mq = __builtin_amdgcn_readfirstlane(mq);
-      if (mq < FD_GBIG && mq + 1 < Gd) {
-        if (Gd < FD_GBIG) {   // exact power-of-two rescale of what has been accumulated under the old exponent
-          const int dlt = mq + 1 - Gd;
-          const float u1 = ldexpf(1.0f, dlt / 2), u2 = ldexpf(1.0f, dlt - dlt / 2);
-#pragma unroll
-          for (int sb = 0; sb < 4; ++sb)
-#pragma unroll
-            for (int eb = 0; eb < 8; ++eb)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) acc[sb][eb][r] = acc[sb][eb][r] * u1 * u2;
-        }
-        Gd = mq + 1;
-      }
+      gd.fold(mq, acc);
       if (!(dbg & 1)) d_dw(i, abp);
     };
 
@@ -465,8 +436,8 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
 
     // ---- partial sums of this (range, half): undo 2^G in two exact steps; the transposed form goes through a per-wave LDS tile so that
     // both forms store 128-byte row pieces
-    if (Gd >= FD_GBIG) Gd = 0;
-    const float u1 = ldexpf(1.0f, -(Gd / 2)), u2 = ldexpf(1.0f, -(Gd - Gd / 2));
+    const SplitPow2 un = gd.undo();
+    const float u1 = un.u1, u2 = un.u2;
     float* X = reinterpret_cast<float*>(smem + wd * (32 * 33 * 4));
     // a lane holds dW[s = 16 sb + 4 kg + r][e = 16 eb + m] of each block.  Natural form: 64-byte row pieces; transposed form: 32 x 32 regions (2 x 2 blocks)
     // through the per-wave LDS tile so that both forms store whole 128-byte row pieces where they can

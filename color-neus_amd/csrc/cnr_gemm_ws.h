@@ -8,6 +8,7 @@
 #include "cnr_backend.h"
 #include "cnr_hip_util.h"
 #include "cnr_gemm_int.h"
+#include "cnr_split.h"
 
 namespace cnr {
 
@@ -32,17 +33,6 @@ constexpr int WS_THREADS = 512;
 constexpr int WS_TLD = 36;
 
 __device__ __forceinline__ float ws_dot4(const f4& a, const f4& b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-
-__device__ __forceinline__ void ws_put4(const f4& v, float sc, unsigned char* dst, int aplane) {
-  f16x4 h1, h2;
-  float x;
-  x = v.x * sc; h1[0] = (_Float16)x; h2[0] = (_Float16)(x - (float)h1[0]);
-  x = v.y * sc; h1[1] = (_Float16)x; h2[1] = (_Float16)(x - (float)h1[1]);
-  x = v.z * sc; h1[2] = (_Float16)x; h2[2] = (_Float16)(x - (float)h1[2]);
-  x = v.w * sc; h1[3] = (_Float16)x; h2[3] = (_Float16)(x - (float)h1[3]);
-  *reinterpret_cast<f16x4*>(dst) = h1;
-  *reinterpret_cast<f16x4*>(dst + aplane) = h2;
-}
 
 // VK / EK >= 0 pin the view / epilogue kind at compile time: the interpreted switches of cnr_views.h fold away and each
 // instantiation only allocates the registers its own prologue and epilogue need (-1 = generic, interpreted at run time).
@@ -138,14 +128,13 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
     const f4 v4 = (K17 && pv4) ? view_finish4(g.A, r4##S_, 256 + scol) : z4;      \
     float mx = fmaxf(fmaxf(fmaxf(ws_absmax4(v0), ws_absmax4(v1)), fmaxf(ws_absmax4(v2), ws_absmax4(v3))), ws_absmax4(v4)); \
     mx = cnr_max16(mx); \
-    float sc = 1.0f;                                                              \
-    if (mx > 0.0f && mx < 3.0e38f) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sc = ldexpf(1.0f, 14 - e_); } /* 2^e_ clamp: subnormal rows must not overflow the scale */ \
+    const float sc = split_row_scale(mx);                                         \
     unsigned char* dst = smem_b + (buf_) * abuf + srow * ald + scol * 2;          \
-    if (pv0) ws_put4(v0, sc, dst, aplane);                                        \
-    if (pv1) ws_put4(v1, sc, dst + 128, aplane);                                  \
-    if (pv2) ws_put4(v2, sc, dst + 256, aplane);                                  \
-    if (pv3) ws_put4(v3, sc, dst + 384, aplane);                                  \
-    if (K17 && pv4) ws_put4(v4, sc, dst + 512, aplane);                           \
+    if (pv0) split_put4(v0, sc, dst, aplane);                                     \
+    if (pv1) split_put4(v1, sc, dst + 128, aplane);                               \
+    if (pv2) split_put4(v2, sc, dst + 256, aplane);                               \
+    if (pv3) split_put4(v3, sc, dst + 384, aplane);                               \
+    if (K17 && pv4) split_put4(v4, sc, dst + 512, aplane);                        \
     float dsum_ = 0.0f;                                                           \
     if (WS_DOT && g.dot_w) {                                                                \
       dsum_ = (ws_dot4(v0, dw0) + ws_dot4(v1, dw1)) + (ws_dot4(v2, dw2) + ws_dot4(v3, dw3)); \
@@ -155,7 +144,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_kernel(const Laye
       reinterpret_cast<float*>(smem_b + (buf_) * abuf + 2 * aplane)[srow] = cnr_pow2_rcp(sc); \
       const long prow_ = WS_TILE(tile_) * WS_TP + srow;                                  \
       if (WS_DOT && g.dot_w && prow_ < Pn) g.dot_out[prow_] = (dsum_ + dot_b) * g.dot_scale; \
-      if (g.rs_out && prow_ < Pn) g.rs_out[prow_] = (mx > 0.0f && mx < 3.0e38f) ? sc : (mx == 0.0f ? 0.0f : __builtin_nanf("")); /* 0: all-zero row, NaN: non-finite row (must keep poisoning the weight gradient) */ \
+      if (g.rs_out && prow_ < Pn) g.rs_out[prow_] = split_rs_value(mx, sc); \
     }                                                                             \
   }
 #define WS_PUT_TILE(buf_, tile_) WS_PUT_SET(buf_, tile_, a)
@@ -430,13 +419,12 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
     const f4 v3 = view_finish4(g.A, r3##S_, 192 + scol);                          \
     float mx = fmaxf(fmaxf(ws_absmax4(v0), ws_absmax4(v1)), fmaxf(ws_absmax4(v2), ws_absmax4(v3))); \
     mx = cnr_max16(mx); \
-    float sc = 1.0f;                                                              \
-    if (mx > 0.0f && mx < 3.0e38f) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sc = ldexpf(1.0f, 14 - e_); } \
+    const float sc = split_row_scale(mx);                                         \
     unsigned char* dst = smem_b + (buf_) * abuf + srow * ald + scol * 2;          \
-    ws_put4(v0, sc, dst, aplane);                                                 \
-    ws_put4(v1, sc, dst + 128, aplane);                                           \
-    ws_put4(v2, sc, dst + 256, aplane);                                           \
-    ws_put4(v3, sc, dst + 384, aplane);                                           \
+    split_put4(v0, sc, dst, aplane);                                              \
+    split_put4(v1, sc, dst + 128, aplane);                                        \
+    split_put4(v2, sc, dst + 256, aplane);                                        \
+    split_put4(v3, sc, dst + 384, aplane);                                        \
     float dsum_ = 0.0f;                                                           \
     if (EK == EK_SDF_TOP && g.dot_w) {                                            \
       dsum_ = (ws_dot4(v0, dw0) + ws_dot4(v1, dw1)) + (ws_dot4(v2, dw2) + ws_dot4(v3, dw3)); \
@@ -446,7 +434,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
       reinterpret_cast<float*>(smem_b + (buf_) * abuf + 2 * aplane)[srow] = cnr_pow2_rcp(sc); \
       const long prow_ = WSS_TILE((tile_) < tlast ? (tile_) : tlast) * WS_TP + srow; \
       if (EK == EK_SDF_TOP && g.dot_w) g.dot_out[prow_] = (dsum_ + dot_b) * g.dot_scale; \
-      if (g.rs_out) g.rs_out[prow_] = (mx > 0.0f && mx < 3.0e38f) ? sc : (mx == 0.0f ? 0.0f : __builtin_nanf("")); \
+      if (g.rs_out) g.rs_out[prow_] = split_rs_value(mx, sc); \
     }                                                                             \
     __builtin_amdgcn_sched_barrier(0);                                            \
     __builtin_amdgcn_s_setprio(0);                                                \
@@ -621,7 +609,6 @@ __global__ __launch_bounds__(WS_THREADS, 1) void layer_gemm_ws_stream_kernel(con
 // a product over points, which is all the MFMA needs.  `src`: the lane's piece for h = 0 (point row kb * 16 + 2 kg + 4 ((lane & 15) >> 2), columns
 // base + (lane & 16) + 4 (lane & 3)); the piece for h = 1 lies one point row (ld bytes) below.
 typedef short ws_s16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ws_f16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f16x8 ws_tr8(const unsigned char* src, int ld) {
   typedef __attribute__((address_space(3))) ws_s16x4* lds_s16x4;
   const ws_s16x4 h0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(src));

@@ -19,6 +19,7 @@
 #include "cnr_loss.h"
 #include "cnr_bodies.h"
 #include "cnr_hip_util.h"
+#include "cnr_split.h"
 
 namespace cnr {
 
@@ -632,14 +633,11 @@ __device__ __forceinline__ void split_planes_row(const float* src, int ld, unsig
   for (int k = threadIdx.x; k < ld; k += 64) mx = fmaxf(mx, fabsf(row[k]));
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-  float sc = 1.0f;
-  if (mx > 0.0f && mx < 3.0e38f) { int e; (void)frexpf(mx, &e); if (e < -100) e = -100; sc = ldexpf(1.0f, 14 - e); }
+  const float sc = split_row_scale(mx);
   for (int k = threadIdx.x; k < ld; k += 64) {
-    const float x = row[k] * sc;
-    const _Float16 h1 = (_Float16)x;
-    const _Float16 h2 = (_Float16)(x - (float)h1);
-    planes[(long)r * ld + k] = __builtin_bit_cast(unsigned short, h1);
-    planes[plane_stride + (long)r * ld + k] = __builtin_bit_cast(unsigned short, h2);
+    const SplitF16 h = split_f16(row[k] * sc);
+    planes[(long)r * ld + k] = __builtin_bit_cast(unsigned short, h.hi);
+    planes[plane_stride + (long)r * ld + k] = __builtin_bit_cast(unsigned short, h.lo);
   }
   if (threadIdx.x == 0) inv_scale[r] = 1.0f / sc;
 }

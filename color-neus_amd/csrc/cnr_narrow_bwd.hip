@@ -22,7 +22,7 @@ namespace cnr {
 
 constexpr int NB_ALD = 256 * 2 + 16;
 constexpr int NB_APLANE = WS_TP * NB_ALD;
-constexpr int NB_ABUF = 2 * NB_APLANE + 256;      // two planes + rs[32] (1 / ss) + e[32] (int: log2(ss sy); NB_EBIG: the row contributes nothing)
+constexpr int NB_ABUF = 2 * NB_APLANE + 256;      // two planes + rs[32] (1 / ss) + e[32] (int: log2(ss sy); SPLIT_GBIG: the row contributes nothing)
 constexpr int NB_YCOLS = 48;
 constexpr int NB_YLD = 144;                       // bytes per POINT row of one Y plane (row-major [point][column], round 6): 48 columns x 2 B + 48 -- 36 dwords = 4 banks mod 16 (ws_tr8)
 constexpr int NB_YPLANE = WS_TP * NB_YLD;
@@ -34,7 +34,6 @@ constexpr int NB_OFF_W = NB_OFF_F + 8 * 64;
 constexpr int NB_WPLANE = NB_YCOLS * NB_ALD;      // W^T planes: 48 rows (input columns) x 256
 constexpr int NB_LDS_NODX = NB_OFF_W;
 constexpr int NB_LDS_DX = NB_OFF_W + 2 * NB_WPLANE;
-constexpr int NB_EBIG = 0x3f000000;
 static_assert(NB_LDS_DX <= 160 * 1024, "LDS budget of one CU");
 
 // DX: the input-side product (needs Wp); DW: the weight / bias gradient (needs Y, partial); SIG: X is the view softplus100'(X) * Xb (the end of the
@@ -121,31 +120,22 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
     float mx = fmaxf(fmaxf(ws_absmax4(v[0]), ws_absmax4(v[1])), fmaxf(ws_absmax4(v[2]), ws_absmax4(v[3])));
     float my = ws_absmax4(y);
     mx = cnr_max16(mx); my = cnr_max16(my);
-    const bool vx = mx > 0.0f && mx < 3.0e38f, vy = my > 0.0f && my < 3.0e38f;
-    float sx = 1.0f, sy = 1.0f;
-    if (vx) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sx = ldexpf(1.0f, 14 - e_); }
-    if (vy) { int e_; (void)frexpf(my, &e_); if (e_ < -100) e_ = -100; sy = ldexpf(1.0f, 14 - e_); }
+    const float sx = split_row_scale(mx), sy = split_row_scale(my);
     unsigned char* B = smem_n + buf * NB_ABUF;
     unsigned char* dst = B + srow * NB_ALD + scol * 2;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) ws_put4(v[q], sx, dst + 128 * q, NB_APLANE);
+    for (int q = 0; q < 4; ++q) split_put4(v[q], sx, dst + 128 * q, NB_APLANE);
     if (DW && ylive) {
-      unsigned char* yb = smem_n + NB_OFF_Y + buf * NB_YBUF + srow * NB_YLD + scol * 2;
-      const float ya[4] = {y.x * sy, y.y * sy, y.z * sy, y.w * sy};
-      ws_f16x4 h1, h2;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { h1[j] = (_Float16)ya[j]; h2[j] = (_Float16)(ya[j] - (float)h1[j]); }
-      *reinterpret_cast<ws_f16x4*>(yb) = h1;
-      *reinterpret_cast<ws_f16x4*>(yb + NB_YPLANE) = h2;
+      split_put4(y, sy, smem_n + NB_OFF_Y + buf * NB_YBUF + srow * NB_YLD + scol * 2, NB_YPLANE);
     }
     if ((tid & 15) == 0) {
       float* rs = reinterpret_cast<float*>(B + 2 * NB_APLANE);
       rs[srow] = cnr_pow2_rcp(sx);
       // a row with a zero operand contributes nothing (its planes are zero); a non-finite row keeps factor 1 so that it poisons the sums
       const bool nonfin = !(mx < 3.0e38f) || !(my < 3.0e38f);
-      int e = NB_EBIG;
-      if (vx && vy) e = (int)((__float_as_uint(sx) >> 23) & 0xff) + (int)((__float_as_uint(sy) >> 23) & 0xff) - 254;
-      if (DW) reinterpret_cast<int*>(rs)[32 + srow] = nonfin ? -NB_EBIG : e;
+      int e = SPLIT_GBIG;
+      if (split_row_valid(mx) && split_row_valid(my)) e = split_exp2_of_product(sx, sy);
+      if (DW) reinterpret_cast<int*>(rs)[32 + srow] = nonfin ? -SPLIT_GBIG : e;
     }
   };
 
@@ -217,11 +207,11 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
     if constexpr (!DW) return;
     // ---- dW of this tile: rows c0 .. c0 + 31
     const int e_l = er[m];
-    int Gt = e_l == -NB_EBIG ? NB_EBIG - 1 : e_l;        // (non-finite rows do not steer the exponent ...)
+    int Gt = e_l == -SPLIT_GBIG ? SPLIT_GBIG - 1 : e_l;        // (non-finite rows do not steer the exponent ...)
     Gt = cnr_pair16_min(cnr_min16(Gt));   // (min over the 32 lanes of a half: DPP row moves + one row swap)
     Gt = __builtin_amdgcn_readfirstlane(Gt);
-    if (Gt == NB_EBIG - 1) Gt = 0;                       // (... but a tile that has nothing else still has to carry them into the sums)
-    if (Gt < NB_EBIG) {
+    if (Gt == SPLIT_GBIG - 1) Gt = 0;                       // (... but a tile that has nothing else still has to carry them into the sums)
+    if (Gt < SPLIT_GBIG) {
       f32x16 tacc[2];
 #pragma unroll
       for (int b = 0; b < 2; ++b)
@@ -233,8 +223,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
       unsigned short* fb = reinterpret_cast<unsigned short*>(smem_n + NB_OFF_F + wave * 64);
       {
         const int d = Gt - e_l;                          // <= 0 for live rows
-        unsigned short bits = (e_l == NB_EBIG || d < -24) ? (unsigned short)0 : d < -14 ? (unsigned short)(1 << (d + 24)) : (unsigned short)((15 + d) << 10);
-        if (e_l == -NB_EBIG) bits = (unsigned short)(15 << 10);
+        unsigned short bits = (e_l == SPLIT_GBIG || d < -24) ? (unsigned short)0 : d < -14 ? (unsigned short)(1 << (d + 24)) : (unsigned short)((15 + d) << 10);
+        if (e_l == -SPLIT_GBIG) bits = (unsigned short)(15 << 10);
         if (lane < 32) fb[ws_kslot(lane)] = bits;   // (in the k order of the transpose-read fragments)
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -263,11 +253,11 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
           tacc[cb] = cacc;
         }
       }
-      const float u1 = ldexpf(1.0f, -(Gt / 2)), u2 = ldexpf(1.0f, -(Gt - Gt / 2));
+      const SplitPow2 un = split_pow2(-Gt);
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) tot[b][r] = fmaf(tacc[b][r] * u1, u2, tot[b][r]);
+        for (int r = 0; r < 16; ++r) tot[b][r] = fmaf(tacc[b][r] * un.u1, un.u2, tot[b][r]);
     }
   };
   // pairs of tiles: every path through the loop body issues the same loads in the same order, so the compiler's count of what is in flight

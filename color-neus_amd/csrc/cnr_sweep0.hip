@@ -29,13 +29,6 @@ constexpr int S0_YBUF = 2 * S0_YPLANE;             // per wave
 constexpr int S0_OFF_T = 2 * S0_ABUF;
 constexpr int S0_OFF_Y = S0_OFF_T + 8 * 32 * WS_TLD * 4;
 constexpr int S0_LDS = S0_OFF_Y + 8 * S0_YBUF;
-constexpr int S0_GBIG = 0x3f000000;
-
-__device__ __forceinline__ float s0_yscale(float sx, int G) {   // 2^G / sx for a power-of-two sx > 0 (exponent arithmetic; underflow flushes to 0)
-  const unsigned bits = __float_as_uint(sx);
-  const int field = G - (int)((bits >> 23) & 0xff) + 254;
-  return field < 1 ? 0.0f : __uint_as_float((unsigned)(field > 254 ? 254 : field) << 23);
-}
 
 __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGemm g, float* partial, int ldk, int tiles_per_wg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
@@ -79,16 +72,14 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     const f4 v = (pv && prow < Pn) ? sraw : z4;
     float mx = ws_absmax4(v);
     mx = cnr_max16(mx);
-    const bool valid = mx > 0.0f && mx < 3.0e38f;
-    float sc = 1.0f;
-    if (valid) { int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100; sc = ldexpf(1.0f, 14 - e_); }
+    const float sc = split_row_scale(mx);
     unsigned char* B = smem_s + buf * S0_ABUF;
     // every column the product loop reads (S0_NKB k16 blocks) is written: columns in [kpad, 48) of a K <= 32 layer get zeros, not whatever
     // an earlier kernel left in LDS (NaN / Inf bit patterns times the zero weights of those blocks would poison the accumulators)
-    if (scol < S0_NKB * 16) ws_put4(v, sc, B + srow * S0_ALD + scol * 2, S0_APLANE);
+    if (scol < S0_NKB * 16) split_put4(v, sc, B + srow * S0_ALD + scol * 2, S0_APLANE);
     if ((tid & 15) == 0) {
       float* rs = reinterpret_cast<float*>(B + 2 * S0_APLANE);
-      const float ssv = valid ? sc : (mx == 0.0f ? 0.0f : __builtin_nanf(""));
+      const float ssv = split_rs_value(mx, sc);
       rs[srow] = cnr_pow2_rcp(sc);
       rs[32 + srow] = ssv;
       if (g.rs_out && prow < Pn) g.rs_out[prow] = ssv;
@@ -111,7 +102,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dacc[i][r] = 0.0f;
-  int G = S0_GBIG;
+  SplitBlockExp ge;
 
   if (n > 0) {
     s_fetch(0);
@@ -152,7 +143,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     __builtin_amdgcn_wave_barrier();
     // ---- epilogue (same arithmetic as epi_finish4_plain<EK_SWEEP>) + the pair's n-side operand u = sp'(z) v
     f4 u[4];
-    int qmin = S0_GBIG;
+    int qmin = SPLIT_GBIG;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int rr = (lane >> 3) + 8 * q, cc = (lane & 7) * 4;
@@ -177,41 +168,24 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
       float mx = ws_absmax4(u[q]);
       mx = cnr_max8(mx);   // (the 8 lanes of a row piece: DPP moves, not LDS-crossbar shuffles)
       const float ss = ssr[rr];
-      if (mx > 0.0f && mx < 3.0e38f && ss > 0.0f) {
-        int e_; (void)frexpf(mx, &e_); if (e_ < -100) e_ = -100;
-        const int e = (int)((__float_as_uint(ss) >> 23) & 0xff) - 127 + 14 - e_;   // log2(ss * se)
+      if (split_row_valid(mx) && ss > 0.0f) {
+        const int e = split_exp2_of_product(ss, split_row_scale(mx));   // log2(ss * se)
         qmin = e < qmin ? e : qmin;
       }
     }
     e_fetch(i + 1);
     qmin = cnr_pair32_min(cnr_pair16_min(cnr_ror8_min(qmin)));
     qmin = __builtin_amdgcn_readfirstlane(qmin);
-    if (qmin < S0_GBIG && qmin + 1 < G) {
-      if (G < S0_GBIG) {
-        const int dlt = qmin + 1 - G;
-        const float u1 = ldexpf(1.0f, dlt / 2), u2 = ldexpf(1.0f, dlt - dlt / 2);
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) dacc[b][r] = dacc[b][r] * u1 * u2;
-      }
-      G = qmin + 1;
-    }
+    ge.fold(qmin, dacc);
     // ---- u' = u * 2^G / ss, split hi / lo, row-major ([point][column], one 8-byte store per plane) into this wave's strip
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int rr = (lane >> 3) + 8 * q, cc = (lane & 7) * 4;
       const float ss = ssr[rr];
-      const float ys = ss > 0.0f ? s0_yscale(ss, G) : ss;   // (0 for an all-zero cbar row, NaN for a non-finite one)
+      const float ys = split_yscale(ss, ge.G);   // (0 for an all-zero cbar row, NaN for a non-finite one)
       f4 e = u[q];
       e.x *= ys; e.y *= ys; e.z *= ys; e.w *= ys;
-      unsigned char* yrow = Yw + rr * S0_YLD + cc * 2;
-      ws_f16x4 h1, h2;
-      h1[0] = (_Float16)e.x; h1[1] = (_Float16)e.y; h1[2] = (_Float16)e.z; h1[3] = (_Float16)e.w;
-      h2[0] = (_Float16)(e.x - (float)h1[0]); h2[1] = (_Float16)(e.y - (float)h1[1]);
-      h2[2] = (_Float16)(e.z - (float)h1[2]); h2[3] = (_Float16)(e.w - (float)h1[3]);
-      *reinterpret_cast<ws_f16x4*>(yrow) = h1;
-      *reinterpret_cast<ws_f16x4*>(yrow + S0_YPLANE) = h2;
+      split_store4(e, Yw + rr * S0_YLD + cc * 2, S0_YPLANE);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -247,8 +221,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     cnr_lds_barrier();
   }
   // ---- partial sums of this range: rows c0 .. c0 + 31 of [Npad = 256][ldk], every slot written in full
-  if (G >= S0_GBIG) G = 0;
-  const float u1 = ldexpf(1.0f, -(G / 2)), u2 = ldexpf(1.0f, -(G - G / 2));
+  const SplitPow2 un = ge.undo();
+  const float u1 = un.u1, u2 = un.u2;
   float* out = partial + (long)blockIdx.x * 256 * ldk;
   const int m = lane & 31, kg = lane >> 5;
 #pragma unroll

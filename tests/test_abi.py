@@ -77,6 +77,31 @@ def test_the_library_reads_the_environment_in_one_place():
     assert "static constexpr int ws_kinds" in hdr and "#ifdef CNR_TUNING" in hdr
 
 
+def test_the_split_f16_rule_has_one_definition():
+    """The row scale, the hi / lo split, 2^G / sx and the block-exponent bookkeeping of the split-f16 products live in csrc/cnr_split.h alone: no other
+    kernel source calls frexpf / ldexpf or defines a *_yscale / *_row_scale function of its own, and the LDS-only barrier has one definition."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    assert os.path.isfile(os.path.join(csrc, "cnr_split.h"))
+    libm, defs, barriers = [], [], []
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, fn)).read()
+        if re.search(r"\b\w*lds_barrier\s*\(\s*\)\s*\{", text):
+            barriers.append(fn)
+        if fn == "cnr_split.h":
+            continue
+        for i, line in enumerate(text.split("\n")):
+            code = line.split("//")[0]
+            if re.search(r"\b(frexpf|ldexpf)\s*\(", code):
+                libm.append((fn, i + 1))
+            if re.search(r"\b(float|int|void|bool)\s+\w*(_yscale|_row_scale)\s*\(", code):
+                defs.append((fn, i + 1))
+    assert not libm, libm
+    assert not defs, defs
+    assert barriers == ["cnr_hip_util.h"], barriers
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
         _lib.RenderLibrary(str(tmp_path / "libcolorneus_hip.so"))

@@ -111,3 +111,58 @@ def test_linear_op_emu():
 @pytest.mark.gpu
 def test_linear_op_hip():
     _check(None, "cuda:0", [1, 33, 1280, 5000])
+
+
+# (k, n_out): the split-f16 stream form of the layer kernel, a narrow input, K beyond 256
+SCALE_SHAPES = [(256, 256), (84, 256), (272, 224)]
+
+
+def _check_scale_rule(library, device):
+    """The row scale of the split-f16 arithmetic is an exact power of two and is undone exactly, so multiplying a row of the input by 2^k multiplies
+    the row of the output by 2^k to the bit -- a property of the design, not a tolerance -- and an all-zero row gives an exactly zero row.  Rows that
+    are zero in either operand contribute exactly nothing to the weight gradient, which therefore keeps the file's 2e-5 of the tensor's maximum
+    against float64 autograd with a third of the rows zeroed in each operand (both, only x, only dy, neither)."""
+    import color_neus_amd as cn
+    lib = cn.load_library(library)
+    g = torch.Generator().manual_seed(1)
+    for n in (33, 1280):   # a ragged last tile; several tiles
+        rows = torch.arange(n)
+        zx, zy = rows % 3 == 0, (rows % 6 == 0) | (rows % 6 == 1)
+        for k, n_out in SCALE_SHAPES:
+            x = torch.randn(n, k, generator=g)
+            dy = torch.randn(n, n_out, generator=g)
+            x[zx] = 0.0
+            dy[zy] = 0.0
+            w = torch.randn(n_out, k, generator=g) / k ** 0.5
+            b = torch.randn(n_out, generator=g) * 0.1
+            s = torch.ldexp(torch.ones(n), torch.randint(-40, 41, (n,), generator=g)).unsqueeze(1)   # 2^k_i, k_i in [-40, 40]
+            x, dy, w, b, s = x.to(device), dy.to(device), w.to(device).requires_grad_(True), b.to(device).requires_grad_(True), s.to(device)
+
+            def run(xin, dyin, bias):
+                xin = xin.clone().requires_grad_(True)
+                y = HipLinear.apply(lib, xin, w, bias, False)
+                return (y.detach(),) + torch.autograd.grad(y, [xin, w] + ([bias] if bias is not None else []), dyin)
+
+            y0, dx0, _ = run(x, dy, None)
+            y1, _, _ = run(x * s, dy, None)
+            _, dx1, _ = run(x, dy * s, None)
+            assert torch.equal(y1, y0 * s), (n, k, n_out, "y", float((y1 - y0 * s).abs().max()))
+            assert torch.equal(dx1, dx0 * s), (n, k, n_out, "dx", float((dx1 - dx0 * s).abs().max()))
+            assert bool((y0[zx.to(device)] == 0).all()) and bool((y0[~zx.to(device)] != 0).any()), (n, k, n_out, "zero rows of y")
+            assert bool((dx0[zy.to(device)] == 0).all()) and bool((dx0[~zy.to(device)] != 0).any()), (n, k, n_out, "zero rows of dx")
+            _, _, hw, hb = run(x, dy, b)
+            ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
+            gw, gb = torch.autograd.grad(ref, [w, b], dy.double())
+            for name, a, r in (("dW", hw, gw), ("db", hb, gb)):
+                err = float((a.double() - r).abs().max()) / max(float(r.abs().max()), 1e-30)
+                assert err < 2e-5, (n, k, n_out, name, err)
+
+
+@pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
+def test_scale_rule_is_exact_emu():
+    _check_scale_rule(N.EMU_LIB, "cpu")
+
+
+@pytest.mark.gpu
+def test_scale_rule_is_exact_hip():
+    _check_scale_rule(None, "cuda:0")
