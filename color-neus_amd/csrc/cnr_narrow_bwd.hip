@@ -288,12 +288,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
   }
 }
 
-int be_narrow_bwd_slots(long P) {
-  const long ntiles = (P + WS_TP - 1) / WS_TP;
-  if (ntiles <= 0) return 0;
-  const long tpw = (ntiles + 255) / 256;
-  return (int)((ntiles + tpw - 1) / tpw);
-}
+static_assert(WS_TP == kCuTilePoints, "cu_tile_slots counts this kernel's tiles");
+int be_narrow_bwd_slots(long P) { return cu_tile_slots(P); }
 
 bool be_narrow_bwd_ok(const NarrowBwd& p) {
   // debugging aid: narrow layer launch + weight-gradient launch as before.  Only the BACKWARD forms (those with a weight gradient): the
@@ -311,9 +307,8 @@ bool be_narrow_bwd_ok(const NarrowBwd& p) {
 }
 
 void be_narrow_bwd(const NarrowBwd& p, cnr_stream s) {
-  const long ntiles = (p.P + WS_TP - 1) / WS_TP;
-  const long tpw = (ntiles + 255) / 256;
-  const int grid = be_narrow_bwd_slots(p.P);
+  const long tpw = tiles_per_workgroup(p.P);
+  const int grid = cu_tile_slots(p.P);
   static DeviceOnce attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&narrow_bwd_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);

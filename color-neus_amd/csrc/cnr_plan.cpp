@@ -503,7 +503,10 @@ static void layout_ctx(Model& m, long R, Arena& a, Ctx& x) {
 // region_floats over its layers and places the pool; the launch code takes the regions in its own order, and take refuses to leave the
 // pool.  Several launches may fill consecutive slot groups of one region (SDF layers: value pair | gradient-chain pair, each either fused
 // into its layer launch or a separate GEMM); finish queues the one reduction over all of them.  Only the group at slot 0 carries column
-// sums.  How many slots a layer gets is the caller's policy (region_slots, dw_chunks).
+// sums.  How many slots a layer gets is the caller's policy (region_slots, dw_chunks).  Who fills which slot group is decided by the
+// callers' plans before they take a region: plan_sdf_backward (SdfBwdPlan: per SDF layer the producer of each pair, value_slots and
+// grad_slots with the gradient group at offset value_slots, checked once against region_slots), plan_stack_layer (a ReLU-stack layer) and
+// narrow_pass_ok (a narrow-input layer).  The execution code reads the plan and never re-derives a slot count.
 // ------------------------------------------------------------------------------------------------
 struct DwRegion { float* part = nullptr; float* csum = nullptr; };   // (part == nullptr: refused by DwPool::take)
 struct DwPool {
@@ -596,8 +599,7 @@ static void bwd_slots(long P, Bwd& b) {
   b.chunk_pts = round_up((int)((P + b.nchunk - 1) / b.nchunk), 16);
   b.fslots = fdw_slots(P);
   b.cap_slots = b.fslots + (b.nchunk > b.fslots ? b.nchunk : b.fslots);   // a fused pair + either a second fused pair or a separate GEMM over nchunk slots
-  const long ntiles = (P + 31) / 32, tpw = (ntiles + 255) / 256;
-  b.cu_slots = ntiles > 0 ? (int)((ntiles + tpw - 1) / tpw) : 0;
+  b.cu_slots = cu_tile_slots(P);
 }
 
 // The SDF half of the backward scratch (sdf_backward: render backward and point-query backward), as the groups between which the render
@@ -1216,14 +1218,15 @@ static bool strip_bwd_ok(const Lin& q, const LayerGemm& g, const DwGemm& d) {
          (g.E.kind == EK_RELU_MASK || g.E.kind == EK_SPLIT) && g.E.split == 256 && g.E.bias == nullptr &&
          d.Y[0].kind == VK_DIRECT && d.Y[0].scale == 1.0f && d.npairs == 1;
 }
-// narrows g to its 256 main columns and returns the strip launch (to be issued after the main launches; then DwPool::strip_columns_of_last_finish)
-static StripBwd take_strips(const Lin& q, LayerGemm& g, const DwGemm& d, const DwRegion& r, const Bwd& b) {
+// narrows g to its 256 main columns and returns the strip launch, complete but for the region (to be issued after the main launches; then
+// DwPool::strip_columns_of_last_finish)
+static StripBwd take_strips(const Lin& q, LayerGemm& g, const DwGemm& d, const Bwd& b) {
   StripBwd sb;
   sb.dout = g.A.a; sb.ldo = g.A.lda; sb.P = g.P; sb.nt = q.k_int - 256; sb.Wt = q.Wt; sb.ldwt = q.ldwt;
   sb.tail = g.E.o2 ? g.E.o2 + (g.E.kind == EK_SPLIT ? g.E.o2_off : 0) : nullptr; sb.ldt = g.E.ld2;
   sb.tail_scale = g.E.kind == EK_SPLIT ? g.E.scale : 1.0f;
   sb.y = d.Y[0].a + 256; sb.ldy = d.Y[0].lda;
-  sb.partial = r.part; sb.npad = q.npad; sb.ldk = q.ldw; sb.nslots = b.nchunk;
+  sb.npad = q.npad; sb.ldk = q.ldw; sb.nslots = b.nchunk;   // (partial: the layer's region, once it is taken)
   g.N = 256; g.E.n_out = 256; g.E.o2 = nullptr;
   return sb;
 }
@@ -1233,17 +1236,6 @@ static bool head_bwd_ok(const Lin& q, const LayerGemm& g) {
   return head_bwd_static_ok(q, g.E.ldaux) && (g.E.ld1 & 3) == 0 && g.A.kind == VK_DIRECT && (g.A.lda & 3) == 0 && g.E.kind == EK_RELU_MASK &&
          g.E.split >= q.k_int && g.E.aux != nullptr && g.E.o1 != nullptr;
 }
-static int run_head_bwd(const Lin& q, const LayerGemm& g, Bwd& b, const float* const* params, float* const* dparams, cnr_stream s) {
-  const DwRegion r = b.dw.take(q, region_slots(q, b));
-  if (!r.part) return -1;
-  HeadBwd h;
-  h.dtop = g.A.a; h.ldt = g.A.lda; h.aux = g.E.aux; h.ldaux = g.E.ldaux; h.W = q.W; h.ldw = q.ldw; h.n = q.n; h.K = q.k_int; h.P = g.P;
-  h.dout = g.E.o1; h.ldo = g.E.ld1; h.partial = r.part; h.colsum = r.csum; h.npad = q.npad; h.ldk = q.ldw; h.nslots = b.nchunk;
-  be_head_bwd(h, s);
-  b.dw.finish(q, r, b.nchunk, b.nchunk, params, dparams);
-  return 0;
-}
-
 // THE plain weight gradient of a layer: a region of cap slots, one GEMM of g's operand pairs over its first nchunk slots, the reduction queued
 static int plain_dw(DwPool& pool, const Lin& q, DwGemm& g, int cap, int nchunk, const float* const* params, float* const* dparams, cnr_stream s) {
   const DwRegion r = pool.take(q, cap);
@@ -1252,78 +1244,102 @@ static int plain_dw(DwPool& pool, const Lin& q, DwGemm& g, int cap, int nchunk, 
   pool.finish(q, r, nchunk, nchunk, params, dparams);
   return 0;
 }
-static int run_dw(const Lin& q, DwGemm& g, Bwd& b, const float* const* params, float* const* dparams, cnr_stream s) {
-  return plain_dw(b.dw, q, g, region_slots(q, b), b.nchunk, params, dparams, s);
-}
+
+// Walk direction (DwFuse::rev) of the fused launch that `pos` launches of its chain precede: the launches of a chain alternate, so that each
+// starts on the rows its producer wrote last (still in L2 / Infinity Cache).  first_rev is the direction of the chain's first launch: upwards
+// (0) for the ReLU stacks, whose first launch is the head kernel, which walks upwards, and for the sweep; downwards (1) for the value backward.
+// The parities are fixed per launch site, so the order of every sum is deterministic.
+static int walk_rev(int pos, int first_rev = 0) { return (pos + first_rev) & 1; }
 
 // Backward of one layer of a ReLU stack (relight rl_mlp, colour): g = the launch that forms the cotangent of the layer's input, d = its
 // weight-gradient pair (X = the output cotangent, Y = the forward input, sy = rs_in, the row scales the forward saved for that input).
-// A narrow head takes the streaming head kernel; otherwise the extra input columns of a 256 + few wide layer go to the strip launch and the
-// rest is one fused layer + weight-gradient launch where the shape allows, or a layer launch and a weight-gradient launch.
-// rev: walk direction of a fused launch, opposite to the launch that wrote this one's input (the head kernel walks upwards, then the
-// stack alternates).  head: the stack's top layer, whose cotangent rows are packed (b.ldtop != kTop) only for the head kernel.
-static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* rs_in, int rev, bool head, Bwd& b, const float* const* params,
-                           float* const* dP, cnr_stream s) {
-  if (head_bwd_ok(q, g)) return run_head_bwd(q, g, b, params, dP, s);
-  if (head && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");   // (layout_bwd decides both from the same predicate)
+// The decision, made before the region is taken and before any launch: a narrow head takes the streaming head kernel; otherwise the extra
+// input columns of a 256 + few wide layer go to the strip launch (g is narrowed to its main columns) and the rest is one fused layer +
+// weight-gradient launch where the shape allows, or a layer launch and a weight-gradient launch.
+// nslots: slots of the (main) weight-gradient launch; rev: walk direction of a fused one; sb: the strip launch, complete but for the region
+struct StackLayerPlan { bool head = false, strips = false, fused = false; int nslots = 0, rev = 0; StripBwd sb; };
+static StackLayerPlan plan_stack_layer(const Lin& q, LayerGemm& g, const DwGemm& d, const float* rs_in, int pos, const Bwd& b) {
+  StackLayerPlan p; p.head = head_bwd_ok(q, g);
+  p.strips = !p.head && strip_bwd_ok(q, g, d);
+  if (p.strips) p.sb = take_strips(q, g, d, b);
+  // layer launch + weight gradient in one launch where the shape allows (cnr_gemm_fdw.hip)
+  p.fused = !p.head && be_fdw_enabled() && fdw_shape_ok(g) && rs_in && q.npad == 256 && q.ldw <= 320;
+  p.nslots = p.fused ? b.fslots : b.nchunk; p.rev = walk_rev(pos);
+  return p;
+}
+// pos: launches of the stack's backward chain before this one (0: the top layer, whose cotangent rows are packed (b.ldtop != kTop) only for
+// the head kernel)
+static int stack_layer_bwd(const Lin& q, LayerGemm& g, DwGemm& d, const float* rs_in, int pos, Bwd& b, const float* const* params, float* const* dP,
+                           cnr_stream s) {
+  StackLayerPlan p = plan_stack_layer(q, g, d, rs_in, pos, b);
+  if (!p.head && pos == 0 && b.ldtop != kTop) return fail("render_backward: packed head cotangents without the streaming head kernel");   // (layout_bwd decides both from the same predicate)
   const DwRegion r = b.dw.take(q, region_slots(q, b));
   if (!r.part) return -1;
-  const bool strips = strip_bwd_ok(q, g, d);
-  StripBwd sb;
-  if (strips) sb = take_strips(q, g, d, r, b);
-  const int kmain = strips ? 256 : 0;
-  // layer launch + weight gradient in one launch where the shape allows (cnr_gemm_fdw.hip)
-  const bool fused = be_fdw_enabled() && fdw_shape_ok(g) && rs_in && q.npad == 256 && q.ldw <= 320;
-  if (fused) {
-    fused_into_region(q, g, d, rs_in, 0, r, 0, b, true, s, kmain, nullptr, rev);
+  const int kmain = p.strips ? 256 : 0;
+  if (p.head) {
+    HeadBwd h;
+    h.dtop = g.A.a; h.ldt = g.A.lda; h.aux = g.E.aux; h.ldaux = g.E.ldaux; h.W = q.W; h.ldw = q.ldw; h.n = q.n; h.K = q.k_int; h.P = g.P;
+    h.dout = g.E.o1; h.ldo = g.E.ld1; h.partial = r.part; h.colsum = r.csum; h.npad = q.npad; h.ldk = q.ldw; h.nslots = p.nslots;
+    be_head_bwd(h, s);
+  } else if (p.fused) {
+    fused_into_region(q, g, d, rs_in, 0, r, 0, b, true, s, kmain, nullptr, p.rev);
   } else {
     if (q.n > 32) g.rs_out = b.rsD;
     be_layer_gemm(g, s);
     d.sx[0] = g.rs_out;
-    dw_into_region(q, d, r, 0, b.nchunk, g.P, true, s, kmain);
+    dw_into_region(q, d, r, 0, p.nslots, g.P, true, s, kmain);
   }
-  if (strips) be_strip_bwd(sb, s);
-  const int nslots = fused ? b.fslots : b.nchunk;
-  b.dw.finish(q, r, nslots, nslots, params, dP);
-  if (strips) b.dw.strip_columns_of_last_finish(b.nchunk);
+  if (p.strips) { p.sb.partial = r.part; be_strip_bwd(p.sb, s); }
+  b.dw.finish(q, r, p.nslots, p.nslots, params, dP);
+  if (p.strips) b.dw.strip_columns_of_last_finish(b.nchunk);
   return 0;
 }
 
-// Steps 4-7 of the backward pass and the point cotangent of step 8: the complete first- and second-order backward of the SDF network, shared
-// by render_backward and cnr_sdf_query_backward (the render path issues the same launches with the same arguments in the same order as
-// before this was a function of its own).  Seeds: b.ZTOP (cotangent of the top layer's outputs [feat | sdf / scale | 0]) and b.gbar_a
-// (cotangent of grad_x sdf).  Entered inside an open range (be_range_push), which it closes after the weight-gradient reductions.
-// Every region of the partial-sum pool is taken before the first launch that writes into one; -1 when the pool refuses.
+// Backward of a narrow-input layer (K <= 48: relight layer 0, SDF layer 0): the cotangent of its input columns, its weight gradient and its
+// bias gradient in one pass over the layer's output cotangent (cnr_narrow_bwd.hip), or a narrow layer launch + a weight-gradient launch.
+// narrow_pass_ok decides, given the descriptor without a region: the shape test must see a backward form (partial set selects the switch
+// be_narrow_bwd_ok honours), so a copy stands on the pool's base for it.
+static bool narrow_pass_ok(NarrowBwd nb, const Lin& q, int hidden, const Bwd& b) {
+  nb.partial = nb.colsum = b.dw.base;
+  return be_fdw_enabled() && q.n == 256 && q.npad == 256 && hidden == 256 && be_narrow_bwd_ok(nb) && be_narrow_bwd_slots(nb.P) <= region_slots(q, b);
+}
+// one_pass: the region (taken here and its reduction queued here, unless the caller shares one it took and finishes it itself: SDF layer 0),
+// the completed descriptor, the launch.  Otherwise the narrow layer launch where the descriptor asks for the input cotangent (dx) and, for a
+// layer with a region of its own, the plain weight gradient; both read the operands the descriptor names.
+static int narrow_layer_bwd(const Lin& q, NarrowBwd nb, bool one_pass, const DwRegion* taken, Bwd& b, const float* const* params, float* const* dP,
+                            cnr_stream s) {
+  if (!one_pass) {
+    LayerGemm g = bwd_gemm(q, nb.P);
+    g.A = direct_view(nb.X, nb.ldx); g.E.kind = EK_STORE; g.E.n_out = nb.ndx; g.E.o1 = nb.dx; g.E.ld1 = nb.lddx;
+    if (nb.dx) be_layer_gemm(g, s);
+    DwGemm d; d.npairs = 1; d.P = nb.P; d.X[0] = g.A; d.Y[0] = direct_view(nb.Y, nb.ldy);
+    return taken ? 0 : plain_dw(b.dw, q, d, region_slots(q, b), b.nchunk, params, dP, s);
+  }
+  const DwRegion r = taken ? *taken : b.dw.take(q, region_slots(q, b));
+  if (!r.part) return -1;
+  nb.partial = r.part; nb.colsum = r.csum;
+  be_narrow_bwd(nb, s);
+  if (!taken) b.dw.finish(q, r, be_narrow_bwd_slots(nb.P), be_narrow_bwd_slots(nb.P), params, dP);
+  return 0;
+}
+
 struct SdfBwdArgs {
   const float* daux_c = nullptr; const float* daux_r = nullptr;   // cotangents of the colour / relight aux rows [p g ..] (render) or null (query)
   bool grad_path = true;    // false: no cotangent on grad_x sdf -- no gbar / second-order sweep (Z2 starts from zero), value pairs only
   bool pts_grad = false;    // form ebar0 / ebars and the total point cotangent b.pbar (camera refinement, point queries)
 };
-static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const float* const* params, float* const* dP /* null: no weight gradients */,
-                         const SdfBwdArgs& sa, cnr_stream s) {
-  const float scale = m.c.sdf_scale;
-  const bool fdw = be_fdw_enabled() && dP != nullptr;   // (the fused layer + weight-gradient launches only where weight gradients are wanted)
-  const bool gfdw = fdw && sa.grad_path;
-  const bool rays_grad = sa.pts_grad;
-  const bool skipnet = has_skip(m);
-  // ---- 4. total d g and the tangent of the embedding
-  GbarFinish gb;
-  gb.P = P; gb.gbar_alpha = b.gbar_a; gb.daux_c = sa.daux_c; gb.daux_r = sa.daux_r; gb.E = x.E; gb.scale = scale;
-  gb.multires = m.c.sdf_multires; gb.gbar_total = b.gbar_t; gb.cbar = b.cbar;
-  if (sa.grad_path) be_gbar_finish(gb, s);
-  // ---- 5. second-order forward sweep (tangent of h_l in the direction induced by gbar)
-  const float inv_scale = 1.0f / scale;
-  auto qbar_view = [&](int l) {
+
+// The launches of steps 5 and 6 of the backward pass and their weight-gradient pairs as descriptors (none of them needs a region).
+struct SdfBwdDescs {
+  const Model& m; long P; const Ctx& x; const Bwd& b; bool rays_grad; float inv_scale;
+  View qbar_view(int l) const {
     View v;
     v.kind = VK_DIRECT;
     if (l == 0) { v.a = b.cbar; v.lda = kEmb; }
     else { v.a = b.VB[l - 1]; v.lda = m.Hs; if (m.skip(l)) v.scale = kInvSqrt2; }   // skip: tail columns of VB[l-1] hold cbar
     return v;
-  };
-  // the launches of steps 5 and 6 as descriptors: each SDF layer's two weight-gradient pairs go into one region of the partial-sum pool,
-  // [value pair (zbar_l, input_l) | gradient-chain pair (u_l, qbar_l)], each either fused into its layer launch (value pair: the
-  // value-backward launch l; gradient-chain pair: the sweep launch l) or left to the separate weight-gradient GEMM of step 7
-  auto sweep_gemm = [&](int l) {
+  }
+  LayerGemm sweep_gemm(int l) const {
     const Lin& q = m.sdf[l];
     LayerGemm g = fwd_gemm(q, P);
     g.A = qbar_view(l);
@@ -1333,8 +1349,8 @@ static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const floa
     g.E.o1 = b.Z2[l]; g.E.ld1 = m.Hs; g.E.o2 = b.VB[l]; g.E.ld2 = m.Hs;
     if (m.skip(l + 1)) { g.E.tail_src = b.cbar; g.E.ld_tail = kEmb; g.E.tail_n = m.emb; }
     return g;
-  };
-  auto vback_gemm = [&](int l) {
+  }
+  LayerGemm vback_gemm(int l) const {
     const Lin& q = m.sdf[l];
     LayerGemm g = bwd_gemm(q, P);
     g.A = l == m.L ? direct_view(b.ZTOP, x.ldztop) : direct_view(b.Z2[l], m.Hs);
@@ -1343,15 +1359,24 @@ static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const floa
                      g.E.o2_acc = l != top_skip(m);   // (the value backward runs from the top layer down: the highest skip layer stores, the others add)
                      g.E.vscale = kInvSqrt2; }   // (vscale: the scale of the layer's input view, for the fused launch's epilogue-side operand)
     return g;
-  };
+  }
+  // The first layer (narrow input): the cotangent of its input columns (camera refinement) and its value pair in one pass over Z2[0]
+  // (cnr_narrow_bwd.hip) instead of a narrow layer launch + a weight-gradient launch; the descriptor without its region
+  NarrowBwd narrow0() const {
+    const Lin& q = m.sdf[0];
+    NarrowBwd nb;
+    nb.X = b.Z2[0]; nb.ldx = m.Hs; nb.Y = x.E; nb.ldy = kEmb; nb.ky = q.k_int; nb.P = P; nb.ldk = q.ldw;
+    if (rays_grad) { narrow_bwd_weights(nb, q); nb.dx = b.ebar0; nb.lddx = kEmb; nb.ndx = m.emb; }
+    return nb;
+  }
   // value pair of layer l: X = zbar_l, Y = the layer's forward input
-  auto value_pair = [&](int l, DwGemm& d) {
+  void value_pair(int l, DwGemm& d) const {
     d.X[0] = l == m.L ? direct_view(b.ZTOP, x.ldztop) : direct_view(b.Z2[l], m.Hs);
     d.Y[0] = sdf_input_view(m, l, x.E, x.Z.data());
     d.sx[0] = b.rsX0[l]; d.sy[0] = x.rsY[l];
-  };
+  }
   // gradient-chain pair of layer l into operand slot i of d: X = u_l = sp'(z_l) v_l, Y = qbar_l
-  auto grad_pair = [&](int l, DwGemm& d, int i) {
+  void grad_pair(int l, DwGemm& d, int i) const {
     if (l == m.L) {
       d.X[i].kind = VK_CONST_COL0; d.X[i].a = b.ZTOP; d.X[i].lda = x.ldztop; d.X[i].scale = inv_scale; d.X[i].math_split = m.F;
       d.Y[i].kind = VK_DIRECT; d.Y[i].a = b.VB[m.L - 1]; d.Y[i].lda = m.Hs;
@@ -1362,122 +1387,146 @@ static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const floa
       d.Y[i] = qbar_view(l);
       d.sx[i] = x.rsX1[l]; d.sy[i] = b.rsY1[l];
     }
-  };
-  std::vector<DwRegion> sreg(m.L + 1);
-  std::vector<char> fuse_v(m.L + 1, 0), fuse_g(m.L + 1, 0);
+  }
+};
+
+// THE place where the SDF backward decides which launch forms which weight-gradient pair.  Each SDF layer's two pairs go into one region of
+// the partial-sum pool, [value pair (zbar_l, input_l) | gradient-chain pair (u_l, qbar_l)]: the value pair in slots [0, value_slots) (it
+// carries the bias column sums), the gradient-chain pair in [value_slots, value_slots + grad_slots).  A pair takes fslots slots when it is
+// fused into its layer launch, the slots of a one-workgroup-per-CU launch from sweep0 / narrow_bwd, and nchunk slots as a separate GEMM (one
+// workgroup per slot: fewer would leave CUs idle); when both are separate one GEMM over nchunk slots forms both.
+// Who forms the value pair: SEPARATE = the weight-gradient GEMM of step 7; FUSED = value-backward launch l (cnr_gemm_fdw.hip); NARROW_PASS =
+// layer 0 only, the one-pass launch that ends step 6 (cnr_narrow_bwd.hip).
+enum class ValueBy : char { SEPARATE, FUSED, NARROW_PASS };
+// Who forms the gradient-chain pair: NONE = there is no gradient path (sa.grad_path == false); SEPARATE = the weight-gradient GEMM of step 7;
+// FUSED = sweep launch l (cnr_gemm_fdw.hip); SWEEP0 = narrow-input layer (layer 0), the sweep launch forms the pair from its epilogue's side
+// inputs, one slot per workgroup (cnr_sweep0.hip); XROW = the fused top layer, whose pair has one live row, the extra row of sweep launch
+// L - 1: no slots of its own.
+enum class GradBy : char { NONE, SEPARATE, FUSED, SWEEP0, XROW };
+struct SdfLayerPlan {
+  ValueBy value = ValueBy::SEPARATE; GradBy grad = GradBy::NONE;
+  int value_slots = 0, grad_slots = 0, value_rev = 0, grad_rev = 0;   // rev: walk directions of value-backward launch l / sweep launch l when fused
+  bool both_in_one() const { return value == ValueBy::SEPARATE && grad == GradBy::SEPARATE; }
+};
+// The top layer (F features + the sdf row, F == 256 = its input width) without launches of its own (top_fused): its value-backward launch
+// (gtop) takes the sdf column of the cotangent as a rank-one update of the 256-wide product (k_extra) and forms the main 256 x 256 weight
+// gradient like any other layer; the sdf ROW of the weight gradient is made of values two launches hold anyway -- the gradient-chain pair's
+// unit vector makes it inv_scale * column sums of VB[L-1], the o2 output of the sweep launch of layer L-1 (xrow1, xrow_mode 1), and the value
+// pair adds sum zbar_sdf[pt] * softplus(z_{L-1})[pt][:], whose factors the value-backward launch has in its epilogue (xrow2, xrow_mode 2).
+// layer: [L + 1]; xrow1 / xrow2: the extra-row requests, complete once the top layer's region is known (xrow, xbias)
+struct SdfBwdPlan { std::vector<SdfLayerPlan> layer; bool top_fused = false; LayerGemm gtop; DwFuse xrow1, xrow2; };
+static SdfBwdPlan plan_sdf_backward(const SdfBwdDescs& D, bool want_dw, const SdfBwdArgs& sa) {
+  const Model& m = D.m; const Ctx& x = D.x; const Bwd& b = D.b;
+  const bool fdw = be_fdw_enabled() && want_dw;   // (the fused layer + weight-gradient launches only where weight gradients are wanted)
+  const bool gfdw = fdw && sa.grad_path;
+  SdfBwdPlan pl; pl.layer.resize(m.L + 1);
   for (int l = 0; l <= m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    sreg[l] = b.dw.take(q, region_slots(q, b));
-    if (!sreg[l].part) { be_range_pop(); return -1; }
+    const Lin& q = m.sdf[l]; SdfLayerPlan& p = pl.layer[l];
     const bool sq = q.npad >= 224 && q.npad <= 256 && q.ldw == 256;
-    auto ok = [&](const LayerGemm& g) { return fdw_shape_ok(g); };
-    if (fdw && sq && l >= 1 && l < m.L && x.rsY[l] && ok(vback_gemm(l))) fuse_v[l] = 1;
-    if (gfdw && sq && l < m.L && x.rsX1[l] && ok(sweep_gemm(l))) fuse_g[l] = 1;
-    // narrow-input layer (the first SDF layer): the sweep launch forms the pair from its epilogue's side inputs, one slot per workgroup (cnr_sweep0.hip)
-    if (gfdw && !fuse_g[l] && l < m.L && q.npad == 256 && be_sweep0_ok(sweep_gemm(l)) && b.nchunk + be_sweep0_slots(P) <= region_slots(q, b)) fuse_g[l] = 2;
+    if (fdw && sq && l >= 1 && l < m.L && x.rsY[l] && fdw_shape_ok(D.vback_gemm(l))) p.value = ValueBy::FUSED;
+    if (sa.grad_path) p.grad = GradBy::SEPARATE;
+    if (gfdw && sq && l < m.L && x.rsX1[l] && fdw_shape_ok(D.sweep_gemm(l))) p.grad = GradBy::FUSED;
+    else if (gfdw && l < m.L && q.npad == 256 && be_sweep0_ok(D.sweep_gemm(l))) p.grad = GradBy::SWEEP0;
+    p.value_rev = walk_rev(m.L - l, 1); p.grad_rev = walk_rev(l);
   }
-  // The first layer (narrow input): the cotangent of its input columns (camera refinement) and its value pair in one pass over Z2[0]
-  // (cnr_narrow_bwd.hip) instead of a narrow layer launch + a weight-gradient launch
-  NarrowBwd nb0;
-  {
-    const Lin& q = m.sdf[0];
-    nb0.X = b.Z2[0]; nb0.ldx = m.Hs; nb0.Y = x.E; nb0.ldy = kEmb; nb0.ky = q.k_int; nb0.P = P;
-    if (rays_grad) {
-      narrow_bwd_weights(nb0, q);
-      nb0.dx = b.ebar0; nb0.lddx = kEmb; nb0.ndx = m.emb;
-    }
-    nb0.partial = sreg[0].part; nb0.ldk = q.ldw; nb0.colsum = sreg[0].csum;
-  }
-  const bool use_nb0 = fdw && m.L >= 1 && !fuse_v[0] && fuse_g[0] != 0 && m.sdf[0].n == 256 && m.sdf[0].npad == 256 && m.Hs == 256 && be_narrow_bwd_ok(nb0) &&
-                       be_narrow_bwd_slots(P) + (fuse_g[0] == 2 ? be_sweep0_slots(P) : fuse_g[0] ? b.fslots : 0) <= region_slots(m.sdf[0], b);
-  // The top layer (F features + the sdf row, F == 256 = its input width) without launches of its own: its value-backward launch takes the
-  // sdf column of the cotangent as a rank-one update of the 256-wide product (k_extra) and forms the main 256 x 256 weight gradient like any
-  // other layer; the sdf ROW of the weight gradient is made of values two launches hold anyway -- the gradient-chain pair's unit vector
-  // makes it inv_scale * column sums of VB[L-1], the o2 output of the sweep launch of layer L-1 (xrow_mode 1), and the value pair adds
-  // sum zbar_sdf[pt] * softplus(z_{L-1})[pt][:], whose factors the value-backward launch has in its epilogue (xrow_mode 2).
+  const GradBy g0 = pl.layer[0].grad;
+  if (fdw && (g0 == GradBy::FUSED || g0 == GradBy::SWEEP0) && narrow_pass_ok(D.narrow0(), m.sdf[0], m.Hs, b)) pl.layer[0].value = ValueBy::NARROW_PASS;
   const Lin& qtop = m.sdf[m.L];
-  LayerGemm gtop = vback_gemm(m.L);
-  gtop.K = 256; gtop.k_extra = 1;
-  const bool no_top = debug_flags().no_top_fuse;   // debugging aid: the top layer as three launches of its own
-  const bool top_fused = !no_top && fdw && be_fdw_xrow() && m.L >= 2 && fuse_g[m.L - 1] && m.F == 256 && qtop.n == 257 && qtop.k_int == 256 &&
-                         qtop.ldw == 256 && qtop.npad <= 288 && x.ldztop >= 260 && x.rsY[m.L] && !m.skip(m.L) && fdw_shape_ok(gtop);
-  if (top_fused) fuse_v[m.L] = 1;
-  DwFuse xrow1, xrow2;
-  xrow1.xrow_mode = 1; xrow1.xrow = sreg[m.L].part + (size_t)256 * qtop.ldw; xrow1.xrow_stride = (long)qtop.npad * qtop.ldw; xrow1.xrow_scale = inv_scale;
-  xrow2 = xrow1;
-  xrow2.xrow_mode = 2; xrow2.xrow_scale = 1.0f; xrow2.xbias = sreg[m.L].csum + 256; xrow2.xbias_stride = qtop.npad;
-  // slot groups of a region: the value pair first (it carries the bias column sums), the gradient-chain pair behind it; a pair takes
-  // fslots slots when it is fused and nchunk slots as a separate GEMM (one workgroup per slot: fewer would leave CUs idle); when neither is
-  // fused one launch over nchunk slots forms both
-  auto value_slots = [&](int l) { return (l == 0 && use_nb0) ? be_narrow_bwd_slots(P) : fuse_v[l] ? b.fslots : b.nchunk; };
-  auto grad_slots = [&](int l) { return !sa.grad_path ? 0 : (l == m.L && top_fused) ? 0 : fuse_g[l] == 2 ? be_sweep0_slots(P) : fuse_g[l] ? b.fslots : (fuse_v[l] ? b.nchunk : 0); };
+  pl.gtop = D.vback_gemm(m.L); pl.gtop.K = 256; pl.gtop.k_extra = 1;
+  // (no_top_fuse: debugging aid, the top layer as three launches of its own)
+  pl.top_fused = !debug_flags().no_top_fuse && fdw && be_fdw_xrow() && m.L >= 2 && pl.layer[m.L - 1].grad == GradBy::FUSED && m.F == 256 && qtop.n == 257 && qtop.k_int == 256 &&
+                 qtop.ldw == 256 && qtop.npad <= 288 && x.ldztop >= 260 && x.rsY[m.L] && !m.skip(m.L) && fdw_shape_ok(pl.gtop);
+  if (pl.top_fused) { pl.layer[m.L].value = ValueBy::FUSED; pl.layer[m.L].grad = GradBy::XROW; }
+  pl.xrow1.xrow_mode = 1; pl.xrow1.xrow_stride = (long)qtop.npad * qtop.ldw; pl.xrow1.xrow_scale = D.inv_scale;
+  pl.xrow2.xrow_mode = 2; pl.xrow2.xrow_stride = pl.xrow1.xrow_stride; pl.xrow2.xrow_scale = 1.0f; pl.xrow2.xbias_stride = qtop.npad;
+  // The slot groups, and the one check that they fit the layer's region.  region_slots reserves room for every combination above, so the
+  // fallback (the one-workgroup-per-CU forms give way to the separate GEMM, whose groups always fit) is not taken at any accepted width.
+  for (int l = 0; l <= m.L; ++l)
+    for (int pass = 0; pass < 2; ++pass) {
+      SdfLayerPlan& p = pl.layer[l];
+      p.value_slots = p.value == ValueBy::NARROW_PASS ? be_narrow_bwd_slots(D.P) : p.value == ValueBy::FUSED ? b.fslots : b.nchunk;
+      p.grad_slots = p.grad == GradBy::SWEEP0 ? be_sweep0_slots(D.P) : p.grad == GradBy::FUSED ? b.fslots : (p.grad == GradBy::SEPARATE && p.value == ValueBy::FUSED) ? b.nchunk : 0;
+      if (p.value_slots + p.grad_slots <= region_slots(m.sdf[l], b)) break;
+      if (p.value == ValueBy::NARROW_PASS) p.value = ValueBy::SEPARATE;
+      if (p.grad == GradBy::SWEEP0) p.grad = GradBy::SEPARATE;
+    }
+  return pl;
+}
+
+// Steps 4-7 of the backward pass and the point cotangent of step 8: the complete first- and second-order backward of the SDF network, shared
+// by render_backward and cnr_sdf_query_backward.  Seeds: b.ZTOP (cotangent of the top layer's outputs [feat | sdf / scale | 0]) and b.gbar_a
+// (cotangent of grad_x sdf).  Entered inside an open range (be_range_push), which it closes after the weight-gradient reductions.
+// The plan is built first; every region of the partial-sum pool is taken before the first launch that writes into one (-1 when the pool
+// refuses); the three loops then issue what the plan says.
+static int sdf_backward(const Model& m, long P, const Ctx& x, Bwd& b, const float* const* params, float* const* dP /* null: no weight gradients */,
+                         const SdfBwdArgs& sa, cnr_stream s) {
+  const float scale = m.c.sdf_scale;
+  const bool rays_grad = sa.pts_grad, skipnet = has_skip(m);
+  const SdfBwdDescs D{m, P, x, b, rays_grad, 1.0f / scale};
+  SdfBwdPlan pl = plan_sdf_backward(D, dP != nullptr, sa);
+  // ---- 4. total d g and the tangent of the embedding
+  GbarFinish gb;
+  gb.P = P; gb.gbar_alpha = b.gbar_a; gb.daux_c = sa.daux_c; gb.daux_r = sa.daux_r; gb.E = x.E; gb.scale = scale;
+  gb.multires = m.c.sdf_multires; gb.gbar_total = b.gbar_t; gb.cbar = b.cbar;
+  if (sa.grad_path) be_gbar_finish(gb, s);
+  std::vector<DwRegion> sreg(m.L + 1);
+  for (int l = 0; l <= m.L; ++l)
+    if (!(sreg[l] = b.dw.take(m.sdf[l], region_slots(m.sdf[l], b))).part) { be_range_pop(); return -1; }
+  pl.xrow1.xrow = pl.xrow2.xrow = sreg[m.L].part + (size_t)256 * m.sdf[m.L].ldw; pl.xrow2.xbias = sreg[m.L].csum + 256;
+  // ---- 5. second-order forward sweep (tangent of h_l in the direction induced by gbar)
   if (!sa.grad_path)   // value path only: the value backward adds into Z2, which no sweep has written
     for (int l = 0; l < m.L; ++l) be_memset_zero(b.Z2[l], (size_t)P * m.Hs * sizeof(float), s);
   for (int l = 0; sa.grad_path && l < m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    LayerGemm g = sweep_gemm(l);
-    if (fuse_g[l] == 2) {
-      be_sweep0_dw(g, sreg[l].part + (size_t)value_slots(l) * q.npad * q.ldw, q.ldw, s);
-    } else if (fuse_g[l]) {
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      grad_pair(l, d, 0);
-      d.sy[0] = nullptr;   // (a fused launch does not need qbar_l's row scales; the unfused fallback then takes the split-bf16 tiles)
-      fused_into_region(q, g, d, x.rsX1[l], 1, sreg[l], value_slots(l), b, false, s, 0, (top_fused && l == m.L - 1) ? &xrow1 : nullptr, l & 1);
-    } else {
-      g.rs_out = b.rsY1[l];
-      be_layer_gemm(g, s);
+    const Lin& q = m.sdf[l]; const SdfLayerPlan& p = pl.layer[l];
+    LayerGemm g = D.sweep_gemm(l);
+    DwGemm d; d.npairs = 1; d.P = P;
+    switch (p.grad) {
+      case GradBy::SWEEP0: be_sweep0_dw(g, sreg[l].part + (size_t)p.value_slots * q.npad * q.ldw, q.ldw, s); break;
+      case GradBy::FUSED:
+        D.grad_pair(l, d, 0);
+        d.sy[0] = nullptr;   // (a fused launch does not need qbar_l's row scales; the unfused fallback then takes the split-bf16 tiles)
+        fused_into_region(q, g, d, x.rsX1[l], 1, sreg[l], p.value_slots, b, false, s, 0, (pl.top_fused && l == m.L - 1) ? &pl.xrow1 : nullptr, p.grad_rev);
+        break;
+      default: g.rs_out = b.rsY1[l]; be_layer_gemm(g, s);
     }
   }
   be_range_pop(); be_range_push("sdf value backward");
   // ---- 6. value-path backward through the SDF net (in place: Z2[l] becomes the total cotangent of z_l)
   for (int l = m.L; l >= 1; --l) {
     const Lin& q = m.sdf[l];
-    const bool top = l == m.L && top_fused;
-    LayerGemm g = top ? gtop : vback_gemm(l);
-    if (fuse_v[l]) {
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      value_pair(l, d);
-      d.sx[0] = nullptr;
-      fused_into_region(q, g, d, x.rsY[l], 0, sreg[l], 0, b, true, s, 0, top ? &xrow2 : nullptr, ((m.L - l) & 1) ^ 1);
-    } else {
-      g.rs_out = b.rsX0[l];
-      be_layer_gemm(g, s);
+    const bool top = l == m.L && pl.top_fused;
+    LayerGemm g = top ? pl.gtop : D.vback_gemm(l);
+    DwGemm d; d.npairs = 1; d.P = P;
+    switch (pl.layer[l].value) {
+      case ValueBy::FUSED:
+        D.value_pair(l, d);
+        d.sx[0] = nullptr;
+        fused_into_region(q, g, d, x.rsY[l], 0, sreg[l], 0, b, true, s, 0, top ? &pl.xrow2 : nullptr, pl.layer[l].value_rev);
+        break;
+      default: g.rs_out = b.rsX0[l]; be_layer_gemm(g, s);
     }
   }
-  if (use_nb0) be_narrow_bwd(nb0, s);
-  else if (rays_grad) {
-    const Lin& q = m.sdf[0];
-    LayerGemm g = bwd_gemm(q, P);
-    g.A = direct_view(b.Z2[0], m.Hs);
-    g.E.kind = EK_STORE; g.E.n_out = m.emb; g.E.o1 = b.ebar0; g.E.ld1 = kEmb;
-    be_layer_gemm(g, s);
-  }
+  // layer 0: one pass into the region it shares with the gradient-chain pair, or (camera refinement, point queries) the narrow layer launch
+  narrow_layer_bwd(m.sdf[0], D.narrow0(), pl.layer[0].value == ValueBy::NARROW_PASS, &sreg[0], b, params, dP, s);
   be_range_pop(); be_range_push("weight gradients: leftovers + finish");
-  // ---- 7. SDF weight gradients that were not formed inside a layer launch: value pair (zbar_l, input_l) + gradient-chain pair (u_l, qbar_l)
+  // ---- 7. SDF weight gradients that were not formed inside a layer launch
   for (int l = 0; dP && l <= m.L; ++l) {
-    const Lin& q = m.sdf[l];
-    const DwRegion& r = sreg[l];
-    if (!fuse_v[l] && !fuse_g[l]) {          // both pairs in one launch sharing the accumulators
-      DwGemm d;
-      d.npairs = sa.grad_path ? 2 : 1; d.P = P;
-      value_pair(l, d);
-      if (sa.grad_path) grad_pair(l, d, 1);
-      dw_into_region(q, d, r, 0, b.nchunk, P, true, s);
-    } else if (l == 0 && use_nb0) {          // (formed by the one-pass launch of step 6)
-    } else if (!fuse_v[l]) {                 // the value pair alone, into the leading slots
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      value_pair(l, d);
-      dw_into_region(q, d, r, 0, value_slots(l), P, true, s);
-    } else if (sa.grad_path && !fuse_g[l] && !(l == m.L && top_fused)) {   // the gradient-chain pair alone, behind the fused value pair
-      DwGemm d;
-      d.npairs = 1; d.P = P;
-      grad_pair(l, d, 0);
-      dw_into_region(q, d, r, value_slots(l), grad_slots(l), P, false, s);
+    const Lin& q = m.sdf[l]; const DwRegion& r = sreg[l]; const SdfLayerPlan& p = pl.layer[l];
+    DwGemm d; d.npairs = 1; d.P = P;
+    switch (p.value) {
+      case ValueBy::SEPARATE:      // the value pair into the leading slots; with a separate gradient-chain pair both in one launch sharing the accumulators
+        D.value_pair(l, d);
+        if (p.both_in_one()) { d.npairs = 2; D.grad_pair(l, d, 1); }
+        dw_into_region(q, d, r, 0, p.value_slots, P, true, s);
+        break;
+      case ValueBy::FUSED:         // the gradient-chain pair alone, behind the fused value pair
+        if (p.grad != GradBy::SEPARATE) break;
+        D.grad_pair(l, d, 0);
+        dw_into_region(q, d, r, p.value_slots, p.grad_slots, P, false, s);
+        break;
+      case ValueBy::NARROW_PASS: break;   // (formed by the one-pass launch of step 6)
     }
-    b.dw.finish(q, r, value_slots(l) + grad_slots(l), value_slots(l), params, dP);
+    b.dw.finish(q, r, p.value_slots + p.grad_slots, p.value_slots, params, dP);
   }
   b.dw.flush(s);   // all partial-sum reductions + weight-norm backward in one launch
   be_range_pop();
@@ -1553,37 +1602,20 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
       g.A = direct_view(dout, ldo);
       g.E.kind = EK_RELU_MASK; g.E.n_out = q.k_int; g.E.split = m.Hr; g.E.o1 = b.D[i]; g.E.ld1 = m.Hr;
       g.E.aux = x.HR[i]; g.E.ldaux = hr_ld(m, x, i); g.E.o2 = (i == y) ? b.gc_b : nullptr; g.E.ld2 = 4;
-      DwGemm d;
-      d.npairs = 1; d.P = P;
+      DwGemm d; d.npairs = 1; d.P = P;
       d.X[0] = g.A; d.sy[0] = x.rsR[i];
       d.Y[0] = relight_input_view(m, i, x);
-      if (stack_layer_bwd(q, g, d, x.rsR[i], (m.NR - 1 - i) & 1, i == m.NR - 1, b, params, dP, s)) return -1;
+      if (stack_layer_bwd(q, g, d, x.rsR[i], m.NR - 1 - i, b, params, dP, s)) return -1;
     }
     {
       const Lin& q = m.rel[0];
-      LayerGemm g = bwd_gemm(q, P);
-      g.A = direct_view(b.D[0], m.Hr);
-      g.E.kind = EK_STORE; g.E.n_out = q.k_int; g.E.o1 = b.dAUXr; g.E.ld1 = kAux;
-      // one pass over D[0] for the cotangent of the layer's inputs, its weight gradient and its bias gradient (cnr_narrow_bwd.hip) ...
+      // one pass over D[0] for the cotangent of the layer's inputs, its weight gradient and its bias gradient, or a narrow layer launch + a
+      // weight-gradient launch (narrow_layer_bwd)
       NarrowBwd nb;
       nb.X = b.D[0]; nb.ldx = m.Hr; nb.Y = x.AUX; nb.ldy = kAux; nb.ky = q.k_int; nb.P = P;
       narrow_bwd_weights(nb, q);
       nb.dx = b.dAUXr; nb.lddx = kAux; nb.ndx = q.k_int; nb.ldk = q.ldw;
-      nb.partial = b.dw.base;   // (placeholder for the shape test; the region is taken below)
-      if (be_fdw_enabled() && q.n == 256 && q.npad == 256 && m.Hr == 256 && be_narrow_bwd_ok(nb) && be_narrow_bwd_slots(P) <= region_slots(q, b)) {
-        const DwRegion r = b.dw.take(q, region_slots(q, b));
-        if (!r.part) return -1;
-        nb.partial = r.part; nb.colsum = r.csum;
-        be_narrow_bwd(nb, s);
-        b.dw.finish(q, r, be_narrow_bwd_slots(P), be_narrow_bwd_slots(P), params, dP);
-      } else {   // ... or a narrow layer launch + a weight-gradient launch
-        be_layer_gemm(g, s);
-        DwGemm d;
-        d.npairs = 1; d.P = P;
-        d.X[0] = g.A;
-        d.Y[0] = relight_input_view(m, -1, x);
-        if (run_dw(q, d, b, params, dP, s)) return -1;
-      }
+      if (narrow_layer_bwd(q, nb, narrow_pass_ok(nb, q, m.Hr, b), nullptr, b, params, dP, s)) return -1;
     }
   }
   be_range_pop(); be_range_push("colour chain backward");
@@ -1605,11 +1637,10 @@ static int render_backward(const cnr_config* cfg, const float* const* params, co
       g.E.o2 = b.dAUXc; g.E.ld2 = kAux;
       g.E.aux = x.featx; g.E.ldaux = x.ldfx;   // (the layer's forward input: the epilogue-side operand of the fused launch)
     }
-    DwGemm d;
-    d.npairs = 1; d.P = P;
+    DwGemm d; d.npairs = 1; d.P = P;
     d.X[0] = g.A; d.sy[0] = x.rsC[l];
     d.Y[0] = color_input_view(m, l, x);
-    if (stack_layer_bwd(q, g, d, x.rsC[l], (m.NC - 1 - l) & 1, l == m.NC - 1, b, params, dP, s)) return -1;
+    if (stack_layer_bwd(q, g, d, x.rsC[l], m.NC - 1 - l, b, params, dP, s)) return -1;
   }
   be_range_pop(); be_range_push("sdf second-order sweep");
   SdfBwdArgs args;
@@ -1687,7 +1718,7 @@ static void layout_vc(Model& m, long n, Arena& a, Ctx& x) {
 // render path's SDF chains and its SDF backward (sdf_backward) on P = round_up(n, kQueryTile) rows.  Padded rows sit at the origin (finite
 // activations), carry zero cotangents (an all-zero row gets a zero row scale, which the split-f16 weight-gradient products treat as a zero
 // row) and are never copied out.  The forward stores the row scales the training forward stores, so the backward makes the same fused choices
-// (fuse_v / fuse_g, use_nb0, top_fused) as a render backward over the same number of points.
+// (plan_sdf_backward) as a render backward over the same number of points.
 // ------------------------------------------------------------------------------------------------
 constexpr long kQueryTile = 128;
 static long query_rows(long n) { return (n + kQueryTile - 1) / kQueryTile * kQueryTile; }

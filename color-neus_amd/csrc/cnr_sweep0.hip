@@ -237,12 +237,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
 }
 
 // workgroups (= partial-sum slots) of the launch for P points: one per CU as soon as there are enough tiles
-int be_sweep0_slots(long P) {
-  const long ntiles = (P + WS_TP - 1) / WS_TP;
-  if (ntiles <= 0) return 0;
-  const long tpw = (ntiles + 255) / 256;
-  return (int)((ntiles + tpw - 1) / tpw);
-}
+static_assert(WS_TP == kCuTilePoints, "cu_tile_slots counts this kernel's tiles");
+int be_sweep0_slots(long P) { return cu_tile_slots(P); }
 
 bool be_sweep0_ok(const LayerGemm& g) {
   const bool off = debug_flags().no_sweep0 || debug_flags().no_fdw;   // debugging aids: separate launches
@@ -255,9 +251,8 @@ bool be_sweep0_ok(const LayerGemm& g) {
 
 // sweep launch g + the pair's weight gradient into be_sweep0_slots(g.P) slots of [256][ldk] floats at `partial`
 void be_sweep0_dw(const LayerGemm& g, float* partial, int ldk, cnr_stream s) {
-  const long ntiles = (g.P + WS_TP - 1) / WS_TP;
-  const long tpw = (ntiles + 255) / 256;
-  const int grid = be_sweep0_slots(g.P);
+  const long tpw = tiles_per_workgroup(g.P);
+  const int grid = cu_tile_slots(g.P);
   static DeviceOnce attr_once;
   if (attr_once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep0_dw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   TimingScope ts_("sweep0_dw", 0, 300, g.P, g.N, g.K, 2, s, layer_gemm_bytes(g) + 4.0 * grid * 256.0 * ldk);

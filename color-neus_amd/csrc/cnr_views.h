@@ -486,6 +486,14 @@ inline bool fdw_shape_ok(const LayerGemm& g) {
     default: return ((e.ld1 | e.ld2 | e.ldz | e.ldv) & 3) == 0 && e.o2 != nullptr;
   }
 }
+// A one-workgroup-per-CU launch over 32-point tiles (cnr_sweep0.hip, cnr_narrow_bwd.hip): every workgroup walks tiles_per_workgroup(P)
+// consecutive tiles and writes one partial-sum slot.  The launchers size their grids and the host plan sizes the pool from this one count.
+constexpr int kCuTilePoints = 32;
+inline long tiles_per_workgroup(long P) { return ((P + kCuTilePoints - 1) / kCuTilePoints + 255) / 256; }
+inline int cu_tile_slots(long P) {
+  const long ntiles = (P + kCuTilePoints - 1) / kCuTilePoints, tpw = tiles_per_workgroup(P);
+  return ntiles > 0 ? (int)((ntiles + tpw - 1) / tpw) : 0;
+}
 inline double fdw_bytes(const LayerGemm& g, const DwFuse& f) {   // the layer launch's operands + the partial sums; S counted once (its second read is an L2 hit)
   // (EK_SPLIT has no epilogue side input: its epilogue-side operand, aux, is an extra read of the fused launch)
   return layer_gemm_bytes(g) + (g.E.kind == EK_SPLIT ? 4.0 * (double)g.P * 256 : 0.0) + 4.0 * f.nslots * (double)f.Npad * f.ldk;

@@ -361,3 +361,407 @@ def test_width_lattice_launch_census():
     assert any(rec[0] == "dw_skinny" for rec in seen)
     missing = [rec for rec in CENSUS if rec not in seen]
     assert CENSUS and not missing, missing
+
+
+# The backward pass's launches under each switch that changes what the host plan fuses, as the ordered (name, kind, nt, P, N, K, pairs) of the
+# library's per-launch records, by case of tests/_bwd_sequence_child.py: [(the settings that give this list, the list)].  The CPU emulation never
+# takes the sweep0 / narrow_bwd / head / strip forms (its be_*_ok return false), so these states of the plan exist only on the device.
+# Recorded on the MI355X from the commit BEFORE the plan (sdf_backward / stack_layer_bwd deciding inline), see profiles/bwd_plan_refactor_ab.txt:
+# a later change of the plan that moves, drops or adds a launch fails here.
+BWD_SWITCHES = ["default", "CNR_NO_FDW", "CNR_FDW_SPLIT", "CNR_NO_TOP_FUSE", "CNR_NO_SWEEP0", "CNR_NO_NARROW_BWD", "CNR_NO_HEAD_BWD", "CNR_NO_STRIP_BWD"]
+BWD_SEQUENCES = {
+    'step_A': [
+        (('default',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('strip_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 33, 2), ('coltop_bwd', 2, 0, 2048, 0, 0, 0),
+            ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 201, 2048, 256, 256, 2), ('strip_bwd', 2, 6, 2048, 256, 6, 1),
+            ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('sweep0_dw', 0, 300, 2048, 256, 39, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 217, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 39, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_FDW',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('strip_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm', 0, 2, 2048, 33, 256, 1), ('dw_gemm', 1, 8112, 2048, 256, 33, 1),
+            ('coltop_bwd', 2, 0, 2048, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('strip_bwd', 2, 6, 2048, 256, 6, 1), ('gbar_finish', 2, 0, 2048, 0, 0, 0),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 39, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 257, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 217, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm', 0, 2, 2048, 39, 256, 1), ('dw_gemm', 1, 8112, 2048, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 2048, 217, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('dw_skinny', 1, 1, 2048, 1, 256, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_FDW_SPLIT',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('strip_bwd', 2, 3, 2048, 256, 3, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('narrow_bwd', 0, 301, 2048, 256, 33, 2), ('coltop_bwd', 2, 0, 2048, 0, 0, 0),
+            ('head_bwd', 2, 3, 2048, 256, 3, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('strip_bwd', 2, 6, 2048, 256, 6, 1), ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('sweep0_dw', 0, 300, 2048, 256, 39, 2),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 217, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 257, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 2048, 217, 256, 1),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 217, 1), ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('narrow_bwd', 0, 301, 2048, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('dw_skinny', 1, 1, 2048, 1, 256, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0),
+            ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_TOP_FUSE',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('strip_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 33, 2), ('coltop_bwd', 2, 0, 2048, 0, 0, 0),
+            ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 201, 2048, 256, 256, 2), ('strip_bwd', 2, 6, 2048, 256, 6, 1),
+            ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('sweep0_dw', 0, 300, 2048, 256, 39, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_gemm_ws', 0, 108, 2048, 256, 257, 1), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 217, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('dw_skinny', 1, 1, 2048, 1, 256, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0),
+            ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_SWEEP0',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('strip_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 33, 2), ('coltop_bwd', 2, 0, 2048, 0, 0, 0),
+            ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 201, 2048, 256, 256, 2), ('strip_bwd', 2, 6, 2048, 256, 6, 1),
+            ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('layer_gemm_ws', 0, 108, 2048, 256, 39, 1), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 217, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_gemm', 0, 2, 2048, 39, 256, 1),
+            ('dw_gemm', 1, 8112, 2048, 256, 39, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 2048, 0, 0, 0),
+            ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_NARROW_BWD',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('strip_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_gemm', 0, 2, 2048, 33, 256, 1), ('dw_gemm', 1, 8112, 2048, 256, 33, 1),
+            ('coltop_bwd', 2, 0, 2048, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 201, 2048, 256, 256, 2),
+            ('strip_bwd', 2, 6, 2048, 256, 6, 1), ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('sweep0_dw', 0, 300, 2048, 256, 39, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 217, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_gemm', 0, 2, 2048, 39, 256, 1), ('dw_gemm', 1, 8112, 2048, 256, 39, 1), ('finish_weight', 2, 0, 4320, 0, 0, 0),
+            ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_HEAD_BWD',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('layer_gemm_ws', 0, 108, 2048, 256, 3, 1),
+            ('dw_skinny', 1, 1, 2048, 3, 256, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('strip_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 33, 2),
+            ('coltop_bwd', 2, 0, 2048, 0, 0, 0), ('layer_gemm_ws', 0, 108, 2048, 256, 3, 1), ('dw_skinny', 1, 1, 2048, 3, 256, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 201, 2048, 256, 256, 2), ('strip_bwd', 2, 6, 2048, 256, 6, 1), ('gbar_finish', 2, 0, 2048, 0, 0, 0),
+            ('sweep0_dw', 0, 300, 2048, 256, 39, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 217, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 39, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0),
+            ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+        (('CNR_NO_STRIP_BWD',), [
+            ('composite_bwd', 2, 0, 64, 0, 0, 0), ('variance_finish', 2, 0, 64, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_gemm', 0, 1, 2048, 3, 256, 1), ('dw_skinny', 1, 2, 2048, 256, 3, 1),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 33, 2),
+            ('coltop_bwd', 2, 0, 2048, 0, 0, 0), ('head_bwd', 2, 3, 2048, 256, 3, 1), ('layer_dw', 0, 209, 2048, 256, 256, 2),
+            ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_dw', 0, 209, 2048, 256, 256, 2), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+            ('layer_gemm', 0, 1, 2048, 6, 256, 1), ('dw_gemm_hx', 1, 4224, 2048, 256, 256, 1), ('dw_skinny', 1, 2, 2048, 256, 6, 1),
+            ('gbar_finish', 2, 0, 2048, 0, 0, 0), ('sweep0_dw', 0, 300, 2048, 256, 39, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2), ('layer_dw', 0, 207, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 217, 2),
+            ('layer_dw', 0, 208, 2048, 256, 256, 2), ('layer_dw', 0, 208, 2048, 256, 256, 2), ('narrow_bwd', 0, 301, 2048, 256, 39, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 2048, 0, 0, 0), ('rays_grad_finish', 2, 0, 64, 0, 0, 0),
+        ]),
+    ],
+    'step_B': [
+        (('default', 'CNR_FDW_SPLIT', 'CNR_NO_TOP_FUSE'), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 33, 2), ('coltop_bwd', 2, 0, 1407, 0, 0, 0),
+            ('head_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('strip_bwd', 2, 6, 1407, 256, 6, 1), ('gbar_finish', 2, 0, 1407, 0, 0, 0), ('sweep0_dw', 0, 300, 1407, 256, 39, 2),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('narrow_bwd', 0, 301, 1407, 256, 39, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('dw_skinny', 1, 1, 1407, 1, 256, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 1407, 0, 0, 0),
+            ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+        (('CNR_NO_FDW',), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm', 0, 2, 1407, 33, 256, 1), ('dw_gemm', 1, 8112, 1407, 256, 33, 1),
+            ('coltop_bwd', 2, 0, 1407, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 6, 1407, 256, 6, 1), ('gbar_finish', 2, 0, 1407, 0, 0, 0),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 39, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm', 0, 2, 1407, 39, 256, 1), ('dw_gemm', 1, 8112, 1407, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 1, 1407, 1, 256, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 1407, 0, 0, 0), ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+        (('CNR_NO_SWEEP0',), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 33, 2), ('coltop_bwd', 2, 0, 1407, 0, 0, 0),
+            ('head_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('strip_bwd', 2, 6, 1407, 256, 6, 1), ('gbar_finish', 2, 0, 1407, 0, 0, 0), ('layer_gemm_ws', 0, 108, 1407, 256, 39, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm', 0, 2, 1407, 39, 256, 1), ('dw_gemm', 1, 8112, 1407, 256, 39, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 1, 1407, 1, 256, 2), ('finish_weight', 2, 0, 4320, 0, 0, 0),
+            ('pbar_finish', 2, 0, 1407, 0, 0, 0), ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+        (('CNR_NO_NARROW_BWD',), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm', 0, 2, 1407, 33, 256, 1), ('dw_gemm', 1, 8112, 1407, 256, 33, 1),
+            ('coltop_bwd', 2, 0, 1407, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 6, 1407, 256, 6, 1), ('gbar_finish', 2, 0, 1407, 0, 0, 0),
+            ('sweep0_dw', 0, 300, 1407, 256, 39, 2), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm', 0, 2, 1407, 39, 256, 1), ('dw_gemm', 1, 8112, 1407, 256, 39, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 1, 1407, 1, 256, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 1407, 0, 0, 0), ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+        (('CNR_NO_HEAD_BWD',), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('layer_gemm_ws', 0, 108, 1407, 256, 3, 1),
+            ('dw_skinny', 1, 1, 1407, 3, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('strip_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 33, 2),
+            ('coltop_bwd', 2, 0, 1407, 0, 0, 0), ('layer_gemm_ws', 0, 108, 1407, 256, 3, 1), ('dw_skinny', 1, 1, 1407, 3, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('strip_bwd', 2, 6, 1407, 256, 6, 1),
+            ('gbar_finish', 2, 0, 1407, 0, 0, 0), ('sweep0_dw', 0, 300, 1407, 256, 39, 2), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 1, 1407, 1, 256, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 1407, 0, 0, 0), ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+        (('CNR_NO_STRIP_BWD',), [
+            ('composite_bwd', 2, 0, 67, 0, 0, 0), ('variance_finish', 2, 0, 67, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm', 0, 1, 1407, 3, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('dw_skinny', 1, 2, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 33, 2),
+            ('coltop_bwd', 2, 0, 1407, 0, 0, 0), ('head_bwd', 2, 3, 1407, 256, 3, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm', 0, 1, 1407, 6, 256, 1), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 2, 1407, 256, 6, 1),
+            ('gbar_finish', 2, 0, 1407, 0, 0, 0), ('sweep0_dw', 0, 300, 1407, 256, 39, 2), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 257, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 217, 1),
+            ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('layer_gemm_ws', 0, 108, 1407, 256, 256, 1), ('narrow_bwd', 0, 301, 1407, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 217, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 1407, 256, 256, 1), ('dw_skinny', 1, 1, 1407, 1, 256, 2),
+            ('finish_weight', 2, 0, 4320, 0, 0, 0), ('pbar_finish', 2, 0, 1407, 0, 0, 0), ('rays_grad_finish', 2, 0, 67, 0, 0, 0),
+        ]),
+    ],
+    'query_want_grad_0': [
+        (('default', 'CNR_NO_TOP_FUSE', 'CNR_NO_SWEEP0', 'CNR_NO_NARROW_BWD', 'CNR_NO_HEAD_BWD', 'CNR_NO_STRIP_BWD'), [
+            ('query_seed', 2, 0, 8704, 0, 0, 0), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 217, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 1), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1),
+            ('dw_skinny', 1, 1, 128, 1, 256, 1), ('finish_weight', 2, 0, 2266, 0, 0, 0), ('pbar_finish', 2, 0, 128, 0, 0, 0),
+            ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_NO_FDW',), [
+            ('query_seed', 2, 0, 8704, 0, 0, 0), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 217, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 1), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 128, 217, 256, 1), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_skinny', 1, 1, 128, 1, 256, 1), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_FDW_SPLIT',), [
+            ('query_seed', 2, 0, 8704, 0, 0, 0), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 217, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 217, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 1),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_skinny', 1, 1, 128, 1, 256, 1), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+    ],
+    'query_want_grad_1': [
+        (('default', 'CNR_NO_HEAD_BWD', 'CNR_NO_STRIP_BWD'), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('sweep0_dw', 0, 300, 128, 256, 39, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 217, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('narrow_bwd', 0, 301, 128, 256, 39, 2), ('finish_weight', 2, 0, 2266, 0, 0, 0), ('pbar_finish', 2, 0, 128, 0, 0, 0),
+            ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_NO_FDW',), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('layer_gemm_ws', 0, 108, 128, 256, 39, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 217, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 2), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 128, 217, 256, 2), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 2),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_skinny', 1, 1, 128, 1, 256, 2), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_FDW_SPLIT',), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('sweep0_dw', 0, 300, 128, 256, 39, 2),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 217, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 128, 217, 256, 1),
+            ('layer_gemm_ws', 0, 108, 128, 256, 217, 1), ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1),
+            ('dw_gemm_bx', 1, 4224, 128, 256, 256, 1), ('layer_gemm_ws', 0, 108, 128, 256, 256, 1), ('narrow_bwd', 0, 301, 128, 256, 39, 2),
+            ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_skinny', 1, 1, 128, 1, 256, 2), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_NO_TOP_FUSE',), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('sweep0_dw', 0, 300, 128, 256, 39, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_gemm_ws', 0, 108, 128, 256, 257, 1), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 217, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('narrow_bwd', 0, 301, 128, 256, 39, 2), ('dw_gemm_hx', 1, 4224, 128, 256, 256, 1), ('dw_skinny', 1, 1, 128, 1, 256, 2),
+            ('finish_weight', 2, 0, 2266, 0, 0, 0), ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_NO_SWEEP0',), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('layer_gemm_ws', 0, 108, 128, 256, 39, 1),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 217, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 2), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+        (('CNR_NO_NARROW_BWD',), [
+            ('query_seed', 2, 0, 8832, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('sweep0_dw', 0, 300, 128, 256, 39, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 207, 128, 256, 256, 2),
+            ('layer_dw', 0, 207, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_dw', 0, 208, 128, 256, 217, 2), ('layer_dw', 0, 208, 128, 256, 256, 2), ('layer_dw', 0, 208, 128, 256, 256, 2),
+            ('layer_gemm', 0, 2, 128, 39, 256, 1), ('dw_gemm', 1, 8112, 128, 256, 39, 1), ('finish_weight', 2, 0, 2266, 0, 0, 0),
+            ('pbar_finish', 2, 0, 128, 0, 0, 0), ('query_out', 2, 0, 192, 0, 0, 0),
+        ]),
+    ],
+}
+
+
+_CHILD_DIED = []     # the setting whose child died with a signal or ran into its time limit: no further child is started on the device
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setting", BWD_SWITCHES)
+def test_backward_launch_sequence_per_switch(setting, tmp_path):
+    """One training step of the DTU-width Color-NeuS configuration with d_rays requested at shape A (2048 points, full tiles: every fused
+    form) and shape B (1407 points, P % 32 = 31: every fallback), and one point-query backward of 64 points with want_grad 0 and 1, in one
+    child process per switch setting (the library reads the switches once per process), one at a time: the whole ordered list of backward
+    launch records equals the recorded one.  After a child that died with a signal or ran into its time limit the remaining settings fail
+    without starting theirs."""
+    import json
+    import subprocess
+    import sys
+    assert not _CHILD_DIED, ("no child started: the child of an earlier setting died or hung", _CHILD_DIED)
+    assert sorted(s for groups in BWD_SEQUENCES.values() for names, _ in groups for s in names) == sorted(BWD_SWITCHES * len(BWD_SEQUENCES))
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_bwd_sequence_child.py")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CNR_")}
+    if setting != "default":
+        env[setting] = "1"
+    out = os.path.join(str(tmp_path), setting + ".json")
+    try:
+        r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=120)
+    except subprocess.TimeoutExpired:
+        _CHILD_DIED.append(setting)
+        raise
+    if r.returncode < 0:
+        _CHILD_DIED.append(setting)
+    assert r.returncode == 0, (setting, r.returncode, r.stdout[-1500:] + r.stderr[-3000:])
+    with open(out) as f:
+        got = json.load(f)
+    assert set(got) == set(BWD_SEQUENCES), (setting, sorted(got))
+    for case, groups in BWD_SEQUENCES.items():
+        want = next(seq for names, seq in groups if setting in names)
+        recs = [tuple(rec) for rec in got[case]]
+        print("%s / %s: %d launches" % (setting, case, len(recs)))
+        assert recs == want, (setting, case, [(i, a, b) for i, (a, b) in enumerate(zip(recs, want)) if a != b][:3], len(recs), len(want))
