@@ -261,7 +261,7 @@ struct ReluChainFwd {
   ChainFwdHead rel_head; int inv_sigmoid = 1;
   float* delta = nullptr;                               // [P][3] relight offsets (pre-activation)
   float* relit = nullptr;                               // [P][4] relight_apply(rgb, delta)
-  int dbg = 0;                                          // ablation switches (CNR_CHAIN_FWD_DBG; wrong results): 1 no saves, 2 no MFMAs, 4 stores without the LDS pass, 8 no global stores
+  int dbg = 0;                                          // ablation switches (CNR_CHAIN_FWD_DBG; wrong results): 1 no saves, 2 no MFMAs, 8 no global stores
   // forward-only render with early-termination compaction (inference): the chains run on the first *P_dev entries of row_idx only -- chain-start
   // rows are read from, and the heads' outputs written to, point row_idx[i]; P is then the upper bound that sizes the launch.  No saves.
   const int* P_dev = nullptr; const int* row_idx = nullptr;

@@ -84,74 +84,58 @@ void be_pack_frags_many(const PackJob* jobs, int count, cnr_stream s) {
 // the sampler's chains, the same for a delay of 0, 1, 2 or 3 barriers.  MFMA time and epilogue time add up whatever the phase relation; the
 // chip runs these kernels at 1.9-2.1 GHz of its 2.4 GHz (GRBM_GUI_ACTIVE / duration), i.e. it is at its power limit either way.
 // ------------------------------------------------------------------------------------------------
+// The kernel's LDS image, stated once: the kernel carves its regions from these byte offsets, the launcher passes the total
+template <int RT, int CB>
+struct SdfValueLds {
+  static constexpr int T = 32 * RT;
+  static constexpr int rs = 2 * T * CH_ALD;                 // (in front: [2][T][CH_ALD] hi | lo planes)  [T] 1 / row scale of the current layer input
+  static constexpr int pm = rs + T * 4;                     // [T][8] per-wave partial row maxima / per-block partial dot products
+  static constexpr int cwb = pm + T * 8 * 4;                // [2][512] column scales | biases of the current / next layer
+  static constexpr int wtop = cwb + 2 * 512 * 4;            // [256] sdf row of the top layer
+  static constexpr int total = wtop + 256 * 4;
+  static_assert((size_t)total <= kChainLdsMax, "LDS budget");
+};
+
 template <int RT, int CB>
 __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_kernel(const SdfValueChain c) {
   constexpr int WAVES = 8 / CB, THREADS = 64 * WAVES;
   constexpr int T = 32 * RT;
   constexpr int APLANE = T * CH_ALD;
+  using Lds = SdfValueLds<RT, CB>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* rs = reinterpret_cast<float*>(smem + 2 * APLANE);   // [T] 1 / row scale of the current layer input
-  float* pm = rs + T;                                        // [T][8] per-wave partial row maxima / partial dot products
-  float* cwb = pm + T * 8;                                   // [2][512] column scales | biases of the current / next layer
-  float* wtop = cwb + 1024;                                  // [256] sdf row of the top layer
+  float* rs = reinterpret_cast<float*>(smem + Lds::rs);
+  float* pm = reinterpret_cast<float*>(smem + Lds::pm);
+  float* cwb = reinterpret_cast<float*>(smem + Lds::cwb);
+  float* wtop = reinterpret_cast<float*>(smem + Lds::wtop);
   const int tid0 = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   const long ntiles = (c.P + T - 1) / T;
-  // per-lane indices are re-derived from a laundered copy of the thread index in every layer iteration: hoisted out of the loops they pin
-  // dozens of address registers for the whole kernel (29 - 33 spilled VGPRs before)
-#define VC_LANE_INDICES                                                                      \
-  int tid = tid0;                                                                            \
-  asm volatile("" : "+v"(tid));                                                              \
-  const int lane = tid & 63, half = lane >> 5, pt = lane & 31;                               \
-  const int cbase = wave * CB * 32 + 16 * half;   /* this lane's 16 consecutive output columns of its j-th block: cbase + 32 j */
 
   f16x8 wr1[4][CB], wr2[4][CB];                              // weight fragment ring: 4 k16 blocks in flight
-  auto wlane_of = [&](const FusedLayer& L, int lane_) __attribute__((always_inline)) { return L.Wf + (long)wave * CB * (L.K >> 4) * 1024 + lane_ * 8; };
-  auto wprime = [&](const FusedLayer& L, int lane_) __attribute__((always_inline)) { chain_wprime<CB>(wr1, wr2, wlane_of(L, lane_), L.K >> 4, 0, L.K >> 4); };
-  auto cw_fetch = [&](const FusedLayer& L, int tid_) __attribute__((always_inline)) {   // threads 0..127: one float4 of [column scales (256) | biases (256)]
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (tid_ < 64) v = *reinterpret_cast<const f4*>(L.wsc + tid_ * 4);
-    else if (tid_ < 128) v = *reinterpret_cast<const f4*>(L.bias + (tid_ - 64) * 4);
-    return v;
+  auto wprime = [&](const FusedLayer& L, int lane_) __attribute__((always_inline)) {
+    chain_wprime<CB>(wr1, wr2, chain_wlane<CB>(L.Wf, L.K >> 4, wave, lane_), L.K >> 4, 0, L.K >> 4);
   };
 
   wprime(c.lay[0], tid0 & 63);
   for (int i = tid0; i < 256; i += THREADS) wtop[i] = c.wtop[i];
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    // ---- layer-0 input: E rows -> planes (16 threads per row, 4 columns each); all row groups are requested before the first is converted
-    // (consumed one by one the compiler waits for each load before it issues the next: RT exposed round trips per tile)
-    constexpr int NPASS = T * 16 / THREADS;
+    const long tile0 = tile * T;
+    const int rows_left = (int)((c.P - tile0) < T ? (c.P - tile0) : T);              // rows of this tile that exist (>= 1)
     {
-    int tid = tid0;
-    asm volatile("" : "+v"(tid));
-    if (tid < 128) *reinterpret_cast<f4*>(cwb + tid * 4) = cw_fetch(c.lay[0], tid);
-    f4 erows[NPASS];
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-      const int row_l = pass * (THREADS / 16) + (tid >> 4), sc4 = (tid & 15) * 4;
-      long grow = tile * T + row_l; if (grow >= c.P) grow = c.P - 1;
-      erows[pass] = *reinterpret_cast<const f4*>(c.E + grow * kEmb + (sc4 < kEmb ? sc4 : 0));
-    }
-#pragma unroll
-    for (int pass = 0; pass < NPASS; ++pass) {
-      const int row_l = pass * (THREADS / 16) + (tid >> 4), sc4 = (tid & 15) * 4;
-      const f4 z4 = {0.f, 0.f, 0.f, 0.f};
-      const f4 v = sc4 < kEmb ? erows[pass] : z4;
-      float mx = ws_absmax4(v);
-      mx = cnr_max16(mx);
-      const float sc = split_row_scale(mx);
-      if (sc4 < kEmb) split_put4(v, sc, smem + row_l * CH_ALD + sc4 * 2, APLANE);
-      if ((tid & 15) == 0) rs[row_l] = cnr_pow2_rcp(sc);
-    }
+      // ---- layer-0 input: E rows -> planes
+      const ChainLane<CB> ln(tid0, wave);
+      chain_cw_park(cwb, ln.tid, chain_cw_fetch(c.lay[0], ln.tid));
+      chain_stage_rows<T, THREADS>(c.E, tile0, rows_left, ln.tid, smem, rs);
     }
     cnr_lds_barrier();
 
     for (int l = 0; l < c.nl; ++l) {
-      VC_LANE_INDICES
+      const ChainLane<CB> ln(tid0, wave);
       const FusedLayer& L = c.lay[l];
       const int nkb = L.K >> 4;
       const bool last = l + 1 == c.nl;
-      const unsigned short* wlane = wlane_of(L, lane);
-      const f4 cw_next = cw_fetch(c.lay[last ? l : l + 1], tid);   // lands while the MFMAs run; parked in LDS behind the row-max barrier
+      const FusedLayer& Ln = c.lay[last ? l : l + 1];
+      const unsigned short* wlane = chain_wlane<CB>(L.Wf, nkb, wave, ln.lane);
+      const f4 cw_next = chain_cw_fetch(Ln, ln.tid);   // lands while the MFMAs run; parked in LDS behind the row-max barrier
       f32x16 acc[CB][RT];
 #pragma unroll
       for (int j = 0; j < CB; ++j)
@@ -159,19 +143,20 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[j][rt][r] = 0.0f;
-      const unsigned char* Ab = smem + pt * CH_ALD + half * 16;
+      const unsigned char* Ab = smem + ln.pt * CH_ALD + ln.half * 16;
       // The k16 blocks of a layer are straight-line code (block count pinned at compile time), weight ring four blocks deep, scheduling fence
       // per block (chain_mfma_blocks in cnr_chain_util.h)
       if (nkb == 16) chain_mfma_blocks<RT, CB, 16>(acc, wr1, wr2, Ab, APLANE, wlane, 16, 0);
       else chain_mfma_blocks<RT, CB, 3>(acc, wr1, wr2, Ab, APLANE, wlane, 3, 0);
       // the next layer's (or the next tile's first layer's) leading weight blocks travel while the epilogue runs
-      wprime(last ? c.lay[0] : c.lay[l + 1], lane);
+      wprime(last ? c.lay[0] : c.lay[l + 1], ln.lane);
 
       // ---- epilogue: z = acc * (1 / row scale) * (1 / column scale) + bias ; a = softplus(z) ; skip concat ; row max
       const float* cw = cwb + (l & 1) * 512;
       const bool next_skip = !last && ((c.skip_mask >> (l + 1)) & 1);
       const float oscale = next_skip ? kInvSqrt2 : 1.0f;
       const bool ragged = L.N < 256;   // wave-uniform: only the layer in front of a skip connection (217 columns + 39 of e)
+      ChainActSoftplus act{next_skip};
       float red[RT], dotj[CB][RT];
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
@@ -181,120 +166,49 @@ __global__ __launch_bounds__(512 / CB, 2 / (3 - CB) + 0) void sdf_value_chain_ke
       }
 #pragma unroll
       for (int j = 0; j < CB; ++j) {
-        const int c0 = cbase + 32 * j;
-        f4 wsc4[4], b4[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          wsc4[q] = *reinterpret_cast<const f4*>(cw + c0 + 4 * q);
-          b4[q] = *reinterpret_cast<const f4*>(cw + 256 + c0 + 4 * q);
-        }
+        const int c0 = ln.cbase + 32 * j;
+        const ChainColumns k = chain_columns(cw, c0);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-          const int row_l = rt * 32 + pt;
-          const f2 rsc = pk_splat(rs[row_l]);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const f2 w = {wsc4[q >> 1][(2 * q) & 3], wsc4[q >> 1][(2 * q + 1) & 3]};
-            const f2 b = {b4[q >> 1][(2 * q) & 3], b4[q >> 1][(2 * q + 1) & 3]};
-            f2 a = {acc[j][rt][2 * q], acc[j][rt][2 * q + 1]};
-            a = pk_fma(a, rsc * w, b);                       // z = acc / (row scale * column scale) + bias
-            a = softplus100_pk(a);
-            if (next_skip) a = a * pk_splat(kInvSqrt2);
-            acc[j][rt][2 * q] = a.x; acc[j][rt][2 * q + 1] = a.y;
-          }
+          const int row_l = rt * 32 + ln.pt;
+          chain_affine16(acc[j][rt], k, rs[row_l], act);
           if (ragged && c0 + 16 > L.N) {
-            // columns >= N (only the lanes that own them enter): [softplus(z) | e] / sqrt(2) for a skip layer (fields.py:86-87), zero
-            // otherwise.  Branch-free per element: the e value is fetched from a clamped index and selected.
-            long grow = tile * T + row_l; if (grow >= c.P) grow = c.P - 1;
-            const float* erow = c.E + grow * kEmb;
-            float ev[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { const int ei = c0 + r - L.N; ev[r] = erow[ei < 0 ? 0 : (ei < kEmb ? ei : kEmb - 1)]; }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int ei = c0 + r - L.N;
-              const float tail = (next_skip && ei < c.emb) ? ev[r] * oscale : 0.0f;
-              acc[j][rt][r] = ei < 0 ? acc[j][rt][r] : tail;
-            }
+            const int row_c = row_l < rows_left ? row_l : rows_left - 1;
+            CHAIN_SKIP_TAIL(acc[j][rt], c0, L.N, c.E + tile0 * kEmb + row_c * kEmb, c.emb, next_skip, oscale)
           }
-          float mx = 0.0f, dot = 0.0f;
-          if (last) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const f4 wt = *reinterpret_cast<const f4*>(wtop + c0 + 4 * q);
-              dot = fmaf(acc[j][rt][4 * q], wt.x, dot); dot = fmaf(acc[j][rt][4 * q + 1], wt.y, dot);
-              dot = fmaf(acc[j][rt][4 * q + 2], wt.z, dot); dot = fmaf(acc[j][rt][4 * q + 3], wt.w, dot);
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(fabsf(acc[j][rt][r]), fabsf(acc[j][rt][r + 1])), mx);
-          }
-          if (last) dotj[j][rt] = dot; else red[rt] = fmaxf(red[rt], mx);
+          if (last) dotj[j][rt] = chain_dot16(acc[j][rt], wtop + c0);
+          else red[rt] = fmaxf(red[rt], chain_absmax16(acc[j][rt]));
         }
       }
-      // partial results per row: the row maximum per wave; the sdf dot product per 32-COLUMN BLOCK (its two 16-column halves added first), slot =
-      // block index -- the same 8 partial sums in the same order for every tile shape, so that the sdf of a point does not depend on how many points
-      // the call holds (round 6: a 1024-ray chunk of a view used to differ from the same rays inside a 65536-ray chunk by one ulp of sdf, because
-      // <2, 2> added the halves of two blocks first; bench.py now asserts that the two chunkings render the same image)
+      // partial results per row: the row maximum per wave; the sdf dot product per 32-column block, slot = block index (chain_partial_sum)
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
         if (last) {
 #pragma unroll
-          for (int j = 0; j < CB; ++j) {
-            const float both = cnr_pair32_sum(dotj[j][rt]);
-            if (half == 0) pm[(rt * 32 + pt) * 8 + wave * CB + j] = both;
-          }
+          for (int j = 0; j < CB; ++j) chain_partial_sum(pm, rt * 32 + ln.pt, wave * CB + j, ln.half, dotj[j][rt]);
         } else {
-          const float both = cnr_pair32_max(red[rt]);
-          if (half == 0) pm[(rt * 32 + pt) * 8 + wave] = both;
+          chain_partial_max(pm, rt * 32 + ln.pt, wave, ln.half, red[rt]);
         }
       }
       cnr_lds_barrier();   // partial maxima visible; every wave is done reading the planes of this layer's input
       if (!last) {
-        if (tid < 128) *reinterpret_cast<f4*>(cwb + ((l + 1) & 1) * 512 + tid * 4) = cw_next;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          const int row_l = rt * 32 + pt;
-          float mx = pm[row_l * 8];
-#pragma unroll
-          for (int w = 1; w < WAVES; ++w) mx = fmaxf(mx, pm[row_l * 8 + w]);
-          const float sc = split_row_scale(mx);
-#pragma unroll
-          for (int j = 0; j < CB; ++j) split_put16(acc[j][rt], sc, smem + row_l * CH_ALD + (cbase + 32 * j) * 2, APLANE);
-          if (wave == 0 && half == 0) rs[row_l] = cnr_pow2_rcp(sc);
-        }
+        chain_cw_park(cwb + ((l + 1) & 1) * 512, ln.tid, cw_next);
+        chain_replane<RT, CB, WAVES>(acc, pm, smem, rs, nullptr, nullptr, false, nullptr, tile0, rows_left, ln, wave);
       } else {
-        // sdf = (softplus(z_top-1) . w_sdf + b_sdf) * top_scale: the per-wave partial sums in a fixed order
-        for (int row = tid; row < T; row += THREADS) {
-          float sum = pm[row * 8];
-#pragma unroll
-          for (int w = 1; w < 8; ++w) sum += pm[row * 8 + w];   // (8 column blocks, whatever the number of waves)
-          const long grow = tile * T + row;
-          if (grow < c.P) c.sdf_out[grow] = (sum + c.btop[0]) * c.top_scale;
-        }
+        chain_sdf_finish<T>(pm, ln.tid, tile0, rows_left, c.btop, c.top_scale, c.sdf_out);
       }
       cnr_lds_barrier();
     }
   }
 }
 
-#undef VC_LANE_INDICES
-
 template <int RT, int CB>
 static void launch_sdf_value_chain(const SdfValueChain& c, cnr_stream s) {
-  constexpr int T = 32 * RT, THREADS = 512 / CB;
-  const size_t lds = (size_t)2 * T * CH_ALD + (size_t)T * 9 * sizeof(float) + (size_t)(1024 + 256) * sizeof(float);
-  static DeviceOnce attr_once;
-  if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sdf_value_chain_kernel<RT, CB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const long ntiles = (c.P + T - 1) / T;
-  const int wgs_env = debug_flags().chain_wgs;
-  const long wgs = wgs_env > 0 ? wgs_env : (lds * 2 <= 160 * 1024 ? 512 : 256);   // persistent: as many workgroups as the chip holds at once
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
+  using Lds = SdfValueLds<RT, CB>;
   double macs = 0.0;
   for (int l = 0; l < c.nl; ++l) macs += (double)c.lay[l].K * 256.0;
-  TimingScope ts_("chain_sdf_value", 3, RT * 10 + CB, c.P, (int)(macs / 256.0), 256, 1, s, (double)c.P * (kEmb + 1) * 4.0);
-  hipLaunchKernelGGL((sdf_value_chain_kernel<RT, CB>), dim3(grid), dim3(THREADS), lds, s, c);
+  chain_launch<&sdf_value_chain_kernel<RT, CB>>(c, 32 * RT, 512 / CB, Lds::total, chain_wgs_for(Lds::total), c.P, "chain_sdf_value", RT * 10 + CB, macs,
+                                                 (double)c.P * (kEmb + 1) * 4.0, s);
 }
 
 bool be_sdf_value_chain(const SdfValueChain& c, cnr_stream s) {
@@ -302,8 +216,10 @@ bool be_sdf_value_chain(const SdfValueChain& c, cnr_stream s) {
   if (off || c.P <= 0) return false;
   for (int l = 0; l < c.nl; ++l)
     if ((c.lay[l].K != 256 && c.lay[l].K != 48) || c.lay[l].N > 256 || c.lay[l].N < 1) return false;   // k16 block counts the kernel pins
+  // tile shape RT * 10 + CB: the tile heights of chain_rt_for (the saving chains' thresholds), two column blocks per wave below 128-point tiles
   const int force = debug_flags().chain_shape;   // tuning aid: 41, 22, 12
-  const int shape = force ? force : (c.P >= 256L * 128 ? 41 : (c.P >= 256L * 64 ? 22 : 12));
+  const int rt = chain_rt_for(c.P, 0);
+  const int shape = force ? force : (rt == 4 ? 41 : (rt == 2 ? 22 : 12));
   if (shape == 41) launch_sdf_value_chain<4, 1>(c, s);
   else if (shape == 22) launch_sdf_value_chain<2, 2>(c, s);
   else launch_sdf_value_chain<1, 2>(c, s);

@@ -33,99 +33,67 @@
 
 namespace cnr {
 
-// What the forward chains store for the backward pass is read again tens of launches later: as NON-TEMPORAL stores these rows do not displace the weight fragments
-// every tile streams from L2: +0.85 ... 1.0 % of the step against plain stores, same bits (profiles/r06_ab_nt_saved_activations.txt)
-#define CH_SAVE_STORE(p_, v_) __builtin_nontemporal_store((v_), reinterpret_cast<f4*>(p_))
+// The kernel's LDS image, stated once: the kernel carves its regions from these byte offsets, the launcher passes the total
+template <int RT>
+struct ReluChainLds {
+  static constexpr int T = 32 * RT;
+  static constexpr int rs = 2 * T * CH_ALD;                 // (in front: [2][T][CH_ALD] hi | lo planes; at the end of a chain [T][8][4] partial head dot products)  [T] 1 / row scale of the current step's input
+  static constexpr int rsf = rs + T * 4;                    // [T] the row scale itself (the extra segment is staged with it)
+  static constexpr int pm = rsf + T * 4;                    // [T][8] per-wave partial row maxima
+  static constexpr int cwb = pm + T * 8 * 4;                // [2][512] column scales | biases of the current / next step
+  static constexpr int rgbs = cwb + 2 * 512 * 4;            // [T][4] output of the colour head (rgb, 0)
+  static constexpr int tb = rgbs + T * 4 * 4;               // [8 waves][16 rows][128 B] transposition buffers
+  static constexpr int total = tb + 8 * 2048;
+  static_assert((size_t)total <= kChainLdsMax, "LDS budget");
+};
 
 template <int RT>
 __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainFwd c) {
   constexpr int T = 32 * RT;
   constexpr int APLANE = T * CH_ALD;
+  using Lds = ReluChainLds<RT>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* rs = reinterpret_cast<float*>(smem + 2 * APLANE);   // [T] 1 / row scale of the current step's input
-  float* rsf = rs + T;                                       // [T] the row scale itself (the extra segment is staged with it)
-  float* pm = rsf + T;                                       // [T][8] per-wave partial row maxima
-  float* cwb = pm + T * 8;                                   // [2][512] column scales | biases of the current / next step
-  float* rgbs = cwb + 1024;                                  // [T][4] output of the colour head (rgb, 0)
+  float* rs = reinterpret_cast<float*>(smem + Lds::rs);
+  float* rsf = reinterpret_cast<float*>(smem + Lds::rsf);
+  float* pm = reinterpret_cast<float*>(smem + Lds::pm);
+  float* cwb = reinterpret_cast<float*>(smem + Lds::cwb);
+  float* rgbs = reinterpret_cast<float*>(smem + Lds::rgbs);
   const int tid0 = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);   // (scalar: the per-wave bases below stay in SGPRs)
-  unsigned char* tb = reinterpret_cast<unsigned char*>(rgbs + T * 4) + wave * 2048;   // this wave's [16 rows][128 B] transposition buffer
+  unsigned char* tb = smem + Lds::tb + wave * 2048;          // this wave's [16 rows][128 B] transposition buffer
   float* hp = reinterpret_cast<float*>(smem);                // [T][8][4] partial head dot products (in the planes: dead at the end of a chain)
   const long P = c.P_dev != nullptr ? (long)*c.P_dev : c.P;   // (compacted runs: only the device knows how many rows there are)
   const int* const ridx = c.row_idx;
   const long ntiles = (P + T - 1) / T;
 
   f16x8 wr1[4][1], wr2[4][1];                                // weight fragment ring: 4 k16 blocks in flight
-  auto wlane_of = [&](const ChainFwdStep& S, int lane_) __attribute__((always_inline)) { return S.Wf + (long)wave * S.nkb_w * 1024 + lane_ * 8; };
-  auto cw_fetch = [&](const ChainFwdStep& S, int tid) __attribute__((always_inline)) {      // threads 0..127: one float4 of [column scales (256) | biases (256)]
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (tid < 64) v = *reinterpret_cast<const f4*>(S.wsc + tid * 4);
-    else if (tid < 128) v = *reinterpret_cast<const f4*>(S.bias + (tid - 64) * 4);
-    return v;
-  };
 
-  chain_wprime<1>(wr1, wr2, wlane_of(c.st[0], tid0 & 63), c.st[0].nkb_w, 0, c.st[0].nkb_main);
+  chain_wprime<1>(wr1, wr2, chain_wlane<1>(c.st[0].Wf, c.st[0].nkb_w, wave, tid0 & 63), c.st[0].nkb_w, 0, c.st[0].nkb_main);
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    if (tid0 < 128) *reinterpret_cast<f4*>(cwb + tid0 * 4) = cw_fetch(c.st[0], tid0);
+    const long tile0 = tile * T;
+    const int rows_left = (int)((P - tile0) < T ? (P - tile0) : T);                // rows of this tile that exist (>= 1)
+    chain_cw_park(cwb, tid0, chain_cw_fetch(c.st[0], tid0));
     for (int s = 0; s < c.nsteps; ++s) {
-      // The thread index is laundered once per step: every per-lane LDS / global offset below is derived from it, so the compiler recomputes
-      // them per step (a few integer operations) instead of hoisting dozens of loop-invariant addresses out of the loops and spilling them.
-      int tid = tid0;
-      asm volatile("" : "+v"(tid));
-      const int lane = tid & 63, half = lane >> 5, pt = lane & 31;
-      const int cbase = wave * 32 + 16 * half;               // this lane's 16 consecutive output columns
+      const ChainLane<1> ln(tid0, wave);
+      const int tid = ln.tid, lane = ln.lane, half = ln.half, pt = ln.pt, cbase = ln.cbase;
       const ChainFwdStep& S = c.st[s];
       const bool last_step = s + 1 == c.nsteps;
       const ChainFwdStep& Sn = c.st[last_step ? 0 : s + 1];
-      const unsigned short* wlane = wlane_of(S, lane);
-      const f4 cw_next = cw_fetch(Sn, tid);                       // lands while the MFMAs run; parked in LDS behind the row-max barrier
+      const unsigned short* wlane = chain_wlane<1>(S.Wf, S.nkb_w, wave, lane);
+      const f4 cw_next = chain_cw_fetch(Sn, tid);    // lands while the MFMAs run; parked in LDS behind the row-max barrier
       float hbias[3] = {0.f, 0.f, 0.f};                           // a head follows this step: its biases now (same reason as for the head's weight rows below)
       if (S.head != 0) {
         const ChainFwdHead& Hh = S.head == 1 ? c.col_head : c.rel_head;
 #pragma unroll
         for (int j = 0; j < 3; ++j) hbias[j] = Hh.bias[j < Hh.n ? j : 0];
       }
-      // ---- a chain starts: its input rows HBM -> registers -> exact row scale -> f16 planes (16 threads per row, 4 columns each)
-      f4 vx[RT];   // the extra input columns of the chain start's rows (x_src == 1): loaded with the row, staged after the main MFMA phase
+      // ---- a chain starts: its input rows -> planes, up to 256 main columns; the extra input columns of the rows (x_src == 1) are loaded with
+      // them and staged after the main MFMA phase
+      f4 vx[RT];
 #pragma unroll
       for (int pass = 0; pass < RT; ++pass) vx[pass] = f4{0.f, 0.f, 0.f, 0.f};
       if (S.in != nullptr) {
-        const int ncol = 16 * S.nkb_main, xcol = S.x_src == 1 ? 16 * S.nkb_x : 0;
-        const long tile0 = tile * T;
-        const int rows_left = (int)((P - tile0) < T ? (P - tile0) : T);              // rows of this tile that exist (>= 1)
-        const float* in_tile = S.in + (ridx != nullptr ? 0 : tile0 * S.ld_in);       // (uniform: scalar base + 32-bit lane offsets)
-        // all loads of the RT row groups first (one exposed memory round trip per chain start, not RT), then the conversion
-        const int sc4 = (tid & 15) * 4;
-        const f4 z4 = {0.f, 0.f, 0.f, 0.f};
-        f4 v0[RT], v1[RT], v2[RT], v3[RT];
-#pragma unroll
-        for (int pass = 0; pass < RT; ++pass) {
-          const int row_l = pass * 32 + (tid >> 4);
-          const int row_c = row_l < rows_left ? row_l : rows_left - 1;               // rows past the end read the last row (never stored)
-          const float* src = ridx != nullptr ? in_tile + (long)ridx[tile0 + row_c] * S.ld_in : in_tile + row_c * S.ld_in;
-          v0[pass] = z4; v1[pass] = z4; v2[pass] = z4; v3[pass] = z4; vx[pass] = z4;
-          if (sc4 < ncol) v0[pass] = *reinterpret_cast<const f4*>(src + sc4);
-          if (64 + sc4 < ncol) v1[pass] = *reinterpret_cast<const f4*>(src + 64 + sc4);
-          if (128 + sc4 < ncol) v2[pass] = *reinterpret_cast<const f4*>(src + 128 + sc4);
-          if (192 + sc4 < ncol) v3[pass] = *reinterpret_cast<const f4*>(src + 192 + sc4);
-          if (sc4 < xcol) vx[pass] = *reinterpret_cast<const f4*>(src + ncol + sc4);   // (here only its magnitude is used: one scale for the whole row)
-        }
-#pragma unroll
-        for (int pass = 0; pass < RT; ++pass) {
-          const int row_l = pass * 32 + (tid >> 4);
-          float mx = fmaxf(fmaxf(fmaxf(ws_absmax4(v0[pass]), ws_absmax4(v1[pass])), fmaxf(ws_absmax4(v2[pass]), ws_absmax4(v3[pass]))), ws_absmax4(vx[pass]));
-          mx = cnr_max16(mx);
-          const float sc = split_row_scale(mx);
-          unsigned char* dst = smem + row_l * CH_ALD + sc4 * 2;
-          if (sc4 < ncol) split_put4(v0[pass], sc, dst, APLANE);
-          if (64 + sc4 < ncol) split_put4(v1[pass], sc, dst + 128, APLANE);
-          if (128 + sc4 < ncol) split_put4(v2[pass], sc, dst + 256, APLANE);
-          if (192 + sc4 < ncol) split_put4(v3[pass], sc, dst + 384, APLANE);
-          if ((tid & 15) == 0) {
-            rs[row_l] = cnr_pow2_rcp(sc); rsf[row_l] = sc;
-            if (S.rs_in != nullptr && row_l < rows_left) S.rs_in[tile0 + row_l] = split_rs_value(mx, sc);
-          }
-        }
+        chain_stage_rows<T, 512, 4, true>(S.in, S.ld_in, 16 * S.nkb_main, S.x_src == 1 ? 16 * S.nkb_x : 0, ridx, tile0, rows_left, tid, smem, rs, rsf, S.rs_in, vx);
         cnr_lds_barrier();
       }
 
@@ -169,59 +137,26 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
         }
       }
       // the next step's (or the next tile's first step's) leading weight blocks travel while the epilogue runs
-      chain_wprime<1>(wr1, wr2, wlane_of(Sn, lane), Sn.nkb_w, 0, Sn.nkb_main);
+      chain_wprime<1>(wr1, wr2, chain_wlane<1>(Sn.Wf, Sn.nkb_w, wave, lane), Sn.nkb_w, 0, Sn.nkb_main);
 
       // ---- epilogue: a = relu(acc / (row scale * column scale) + bias) ; row max
       const float* cw = cwb + (s & 1) * 512;
       const bool chain_end = S.head != 0;                     // a head follows: the next step (if any) starts from global rows
       {
-        f4 wsc4[4], b4[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          wsc4[q] = *reinterpret_cast<const f4*>(cw + cbase + 4 * q);
-          b4[q] = *reinterpret_cast<const f4*>(cw + 256 + cbase + 4 * q);
-        }
+        const ChainColumns k = chain_columns(cw, cbase);
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
           const int row_l = rt * 32 + pt;
-          const f2 rsc = pk_splat(rs[row_l]);
-          float mx = 0.0f;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const f2 w = {wsc4[q >> 1][(2 * q) & 3], wsc4[q >> 1][(2 * q + 1) & 3]};
-            const f2 b = {b4[q >> 1][(2 * q) & 3], b4[q >> 1][(2 * q + 1) & 3]};
-            f2 a = {acc[rt][2 * q], acc[rt][2 * q + 1]};
-            a = pk_fma(a, rsc * w, b);
-            a.x = fmaxf(a.x, 0.0f); a.y = fmaxf(a.y, 0.0f);
-            acc[rt][2 * q] = a.x; acc[rt][2 * q + 1] = a.y;
-            mx = fmaxf(fmaxf(a.x, a.y), mx);
-          }
-          if (!chain_end) {
-            const float both = cnr_pair32_max(mx);
-            if (half == 0) pm[row_l * 8 + wave] = both;
-          }
+          ChainActRelu act;
+          chain_affine16(acc[rt], k, rs[row_l], act);
+          if (!chain_end) chain_partial_max(pm, row_l, wave, half, act.mx);
         }
       }
       cnr_lds_barrier();   // partial maxima visible; every wave is done reading the planes of this step's input
-      if (tid < 128) *reinterpret_cast<f4*>(cwb + ((last_step ? 0 : s + 1) & 1) * 512 + tid * 4) = cw_next;
+      chain_cw_park(cwb + ((last_step ? 0 : s + 1) & 1) * 512, tid, cw_next);
       if (!chain_end) {
         // ---- the next step's input planes (its extra segment, if it comes from the colour head, shares the row scale)
-        const bool with_rgb = Sn.x_src == 2;
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          const int row_l = rt * 32 + pt;
-          float mx = pm[row_l * 8];
-#pragma unroll
-          for (int w = 1; w < 8; ++w) mx = fmaxf(mx, pm[row_l * 8 + w]);
-          if (with_rgb) { const f4 g = *reinterpret_cast<const f4*>(rgbs + row_l * 4); mx = fmaxf(mx, ws_absmax4(g)); }
-          const float sc = split_row_scale(mx);
-          split_put16(acc[rt], sc, smem + row_l * CH_ALD + cbase * 2, APLANE);
-          if (wave == 0 && half == 0) {
-            rs[row_l] = cnr_pow2_rcp(sc); rsf[row_l] = sc;
-            const long grow = tile * T + row_l;
-            if (Sn.rs_in != nullptr && grow < P) Sn.rs_in[grow] = split_rs_value(mx, sc);
-          }
-        }
+        chain_replane<RT, 1, 8>(acc1, pm, smem, rs, rsf, rgbs, Sn.x_src == 2, Sn.rs_in, tile0, rows_left, ln, wave);
       }
       if (chain_end) {
         // ---- the 3-wide head on the ReLU output still in registers: fp32 dot products, partial sums per (row, wave) in a fixed order.
@@ -245,37 +180,11 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
           }
         }
       }
-      // ---- the ReLU output rows for the backward pass: 32 x 32 block -> LDS (16 rows at a time) -> 8 rows x 128 contiguous bytes per store
+      // ---- the ReLU output rows for the backward pass (read again only by the backward pass)
       if (S.save != nullptr && !(CNR_ABLATION(c.dbg) & 1)) {
-        const long tile0 = tile * T;
-        const int rows_left = (int)((P - tile0) < T ? (P - tile0) : T);
         float* save_tile = S.save + tile0 * S.ld_save + wave * 32;                   // (uniform)
-        const int sv_off = (lane >> 3) * S.ld_save + (lane & 7) * 4;                 // this lane's row / 16-byte chunk within an 8-row group
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-          for (int hpass = 0; hpass < 2; ++hpass) {
-            if ((pt >> 4) == hpass) {
-              const int r = pt & 15;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const f4 v = {acc[rt][4 * q], acc[rt][4 * q + 1], acc[rt][4 * q + 2], acc[rt][4 * q + 3]};
-                *reinterpret_cast<f4*>(tb + r * 128 + (((4 * half + q) ^ (r & 7)) << 4)) = v;
-              }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-              const int r = (lane >> 3) + 8 * i, ch = lane & 7;
-              const f4 v = *reinterpret_cast<const f4*>(tb + r * 128 + ((ch ^ (r & 7)) << 4));
-              const int row0 = rt * 32 + hpass * 16 + 8 * i;                         // first row of this 8-row group within the tile
-              if (row0 + (lane >> 3) < rows_left && !(CNR_ABLATION(c.dbg) & 8)) CH_SAVE_STORE(save_tile + row0 * S.ld_save + sv_off, v);   // (read again only by the backward pass)
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
+        for (int rt = 0; rt < RT; ++rt) chain_save_block<true, true>(acc[rt], tb, save_tile, S.ld_save, rt * 32, rows_left, lane, !(CNR_ABLATION(c.dbg) & 8));
       }
       if (chain_end) {
         const ChainFwdHead& H = S.head == 1 ? c.col_head : c.rel_head;
@@ -328,57 +237,45 @@ __global__ __launch_bounds__(512, 1) void relu_chain_fwd_kernel(const ReluChainF
 }
 
 // ------------------------------------------------------------------------------------------------
-// A wave's 32 x 32 output block (lane = row pt, 16 consecutive columns per half) -> global rows: through the wave's private 2 KB LDS buffer,
-// 16 rows at a time (XOR-swizzled 16-byte chunks: conflict-free both ways), stored as 8 rows x 128 contiguous bytes per instruction.
-// dst_tile: first row of the tile (uniform) + the wave's first column; row_base: the block's first row within the tile.
-// ------------------------------------------------------------------------------------------------
-template <bool NT = false>
-__device__ __forceinline__ void chain_save_block(const f32x16& a, unsigned char* tb, float* dst_tile, int ld, int row_base, int rows_left, int lane) {
-  const int half = lane >> 5, pt = lane & 31;
-  const int sv_off = (lane >> 3) * ld + (lane & 7) * 4;
-#pragma unroll
-  for (int hpass = 0; hpass < 2; ++hpass) {
-    if ((pt >> 4) == hpass) {
-      const int r = pt & 15;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f4 v = {a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
-        *reinterpret_cast<f4*>(tb + r * 128 + (((4 * half + q) ^ (r & 7)) << 4)) = v;
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = (lane >> 3) + 8 * i, ch = lane & 7;
-      const f4 v = *reinterpret_cast<const f4*>(tb + r * 128 + ((ch ^ (r & 7)) << 4));
-      const int row0 = row_base + hpass * 16 + 8 * i;
-      if (row0 + (lane >> 3) < rows_left) { if (NT) CH_SAVE_STORE(dst_tile + row0 * ld + sv_off, v); else *reinterpret_cast<f4*>(dst_tile + row0 * ld + sv_off) = v; }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // The SAVING SDF value chain (SdfSaveChain): sdf_value_chain_kernel<RT, 1> of cnr_chain.hip plus the stores the backward pass needs.
 // Per hidden layer: z = acc / (row scale x column scale) + bias is stored (through chain_save_block) BEFORE the activation; the layer in front
 // of a skip connection stores [z | e] (what the per-layer launches' tail fill writes) and hands [softplus(z) | e] / sqrt(2) to the next layer.
 // The top layer's 256 feature rows are one more MFMA step whose output goes straight to the colour network's input buffer.
+// Shared with the other two chains (cnr_chain_util.h): lane indices, weight-lane address, column-scale fetch / park, chain_save_block,
+// chain_absmax16, chain_dot16, chain_sdf_finish (the sdf's summation order: the same code as the value chain's), LDS layout, launcher.
+// Written out HERE, in the form this kernel has always had: the chain start, the epilogue affine, the skip tail, the softplus pass, the
+// partial-result stores and the replane.  With the shared blocks there (chain_stage_rows, chain_affine16, CHAIN_SKIP_TAIL, chain_replane ...)
+// the kernel has the registers of this form or fewer but 4741 instruction lines against 4673 in <4>, and the launch takes 2.21 ms against
+// 2.16 ms at 524 288 points (profiles/chain_refactor_ab.txt); as written it compiles to this form's instructions.
 // ------------------------------------------------------------------------------------------------
+// The kernel's LDS image, stated once: the kernel carves its regions from these byte offsets, the launcher passes the total
+template <int RT>
+struct SdfSaveLds {
+  static constexpr int T = 32 * RT;
+  static constexpr int rs = 2 * T * CH_ALD;                 // (in front: [2][T][CH_ALD] hi | lo planes)  [T] 1 / row scale of the current layer input
+  static constexpr int pm = rs + T * 4;                     // [T][8] per-wave partial row maxima
+  static constexpr int pd = pm + T * 8 * 4;                 // [T][8] per-wave partial dot products of the sdf row
+  static constexpr int cwb = pd + T * 8 * 4;                // [512] column scales | biases of the step in flight (rewritten behind the row-max barrier: every wave has read its values by then)
+  static constexpr int wtop = cwb + 512 * 4;                // [256] sdf row of the top layer
+  static constexpr int tb = wtop + 256 * 4;                 // [8 waves][16 rows][128 B] transposition buffers
+  static constexpr int total = tb + 8 * 2048;
+  static_assert((size_t)total <= kChainLdsMax, "LDS budget");
+};
+
 template <int RT>
 __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveChain c) {
   constexpr int T = 32 * RT;
   constexpr int APLANE = T * CH_ALD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* rs = reinterpret_cast<float*>(smem + 2 * APLANE);   // [T] 1 / row scale of the current layer input
-  float* pm = rs + T;                                        // [T][8] per-wave partial row maxima
-  float* pd = pm + T * 8;                                    // [T][8] per-wave partial dot products of the sdf row
-  float* cwb = pd + T * 8;                                   // [512] column scales | biases of the step in flight (rewritten behind the row-max barrier: every wave has read its values by then)
-  float* wtop = cwb + 512;                                   // [256] sdf row of the top layer
+  using Lds = SdfSaveLds<RT>;
+  float* rs = reinterpret_cast<float*>(smem + Lds::rs);
+  float* pm = reinterpret_cast<float*>(smem + Lds::pm);
+  float* pd = reinterpret_cast<float*>(smem + Lds::pd);
+  float* cwb = reinterpret_cast<float*>(smem + Lds::cwb);
+  float* wtop = reinterpret_cast<float*>(smem + Lds::wtop);
   const int tid0 = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-  unsigned char* tb = reinterpret_cast<unsigned char*>(wtop + 256) + wave * 2048;
+  unsigned char* tb = smem + Lds::tb + wave * 2048;
   const SdfValueChain& v = c.v;
   const long ntiles = (v.P + T - 1) / T;
   const int nsteps = v.nl + 1;                               // hidden layers + the feature rows of the top layer
@@ -386,23 +283,15 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
   // two kernel-argument references would make the compiler copy the argument block to scratch)
 
   f16x8 wr1[4][1], wr2[4][1];
-  auto wlane_of = [&](const FusedLayer& L, int lane_) __attribute__((always_inline)) { return L.Wf + (long)wave * (L.K >> 4) * 1024 + lane_ * 8; };
-  auto cw_fetch = [&](const FusedLayer& L, int tid) __attribute__((always_inline)) {
-    f4 x = {0.f, 0.f, 0.f, 0.f};
-    if (tid < 64) x = *reinterpret_cast<const f4*>(L.wsc + tid * 4);
-    else if (tid < 128) x = *reinterpret_cast<const f4*>(L.bias + (tid - 64) * 4);
-    return x;
-  };
-  chain_wprime<1>(wr1, wr2, wlane_of(v.lay[0], tid0 & 63), v.lay[0].K >> 4, 0, v.lay[0].K >> 4);
+  chain_wprime<1>(wr1, wr2, chain_wlane<1>(v.lay[0].Wf, v.lay[0].K >> 4, wave, tid0 & 63), v.lay[0].K >> 4, 0, v.lay[0].K >> 4);
   for (int i = tid0; i < 256; i += 512) wtop[i] = v.wtop[i];
   for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long tile0 = tile * T;
     const int rows_left = (int)((v.P - tile0) < T ? (v.P - tile0) : T);
     {
       // ---- layer-0 input: E rows -> planes (16 threads per row, 4 columns each)
-      int tid = tid0;
-      asm volatile("" : "+v"(tid));
-      if (tid < 128) *reinterpret_cast<f4*>(cwb + tid * 4) = cw_fetch(v.lay[0], tid);
+      const int tid = ChainLane<1>(tid0, wave).tid;
+      if (tid < 128) chain_cw_park(cwb, tid, chain_cw_fetch(v.lay[0], tid));   // (fetched by the threads that park: no load for the others)
       const int sc4 = (tid & 15) * 4;
       f4 x[RT];
 #pragma unroll
@@ -424,15 +313,13 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
       cnr_lds_barrier();
     }
     for (int l = 0; l < nsteps; ++l) {
-      int tid = tid0;
-      asm volatile("" : "+v"(tid));
-      const int lane = tid & 63, half = lane >> 5, pt = lane & 31;
-      const int cbase = wave * 32 + 16 * half;
+      const ChainLane<1> ln(tid0, wave);
+      const int tid = ln.tid, lane = ln.lane, half = ln.half, pt = ln.pt, cbase = ln.cbase;
       const bool is_top = l == v.nl, last_hidden = l + 1 == v.nl;
       const FusedLayer& L = v.lay[l];
       const FusedLayer& Ln = v.lay[is_top ? 0 : l + 1];
       const int nkb = L.K >> 4;
-      const f4 cw_next = cw_fetch(Ln, tid);
+      const f4 cw_next = chain_cw_fetch(Ln, tid);
       f32x16 acc1[1][RT];
       f32x16 (&acc)[RT] = acc1[0];
 #pragma unroll
@@ -440,9 +327,9 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[rt][r] = 0.0f;
       const unsigned char* Ab = smem + pt * CH_ALD + half * 16;
-      if (nkb == 16) chain_mfma_blocks<RT, 1, 16>(acc1, wr1, wr2, Ab, APLANE, wlane_of(L, lane), 16, 0);
-      else chain_mfma_blocks<RT, 1, 3>(acc1, wr1, wr2, Ab, APLANE, wlane_of(L, lane), 3, 0);
-      chain_wprime<1>(wr1, wr2, wlane_of(Ln, lane), Ln.K >> 4, 0, Ln.K >> 4);
+      if (nkb == 16) chain_mfma_blocks<RT, 1, 16>(acc1, wr1, wr2, Ab, APLANE, chain_wlane<1>(L.Wf, nkb, wave, lane), 16, 0);
+      else chain_mfma_blocks<RT, 1, 3>(acc1, wr1, wr2, Ab, APLANE, chain_wlane<1>(L.Wf, nkb, wave, lane), 3, 0);
+      chain_wprime<1>(wr1, wr2, chain_wlane<1>(Ln.Wf, Ln.K >> 4, wave, lane), Ln.K >> 4, 0, Ln.K >> 4);
 
       const float* cw = cwb;
       const bool next_skip = !is_top && !last_hidden && ((v.skip_mask >> (l + 1)) & 1);
@@ -497,20 +384,8 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
               if (next_skip) a = a * pk_splat(kInvSqrt2);
               acc[rt][2 * q] = a.x; acc[rt][2 * q + 1] = a.y;
             }
-            float mx = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) mx = fmaxf(fmaxf(fabsf(acc[rt][r]), fabsf(acc[rt][r + 1])), mx);
-            rmax[rt] = mx;
-            if (last_hidden) {
-              float dot = 0.0f;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const f4 wt = *reinterpret_cast<const f4*>(wtop + cbase + 4 * q);
-                dot = fmaf(acc[rt][4 * q], wt.x, dot); dot = fmaf(acc[rt][4 * q + 1], wt.y, dot);
-                dot = fmaf(acc[rt][4 * q + 2], wt.z, dot); dot = fmaf(acc[rt][4 * q + 3], wt.w, dot);
-              }
-              rdot[rt] = dot;
-            }
+            rmax[rt] = chain_absmax16(acc[rt]);
+            if (last_hidden) rdot[rt] = chain_dot16(acc[rt], wtop + cbase);
           }
         }
       }
@@ -523,7 +398,7 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
         }
       }
       cnr_lds_barrier();   // partial maxima / dots visible; every wave is done reading the planes of this step's input
-      if (tid < 128) *reinterpret_cast<f4*>(cwb + tid * 4) = cw_next;
+      chain_cw_park(cwb, tid, cw_next);
       if (!is_top) {
         float* rso = c.rs[l + 1];
 #pragma unroll
@@ -539,13 +414,7 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
             if (rso != nullptr && row_l < rows_left) rso[tile0 + row_l] = split_rs_value(mx, sc);
           }
         }
-        if (last_hidden && tid < T) {
-          // sdf = (softplus(z_top-1) . w_sdf + b_sdf) * top_scale: the per-wave partial sums in a fixed order
-          float sum = pd[tid * 8];
-#pragma unroll
-          for (int w = 1; w < 8; ++w) sum += pd[tid * 8 + w];
-          if (tid < rows_left) v.sdf_out[tile0 + tid] = (sum + v.btop[0]) * v.top_scale;
-        }
+        if (last_hidden) chain_sdf_finish<T>(pd, tid, tile0, rows_left, v.btop, v.top_scale, v.sdf_out);
       }
       cnr_lds_barrier();
     }
@@ -554,22 +423,11 @@ __global__ __launch_bounds__(512, 1) void sdf_save_chain_kernel(const SdfSaveCha
 
 template <int RT>
 static void launch_sdf_save_chain(const SdfSaveChain& c, cnr_stream s) {
-  constexpr int T = 32 * RT;
-  const size_t lds = (size_t)2 * T * CH_ALD + (size_t)T * 17 * sizeof(float) + (size_t)(512 + 256) * sizeof(float) + (size_t)8 * 2048;
-  static_assert((size_t)2 * T * CH_ALD + (size_t)T * 17 * sizeof(float) + (size_t)(512 + 256) * sizeof(float) + (size_t)8 * 2048 <= 160 * 1024, "LDS budget");
-  static DeviceOnce attr_once;
-  if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sdf_save_chain_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const long ntiles = (c.v.P + T - 1) / T;
-  const int wgs_env = debug_flags().chain_wgs;
-  const long wgs = wgs_env > 0 ? wgs_env : 256;
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
   double macs = 256.0 * 256.0, bytes = (double)c.v.P * ((kEmb + 1) * 4.0 + 1024.0);
   for (int l = 0; l < c.v.nl; ++l) { macs += (double)c.v.lay[l].K * 256.0; bytes += (double)c.v.P * (1024.0 + (c.rs[l + 1] ? 4.0 : 0.0)); }
-  TimingScope ts_("chain_sdf_fwd", 3, RT * 10 + 1, c.v.P, (int)(macs / 256.0), 256, 1, s, bytes);
   SdfSaveChain cc = c;
   cc.v.lay[c.v.nl] = c.top;
-  hipLaunchKernelGGL((sdf_save_chain_kernel<RT>), dim3(grid), dim3(512), lds, s, cc);
+  chain_launch<&sdf_save_chain_kernel<RT>>(cc, 32 * RT, 512, SdfSaveLds<RT>::total, 256, c.v.P, "chain_sdf_fwd", RT * 10 + 1, macs, bytes, s);
 }
 
 bool be_sdf_save_chain(const SdfSaveChain& c, cnr_stream s) {
@@ -581,8 +439,7 @@ bool be_sdf_save_chain(const SdfSaveChain& c, cnr_stream s) {
     if (l + 1 < v.nl && v.lay[l].N < 256 && !((v.skip_mask >> (l + 1)) & 1)) return false;   // a narrow layer only in front of a skip connection
   }
   if (v.lay[v.nl - 1].N != 256 || c.top.K != 256 || c.top.N != 256 || !c.top.Wf || !c.feat || (c.ld_feat & 3) || (c.ldz & 3) || c.ldz < 256) return false;
-  const int force = debug_flags().chain_fwd_rt;
-  const int rt = force ? force : (v.P >= 256L * 128 ? 4 : (v.P >= 256L * 64 ? 2 : 1));
+  const int rt = chain_rt_for(v.P, debug_flags().chain_fwd_rt);
   if (rt == 4) launch_sdf_save_chain<4>(c, s);
   else if (rt == 2) launch_sdf_save_chain<2>(c, s);
   else launch_sdf_save_chain<1>(c, s);
@@ -592,15 +449,6 @@ bool be_sdf_save_chain(const SdfSaveChain& c, cnr_stream s) {
 
 template <int RT>
 static void launch_relu_chain_fwd(const ReluChainFwd& c, cnr_stream s) {
-  constexpr int T = 32 * RT;
-  const size_t lds = (size_t)2 * T * CH_ALD + (size_t)T * (2 + 8 + 4) * sizeof(float) + (size_t)1024 * sizeof(float) + (size_t)8 * 2048;
-  static DeviceOnce attr_once;
-  if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&relu_chain_fwd_kernel<RT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  const long ntiles = (c.P + T - 1) / T;
-  const int wgs_env = debug_flags().chain_wgs;
-  const long wgs = wgs_env > 0 ? wgs_env : 256;   // persistent, one workgroup per CU
-  const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
   double macs = 0.0, bytes = 0.0;
   for (int i = 0; i < c.nsteps; ++i) {
     const ChainFwdStep& S = c.st[i];
@@ -610,11 +458,9 @@ static void launch_relu_chain_fwd(const ReluChainFwd& c, cnr_stream s) {
     if (S.rs_in) bytes += (double)c.P * 4.0;
     if (S.head) bytes += (double)c.P * (S.head == 1 ? (c.rgb_tail ? 80.0 : 16.0) : 28.0);
   }
-  TimingScope ts_("chain_fwd", 3, RT * 10 + 1, c.P, (int)(macs / 256.0), 256, 1, s, bytes);
-  const int dbg = debug_flags().chain_fwd_dbg;
   ReluChainFwd cc = c;
-  cc.dbg = dbg;
-  hipLaunchKernelGGL((relu_chain_fwd_kernel<RT>), dim3(grid), dim3(512), lds, s, cc);
+  cc.dbg = debug_flags().chain_fwd_dbg;
+  chain_launch<&relu_chain_fwd_kernel<RT>>(cc, 32 * RT, 512, ReluChainLds<RT>::total, 256, c.P, "chain_fwd", RT * 10 + 1, macs, bytes, s);   // (one workgroup per CU)
 }
 
 bool be_relu_chain_fwd_enabled() {
@@ -642,8 +488,7 @@ bool be_relu_chain_fwd(const ReluChainFwd& c, cnr_stream s) {
     if (S.head == 2 && (!c.rel_head.W || c.rel_head.n < 1 || c.rel_head.n > 3 || (c.rel_head.ldw & 3) || !c.delta || !c.relit)) return false;
   }
   if (c.st[c.nsteps - 1].head == 0) return false;
-  const int force = debug_flags().chain_fwd_rt;   // tuning aid: 4, 2, 1
-  const int rt = force ? force : (c.P >= 256L * 128 ? 4 : (c.P >= 256L * 64 ? 2 : 1));
+  const int rt = chain_rt_for(c.P, debug_flags().chain_fwd_rt);   // (tuning aid: 4, 2, 1)
   if (rt == 4) launch_relu_chain_fwd<4>(c, s);
   else if (rt == 2) launch_relu_chain_fwd<2>(c, s);
   else launch_relu_chain_fwd<1>(c, s);

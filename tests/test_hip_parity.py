@@ -475,6 +475,35 @@ def test_fused_sdf_chain_matches_per_layer_kernels(tmp_path):
             assert float(np.abs(a.reshape(-1) - ref).max()) < 2e-5 * scale, n
 
 
+def test_sdf_does_not_depend_on_the_tile_shape_of_its_call():
+    """The sdf of a point is the same to the bit whatever tile shape the call that holds it runs with: the same first 100 points inside calls of
+    100, 16391 and 32771 points (tile shapes <1, 2>, <2, 2> and <4, 1> of the value chain, each call with a ragged last tile).  The shared dot /
+    finish blocks (chain_dot16, chain_partial_sum, chain_sdf_finish in cnr_chain_util.h) add a row's 8 per-block partial sums in slot order for
+    every shape.  The shapes are read from the launch records (chain_sdf_value: RT * 10 + CB), not assumed from the thresholds."""
+    from oracle import colorneus_oracle as O
+    ocfg = O.dtu_config()
+    r = N.make_renderer(ocfg, O.init_params(ocfg, seed=0, dtype=torch.float32, trained_like=True), None, DEV)
+    pts = (torch.rand(32771, 3, generator=torch.Generator().manual_seed(23)) * 2 - 1).to(DEV)
+    lib = r._lib
+    res, shapes = {}, {}
+    torch.cuda.synchronize()
+    lib.timing_enable(True)
+    try:
+        for n in (100, 16391, 32771):
+            lib.timing_collect()
+            res[n] = r.sdf(pts[:n])[:100].cpu().numpy()
+            torch.cuda.synchronize()
+            shapes[n] = [(rec[2], rec[3]) for rec in lib.timing_collect() if rec[0] == "chain_sdf_value"]
+    finally:
+        lib.timing_enable(False)
+    for n, (shape, tile) in {100: (12, 32), 16391: (22, 64), 32771: (41, 128)}.items():
+        assert shapes[n] == [(shape, n)], (n, shapes[n])      # one launch over all n points in that shape ...
+        assert n % tile != 0                                  # ... with a ragged last tile
+    assert np.isfinite(res[100]).all() and float(np.abs(res[100]).max()) > 0.0
+    for n in (16391, 32771):
+        assert np.array_equal(res[100].view(np.uint32), res[n].view(np.uint32)), (n, int((res[100] != res[n]).sum()))
+
+
 _CHAIN_CHILD = r"""
 import sys, os
 root, out = sys.argv[1], sys.argv[2]
