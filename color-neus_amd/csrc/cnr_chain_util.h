@@ -381,14 +381,12 @@ inline long chain_wgs_for(size_t lds) { return lds * 2 <= kChainLdsMax ? 512 : 2
 // at once; CNR_CHAIN_WGS of the tuning build overrides), launch record (kind = RT * 10 + CB), launch.
 template <auto Kernel, class Arg>
 void chain_launch(const Arg& arg, int T, int threads, size_t lds, long wgs, long P, const char* name, int kind, double macs, double bytes, cnr_stream s) {
-  static DeviceOnce attr_once;
-  if (attr_once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainLdsMax);
   const long ntiles = (P + T - 1) / T;
   const int wgs_env = debug_flags().chain_wgs;
   if (wgs_env > 0) wgs = wgs_env;
   const unsigned grid = (unsigned)(ntiles < wgs ? ntiles : wgs);
   TimingScope ts_(name, 3, kind, P, (int)(macs / 256.0), 256, 1, s, bytes);
-  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(threads), lds, s, arg);
+  launch_lds<Kernel>(dim3(grid), dim3(threads), lds, kChainLdsMax, s, arg);
 }
 
 }  // namespace cnr

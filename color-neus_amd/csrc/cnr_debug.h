@@ -31,7 +31,7 @@
 //   CNR_ROCTX                roctx             roctx ranges around the phases of the forward / backward calls
 //   -- CNR_TUNING build only (constants otherwise) --
 //   CNR_WS_KINDS (0xffff) CNR_WS_MINW (96) CNR_WS_WGS (256) CNR_WS_MINTPW (1) CNR_CHAIN_WGS (0 = default) CNR_CHAIN_SHAPE (0; 41 | 22 | 12)
-//   CNR_CHAIN_FWD_RT (0; 4 | 2 | 1) CNR_CHAIN_SDF_MAXP (unbounded) CNR_FDW_DEEP (0; bit 0 / 1: deeper prefetch of the P / D waves)
+//   CNR_CHAIN_FWD_RT (0; 4 | 2 | 1) CNR_CHAIN_SDF_MAXP (unbounded)
 //   CNR_FDW_NOREV (0) CNR_FDW_REVMODE (0) and the ABLATION words CNR_FDW_DBG / CNR_CHAIN_FWD_DBG (parts of a kernel switched off: WRONG results)
 #pragma once
 
@@ -43,11 +43,11 @@ struct DebugFlags {
        no_narrow_dx = false, disable_ws = false, ws_generic = false, ws_nostream = false, dw_fp32 = false, dw_bf16 = false, roctx = false;
   int ws_serp = 1;
 #ifdef CNR_TUNING
-  int ws_kinds = 0xffff, ws_minw = 96, ws_wgs = 256, ws_mintpw = 1, chain_wgs = 0, chain_shape = 0, chain_fwd_rt = 0, fdw_deep = 0, fdw_norev = 0,
+  int ws_kinds = 0xffff, ws_minw = 96, ws_wgs = 256, ws_mintpw = 1, chain_wgs = 0, chain_shape = 0, chain_fwd_rt = 0, fdw_norev = 0,
       fdw_revmode = 0, fdw_dbg = 0, chain_fwd_dbg = 0;
   long chain_sdf_maxp = 1L << 62;
 #else
-  static constexpr int ws_kinds = 0xffff, ws_minw = 96, ws_wgs = 256, ws_mintpw = 1, chain_wgs = 0, chain_shape = 0, chain_fwd_rt = 0, fdw_deep = 0,
+  static constexpr int ws_kinds = 0xffff, ws_minw = 96, ws_wgs = 256, ws_mintpw = 1, chain_wgs = 0, chain_shape = 0, chain_fwd_rt = 0,
                        fdw_norev = 0, fdw_revmode = 0, fdw_dbg = 0, chain_fwd_dbg = 0;
   static constexpr long chain_sdf_maxp = 1L << 62;
 #endif

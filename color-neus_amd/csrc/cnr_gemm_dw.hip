@@ -17,6 +17,27 @@ namespace cnr {
 // points per slab: 16 for the square tile; the skinny tail tiles are latency-bound streams, so they take as many as LDS holds
 constexpr int dw_bp(int tn, int tk) { return tn + tk <= 288 ? 64 : (tn + tk <= 320 ? 48 : 16); }
 
+// a wave's [MT x KT] accumulator blocks of 32 x 32 (lane map of the 32 x 32 MFMAs) into the workgroup's partial-sum slot [Npad][ldk], rows from n0,
+// columns from k0 (both with the wave's offset), times the exact factors u1 * u2 where the sums carry a block exponent (UNDO)
+template <bool UNDO, int MT, int KT>
+__device__ __forceinline__ void dw_store_partial(float* out, const DwGemm& g, const f32x16 (&acc)[MT][KT], int n0, int k0, int lane, float u1 = 1.0f, float u2 = 1.0f) {
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+      const int kk = k0 + j * 32 + (lane & 31);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = n0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (n < g.Npad && kk < g.ldk) out[(long)n * g.ldk + kk] = UNDO ? acc[i][j][r] * u1 * u2 : acc[i][j][r];
+      }
+    }
+}
+// the view kinds of the operand pairs of a launch, for the dispatch onto the instantiations with pinned kinds (-1: no second pair)
+struct DwKinds { int x0, y0, x1, y1; };
+static DwKinds dw_kinds(const DwGemm& g) { return {g.X[0].kind, g.Y[0].kind, g.npairs > 1 ? g.X[1].kind : -1, g.npairs > 1 ? g.Y[1].kind : -1}; }
+#define DW_KINDS_CASE(launch_, k_, A_, B_, C_, D_) if (k_.x0 == A_ && k_.y0 == B_ && k_.x1 == C_ && k_.y1 == D_) { launch_<A_, B_, C_, D_>(g, n0, k0, s); return; }
+
 template <int WR, int WC, int MT, int KT, int KINDS = 0>
 __global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, int k0) {
   constexpr int TN = WR * MT * 32, TK = WC * KT * 32;
@@ -146,18 +167,7 @@ __global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, in
 #undef DW_FETCH_
 #undef DW_FINISH_
 
-  float* out = g.partial + chunk * (long)g.Npad * g.ldk;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < KT; ++j) {
-      const int kk = k0 + wc * KT * 32 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wr * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (n < g.Npad && kk < g.ldk) out[(long)n * g.ldk + kk] = acc[i][j][r];
-      }
-    }
+  dw_store_partial<false>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * MT * 32, k0 + wc * KT * 32, lane);
   if (want_colsum && tid < TN && n0 + tid < g.Npad) g.colsum[chunk * g.Npad + n0 + tid] = csum;
 }
 
@@ -166,13 +176,9 @@ static void launch_dw(const DwGemm& g, int n0, int k0, cnr_stream s) {
   constexpr int TN = WR * MT * 32, TK = WC * KT * 32;
   constexpr int DW_BP = dw_bp(TN, TK);
   const size_t lds = (size_t)(2 * DW_BP * (TN + TK)) * sizeof(float);
-  static DeviceOnce attr_once;   // the opt-in is per device
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_gemm_kernel<WR, WC, MT, KT, KINDS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   const int tn_ = (g.N - n0) < TN ? (g.N - n0) : TN, tk_ = (g.K - k0) < TK ? (g.K - k0) : TK;
   TimingScope ts_("dw_gemm", 1, WR * 1000 + WC * 100 + MT * 10 + KT, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  hipLaunchKernelGGL((dw_gemm_kernel<WR, WC, MT, KT, KINDS>), dim3(g.nchunk), dim3(512), lds, s, g, n0, k0);
+  launch_lds<dw_gemm_kernel<WR, WC, MT, KT, KINDS>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
 }
 
 // ================================================================================================
@@ -342,18 +348,7 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_bx_kernel(const DwGemm g_in, i
 #undef DX_FETCH_
 #undef DX_FINISH_
 
-  float* out = g.partial + chunk * (long)g.Npad * g.ldk;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kk = k0 + wc * 128 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (n < g.Npad && kk < g.ldk) out[(long)n * g.ldk + kk] = acc[i][j][r];
-      }
-    }
+  dw_store_partial<false>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * 64, k0 + wc * 128, lane);
   if (want_colsum) {   // bias gradient: the four point-quad owners of a column group add their sums in a fixed order
     float* cs = reinterpret_cast<float*>(smem_d);          // [4 quads][256 columns]; the slab buffers are dead now
     if (!is_y) *reinterpret_cast<f4*>(cs + q * 256 + c4 * 4) = csum;
@@ -365,25 +360,19 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_bx_kernel(const DwGemm g_in, i
 template <int XK0, int YK0, int XK1, int YK1>
 static void launch_dw_bx_t(const DwGemm& g, int n0, int k0, cnr_stream s) {
   const size_t lds = (size_t)2 * DX_BUF;
-  static DeviceOnce attr_once;   // the opt-in is per device
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_gemm_bx_kernel<XK0, YK0, XK1, YK1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   const int tn_ = (g.N - n0) < 256 ? (g.N - n0) : 256, tk_ = (g.K - k0) < 256 ? (g.K - k0) : 256;
   TimingScope ts_("dw_gemm_bx", 1, 4224, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  hipLaunchKernelGGL((dw_gemm_bx_kernel<XK0, YK0, XK1, YK1>), dim3(g.nchunk), dim3(512), lds, s, g, n0, k0);
+  launch_lds<dw_gemm_bx_kernel<XK0, YK0, XK1, YK1>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
 }
 
 static void launch_dw_bx(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const int x0 = g.X[0].kind, y0 = g.Y[0].kind, x1 = g.npairs > 1 ? g.X[1].kind : -1, y1 = g.npairs > 1 ? g.Y[1].kind : -1;
-#define DX_CASE(A_, B_, C_, D_) if (x0 == A_ && y0 == B_ && x1 == C_ && y1 == D_) { launch_dw_bx_t<A_, B_, C_, D_>(g, n0, k0, s); return; }
+  const DwKinds k = dw_kinds(g);
   // the operand combinations of the render plan (cnr_plan.cpp): MLP layers, SDF value + gradient-chain pairs
-  DX_CASE(VK_DIRECT, VK_DIRECT, -1, -1)
-  DX_CASE(VK_DIRECT, VK_SOFTPLUS, -1, -1)
-  DX_CASE(VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
-  DX_CASE(VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
-  DX_CASE(VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT)
-#undef DX_CASE
+  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_DIRECT, -1, -1)
+  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, -1, -1)
+  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
+  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
+  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT)
   launch_dw_bx_t<-1, -1, -1, -1>(g, n0, k0, s);
 }
 
@@ -558,19 +547,7 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
 
   // undo 2^G in two exact steps (G can exceed the fp32 exponent range of a single factor)
   const SplitPow2 un = split_pow2(-G);
-  const float u1 = un.u1, u2 = un.u2;
-  float* out = g.partial + chunk * (long)g.Npad * g.ldk;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int kk = k0 + wc * 128 + j * 32 + (lane & 31);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (n < g.Npad && kk < g.ldk) out[(long)n * g.ldk + kk] = acc[i][j][r] * u1 * u2;
-      }
-    }
+  dw_store_partial<true>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * 64, k0 + wc * 128, lane, un.u1, un.u2);
   if (want_colsum) {
     float* cs = reinterpret_cast<float*>(smem_d);
     if (!is_y) *reinterpret_cast<f4*>(cs + q * 256 + c4 * 4) = csum;
@@ -582,23 +559,17 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, i
 template <int XK0, int YK0, int XK1, int YK1>
 static void launch_dw_hx_t(const DwGemm& g, int n0, int k0, cnr_stream s) {
   const size_t lds = (size_t)2 * DH_BUF;
-  static DeviceOnce attr_once;   // the opt-in is per device
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_gemm_hx_kernel<XK0, YK0, XK1, YK1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   const int tn_ = (g.N - n0) < 256 ? (g.N - n0) : 256, tk_ = (g.K - k0) < 256 ? (g.K - k0) : 256;
   TimingScope ts_("dw_gemm_hx", 1, 4224, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  hipLaunchKernelGGL((dw_gemm_hx_kernel<XK0, YK0, XK1, YK1>), dim3(g.nchunk), dim3(512), lds, s, g, n0, k0);
+  launch_lds<dw_gemm_hx_kernel<XK0, YK0, XK1, YK1>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
 }
 
 static void launch_dw_hx(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const int x0 = g.X[0].kind, y0 = g.Y[0].kind, x1 = g.npairs > 1 ? g.X[1].kind : -1, y1 = g.npairs > 1 ? g.Y[1].kind : -1;
-#define DH_CASE(A_, B_, C_, D_) if (x0 == A_ && y0 == B_ && x1 == C_ && y1 == D_) { launch_dw_hx_t<A_, B_, C_, D_>(g, n0, k0, s); return; }
-  DH_CASE(VK_DIRECT, VK_DIRECT, -1, -1)
-  DH_CASE(VK_DIRECT, VK_SOFTPLUS, -1, -1)
-  DH_CASE(VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
-  DH_CASE(VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
-#undef DH_CASE
+  const DwKinds k = dw_kinds(g);
+  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_DIRECT, -1, -1)
+  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, -1, -1)
+  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
+  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
   launch_dw_hx_t<-1, -1, -1, -1>(g, n0, k0, s);
 }
 
@@ -708,14 +679,10 @@ __global__ __launch_bounds__(SK_WAVES * 64) void dw_skinny_kernel(const DwGemm g
 template <bool NARROW_X, bool NG2, int KINDS>
 static void launch_dw_skinny_td(const DwGemm& g, int n0, int k0, int ncnt, cnr_stream s) {
   const size_t lds = ((size_t)SK_WAVES * 8 * 256 + SK_WAVES * 8) * sizeof(float);
-  static DeviceOnce attr_once;   // the opt-in is per device
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dw_skinny_kernel<NARROW_X, NG2, KINDS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   const int wide = NARROW_X ? ((g.K - k0) < 256 ? (g.K - k0) : 256) : ((g.N - n0) < 256 ? (g.N - n0) : 256);
   const int tn_ = NARROW_X ? ncnt : wide, tk_ = NARROW_X ? wide : ncnt;
   TimingScope ts_("dw_skinny", 1, NARROW_X ? 1 : 2, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  hipLaunchKernelGGL((dw_skinny_kernel<NARROW_X, NG2, KINDS>), dim3(g.nchunk), dim3(SK_WAVES * 64), lds, s, g, n0, k0, ncnt);
+  launch_lds<dw_skinny_kernel<NARROW_X, NG2, KINDS>>(dim3(g.nchunk), dim3(SK_WAVES * 64), lds, lds, s, g, n0, k0, ncnt);
 }
 
 template <bool NARROW_X, bool NG2>

@@ -30,7 +30,6 @@ namespace cnr {
 // (profiles/r06_mfma_shapes.txt: 1950 against 1705 TFLOP/s with the matrix pipe alone at the board's power limit) -- and this kernel's time is its joules.
 // So product and weight gradient run on 16 x 16 x 32 blocks (same LDS planes, same register budget: 128 weight registers, 16 / 128 accumulators);
 // the 32 x 32 x 16 form was 2 % slower per step (profiles/r06_ab_mfma16_layer_dw.txt) and was removed.
-typedef float fd_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int FD_TP = 32;                        // points per tile
 constexpr int FD_ALD = 256 * 2 + 16;             // bytes per LDS row of one S plane (+16: conflict-free ds_read_b128 of the product fragments)
 constexpr int FD_APLANE = FD_TP * FD_ALD;
@@ -38,7 +37,7 @@ constexpr int FD_ABUF = 2 * FD_APLANE + 256;     // two planes + rs[32] (1 / row
 constexpr int FD_YLD = 128 * 2 + 16;             // bytes per POINT row of one Ep' plane (round 6: row-major [point][column], see fd_tr8): 128 columns x 2 B + 16
 constexpr int FD_YPLANE = FD_TP * FD_YLD;
 constexpr int FD_YBUF = 2 * FD_YPLANE;
-constexpr int FD_TLD = 36;
+constexpr int FD_TLD = WS_TLD;
 constexpr int FD_TBYTES = 32 * FD_TLD * 4;       // accumulator transposition buffer of one P wave
 constexpr int FD_OFF_Y = 3 * FD_ABUF;
 constexpr int FD_OFF_T = FD_OFF_Y + 2 * FD_YBUF;
@@ -71,14 +70,12 @@ __device__ __forceinline__ f4 fd_ep4(const Epi& e, const EpiRaw4& raw) {
 }
 
 
-// DP: the P waves keep the epilogue side inputs of TWO tiles in flight (tile i + 2 is requested while tile i is finished);
-// DD: the D waves keep two input tiles in flight (tile i + 3 is requested when tile i + 1 has been converted).
 // NKB: k16 blocks of the layer product (16; 14 for the 217-wide SDF layer in front of the skip connection, whose pad columns are zero)
 // XR: DwFuse::xrow_mode (0 none; 1 column sums of the o2 output of an EK_SWEEP launch; 2 EK_VBACK launch with k_extra: rank-one update of the
 // product by A column 256 and the row of that column's products with Ep) -- the sdf row of the 257-wide top SDF layer, see cnr_plan.cpp
 // TAILF: the epilogue keeps its tail fill (sweep launch of the layer below a skip connection) and runs the general 16-byte epilogue code
 // SPLITF: the value-backward epilogue keeps its split point (layer fed by a skip connection; see fdw_shape_ok), general 16-byte epilogue code
-template <int EK, bool DP, bool DD, int NKB = 16, int XR = 0, bool TAILF = false, bool SPLITF = false>
+template <int EK, int NKB = 16, int XR = 0, bool TAILF = false, bool SPLITF = false>
 __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, const DwFuse f, int tiles_per_range, int dbg_in) {
   const int dbg = CNR_ABLATION(dbg_in);   // (CNR_FDW_DBG of the tuning build: parts of the kernel switched off; the constant 0 in the product build)
   LayerGemm g = g_in;
@@ -108,17 +105,12 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
   // blocks b and b + 8 (same XCD under the observed round-robin placement: a speed matter only) are the two column halves of one range
   const int b = blockIdx.x;
   const int half = (b >> 3) & 1, range = (b >> 4) * 8 + (b & 7);
-  const long ntiles = g.P / FD_TP;
-  const long t0 = (long)range * tiles_per_range;
-  const int n = t0 < ntiles ? (int)((ntiles - t0) < tiles_per_range ? (ntiles - t0) : tiles_per_range) : 0;
+  // f.rev: this launch walks every range downwards: consecutive launches of a backward chain alternate (WsRange).  Fixed per launch site: deterministic
+  const WsRange R(g.P / FD_TP, (long)range * tiles_per_range, tiles_per_range, f.rev);
+  const int n = R.n;
   int* info = reinterpret_cast<int*>(smem + FD_OFF_INFO);
   float* out = f.partial + (long)range * f.Npad * f.ldk;
   const bool isP = wave < 4;
-  const int nlast = n > 0 ? n - 1 : 0;
-  // f.rev: this launch walks every range downwards (the loop counter i maps to tile t0 + nlast - i): consecutive launches of a backward chain
-  // alternate, so a launch starts on the rows its producer wrote last (still in L2 / Infinity Cache).  Fixed per launch site: deterministic
-  const int rev = f.rev;
-#define FD_TILE(i_) (t0 + (rev ? nlast - (i_) : (i_)))
 
   if (isP) {
     // ================================================================ P waves
@@ -126,15 +118,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     // weights of this wave's 2 x 16 output columns as B fragments of the 16 x 16 x 32 MFMA: lane (n = lane & 15, kg = lane >> 4) holds W[c0 + 16 cb + n][32 kb + 8 kg ..]
     constexpr int NKB2 = NKB / 2;
     f16x8 w1[NKB2][2], w2[NKB2][2];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const unsigned short* wp = g.Wp + (long)(c0 + 16 * cb + (lane & 15)) * g.ldw + (lane >> 4) * 8;
-#pragma unroll
-      for (int kb = 0; kb < NKB2; ++kb) {
-        w1[kb][cb] = *reinterpret_cast<const f16x8*>(wp + kb * 32);
-        w2[kb][cb] = *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 32);
-      }
-    }
+    ws_wfrag16<NKB2>(w1, w2, g, c0, lane);
     const int ecol = c0 + (lane & 7) * 4;
     const f4 wsc = *reinterpret_cast<const f4*>(g.wscale + ecol);
     const f4 bias4 = epi_bias4(g.E, ecol);
@@ -146,9 +130,9 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
       wr1.x = g.W[(long)(ecol + 0) * g.ldw + 256]; wr1.y = g.W[(long)(ecol + 1) * g.ldw + 256];
       wr1.z = g.W[(long)(ecol + 2) * g.ldw + 256]; wr1.w = g.W[(long)(ecol + 3) * g.ldw + 256];
     }
-    // one tile: product, epilogue, Ep' tile; `ern` holds this tile's side inputs and receives those of tile i + ahead (clamped to the range)
-    auto p_tile = [&](const int i, const int ab, EpiRaw4 (&ern)[4], const int ahead) {
-      const long t = FD_TILE(i);
+    // one tile: product, epilogue, Ep' tile; `ern` holds this tile's side inputs and receives those of tile i + 1 (clamped to the range)
+    auto p_tile = [&](const int i, const int ab, EpiRaw4 (&ern)[4]) {
+      const long t = R.tile(i);
       const unsigned char* B = smem + ab * FD_ABUF;
       {
         const int* qi = info + ab * 4;
@@ -160,54 +144,27 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
 #pragma unroll
         for (int q = 0; q < 4; ++q) zq[q] = g.A.a[(t * FD_TP + (lane >> 3) + 8 * q) * g.A.lda + 256];
       }
-      fd_f32x4 acc[2][2];   // [row block of 16 points][column block of 16 columns]
+      f32x4 acc[2][2];   // [row block of 16 points][column block of 16 columns]
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
           for (int j = 0; j < 4; ++j) acc[rb][cb][j] = 0.0f;
-      const unsigned char* Ab = B + (lane & 15) * FD_ALD + (lane >> 4) * 16;   // A fragment: S'[16 rb + (lane & 15)][32 kb + 8 (lane >> 4) ..]
-      if (!(dbg & 4))
-#pragma unroll
-      for (int kb = 0; kb < NKB2; ++kb) {
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) {
-          const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + rb * 16 * FD_ALD + kb * 64);
-          const f16x8 a2 = *reinterpret_cast<const f16x8*>(Ab + rb * 16 * FD_ALD + FD_APLANE + kb * 64);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            fd_f32x4 c = acc[rb][cb];
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, w2[kb][cb], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, w1[kb][cb], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, w1[kb][cb], c, 0, 0, 0);
-            acc[rb][cb] = c;
-          }
-        }
-      }
+      if (!(dbg & 4)) ws_product16<NKB2>(acc, B + (lane & 15) * FD_ALD + (lane >> 4) * 16, FD_ALD, FD_APLANE, w1, w2);
       __builtin_amdgcn_sched_barrier(0);
       const float* rs = reinterpret_cast<const float*>(B + 2 * FD_APLANE);
       const float* ssr = rs + 32;
-      {
-        const int q4 = lane >> 4, cl = lane & 15;   // result block: rows 4 q4 + r, column cl
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) T[(16 * rb + 4 * q4 + r) * FD_TLD + 16 * cb + cl] = acc[rb][cb][r];
-      }
+      ws_acc_to_tile16(T, acc, lane);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      const long tn = FD_TILE(i + ahead < nlast ? i + ahead : nlast);
+      const long tn = R.prefetch(i + 1);
       unsigned char* Yb = smem + FD_OFF_Y + (i & 1) * FD_YBUF;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int rr = (lane >> 3) + 8 * q, cc = (lane & 7) * 4;
         const long row = t * FD_TP + rr;
-        const float rsc = rs[rr];
-        f4 v = *reinterpret_cast<const f4*>(T + rr * FD_TLD + cc);
-        v.x *= rsc * wsc.x; v.y *= rsc * wsc.y; v.z *= rsc * wsc.z; v.w *= rsc * wsc.w;
+        f4 v = ws_tile_row4(T, rs, rr, cc, wsc);
         f4 ep = fd_ep4<EK>(g.E, ern[q]);
         if constexpr (SPLITF) {   // [softplus(z) | z] * vscale: the layer's forward input as its view forms it
           const f4 zz = ern[q].a;
@@ -236,31 +193,15 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_sched_barrier(0);
     };
-    EpiRaw4 ernA[4], ernB[4];
+    EpiRaw4 ern[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      ernA[q] = fetch_side(FD_TILE(0) * FD_TP + (lane >> 3) + 8 * q, ecol);   // (a range past the end is clamped to tile 0 of the launch: loaded, never used)
-      if (DP) ernB[q] = fetch_side(FD_TILE(1 < nlast ? 1 : nlast) * FD_TP + (lane >> 3) + 8 * q, ecol);
-    }
+    for (int q = 0; q < 4; ++q) ern[q] = fetch_side(R.tile(0) * FD_TP + (lane >> 3) + 8 * q, ecol);   // (a range past the end is clamped to tile 0 of the launch: loaded, never used)
     cnr_lds_barrier();   // tile 0 staged
     int ab = 0;
-    if (!DP) {
-      for (int i = 0; i <= n; ++i) {
-        if (i < n) p_tile(i, ab, ernA, 1);
-        ab = ab == 2 ? 0 : ab + 1;
-        cnr_lds_barrier();
-      }
-    } else {
-      for (int i = 0; i <= n; i += 2) {
-        if (i < n) p_tile(i, ab, ernA, 2);
-        ab = ab == 2 ? 0 : ab + 1;
-        cnr_lds_barrier();
-        if (i + 1 <= n) {
-          if (i + 1 < n) p_tile(i + 1, ab, ernB, 2);
-          ab = ab == 2 ? 0 : ab + 1;
-          cnr_lds_barrier();
-        }
-      }
+    for (int i = 0; i <= n; ++i) {
+      if (i < n) p_tile(i, ab, ern);
+      ab = ab == 2 ? 0 : ab + 1;
+      cnr_lds_barrier();
     }
     if constexpr (XR != 0) {
       // the extra row of this (range, half): fold the 8 row lanes (lane >> 3) in a fixed order; lanes 0..7 then hold this wave's 32 columns
@@ -286,7 +227,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     const int wd = wave - 4, dt = tid - 256;
     const int srow = dt >> 4, scol = (dt & 15) * 4;
     const int m = lane & 15, kg = lane >> 4;   // result blocks: column m, rows 4 kg + r
-    fd_f32x4 acc[4][8];                        // [block of 16 S columns (rows of dW)][block of 16 Ep columns]: 128 registers
+    f32x4 acc[4][8];                        // [block of 16 S columns (rows of dW)][block of 16 Ep columns]: 128 registers
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -302,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
     const float ascale = g.A.scale;
 
     auto d_fetch = [&](int i, RawTile& rt) {
-      const long t = FD_TILE(i < nlast ? i : nlast);   // (clamped: the redundant request at the end of a range is never converted)
+      const long t = R.prefetch(i);   // (clamped: the redundant request at the end of a range is never converted)
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const long row = t * FD_TP + srow + 16 * p;
@@ -312,6 +253,8 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         rt.se[p] = f.se[row];
       }
     };
+    // d_put and d_dw are ws_stage_put and the weight-gradient fragment step of cnr_ws_tile.h in this kernel's own words: through the shared functions
+    // every instantiation grew by 50 - 80 instruction lines and the launch was 0.6 % slower (profiles/ws_refactor_ab.txt)
     auto d_put = [&](int i, int ab, const RawTile& rt) {
       unsigned char* B = smem + ab * FD_ABUF;
       float* rs = reinterpret_cast<float*>(B + 2 * FD_APLANE);
@@ -339,7 +282,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
         if ((dt & 15) == 0) {
           rs[row_l] = cnr_pow2_rcp(sc);
           rs[32 + row_l] = ssv;
-          if (g.rs_out && half == 0) g.rs_out[FD_TILE(i) * FD_TP + row_l] = ssv;
+          if (g.rs_out && half == 0) g.rs_out[R.tile(i) * FD_TP + row_l] = ssv;
         }
         const float se = rt.se[p];
         if (split_row_valid(mx) && se > 0.0f) {
@@ -369,7 +312,7 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
           const f16x8 b2 = ws_tr8(ysrc + FD_YPLANE, FD_YLD);
 #pragma unroll
           for (int sb = 0; sb < 4; ++sb) {
-            fd_f32x4 c = acc[sb][eb];
+            f32x4 c = acc[sb][eb];
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[sb][0], b2, c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[sb][1], b1, c, 0, 0, 0);
             c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[sb][0], b1, c, 0, 0, 0);
@@ -388,50 +331,24 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
       if (!(dbg & 1)) d_dw(i, abp);
     };
 
-    RawTile ta, tb;
+    RawTile ta;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) { ta.r[p][q] = z4; tb.r[p][q] = z4; }
-      ta.se[p] = 0.f; tb.se[p] = 0.f;
+      for (int q = 0; q < 4; ++q) ta.r[p][q] = z4;
+      ta.se[p] = 0.f;
     }
     int ab = 0;   // buffer of tile i
-    if (!DD) {
-      if (n > 0) { d_fetch(0, ta); d_put(0, 0, ta); }
-      if (n > 1) d_fetch(1, ta);
-      cnr_lds_barrier();   // tile 0 staged
-      for (int i = 0; i <= n; ++i) {
-        const int abn = ab == 2 ? 0 : ab + 1, abp = ab == 0 ? 2 : ab - 1;
-        if (i + 1 < n) d_put(i + 1, abn, ta);
-        if (i + 2 < n) d_fetch(i + 2, ta);
-        if (i >= 1) d_acc(i - 1, abp);
-        ab = abn;
-        cnr_lds_barrier();
-      }
-    } else {
-      // tile j travels in set a for even j, in set b for odd j; a set is re-requested (tile j + 2) right after its conversion
-      if (n > 0) { d_fetch(0, ta); d_put(0, 0, ta); }
-      d_fetch(1, tb);
-      d_fetch(2, ta);
-      cnr_lds_barrier();   // tile 0 staged
-      for (int i = 0; i <= n; i += 2) {
-        {
-          const int abn = ab == 2 ? 0 : ab + 1, abp = ab == 0 ? 2 : ab - 1;
-          if (i + 1 < n) d_put(i + 1, abn, tb);
-          d_fetch(i + 3, tb);
-          if (i >= 1) d_acc(i - 1, abp);
-          ab = abn;
-          cnr_lds_barrier();
-        }
-        if (i + 1 <= n) {
-          const int abn = ab == 2 ? 0 : ab + 1, abp = ab == 0 ? 2 : ab - 1;
-          if (i + 2 < n) d_put(i + 2, abn, ta);
-          d_fetch(i + 4, ta);
-          d_acc(i, abp);
-          ab = abn;
-          cnr_lds_barrier();
-        }
-      }
+    if (n > 0) { d_fetch(0, ta); d_put(0, 0, ta); }
+    if (n > 1) d_fetch(1, ta);
+    cnr_lds_barrier();   // tile 0 staged
+    for (int i = 0; i <= n; ++i) {
+      const int abn = ab == 2 ? 0 : ab + 1, abp = ab == 0 ? 2 : ab - 1;
+      if (i + 1 < n) d_put(i + 1, abn, ta);
+      if (i + 2 < n) d_fetch(i + 2, ta);
+      if (i >= 1) d_acc(i - 1, abp);
+      ab = abn;
+      cnr_lds_barrier();
     }
 
     // ---- partial sums of this (range, half): undo 2^G in two exact steps; the transposed form goes through a per-wave LDS tile so that
@@ -496,31 +413,14 @@ __global__ __launch_bounds__(512, 1) void layer_dw_kernel(const LayerGemm g_in, 
   }
 }
 
-#undef FD_TILE
 
-template <int EK, bool DP, bool DD, int NKB = 16, int XR = 0, bool TAILF = false, bool SPLITF = false>
-static void launch_fdw_v(const LayerGemm& g, const DwFuse& f, cnr_stream s) {
-  static DeviceOnce attr_once;
-  if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layer_dw_kernel<EK, DP, DD, NKB, XR, TAILF, SPLITF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+template <int EK, int NKB = 16, int XR = 0, bool TAILF = false, bool SPLITF = false>
+static void launch_fdw(const LayerGemm& g, const DwFuse& f, cnr_stream s) {
   const long ntiles = g.P / FD_TP;
   const int tpr = (int)((ntiles + f.nslots - 1) / f.nslots);
   TimingScope ts_("layer_dw", 0, 200 + EK, g.P, 256, g.K, 2, s, fdw_bytes(g, f));   // pairs = 2: the layer product + the weight-gradient product
   const int dbg = debug_flags().fdw_dbg;   // ablation word of the tuning build (timing experiments only: results are wrong); 0 in the product build
-  hipLaunchKernelGGL((layer_dw_kernel<EK, DP, DD, NKB, XR, TAILF, SPLITF>), dim3(2 * f.nslots), dim3(512), FD_LDS, s, g, f, tpr, dbg);
-}
-template <int EK>
-static void launch_fdw(const LayerGemm& g, const DwFuse& f, cnr_stream s) {
-#ifdef CNR_TUNING
-  switch (debug_flags().fdw_deep & 3) {   // tuning aid: bit 0 = DP, bit 1 = DD (deeper prefetch: 1-5 % slower, spills; instantiated in the tuning build only)
-    case 0: launch_fdw_v<EK, false, false>(g, f, s); break;
-    case 1: launch_fdw_v<EK, true, false>(g, f, s); break;
-    case 2: launch_fdw_v<EK, false, true>(g, f, s); break;
-    default: launch_fdw_v<EK, true, true>(g, f, s); break;
-  }
-#else
-  launch_fdw_v<EK, false, false>(g, f, s);
-#endif
+  launch_lds<layer_dw_kernel<EK, NKB, XR, TAILF, SPLITF>>(dim3(2 * f.nslots), dim3(512), FD_LDS, 160 * 1024, s, g, f, tpr, dbg);
 }
 
 bool be_fdw_enabled() {
@@ -544,15 +444,15 @@ void be_layer_dw_gemm(const LayerGemm& g, const DwGemm& d, const DwFuse& f, cnr_
     return;
   }
   // the fused launch covers output columns [0, 256) and the 256 x 256 main tile of the weight gradient
-  if (f.xrow_mode == 2 && g.E.kind == EK_VBACK && g.k_extra == 1 && g.K == 256) launch_fdw_v<EK_VBACK, false, false, 16, 2>(g, f, s);
-  else if (f.xrow_mode == 1 && g.E.kind == EK_SWEEP && g.K > 240) launch_fdw_v<EK_SWEEP, false, false, 16, 1>(g, f, s);
-  else if (g.E.kind == EK_SWEEP && g.E.tail_src != nullptr) launch_fdw_v<EK_SWEEP, false, false, 16, 0, true>(g, f, s);
-  else if (g.E.kind == EK_VBACK && g.E.split < 256) launch_fdw_v<EK_VBACK, false, false, 16, 0, false, true>(g, f, s);
-  else if (g.K <= 224) launch_fdw_v<EK_VBACK, false, false, 14>(g, f, s);
+  if (f.xrow_mode == 2 && g.E.kind == EK_VBACK && g.k_extra == 1 && g.K == 256) launch_fdw<EK_VBACK, 16, 2>(g, f, s);
+  else if (f.xrow_mode == 1 && g.E.kind == EK_SWEEP && g.K > 240) launch_fdw<EK_SWEEP, 16, 1>(g, f, s);
+  else if (g.E.kind == EK_SWEEP && g.E.tail_src != nullptr) launch_fdw<EK_SWEEP, 16, 0, true>(g, f, s);
+  else if (g.E.kind == EK_VBACK && g.E.split < 256) launch_fdw<EK_VBACK, 16, 0, false, true>(g, f, s);
+  else if (g.K <= 224) launch_fdw<EK_VBACK, 14>(g, f, s);
   else switch (g.E.kind) {
     case EK_RELU_MASK: launch_fdw<EK_RELU_MASK>(g, f, s); break;
     case EK_VBACK: launch_fdw<EK_VBACK>(g, f, s); break;
-    case EK_SPLIT: launch_fdw_v<EK_SPLIT, false, false>(g, f, s); break;
+    case EK_SPLIT: launch_fdw<EK_SPLIT>(g, f, s); break;
     default: launch_fdw<EK_SWEEP>(g, f, s); break;
   }
   CNR_LAUNCH_CHECK("layer_dw");

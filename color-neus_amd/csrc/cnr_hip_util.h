@@ -8,7 +8,7 @@ extern const char* g_first_error_where;
 void timing_begin(const char* name, int kind, int nt, long P, int N, int K, int pairs, hipStream_t s, double bytes);
 void timing_end(hipStream_t s);
 // hipFuncSetAttribute is a per-device setting: remember per (kernel instantiation, device) that it has been applied.
-// Usage: static DeviceOnce once; if (once.first()) hipFuncSetAttribute(...);
+// (launch_lds below is its user: one opt-in per kernel instantiation and device)
 struct DeviceOnce {
   bool done[64] = {};
   bool first() {
@@ -19,6 +19,14 @@ struct DeviceOnce {
     return true;
   }
 };
+// Launch of a kernel that needs more dynamic LDS than the default limit: the opt-in up to `lds_max` bytes, once per kernel instantiation and
+// device, then the launch with `lds` bytes.  (A launch record is the caller's: a TimingScope around the call.)
+template <auto Kernel, class... Args>
+void launch_lds(dim3 grid, dim3 block, size_t lds, size_t lds_max, hipStream_t s, const Args&... args) {
+  static DeviceOnce attr_once;
+  if (attr_once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+}
 struct TimingScope {
   hipStream_t s;
   TimingScope(const char* name, int kind, int nt, long P, int N, int K, int pairs, hipStream_t st, double bytes = 0.0) : s(st) {

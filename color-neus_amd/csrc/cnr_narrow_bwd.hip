@@ -43,11 +43,8 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_n[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long Pn = p.P;
-  const long ntiles = (Pn + WS_TP - 1) / WS_TP;
-  const long t0 = (long)blockIdx.x * tiles_per_wg;
-  long t1 = t0 + tiles_per_wg;
-  if (t1 > ntiles) t1 = ntiles;
-  const int n = t1 > t0 ? (int)(t1 - t0) : 0;
+  const WsRange R((Pn + WS_TP - 1) / WS_TP, (long)blockIdx.x * tiles_per_wg, tiles_per_wg, 0);
+  const int n = R.n;
   const int c0 = wave * 32;
   const bool has_w = DX && c0 < 64;
   // ---- W^T planes of the dX product into LDS (rows = input columns c < 48; a row beyond w_rows is zero)
@@ -83,7 +80,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
   ra.y = z4; rb.y = z4;
   const bool want_cs = p.colsum != nullptr;   // (then column ky of Y is a column of ones: ky < 48)
   auto s_fetch = [&](int i, RawTile& rt) __attribute__((always_inline)) {
-    long row = (t0 + (i < n ? i : (n > 0 ? n - 1 : 0))) * WS_TP + srow;
+    long row = R.prefetch(i) * WS_TP + srow;
     if (row >= Pn) row = Pn - 1;
     const float* src = p.X + row * p.ldx + scol;
 #pragma unroll
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
     if constexpr (DW) rt.y = *reinterpret_cast<const f4*>(p.Y + row * p.ldy + (ylive ? scol : 0));   // (every lane loads: a branch here costs the compiler its count of loads in flight)
   };
   auto s_put = [&](int i, int buf, const RawTile& rt) __attribute__((always_inline)) {
-    const bool live = (t0 + i) * WS_TP + srow < Pn;
+    const bool live = R.tile(i) * WS_TP + srow < Pn;
     f4 v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -117,20 +114,16 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
       if (scol + 3 == p.ky) y.w = 1.0f;
     }
     if (!ylive) y = z4;
-    float mx = fmaxf(fmaxf(ws_absmax4(v[0]), ws_absmax4(v[1])), fmaxf(ws_absmax4(v[2]), ws_absmax4(v[3])));
-    float my = ws_absmax4(y);
-    mx = cnr_max16(mx); my = cnr_max16(my);
-    const float sx = split_row_scale(mx), sy = split_row_scale(my);
     unsigned char* B = smem_n + buf * NB_ABUF;
-    unsigned char* dst = B + srow * NB_ALD + scol * 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) split_put4(v[q], sx, dst + 128 * q, NB_APLANE);
-    if (DW && ylive) {
-      split_put4(y, sy, smem_n + NB_OFF_Y + buf * NB_YBUF + srow * NB_YLD + scol * 2, NB_YPLANE);
-    }
-    if ((tid & 15) == 0) {
-      float* rs = reinterpret_cast<float*>(B + 2 * NB_APLANE);
-      rs[srow] = cnr_pow2_rcp(sx);
+    float* rs = reinterpret_cast<float*>(B + 2 * NB_APLANE);
+    const bool owner = (tid & 15) == 0;
+    const bool allx[4] = {true, true, true, true}, ylv[1] = {DW && ylive};
+    const f4 yv[1] = {y};
+    // the X tile like a layer input; the Y tile with its own row scale (its 1 / scale is not needed: the owner flag is off)
+    const WsRowScale rx = ws_stage_put<4>(v, allx, B + srow * NB_ALD + scol * 2, NB_APLANE, rs, srow, owner);
+    const WsRowScale ry = ws_stage_put<1>(yv, ylv, smem_n + NB_OFF_Y + buf * NB_YBUF + srow * NB_YLD + scol * 2, NB_YPLANE, rs, srow, false);
+    const float mx = rx.mx, my = ry.mx, sx = rx.sc, sy = ry.sc;
+    if (owner) {
       // a row with a zero operand contributes nothing (its planes are zero); a non-finite row keeps factor 1 so that it poisons the sums
       const bool nonfin = !(mx < 3.0e38f) || !(my < 3.0e38f);
       int e = SPLIT_GBIG;
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
   cnr_lds_barrier();
   const int m = lane & 31, kg = lane >> 5;
   auto tile = [&](const int i, const int buf) __attribute__((always_inline)) {
-    const long t = t0 + i;
+    const long t = R.tile(i);
     const unsigned char* B = smem_n + buf * NB_ABUF;
     const float* rs = reinterpret_cast<const float*>(B + 2 * NB_APLANE);
     const int* er = reinterpret_cast<const int*>(rs) + 32;
@@ -167,18 +160,13 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
       const int wrow = c0 + m;
       const unsigned char* Wb = smem_n + NB_OFF_W + (wrow < NB_YCOLS ? wrow : 0) * NB_ALD + kg * 16;
       const bool wlive = wrow < NB_YCOLS;
-#pragma unroll
-      for (int kb = 0; kb < 16; ++kb) {
+      ws_product32<16>(acc, Ab, NB_APLANE, 16, [&](const int kb, f16x8& w1, f16x8& w2) {   // (the weight planes out of LDS)
         const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + kb * 32);
-        const f16x8 a2 = *reinterpret_cast<const f16x8*>(Ab + NB_APLANE + kb * 32);
-        f16x8 w1 = *reinterpret_cast<const f16x8*>(Wb + kb * 32);
-        f16x8 w2 = *reinterpret_cast<const f16x8*>(Wb + NB_WPLANE + kb * 32);
+        w1 = *reinterpret_cast<const f16x8*>(Wb + kb * 32);
+        w2 = *reinterpret_cast<const f16x8*>(Wb + NB_WPLANE + kb * 32);
         if (!wlive) { w1 = z8; w2 = z8; }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, w1, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w1, acc, 0, 0, 0);
-      }
+      });
+      // (ws_acc_to_tile32 in the kernel's own words: through the shared function the product-only SIG instantiation takes 168 VGPRs against 164)
 #pragma unroll
       for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * kg) * WS_TLD + m] = acc[r];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -187,9 +175,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
       for (int q = 0; q < 4; ++q) {
         const int rr = (lane >> 3) + 8 * q, cc = (lane & 7) * 4;
         const long row = t * WS_TP + rr;
-        const float rsc = rs[rr];
-        f4 v = *reinterpret_cast<const f4*>(T + rr * WS_TLD + cc);
-        v.x *= rsc * wsc.x; v.y *= rsc * wsc.y; v.z *= rsc * wsc.z; v.w *= rsc * wsc.w;
+        const f4 v = ws_tile_row4(T, rs, rr, cc, wsc);
         const int col = c0 + cc;
         if (row < Pn) {
           float* o = p.dx + row * p.lddx + col;
@@ -232,26 +218,11 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const f16x8 fv = *reinterpret_cast<const f16x8*>(fb + kb * 16 + kg * 8);
-        const int prow = kb * 16 + kg * 2 + 4 * ((lane & 15) >> 2), pcol = (m & 16) + (lane & 3) * 4;   // this lane's piece of a [4 points][16 columns] block
-        f16x8 a1 = ws_tr8(B + prow * NB_ALD + (c0 + pcol) * 2, NB_ALD);
-        f16x8 a2 = ws_tr8(B + NB_APLANE + prow * NB_ALD + (c0 + pcol) * 2, NB_ALD);
+        const WsTrPiece pc = ws_tr_piece32(lane, kb);   // this lane's piece of a [4 points][16 columns] block
+        f16x8 a1 = ws_tr8(B + pc.prow * NB_ALD + (c0 + pc.pcol) * 2, NB_ALD);
+        f16x8 a2 = ws_tr8(B + NB_APLANE + pc.prow * NB_ALD + (c0 + pc.pcol) * 2, NB_ALD);
         a1 = a1 * fv; a2 = a2 * fv;
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const int c = cb * 32 + m;
-          const unsigned char* ysrc = Yb + prow * NB_YLD + (cb * 32 + pcol) * 2;   // (columns 48 .. 63 of the second block: the pad behind a row, masked below)
-          f16x8 b1 = ws_tr8(ysrc, NB_YLD);
-          f16x8 b2 = ws_tr8(ysrc + NB_YPLANE, NB_YLD);
-          if (c >= NB_YCOLS) {
-            const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-            b1 = z8; b2 = z8;
-          }
-          f32x16 cacc = tacc[cb];
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, cacc, 0, 0, 0);
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, b1, cacc, 0, 0, 0);
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, cacc, 0, 0, 0);
-          tacc[cb] = cacc;
-        }
+        ws_dw_step32(tacc, a1, a2, Yb, NB_YLD, NB_YPLANE, pc, lane, NB_YCOLS);   // (columns 48 .. 63 of the second block: the pad behind a row, masked)
       }
       const SplitPow2 un = split_pow2(-Gt);
 #pragma unroll
@@ -274,17 +245,14 @@ __global__ __launch_bounds__(WS_THREADS, 1) void narrow_bwd_kernel(const NarrowB
   }
   if (n & 1) tile(n - 1, 0);
   if constexpr (!DW) return;
-  // ---- partial sums of this range: [256][ldk], every slot written in full
-  float* out = p.partial + (long)blockIdx.x * 256 * p.ldk;
+  // ---- partial sums of this range: [256][ldk], every slot written in full; the ones column (column ky of the block) is the bias gradient
+  ws_store_slot32<false>(p.partial + (long)blockIdx.x * 256 * p.ldk, p.ldk, c0, lane, tot, p.ky);
+  if (want_cs) {
 #pragma unroll
-  for (int cb = 0; cb < 2; ++cb) {
-    const int c = cb * 32 + m;
+    for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = c0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-      if (c < p.ldk) out[(long)j * p.ldk + c] = c < p.ky ? tot[cb][r] : 0.0f;
-      if (want_cs && c == p.ky) p.colsum[(long)blockIdx.x * 256 + j] = tot[cb][r];   // the ones column: bias gradient
-    }
+      for (int r = 0; r < 16; ++r)
+        if (cb * 32 + m == p.ky) p.colsum[(long)blockIdx.x * 256 + c0 + (r & 3) + 8 * (r >> 2) + 4 * kg] = tot[cb][r];
   }
 }
 
@@ -309,20 +277,13 @@ bool be_narrow_bwd_ok(const NarrowBwd& p) {
 void be_narrow_bwd(const NarrowBwd& p, cnr_stream s) {
   const long tpw = tiles_per_workgroup(p.P);
   const int grid = cu_tile_slots(p.P);
-  static DeviceOnce attr_once;
-  if (attr_once.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&narrow_bwd_kernel<true, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&narrow_bwd_kernel<false, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&narrow_bwd_kernel<true, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&narrow_bwd_kernel<true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   const bool dw = p.partial != nullptr;
   const double bytes = 4.0 * (double)p.P * (256 + (p.Xb ? 256 : 0) + (dw ? p.ky : 0) + (p.Wp ? p.ndx : 0)) + (dw ? 4.0 * grid * 256.0 * (p.ldk + 1) : 0.0);
   TimingScope ts_(dw ? "narrow_bwd" : "narrow_dx", 0, 301, p.P, dw ? 256 : p.ndx, dw ? p.ky : 256, (p.Wp ? 1 : 0) + (dw ? 1 : 0), s, bytes);
-  if (!dw && p.Xb) hipLaunchKernelGGL((narrow_bwd_kernel<true, false, true>), dim3(grid), dim3(WS_THREADS), NB_LDS_DX, s, p, (int)tpw);
-  else if (!dw) hipLaunchKernelGGL((narrow_bwd_kernel<true, false, false>), dim3(grid), dim3(WS_THREADS), NB_LDS_DX, s, p, (int)tpw);
-  else if (p.Wp) hipLaunchKernelGGL((narrow_bwd_kernel<true, true, false>), dim3(grid), dim3(WS_THREADS), NB_LDS_DX, s, p, (int)tpw);
-  else hipLaunchKernelGGL((narrow_bwd_kernel<false, true, false>), dim3(grid), dim3(WS_THREADS), NB_LDS_NODX, s, p, (int)tpw);
+  if (!dw && p.Xb) launch_lds<narrow_bwd_kernel<true, false, true>>(dim3(grid), dim3(WS_THREADS), NB_LDS_DX, 160 * 1024, s, p, (int)tpw);
+  else if (!dw) launch_lds<narrow_bwd_kernel<true, false, false>>(dim3(grid), dim3(WS_THREADS), NB_LDS_DX, 160 * 1024, s, p, (int)tpw);
+  else if (p.Wp) launch_lds<narrow_bwd_kernel<true, true, false>>(dim3(grid), dim3(WS_THREADS), NB_LDS_DX, 160 * 1024, s, p, (int)tpw);
+  else launch_lds<narrow_bwd_kernel<false, true, false>>(dim3(grid), dim3(WS_THREADS), NB_LDS_NODX, 160 * 1024, s, p, (int)tpw);
   CNR_LAUNCH_CHECK("narrow_bwd");
 }
 

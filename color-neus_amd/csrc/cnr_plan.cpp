@@ -41,7 +41,7 @@ const DebugFlags& debug_flags() {
 #ifdef CNR_TUNING
         {"CNR_WS_KINDS", &DebugFlags::ws_kinds}, {"CNR_WS_MINW", &DebugFlags::ws_minw}, {"CNR_WS_WGS", &DebugFlags::ws_wgs}, {"CNR_WS_MINTPW", &DebugFlags::ws_mintpw},
         {"CNR_CHAIN_WGS", &DebugFlags::chain_wgs}, {"CNR_CHAIN_SHAPE", &DebugFlags::chain_shape}, {"CNR_CHAIN_FWD_RT", &DebugFlags::chain_fwd_rt},
-        {"CNR_FDW_DEEP", &DebugFlags::fdw_deep}, {"CNR_FDW_NOREV", &DebugFlags::fdw_norev}, {"CNR_FDW_REVMODE", &DebugFlags::fdw_revmode},
+        {"CNR_FDW_NOREV", &DebugFlags::fdw_norev}, {"CNR_FDW_REVMODE", &DebugFlags::fdw_revmode},
         {"CNR_FDW_DBG", &DebugFlags::fdw_dbg}, {"CNR_CHAIN_FWD_DBG", &DebugFlags::chain_fwd_dbg},
 #endif
     };

@@ -69,6 +69,19 @@ __device__ __forceinline__ void split_put16(const f32x16& a, float sc, unsigned 
   *reinterpret_cast<f16x8*>(dst + plane + 16) = h2b;
 }
 
+// ---- the three MFMAs of one split product --------------------------------------------------------------------------------------------
+// c += a b for a = a1 + a2, b = b1 + b2 (hi + lo planes): a1 b2 + a2 b1 + a1 b1, small terms first; the dropped a2 b2 is < 2^-22 relative
+__device__ __forceinline__ void split_mfma3_32(f32x16& c, const f16x8& a1, const f16x8& a2, const f16x8& b1, const f16x8& b2) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, b1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, c, 0, 0, 0);
+}
+__device__ __forceinline__ void split_mfma3_16(f32x4& c, const f16x8& a1, const f16x8& a2, const f16x8& b1, const f16x8& b2) {
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b2, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2, b1, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b1, c, 0, 0, 0);
+}
+
 // ---- the block exponent of a contraction over points ------------------------------------------------------------------------------
 constexpr int SPLIT_GBIG = 0x3f000000;   // "no point with two non-zero rows yet"
 // log2(sa * sb) of two power-of-two scales, from their exponent fields

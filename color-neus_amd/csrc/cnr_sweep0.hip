@@ -34,24 +34,13 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long Pn = g.P;
-  const long ntiles = (Pn + WS_TP - 1) / WS_TP;
-  const long t0 = (long)blockIdx.x * tiles_per_wg;
-  long t1 = t0 + tiles_per_wg;
-  if (t1 > ntiles) t1 = ntiles;
-  const int n = t1 > t0 ? (int)(t1 - t0) : 0;
+  const WsRange R((Pn + WS_TP - 1) / WS_TP, (long)blockIdx.x * tiles_per_wg, tiles_per_wg, 0);
+  const int n = R.n;
   const int c0 = wave * 32;
   const int kpad = ((g.K + 15) >> 4) * 16;
 
   f16x8 w1[S0_NKB], w2[S0_NKB];
-  {
-    const unsigned short* wp = g.Wp + (long)(c0 + (lane & 31)) * g.ldw + (lane >> 5) * 8;
-#pragma unroll
-    for (int kb = 0; kb < S0_NKB; ++kb) {
-      const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-      w1[kb] = kb * 16 < kpad ? *reinterpret_cast<const f16x8*>(wp + kb * 16) : z8;
-      w2[kb] = kb * 16 < kpad ? *reinterpret_cast<const f16x8*>(wp + g.wp_stride + kb * 16) : z8;
-    }
-  }
+  ws_wfrag32<S0_NKB, true>(w1, w2, g, c0 + (lane & 31), lane, kpad >> 4);
   const int ecol = c0 + (lane & 7) * 4;
   const f4 wsc = *reinterpret_cast<const f4*>(g.wscale + ecol);
   float* T = reinterpret_cast<float*>(smem_s + S0_OFF_T) + wave * (32 * WS_TLD);
@@ -63,24 +52,22 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
   const f4 z4 = {0.f, 0.f, 0.f, 0.f};
   f4 sraw = z4;
   auto s_fetch = [&](int i) {
-    long row = (t0 + (i < n ? i : (n > 0 ? n - 1 : 0))) * WS_TP + srow;
+    long row = R.prefetch(i) * WS_TP + srow;
     if (row >= Pn) row = Pn - 1;
     if (pv) sraw = *reinterpret_cast<const f4*>(g.A.a + row * g.A.lda + scol);
   };
   auto s_put = [&](int i, int buf) {
-    const long prow = (t0 + i) * WS_TP + srow;
-    const f4 v = (pv && prow < Pn) ? sraw : z4;
-    float mx = ws_absmax4(v);
-    mx = cnr_max16(mx);
-    const float sc = split_row_scale(mx);
+    const long prow = R.tile(i) * WS_TP + srow;
+    const f4 v[1] = {(pv && prow < Pn) ? sraw : z4};
     unsigned char* B = smem_s + buf * S0_ABUF;
+    float* rs = reinterpret_cast<float*>(B + 2 * S0_APLANE);
     // every column the product loop reads (S0_NKB k16 blocks) is written: columns in [kpad, 48) of a K <= 32 layer get zeros, not whatever
     // an earlier kernel left in LDS (NaN / Inf bit patterns times the zero weights of those blocks would poison the accumulators)
-    if (scol < S0_NKB * 16) split_put4(v, sc, B + srow * S0_ALD + scol * 2, S0_APLANE);
-    if ((tid & 15) == 0) {
-      float* rs = reinterpret_cast<float*>(B + 2 * S0_APLANE);
-      const float ssv = split_rs_value(mx, sc);
-      rs[srow] = cnr_pow2_rcp(sc);
+    const bool live[1] = {scol < S0_NKB * 16};
+    const bool owner = (tid & 15) == 0;
+    const WsRowScale rsc = ws_stage_put<1>(v, live, B + srow * S0_ALD + scol * 2, S0_APLANE, rs, srow, owner);
+    if (owner) {
+      const float ssv = split_rs_value(rsc.mx, rsc.sc);
       rs[32 + srow] = ssv;
       if (g.rs_out && prow < Pn) g.rs_out[prow] = ssv;
     }
@@ -88,7 +75,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
   // side inputs of the epilogue: z and v of this lane's 4 columns in 4 row groups
   EpiRaw4 er[4];
   auto e_fetch = [&](int i) {
-    const long t = t0 + (i < n ? i : (n > 0 ? n - 1 : 0));
+    const long t = R.prefetch(i);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       long row = t * WS_TP + (lane >> 3) + 8 * q;
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
   cnr_lds_barrier();
   for (int i = 0; i < n; ++i) {
     const int buf = i & 1;
-    const long t = t0 + i;
+    const long t = R.tile(i);
     if (i + 1 < n) s_put(i + 1, buf ^ 1);
     s_fetch(i + 2);
     const unsigned char* B = smem_s + buf * S0_ABUF;
@@ -121,24 +108,10 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    {
-      const unsigned char* Ab = B + (lane & 31) * S0_ALD + (lane >> 5) * 16;
-#pragma unroll
-      for (int kb = 0; kb < S0_NKB; ++kb) {
-        const f16x8 a1 = *reinterpret_cast<const f16x8*>(Ab + kb * 32);
-        const f16x8 a2 = *reinterpret_cast<const f16x8*>(Ab + S0_APLANE + kb * 32);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w2[kb], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, w1[kb], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, w1[kb], acc, 0, 0, 0);
-      }
-    }
+    ws_product32<S0_NKB>(acc, B + (lane & 31) * S0_ALD + (lane >> 5) * 16, S0_APLANE, S0_NKB, [&](const int kb, f16x8& a, f16x8& b) { a = w1[kb]; b = w2[kb]; });
     const float* rs = reinterpret_cast<const float*>(B + 2 * S0_APLANE);
     const float* ssr = rs + 32;
-    {
-      const int hi = lane >> 5, cl = lane & 31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) T[((r & 3) + 8 * (r >> 2) + 4 * hi) * WS_TLD + cl] = acc[r];
-    }
+    ws_acc_to_tile32(T, acc, lane >> 5, lane & 31);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // ---- epilogue (same arithmetic as epi_finish4_plain<EK_SWEEP>) + the pair's n-side operand u = sp'(z) v
@@ -148,9 +121,7 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     for (int q = 0; q < 4; ++q) {
       const int rr = (lane >> 3) + 8 * q, cc = (lane & 7) * 4;
       const long row = t * WS_TP + rr;
-      const float rsc = rs[rr];
-      f4 v = *reinterpret_cast<const f4*>(T + rr * WS_TLD + cc);
-      v.x *= rsc * wsc.x; v.y *= rsc * wsc.y; v.z *= rsc * wsc.z; v.w *= rsc * wsc.w;
+      const f4 v = ws_tile_row4(T, rs, rr, cc, wsc);
       const f4 zz = er[q].a, vv = er[q].b;
       const float s1x = softplus100_d1(zz.x), s1y = softplus100_d1(zz.y), s1z = softplus100_d1(zz.z), s1w = softplus100_d1(zz.w);
       const float vx = vv.x * g.E.vscale, vy = vv.y * g.E.vscale, vz = vv.z * g.E.vscale, vw = vv.w * g.E.vscale;
@@ -189,51 +160,21 @@ __global__ __launch_bounds__(WS_THREADS, 1) void sweep0_dw_kernel(const LayerGem
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    // ---- dW[j][c] += sum over the tile's points of u'[pt][j] * cbar'[pt][c]
-    {
-      const int m = lane & 31, kg = lane >> 5;
+    // ---- dW[j][c] += sum over the tile's points of u'[pt][j] * cbar'[pt][c]: both fragments out of row-major planes by the LDS transpose read
+    // (ws_tr8: block rows 4 points apart; the cbar planes' row stride of 112 B puts them 48 banks apart, as good as 16)
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        // both fragments out of row-major planes by the LDS transpose read (ws_tr8, cnr_gemm_ws.h: block rows 4 points apart; the cbar planes'
-        // row stride of 112 B puts them 48 banks apart, as good as 16)
-        const int prow = kb * 16 + kg * 2 + 4 * ((lane & 15) >> 2), pcol = (m & 16) + (lane & 3) * 4;
-        const unsigned char* ysrc = Yw + prow * S0_YLD + pcol * 2;
-        const f16x8 a1 = ws_tr8(ysrc, S0_YLD);
-        const f16x8 a2 = ws_tr8(ysrc + S0_YPLANE, S0_YLD);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const int c = cb * 32 + m;
-          const unsigned char* src = B + prow * S0_ALD + (cb * 32 + pcol) * 2;   // (columns >= kpad: whatever lies behind the row, masked below)
-          f16x8 b1 = ws_tr8(src, S0_ALD);
-          f16x8 b2 = ws_tr8(src + S0_APLANE, S0_ALD);
-          if (c >= kpad) {
-            const f16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-            b1 = z8; b2 = z8;
-          }
-          f32x16 cacc = dacc[cb];
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b2, cacc, 0, 0, 0);
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, b1, cacc, 0, 0, 0);
-          cacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, cacc, 0, 0, 0);
-          dacc[cb] = cacc;
-        }
-      }
+    for (int kb = 0; kb < 2; ++kb) {
+      const WsTrPiece pc = ws_tr_piece32(lane, kb);
+      const unsigned char* ysrc = Yw + pc.prow * S0_YLD + pc.pcol * 2;
+      const f16x8 a1 = ws_tr8(ysrc, S0_YLD);
+      const f16x8 a2 = ws_tr8(ysrc + S0_YPLANE, S0_YLD);
+      ws_dw_step32(dacc, a1, a2, B, S0_ALD, S0_APLANE, pc, lane, kpad);   // (columns >= kpad: whatever lies behind the row, masked)
     }
     cnr_lds_barrier();
   }
   // ---- partial sums of this range: rows c0 .. c0 + 31 of [Npad = 256][ldk], every slot written in full
   const SplitPow2 un = ge.undo();
-  const float u1 = un.u1, u2 = un.u2;
-  float* out = partial + (long)blockIdx.x * 256 * ldk;
-  const int m = lane & 31, kg = lane >> 5;
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb) {
-    const int c = cb * 32 + m;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = c0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-      if (c < ldk) out[(long)j * ldk + c] = c < kpad ? dacc[cb][r] * u1 * u2 : 0.0f;
-    }
-  }
+  ws_store_slot32<true>(partial + (long)blockIdx.x * 256 * ldk, ldk, c0, lane, dacc, kpad, un.u1, un.u2);
 }
 
 // workgroups (= partial-sum slots) of the launch for P points: one per CU as soon as there are enough tiles
@@ -253,10 +194,8 @@ bool be_sweep0_ok(const LayerGemm& g) {
 void be_sweep0_dw(const LayerGemm& g, float* partial, int ldk, cnr_stream s) {
   const long tpw = tiles_per_workgroup(g.P);
   const int grid = cu_tile_slots(g.P);
-  static DeviceOnce attr_once;
-  if (attr_once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep0_dw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   TimingScope ts_("sweep0_dw", 0, 300, g.P, g.N, g.K, 2, s, layer_gemm_bytes(g) + 4.0 * grid * 256.0 * ldk);
-  hipLaunchKernelGGL(sweep0_dw_kernel, dim3(grid), dim3(WS_THREADS), S0_LDS, s, g, partial, ldk, (int)tpw);
+  launch_lds<sweep0_dw_kernel>(dim3(grid), dim3(WS_THREADS), S0_LDS, 160 * 1024, s, g, partial, ldk, (int)tpw);
   CNR_LAUNCH_CHECK("sweep0_dw");
 }
 

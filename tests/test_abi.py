@@ -102,6 +102,25 @@ def test_the_split_f16_rule_has_one_definition():
     assert barriers == ["cnr_hip_util.h"], barriers
 
 
+def test_the_layer_tile_steps_have_one_definition():
+    """The opt-in to a CU's whole LDS is made by launch_lds (cnr_hip_util.h) alone: no launcher calls hipFuncSetAttribute itself.  The read-back
+    of an accumulator block from a wave's transposition tile (row scale times column scale undone) is ws_tile_row4 (cnr_ws_tile.h) alone."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    # cnr_kernels.hip: launch_strip_bwd, a file the tile-step change left alone (64 KiB for strip_bwd_kernel)
+    attr_allowed = {"cnr_hip_util.h", "cnr_chain_util.h", "cnr_kernels.hip"}
+    attr, readback = [], []
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h", ".cpp")):
+            continue
+        code = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, fn)).read().split("\n"))
+        if "hipFuncSetAttribute(" in code:
+            attr.append(fn)
+        if re.search(r"rsc\s*\*\s*wsc", code):
+            readback.append(fn)
+    assert "cnr_hip_util.h" in attr and set(attr) <= attr_allowed, attr
+    assert readback == ["cnr_ws_tile.h"], readback
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
         _lib.RenderLibrary(str(tmp_path / "libcolorneus_hip.so"))

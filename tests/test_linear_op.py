@@ -166,3 +166,60 @@ def test_scale_rule_is_exact_emu():
 @pytest.mark.gpu
 def test_scale_rule_is_exact_hip():
     _check_scale_rule(None, "cuda:0")
+
+
+# (k, n_out, relu): K = 256 (the stream form of the layer kernel where n allows it), a narrow input, K beyond 256 (17 k16 blocks), no ReLU
+TILE_SHAPES = [(256, 256, True), (84, 256, True), (272, 224, True), (256, 256, False)]
+
+
+def _check_rows_do_not_depend_on_their_tile(library, device, pairs, want_ws):
+    """Row r of y is a function of row r of x, W and b alone (the row scale is per row, the summation order over K is fixed), and row r of dx of
+    row r of dy, y and W alone.  So a short call on the first rows of a long call's input returns the long call's first rows to the bit, whichever
+    workgroup, wave group, LDS buffer, staging register set, walk direction (it alternates from launch to launch) or ragged last tile a row met.
+    Both calls of a pair must take the same kernels: the launch records of the two calls are the same sequence of (name, kind, nt, N, K).  The
+    records do not tell the stream form of layer_gemm_ws from the general one (same name and nt); the host picks between them by K, the epilogue
+    and `n % 32 == 0` only (ws_stream_ok), so a pair is two multiples of 32 or two ragged counts, which is asserted as well."""
+    import color_neus_amd as cn
+    lib = cn.load_library(library)
+    g = torch.Generator().manual_seed(2)
+    lib.timing_enable(True)
+    try:
+        for k, n_out, relu in TILE_SHAPES:
+            w = (torch.randn(n_out, k, generator=g) / k ** 0.5).to(device).requires_grad_(True)
+            b = (torch.randn(n_out, generator=g) * 0.1).to(device).requires_grad_(True)
+            for n_short, n_long in pairs:
+                assert (n_short % 32 == 0) == (n_long % 32 == 0), (n_short, n_long)
+                x = torch.randn(n_long, k, generator=g).to(device)
+                dy = torch.randn(n_long, n_out, generator=g).to(device)
+
+                def run(n):
+                    lib.timing_collect()
+                    xin = x[:n].clone().requires_grad_(True)
+                    y = HipLinear.apply(lib, xin, w, b, relu)
+                    (dx,) = torch.autograd.grad(y, [xin], dy[:n].contiguous())
+                    if xin.is_cuda:
+                        torch.cuda.synchronize()
+                    return y.detach(), dx, [(rec[0], rec[1], rec[2], rec[4], rec[5]) for rec in lib.timing_collect()]
+
+                ys, dxs, recs_s = run(n_short)
+                yl, dxl, recs_l = run(n_long)
+                print("rows / tile:", (k, n_out, relu), (n_short, n_long), recs_l)
+                assert recs_s == recs_l, (k, n_out, relu, n_short, n_long, recs_s, recs_l)
+                if want_ws:
+                    assert any(rec[0] in ("layer_gemm_ws", "layer_dw") for rec in recs_l), recs_l
+                assert torch.equal(ys, yl[:n_short]), (k, n_out, relu, n_short, n_long, "y", float((ys - yl[:n_short]).abs().max()))
+                assert torch.equal(dxs, dxl[:n_short]), (k, n_out, relu, n_short, n_long, "dx", float((dxs - dxl[:n_short]).abs().max()))
+                assert bool((yl != 0).any()) and bool((dxl != 0).any())
+    finally:
+        lib.timing_enable(False)
+
+
+@pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
+def test_rows_do_not_depend_on_their_tile_emu():
+    _check_rows_do_not_depend_on_their_tile(N.EMU_LIB, "cpu", [(37, 200), (64, 192)], False)
+
+
+@pytest.mark.gpu
+def test_rows_do_not_depend_on_their_tile_hip():
+    # 513 tiles: 3 tiles per workgroup, both LDS buffers and both staging sets | a 5-row last tile against a 3-row one
+    _check_rows_do_not_depend_on_their_tile(None, "cuda:0", [(64, 16416), (37, 16419)], True)
