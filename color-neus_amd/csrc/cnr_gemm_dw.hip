@@ -33,13 +33,93 @@ __device__ __forceinline__ void dw_store_partial(float* out, const DwGemm& g, co
       }
     }
 }
-// the view kinds of the operand pairs of a launch, for the dispatch onto the instantiations with pinned kinds (-1: no second pair)
-struct DwKinds { int x0, y0, x1, y1; };
-static DwKinds dw_kinds(const DwGemm& g) { return {g.X[0].kind, g.Y[0].kind, g.npairs > 1 ? g.X[1].kind : -1, g.npairs > 1 ? g.Y[1].kind : -1}; }
-#define DW_KINDS_CASE(launch_, k_, A_, B_, C_, D_) if (k_.x0 == A_ && k_.y0 == B_ && k_.x1 == C_ && k_.y1 == D_) { launch_<A_, B_, C_, D_>(g, n0, k0, s); return; }
 
-template <int WR, int WC, int MT, int KT, int KINDS = 0>
-__global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, int k0) {
+// The view kinds of a launch pinned at compile time, so that the interpreted prologue folds away.  ONE description generates both sides: the kernel
+// applies it to its copy of the launch (apply), the host asks it which launches may take the instantiation (matches).  X0 < 0: nothing is pinned
+// (interpreted at run time); X1 < 0: exactly one pair; ONES: the operands whose scale is pinned to 1 (bit 0 / 1: X / Y of pair 0, bit 2 / 3: of pair 1).
+template <int X0, int Y0, int X1 = -1, int Y1 = -1, unsigned ONES = 0>
+struct DwPin {
+  static constexpr bool pinned = X0 >= 0;
+  static constexpr bool one_pair = pinned && X1 < 0;   // the pair index folds to 0
+  static __host__ __device__ __forceinline__ void apply(DwGemm& g) {
+    constexpr int kind[4] = {X0, Y0, X1, Y1};
+    View* const v[4] = {&g.X[0], &g.Y[0], &g.X[1], &g.Y[1]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (kind[i] >= 0) { v[i]->kind = kind[i]; if (ONES >> i & 1) v[i]->scale = 1.0f; }
+  }
+  static bool matches(const DwGemm& g) {
+    if (!pinned) return true;
+    if (g.npairs != (one_pair ? 1 : 2)) return false;
+    constexpr int kind[4] = {X0, Y0, X1, Y1};
+    const View* const v[4] = {&g.X[0], &g.Y[0], &g.X[1], &g.Y[1]};
+    for (int i = 0; i < 2 * g.npairs; ++i)
+      if (v[i]->kind != kind[i] || ((ONES >> i & 1) && v[i]->scale != 1.0f)) return false;
+    return true;
+  }
+};
+typedef DwPin<-1, -1> DwInterpreted;
+constexpr unsigned DW_ONES_ALL = 0xf;
+// the instantiations of a kernel: the first pin of the list that matches the launch takes it (every list ends with DwInterpreted)
+template <class... PINS>
+struct DwPinList {
+  template <class LAUNCH>
+  static void first_match(const DwGemm& g, LAUNCH&& launch) {
+    bool done = false;
+    ((done = done || (PINS::matches(g) ? (launch(PINS{}), true) : false)), ...);
+  }
+};
+
+// 16-point slabs are dealt round-robin to the workgroups (the i-th slab of workgroup `chunk` is slab i * nchunk + chunk): at any moment the CUs read one
+// contiguous stretch of X and Y, which spreads over all HBM channels.  Every kernel that sums over points in this order takes it from here: the
+// partial sums must stay in a fixed order.
+struct DwSlabs {
+  long total;          // slabs of the point range
+  long n;              // slabs of this workgroup
+  long chunk; int nchunk;
+  __device__ __forceinline__ DwSlabs(long P, long chunk_, int nchunk_)
+      : total((P + 15) / 16), n(chunk_ < total ? (total - chunk_ + nchunk_ - 1) / nchunk_ : 0), chunk(chunk_), nchunk(nchunk_) {}
+  __device__ __forceinline__ long first_point(long i) const { return (i * nchunk + chunk) * 16; }   // of this workgroup's i-th slab
+};
+
+// one operand's part of a slab in flight (dw_gemm_kernel): NR 16-byte column groups per thread, raw as fetched
+template <int NR>
+struct DwStaged { f4 a[NR], b[NR]; bool ok[NR]; };
+// fetch: BP points from pbase x TW columns from col0 (points at and beyond p_end read the last point and are zeroed in dw_finish)
+template <int TW, int BP, int NR>
+__device__ __forceinline__ void dw_fetch(DwStaged<NR>& r, const View& v, long pbase, long p_end, int col0, int tid) {
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int idx = tid + i * 512;
+    if ((BP * TW / 4) % 512 == 0 || idx < BP * TW / 4) {
+      const int pl = idx / (TW / 4), c4 = idx % (TW / 4);
+      long pt = pbase + pl;
+      r.ok[i] = pt < p_end;
+      if (!r.ok[i]) pt = p_end - 1;
+      const Raw4 q = view_fetch4(v, pt, col0 + c4 * 4);
+      r.a[i] = q.a; r.b[i] = q.b;
+    }
+  }
+}
+// finish: the view's math, into the operand's LDS slab [BP][TW]
+template <int TW, int BP, int NR>
+__device__ __forceinline__ void dw_finish(const DwStaged<NR>& r, const View& v, float* dst, int col0, int tid) {
+  const f4 z4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NR; ++i) {
+    const int idx = tid + i * 512;
+    if ((BP * TW / 4) % 512 == 0 || idx < BP * TW / 4) {
+      Raw4 q; q.a = r.a[i]; q.b = r.b[i];
+      const f4 val = view_finish4(v, q, col0 + (idx % (TW / 4)) * 4);
+      *reinterpret_cast<f4*>(dst + idx * 4) = r.ok[i] ? val : z4;
+    }
+  }
+}
+
+template <int WR, int WC, int MT, int KT, class PIN = DwInterpreted>
+__global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g_in, int n0, int k0) {
+  DwGemm g = g_in;
+  PIN::apply(g);
   constexpr int TN = WR * MT * 32, TK = WC * KT * 32;
   constexpr int DW_BP = dw_bp(TN, TK);
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -54,7 +134,6 @@ __global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, in
   const int nslab_pair = p_end > p_begin ? (int)((p_end - p_begin + DW_BP - 1) / DW_BP) : 0;
   const int nslab = nslab_pair * g.npairs;
   constexpr int NX = (DW_BP * TN / 4 + 511) / 512, NY = (DW_BP * TK / 4 + 511) / 512;
-  constexpr bool NX_EXACT = (DW_BP * TN / 4) % 512 == 0, NY_EXACT = (DW_BP * TK / 4) % 512 == 0;
 
   f32x16 acc[MT][KT];
 #pragma unroll
@@ -64,82 +143,34 @@ __global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, in
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-  f4 rxa[NX], rxb[NX], rya[NY], ryb[NY];
-  bool okx[NX], oky[NY];
+  DwStaged<NX> rx;
+  DwStaged<NY> ry;
   int staged_pair = 0;
   float csum = 0.0f;
   const bool want_colsum = g.colsum != nullptr && k0 == 0;
 
-  // local views with the kinds pinned for the specialised instantiations (KINDS: 0 interpreted, 1 single pair all-direct, 2 SDF layer 0)
-  View vX0 = g.X[0], vY0 = g.Y[0], vX1 = g.X[1], vY1 = g.Y[1];
-  if (KINDS == 1) { vX0.kind = VK_DIRECT; vY0.kind = VK_DIRECT; vX0.scale = 1.0f; vY0.scale = 1.0f; }
-  if (KINDS == 2) { vX0.kind = VK_DIRECT; vY0.kind = VK_DIRECT; vX1.kind = VK_SIGMUL; vY1.kind = VK_DIRECT;
-                    vX0.scale = 1.0f; vY0.scale = 1.0f; vX1.scale = 1.0f; vY1.scale = 1.0f; }
-#define DW_FETCH_(X_, Y_)                                                                                 \
-  {                                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < NX; ++i) {                                                      \
-      const int idx = tid + i * 512;                                                                      \
-      if (NX_EXACT || idx < DW_BP * TN / 4) {                                                             \
-        const int pl = idx / (TN / 4), c4 = idx % (TN / 4);                                               \
-        long pt = pbase_ + pl;                                                                            \
-        okx[i] = pt < p_end;                                                                              \
-        if (!okx[i]) pt = p_end - 1;                                                                      \
-        const Raw4 q_ = view_fetch4(X_, pt, n0 + c4 * 4);                                                 \
-        rxa[i] = q_.a; rxb[i] = q_.b;                                                                     \
-      }                                                                                                   \
-    }                                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < NY; ++i) {                                                      \
-      const int idx = tid + i * 512;                                                                      \
-      if (NY_EXACT || idx < DW_BP * TK / 4) {                                                             \
-        const int pl = idx / (TK / 4), c4 = idx % (TK / 4);                                               \
-        long pt = pbase_ + pl;                                                                            \
-        oky[i] = pt < p_end;                                                                              \
-        if (!oky[i]) pt = p_end - 1;                                                                      \
-        const Raw4 q_ = view_fetch4(Y_, pt, k0 + c4 * 4);                                                 \
-        rya[i] = q_.a; ryb[i] = q_.b;                                                                     \
-      }                                                                                                   \
-    }                                                                                                     \
-  }
-#define DW_LOAD_SLAB(s_)                                                                                  \
-  {                                                                                                       \
-    const int pair_ = KINDS == 1 ? 0 : (s_) / nslab_pair;                                                 \
-    staged_pair = pair_;                                                                                  \
-    const long pbase_ = p_begin + (long)((s_) - pair_ * nslab_pair) * DW_BP;                              \
-    if (pair_ == 0) DW_FETCH_(vX0, vY0) else DW_FETCH_(vX1, vY1)                                          \
-  }
-#define DW_FINISH_(X_, Y_, buf_)                                                                          \
-  {                                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < NX; ++i) {                                                      \
-      const int idx = tid + i * 512;                                                                      \
-      if (NX_EXACT || idx < DW_BP * TN / 4) {                                                             \
-        Raw4 q_; q_.a = rxa[i]; q_.b = rxb[i];                                                            \
-        const f4 v_ = view_finish4(X_, q_, n0 + (idx % (TN / 4)) * 4);                                    \
-        *reinterpret_cast<f4*>(Xs + (buf_) * DW_BP * TN + idx * 4) = okx[i] ? v_ : z4_;                   \
-      }                                                                                                   \
-    }                                                                                                     \
-    _Pragma("unroll") for (int i = 0; i < NY; ++i) {                                                      \
-      const int idx = tid + i * 512;                                                                      \
-      if (NY_EXACT || idx < DW_BP * TK / 4) {                                                             \
-        Raw4 q_; q_.a = rya[i]; q_.b = ryb[i];                                                            \
-        const f4 v_ = view_finish4(Y_, q_, k0 + (idx % (TK / 4)) * 4);                                    \
-        *reinterpret_cast<f4*>(Ys + (buf_) * DW_BP * TK + idx * 4) = oky[i] ? v_ : z4_;                   \
-      }                                                                                                   \
-    }                                                                                                     \
-  }
-#define DW_STORE_SLAB(buf_)                                                                               \
-  {                                                                                                       \
-    const f4 z4_ = {0.f, 0.f, 0.f, 0.f};                                                                  \
-    if (staged_pair == 0) DW_FINISH_(vX0, vY0, buf_) else DW_FINISH_(vX1, vY1, buf_)                      \
-  }
+  auto load_slab = [&](int s) {
+    const int pair = PIN::one_pair ? 0 : s / nslab_pair;
+    staged_pair = pair;
+    const long pbase = p_begin + (long)(s - pair * nslab_pair) * DW_BP;
+    if (pair == 0) { dw_fetch<TN, DW_BP>(rx, g.X[0], pbase, p_end, n0, tid); dw_fetch<TK, DW_BP>(ry, g.Y[0], pbase, p_end, k0, tid); }
+    else { dw_fetch<TN, DW_BP>(rx, g.X[1], pbase, p_end, n0, tid); dw_fetch<TK, DW_BP>(ry, g.Y[1], pbase, p_end, k0, tid); }
+  };
+  auto store_slab = [&](int buf) {   // (a branch per pair, not a selected view: each side keeps its pinned kinds)
+    float* const xd = Xs + buf * DW_BP * TN;
+    float* const yd = Ys + buf * DW_BP * TK;
+    if (staged_pair == 0) { dw_finish<TN, DW_BP>(rx, g.X[0], xd, n0, tid); dw_finish<TK, DW_BP>(ry, g.Y[0], yd, k0, tid); }
+    else { dw_finish<TN, DW_BP>(rx, g.X[1], xd, n0, tid); dw_finish<TK, DW_BP>(ry, g.Y[1], yd, k0, tid); }
+  };
 
   if (nslab > 0) {
-    DW_LOAD_SLAB(0)
-    DW_STORE_SLAB(0)
+    load_slab(0);
+    store_slab(0);
   }
   __syncthreads();
   for (int s = 0; s < nslab; ++s) {
     const int buf = s & 1;
-    if (s + 1 < nslab) DW_LOAD_SLAB(s + 1)
+    if (s + 1 < nslab) load_slab(s + 1);
     const float* Xb = Xs + buf * DW_BP * TN + (lane >> 5) * TN + wr * MT * 32 + (lane & 31);
     const float* Yb = Ys + buf * DW_BP * TK + (lane >> 5) * TK + wc * KT * 32 + (lane & 31);
 #pragma unroll
@@ -159,38 +190,44 @@ __global__ __launch_bounds__(512) void dw_gemm_kernel(const DwGemm g, int n0, in
 #pragma unroll
       for (int pl = 0; pl < DW_BP; ++pl) csum += xc[pl * TN];
     }
-    if (s + 1 < nslab) DW_STORE_SLAB(buf ^ 1)
+    if (s + 1 < nslab) store_slab(buf ^ 1);
     __syncthreads();
   }
-#undef DW_LOAD_SLAB
-#undef DW_STORE_SLAB
-#undef DW_FETCH_
-#undef DW_FINISH_
 
   dw_store_partial<false>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * MT * 32, k0 + wc * KT * 32, lane);
   if (want_colsum && tid < TN && n0 + tid < g.Npad) g.colsum[chunk * g.Npad + n0 + tid] = csum;
 }
 
-template <int WR, int WC, int MT, int KT, int KINDS = 0>
+template <int WR, int WC, int MT, int KT, class PIN = DwInterpreted>
 static void launch_dw(const DwGemm& g, int n0, int k0, cnr_stream s) {
   constexpr int TN = WR * MT * 32, TK = WC * KT * 32;
   constexpr int DW_BP = dw_bp(TN, TK);
   const size_t lds = (size_t)(2 * DW_BP * (TN + TK)) * sizeof(float);
   const int tn_ = (g.N - n0) < TN ? (g.N - n0) : TN, tk_ = (g.K - k0) < TK ? (g.K - k0) : TK;
   TimingScope ts_("dw_gemm", 1, WR * 1000 + WC * 100 + MT * 10 + KT, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  launch_lds<dw_gemm_kernel<WR, WC, MT, KT, KINDS>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
+  launch_lds<dw_gemm_kernel<WR, WC, MT, KT, PIN>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
 }
 
 // ================================================================================================
-// weight-gradient GEMM, 256 x 256 output tile, split-bf16 matrix cores
+// weight-gradient GEMM, 256 x 256 output tile on the matrix cores, fp32 operands split into 16-bit planes: ONE kernel over a format
 //
 // Same output-stationary structure as dw_gemm_kernel<4,2,2,4> (128 accumulator registers per wave, one workgroup per point
-// chunk), but each fp32 operand element is split into three bf16 terms x = x1 + x2 + x3 (8 + 8 + 8 significand bits, the fp32
-// exponent range is kept, so no scaling is needed along the contraction over points) and each product is evaluated as six
-// v_mfma_f32_32x32x16_bf16 (x1y1 + x1y2 + x2y1 + x2y2 + x1y3 + x3y1, small terms first; the dropped terms are < 2^-25
-// relative).  6 x 32 cycles per 32x32x16 block against 8 x 64 for v_mfma_f32_32x32x2_f32: 2.7x the matrix rate at fp32 accuracy.
+// slice).  A format states what differs: the number of planes, the fragment type, how a staged block is split and stored, the
+// MFMA sequence of one column tile, whether the operands carry per-point scales (SCALED), its barrier and its pinned launches.
 //
-// LDS: per operand and plane the 16-point slab is stored as [half h][j = n % 4][c = n / 4][8 points] bf16 with 1088-byte
+// DwBf16 (split-bf16): x = x1 + x2 + x3 (8 + 8 + 8 significand bits, the fp32 exponent range is kept, so no scaling is needed
+// along the contraction over points); a product is six v_mfma_f32_32x32x16_bf16 (x1y1 + x1y2 + x2y1 + x2y2 + x1y3 + x3y1, small
+// terms first; the dropped terms are < 2^-25 relative).  6 x 32 cycles per 32x32x16 block against 8 x 64 for
+// v_mfma_f32_32x32x2_f32: 2.7x the matrix rate at fp32 accuracy.
+//
+// DwF16 (split-f16, three MFMAs per product instead of six): along the contraction a scale can only be used if it cancels per
+// point: X'[pt] = X[pt] * sx[pt] (the power of two that lifts the row into the top f16 binade -- emitted for free by the layer
+// GEMM that consumed the same operand, LayerGemm::rs_out) and Y'[pt] = Y[pt] * 2^G / sx[pt], so X'^T Y' = 2^G X^T Y exactly.
+// G = 1 + min over the workgroup's points of log2(sx * sy) keeps every Y' row below 2^15; points whose product is far below the
+// largest one lose relative precision in Y' but their absolute error stays below 2^-40 of the largest term.  Both operands are
+// split hi + lo (11 + 11 bits) and x1 y2 + x2 y1 + x1 y1 is accumulated in fp32; the result is scaled back by 2^-G (exact).
+//
+// LDS: per operand and plane the 16-point slab is stored as [half h][j = n % 4][c = n / 4][8 points] of 16 bits with 1088-byte
 // j-regions: the staging threads (4 columns x 4 points each) write 8-byte point quads, adjacent lanes adjacent quads
 // (conflict-free), and an MFMA lane reads the 16 bytes of its row n / point half h (conflict-free: 16 lanes cover 16
 // distinct 16-byte bank groups).
@@ -199,9 +236,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int DX_JREG = 1088;                 // bytes per j-region (64 columns x 16 bytes + 64 bytes of bank rotation)
 constexpr int DX_HALF = 4 * DX_JREG;          // one point half (8 points) of one plane
-constexpr int DX_PLANE = 2 * DX_HALF;         // one bf16 plane of a 16-point x 256-column slab
-constexpr int DX_OPER = 3 * DX_PLANE;         // three planes
-constexpr int DX_BUF = 2 * DX_OPER;           // X and Y
+constexpr int DX_PLANE = 2 * DX_HALF;         // one 16-bit plane of a 16-point x 256-column slab
 
 __device__ __forceinline__ void dx_split3(float x, __bf16& h1, __bf16& h2, __bf16& h3) {
   h1 = (__bf16)x;
@@ -211,24 +246,104 @@ __device__ __forceinline__ void dx_split3(float x, __bf16& h1, __bf16& h2, __bf1
   h3 = (__bf16)r;
 }
 
-// XK0 / YK0 / XK1 / YK1 >= 0 pin the view kinds of the operand pairs at compile time (-1 = interpreted at run time)
-template <int XK0, int YK0, int XK1, int YK1>
-__global__ __launch_bounds__(512, 1) void dw_gemm_bx_kernel(const DwGemm g_in, int n0, int k0) {
+// In both formats the two row tiles of a wave alternate (c0, c1) so that back-to-back MFMAs never depend on each other; that hand
+// interleaving is why DwF16 does not call split_mfma3_32 twice, which would state another order.
+struct DwBf16 {
+  static constexpr const char* name = "dw_gemm_bx";
+  static constexpr int PLANES = 3;
+  static constexpr bool SCALED = false;
+  typedef bf16x8 frag;
+  static __device__ __forceinline__ void barrier() { __syncthreads(); }
+  // one column of a staged block (4 points) -> an 8-byte point quad per plane
+  static __device__ __forceinline__ void store4(const f4& c, unsigned char* d) {
+    bf16x4 h1, h2, h3;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { __bf16 a_, b_, c_; dx_split3(c[i], a_, b_, c_); h1[i] = a_; h2[i] = b_; h3[i] = c_; }
+    *reinterpret_cast<bf16x4*>(d) = h1;
+    *reinterpret_cast<bf16x4*>(d + DX_PLANE) = h2;
+    *reinterpret_cast<bf16x4*>(d + 2 * DX_PLANE) = h3;
+  }
+  static __device__ __forceinline__ void mfma(f32x16& c0, f32x16& c1, const frag (&a)[2][3], const frag (&b)[3]) {
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][2], b[0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][2], b[0], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[2], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[2], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b[1], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b[1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b[0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b[0], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[1], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[0], c1, 0, 0, 0);
+  }
+  // the operand combinations of the render plan (cnr_plan.cpp): MLP layers, SDF value + gradient-chain pairs
+  typedef DwPinList<DwPin<VK_DIRECT, VK_DIRECT>, DwPin<VK_DIRECT, VK_SOFTPLUS>, DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT>,
+                    DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT>, DwPin<VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT>, DwInterpreted> Pins;
+};
+struct DwF16 {
+  static constexpr const char* name = "dw_gemm_hx";
+  static constexpr int PLANES = 2;
+  static constexpr bool SCALED = true;
+  typedef f16x8 frag;
+  static __device__ __forceinline__ void barrier() { cnr_lds_barrier(); }
+  static __device__ __forceinline__ void store4(const f4& c, unsigned char* d) { split_store4(c, d, DX_PLANE); }
+  static __device__ __forceinline__ void mfma(f32x16& c0, f32x16& c1, const frag (&a)[2][2], const frag (&b)[2]) {
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b[1], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b[1], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][1], b[0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][1], b[0], c1, 0, 0, 0);
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b[0], c0, 0, 0, 0);
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b[0], c1, 0, 0, 0);
+  }
+  typedef DwPinList<DwPin<VK_DIRECT, VK_DIRECT>, DwPin<VK_DIRECT, VK_SOFTPLUS>, DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT>,
+                    DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT>, DwInterpreted> Pins;
+};
+template <class F> constexpr int dw_split_oper = F::PLANES * DX_PLANE;     // one operand's planes of a slab
+template <class F> constexpr int dw_split_buf = 2 * dw_split_oper<F>;      // X and Y; the kernel double-buffers
+
+template <class F, class PIN>
+__global__ __launch_bounds__(512, 1) void dw_gemm_split_kernel(const DwGemm g_in, int n0, int k0) {
   DwGemm g = g_in;
-  if (XK0 >= 0) g.X[0].kind = XK0;
-  if (YK0 >= 0) g.Y[0].kind = YK0;
-  if (XK1 >= 0) g.X[1].kind = XK1;
-  if (YK1 >= 0) g.Y[1].kind = YK1;
+  PIN::apply(g);
+  constexpr int OPER = dw_split_oper<F>, BUF = dw_split_buf<F>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_d[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;               // 4 x 2 waves, 64 x 128 outputs each
-  // 16-point slabs are dealt round-robin to the workgroups (slab = i * nchunk + chunk): at any moment the CUs read one
-  // contiguous stretch of X and Y, which spreads over all HBM channels; the partial sums stay in a fixed order
   const long chunk = blockIdx.x;
   const long p_end = g.P;
-  const long total_slabs = (g.P + 15) / 16;
-  const int nslab_pair = chunk < total_slabs ? (int)((total_slabs - chunk + g.nchunk - 1) / g.nchunk) : 0;
+  const DwSlabs slabs(g.P, chunk, g.nchunk);
+  const int nslab_pair = (int)slabs.n;
   const int nslab = nslab_pair * g.npairs;
+  // SCALED: exponent of this workgroup's slice of the point range: G = 1 + min log2(sx * sy) over its own points (both pairs, all-zero rows
+  // excluded): no separate reduction launch, and a slice of small-magnitude points keeps its own dynamic range
+  int G = 0;
+  if constexpr (F::SCALED) {
+    G = SPLIT_GBIG;
+    const int npts = nslab_pair * 16;
+    auto scan = [&](const float* sxp, const float* syp) {   // (no run-time index into g: the struct must stay in registers)
+      for (int i = tid; i < npts; i += 512) {
+        const long pt = slabs.first_point(i >> 4) + (i & 15);
+        if (pt < p_end) {
+          const float a = sxp[pt], b = syp[pt];   // powers of two (or 0 / NaN)
+          const int e = split_exp2_of_product(a, b) + 1;
+          if (a > 0.0f && b > 0.0f && e < G) G = e;
+        }
+      }
+    };
+    scan(g.sx[0], g.sy[0]);
+    if (g.npairs > 1) scan(g.sx[1], g.sy[1]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(G, d); G = o < G ? o : G; }
+    int* red = reinterpret_cast<int*>(smem_d);
+    if (lane == 0) red[wave] = G;
+    F::barrier();
+#pragma unroll
+    for (int w = 0; w < 8; ++w) { const int o = red[w]; G = o < G ? o : G; }
+    F::barrier();
+    G = __builtin_amdgcn_readfirstlane(G);                // (uniform: keep it in a scalar register)
+    if (G >= SPLIT_GBIG) G = 0;                           // no point with two non-zero rows: everything is zero anyway
+  }
 
   f32x16 acc[2][4];
 #pragma unroll
@@ -244,50 +359,57 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_bx_kernel(const DwGemm g_in, i
   const int qlo = st & 1, c4 = (st >> 1) & 63, qhi = st >> 7;
   const int q = qhi * 2 + qlo;                          // point quad of the slab
   const int scol = (is_y ? k0 : n0) + c4 * 4;
-  unsigned char* const sdst = smem_d + (is_y ? DX_OPER : 0) + qhi * DX_HALF + c4 * 16 + qlo * 8;
+  unsigned char* const sdst = smem_d + (is_y ? OPER : 0) + qhi * DX_HALF + c4 * 16 + qlo * 8;
   f4 ra[4], rb[4];
+  [[maybe_unused]] float rsx[4];                          // SCALED: sx of the 4 points this thread stages
   bool okp[4];
   int staged_pair = 0;
   f4 csum = {0.f, 0.f, 0.f, 0.f};
   const bool want_colsum = g.colsum != nullptr && k0 == 0;
 
-#define DX_FETCH_(V_)                                                                      \
+#define DT_FETCH_(V_)                                                                      \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                          \
     long pt = pbase_ + i;                                                                  \
     okp[i] = pt < p_end;                                                                   \
     if (!okp[i]) pt = p_end - 1;                                                           \
     const Raw4 q_ = view_fetch4(V_, pt, scol);                                             \
     ra[i] = q_.a; rb[i] = q_.b;                                                            \
+    if constexpr (F::SCALED) rsx[i] = sxp_[pt];                                            \
   }
-#define DX_LOAD_SLAB(s_)                                                                   \
+#define DT_LOAD_SLAB(s_)                                                                   \
   {                                                                                        \
-    const int pair_ = (s_) / nslab_pair;                                                   \
+    const int pair_ = PIN::one_pair ? 0 : (s_) / nslab_pair;                               \
     staged_pair = pair_;                                                                   \
-    const long pbase_ = ((long)((s_) - pair_ * nslab_pair) * g.nchunk + chunk) * 16 + q * 4; \
-    if (pair_ == 0) { if (is_y) { DX_FETCH_(g.Y[0]) } else { DX_FETCH_(g.X[0]) } }         \
-    else { if (is_y) { DX_FETCH_(g.Y[1]) } else { DX_FETCH_(g.X[1]) } }                    \
+    const long pbase_ = slabs.first_point((s_) - pair_ * nslab_pair) + q * 4;              \
+    [[maybe_unused]] const float* sxp_ = pair_ == 0 ? g.sx[0] : g.sx[1];                   \
+    if (pair_ == 0) { if (is_y) { DT_FETCH_(g.Y[0]) } else { DT_FETCH_(g.X[0]) } }         \
+    else { if (is_y) { DT_FETCH_(g.Y[1]) } else { DT_FETCH_(g.X[1]) } }                    \
   }
-#define DX_FINISH_(V_)                                                                     \
+#define DT_FINISH_(V_)                                                                     \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                          \
     Raw4 q_; q_.a = ra[i]; q_.b = rb[i];                                                   \
     v_[i] = okp[i] ? view_finish4(V_, q_, scol) : z4_;                                     \
   }
-#define DX_STORE_SLAB(buf_)                                                                \
+#define DT_STORE_SLAB(buf_)                                                                \
   {                                                                                        \
     const f4 z4_ = {0.f, 0.f, 0.f, 0.f};                                                   \
     f4 v_[4];                                                                              \
-    if (staged_pair == 0) { if (is_y) { DX_FINISH_(g.Y[0]) } else { DX_FINISH_(g.X[0]) } } \
-    else { if (is_y) { DX_FINISH_(g.Y[1]) } else { DX_FINISH_(g.X[1]) } }                  \
+    if (staged_pair == 0) { if (is_y) { DT_FINISH_(g.Y[0]) } else { DT_FINISH_(g.X[0]) } } \
+    else { if (is_y) { DT_FINISH_(g.Y[1]) } else { DT_FINISH_(g.X[1]) } }                  \
     if (want_colsum && !is_y && staged_pair == 0) {                                        \
       _Pragma("unroll") for (int i = 0; i < 4; ++i) { csum.x += v_[i].x; csum.y += v_[i].y; csum.z += v_[i].z; csum.w += v_[i].w; } \
     }                                                                                      \
-    unsigned char* d_ = sdst + (buf_) * DX_BUF;                                            \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                        \
-      bf16x4 h1, h2, h3;                                                                   \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) { __bf16 a_, b_, c_; dx_split3(v_[i][j], a_, b_, c_); h1[i] = a_; h2[i] = b_; h3[i] = c_; } \
-      *reinterpret_cast<bf16x4*>(d_ + j * DX_JREG) = h1;                                   \
-      *reinterpret_cast<bf16x4*>(d_ + DX_PLANE + j * DX_JREG) = h2;                        \
-      *reinterpret_cast<bf16x4*>(d_ + 2 * DX_PLANE + j * DX_JREG) = h3;                    \
+    if constexpr (F::SCALED) {                                                             \
+      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                      \
+        float f_ = rsx[i];                                                                 \
+        if (is_y) f_ = split_yscale(f_, G);                                                \
+        v_[i].x *= f_; v_[i].y *= f_; v_[i].z *= f_; v_[i].w *= f_;                        \
+      }                                                                                    \
+    }                                                                                      \
+    unsigned char* d_ = sdst + (buf_) * BUF;                                               \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {   /* column j of the 4 points */       \
+      const f4 c_ = {v_[0][j], v_[1][j], v_[2][j], v_[3][j]};                              \
+      F::store4(c_, d_ + j * DX_JREG);                                                     \
     }                                                                                      \
   }
 
@@ -296,304 +418,85 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_bx_kernel(const DwGemm g_in, i
   // matrix pipe and the VALU / LDS-store path overlap.  X waves: load(s+1) | MFMA(s) | store(s+1);  Y waves: store(s+1),
   // load(s+2) | MFMA(s).  One barrier per slab.
   if (nslab > 0) {
-    DX_LOAD_SLAB(0)
-    DX_STORE_SLAB(0)
-    if (is_y && nslab > 1) DX_LOAD_SLAB(1)
+    DT_LOAD_SLAB(0)
+    DT_STORE_SLAB(0)
+    if (is_y && nslab > 1) DT_LOAD_SLAB(1)
   }
-  __syncthreads();
+  F::barrier();
   // operand fragment addresses of this lane: row / column (lane & 31) of each 32-wide tile, point half (lane >> 5)
   const int ln = lane & 31, lh = lane >> 5;
   const int xoff = lh * DX_HALF + (ln & 3) * DX_JREG + (wr * 16 + (ln >> 2)) * 16;              // + i * 8 * 16 per n-tile
-  const int yoff = DX_OPER + lh * DX_HALF + (ln & 3) * DX_JREG + (wc * 32 + (ln >> 2)) * 16;    // + j * 8 * 16 per k-tile
+  const int yoff = OPER + lh * DX_HALF + (ln & 3) * DX_JREG + (wc * 32 + (ln >> 2)) * 16;       // + j * 8 * 16 per k-tile
   for (int s = 0; s < nslab; ++s) {
     const int buf = s & 1;
     if (!is_y) {
-      if (s + 1 < nslab) DX_LOAD_SLAB(s + 1)
+      if (s + 1 < nslab) DT_LOAD_SLAB(s + 1)
     } else if (s + 1 < nslab) {
-      DX_STORE_SLAB(buf ^ 1)
-      if (s + 2 < nslab) DX_LOAD_SLAB(s + 2)
+      DT_STORE_SLAB(buf ^ 1)
+      if (s + 2 < nslab) DT_LOAD_SLAB(s + 2)
     }
-    const unsigned char* B_ = smem_d + buf * DX_BUF;
-    bf16x8 a[2][3];
+    const unsigned char* B_ = smem_d + buf * BUF;
+    typename F::frag a[2][F::PLANES];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) a[i][p] = *reinterpret_cast<const bf16x8*>(B_ + xoff + p * DX_PLANE + i * 128);
+      for (int p = 0; p < F::PLANES; ++p) a[i][p] = *reinterpret_cast<const typename F::frag*>(B_ + xoff + p * DX_PLANE + i * 128);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      bf16x8 b[3];
+      typename F::frag b[F::PLANES];
 #pragma unroll
-      for (int p = 0; p < 3; ++p) b[p] = *reinterpret_cast<const bf16x8*>(B_ + yoff + p * DX_PLANE + j * 128);
-      // the two row tiles alternate so that back-to-back MFMAs never depend on each other
+      for (int p = 0; p < F::PLANES; ++p) b[p] = *reinterpret_cast<const typename F::frag*>(B_ + yoff + p * DX_PLANE + j * 128);
       f32x16 c0 = acc[0][j], c1 = acc[1][j];
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][2], b[0], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][2], b[0], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[2], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[2], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b[1], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b[1], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][1], b[0], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][1], b[0], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[1], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[1], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[0], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[0], c1, 0, 0, 0);
+      F::mfma(c0, c1, a, b);
       acc[0][j] = c0; acc[1][j] = c1;
     }
-    if (!is_y && s + 1 < nslab) DX_STORE_SLAB(buf ^ 1)
-    __syncthreads();
+    if (!is_y && s + 1 < nslab) DT_STORE_SLAB(buf ^ 1)
+    F::barrier();
   }
-#undef DX_LOAD_SLAB
-#undef DX_STORE_SLAB
-#undef DX_FETCH_
-#undef DX_FINISH_
+#undef DT_LOAD_SLAB
+#undef DT_STORE_SLAB
+#undef DT_FETCH_
+#undef DT_FINISH_
 
-  dw_store_partial<false>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * 64, k0 + wc * 128, lane);
+  // SCALED: undo 2^G in two exact steps (G can exceed the fp32 exponent range of a single factor)
+  SplitPow2 un = {1.0f, 1.0f};
+  if constexpr (F::SCALED) un = split_pow2(-G);
+  dw_store_partial<F::SCALED>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * 64, k0 + wc * 128, lane, un.u1, un.u2);
   if (want_colsum) {   // bias gradient: the four point-quad owners of a column group add their sums in a fixed order
     float* cs = reinterpret_cast<float*>(smem_d);          // [4 quads][256 columns]; the slab buffers are dead now
     if (!is_y) *reinterpret_cast<f4*>(cs + q * 256 + c4 * 4) = csum;
-    __syncthreads();
+    F::barrier();
     if (tid < 256 && n0 + tid < g.Npad) g.colsum[chunk * g.Npad + n0 + tid] = ((cs[tid] + cs[256 + tid]) + cs[512 + tid]) + cs[768 + tid];
   }
 }
 
-template <int XK0, int YK0, int XK1, int YK1>
-static void launch_dw_bx_t(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const size_t lds = (size_t)2 * DX_BUF;
-  const int tn_ = (g.N - n0) < 256 ? (g.N - n0) : 256, tk_ = (g.K - k0) < 256 ? (g.K - k0) : 256;
-  TimingScope ts_("dw_gemm_bx", 1, 4224, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  launch_lds<dw_gemm_bx_kernel<XK0, YK0, XK1, YK1>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
-}
-
-static void launch_dw_bx(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const DwKinds k = dw_kinds(g);
-  // the operand combinations of the render plan (cnr_plan.cpp): MLP layers, SDF value + gradient-chain pairs
-  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_DIRECT, -1, -1)
-  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, -1, -1)
-  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
-  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
-  DW_KINDS_CASE(launch_dw_bx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT)
-  launch_dw_bx_t<-1, -1, -1, -1>(g, n0, k0, s);
-}
-
-// ================================================================================================
-// weight-gradient GEMM, 256 x 256 output tile, split-f16 matrix cores (three MFMAs per product instead of six)
-//
-// Along the contraction (points) a scale can only be used if it cancels per point: X'[pt] = X[pt] * sx[pt] (the power of
-// two that lifts the row into the top f16 binade -- emitted for free by the layer GEMM that consumed the same operand,
-// LayerGemm::rs_out) and Y'[pt] = Y[pt] * 2^G / sx[pt], so X'^T Y' = 2^G X^T Y exactly.  G = 1 + min over the workgroup's points of
-// log2(sx * sy) keeps every Y' row below 2^15; points whose product is far below the largest one lose relative
-// precision in Y' but their absolute error stays below 2^-40 of the largest term.  Both operands are split hi + lo
-// (11 + 11 bits) and x1 y2 + x2 y1 + x1 y1 is accumulated in fp32; the result is scaled back by 2^-G (exact).
-// Structure, LDS layout and wave phase shift as dw_gemm_bx_kernel (two planes per operand instead of three).
-// ================================================================================================
-constexpr int DH_OPER = 2 * DX_PLANE;
-constexpr int DH_BUF = 2 * DH_OPER;
-
-template <int XK0, int YK0, int XK1, int YK1>
-__global__ __launch_bounds__(512, 1) void dw_gemm_hx_kernel(const DwGemm g_in, int n0, int k0) {
-  DwGemm g = g_in;
-  if (XK0 >= 0) g.X[0].kind = XK0;
-  if (YK0 >= 0) g.Y[0].kind = YK0;
-  if (XK1 >= 0) g.X[1].kind = XK1;
-  if (YK1 >= 0) g.Y[1].kind = YK1;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_d[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const long chunk = blockIdx.x;
-  const long p_end = g.P;
-  const long total_slabs = (g.P + 15) / 16;
-  const int nslab_pair = chunk < total_slabs ? (int)((total_slabs - chunk + g.nchunk - 1) / g.nchunk) : 0;
-  const int nslab = nslab_pair * g.npairs;
-  // exponent of this workgroup's slice of the point range: G = 1 + min log2(sx * sy) over its own points (both pairs, all-zero rows
-  // excluded): no separate reduction launch, and a slice of small-magnitude points keeps its own dynamic range
-  int G = SPLIT_GBIG;
-  {
-    const int npts = nslab_pair * 16;
-    auto scan = [&](const float* sxp, const float* syp) {   // (no run-time index into g: the struct must stay in registers)
-      for (int i = tid; i < npts; i += 512) {
-        const long pt = ((long)(i >> 4) * g.nchunk + chunk) * 16 + (i & 15);
-        if (pt < p_end) {
-          const float a = sxp[pt], b = syp[pt];   // powers of two (or 0 / NaN)
-          const int e = split_exp2_of_product(a, b) + 1;
-          if (a > 0.0f && b > 0.0f && e < G) G = e;
-        }
-      }
-    };
-    scan(g.sx[0], g.sy[0]);
-    if (g.npairs > 1) scan(g.sx[1], g.sy[1]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(G, d); G = o < G ? o : G; }
-    int* red = reinterpret_cast<int*>(smem_d);
-    if (lane == 0) red[wave] = G;
-    cnr_lds_barrier();
-#pragma unroll
-    for (int w = 0; w < 8; ++w) { const int o = red[w]; G = o < G ? o : G; }
-    cnr_lds_barrier();
-    G = __builtin_amdgcn_readfirstlane(G);                // (uniform: keep it in a scalar register)
-    if (G >= SPLIT_GBIG) G = 0;                           // no point with two non-zero rows: everything is zero anyway
-  }
-
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-  const bool is_y = tid >= 256;
-  const int st = tid & 255;
-  const int qlo = st & 1, c4 = (st >> 1) & 63, qhi = st >> 7;
-  const int q = qhi * 2 + qlo;
-  const int scol = (is_y ? k0 : n0) + c4 * 4;
-  unsigned char* const sdst = smem_d + (is_y ? DH_OPER : 0) + qhi * DX_HALF + c4 * 16 + qlo * 8;
-  f4 ra[4], rb[4];
-  float rsx[4];                                           // sx of the 4 points this thread stages
-  bool okp[4];
-  int staged_pair = 0;
-  f4 csum = {0.f, 0.f, 0.f, 0.f};
-  const bool want_colsum = g.colsum != nullptr && k0 == 0;
-
-#define DH_FETCH_(V_)                                                                      \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                          \
-    long pt = pbase_ + i;                                                                  \
-    okp[i] = pt < p_end;                                                                   \
-    if (!okp[i]) pt = p_end - 1;                                                           \
-    const Raw4 q_ = view_fetch4(V_, pt, scol);                                             \
-    ra[i] = q_.a; rb[i] = q_.b;                                                            \
-    rsx[i] = sxp_[pt];                                                                     \
-  }
-  constexpr bool kOnePair = XK0 >= 0 && XK1 < 0;   // specialised single-pair instantiation: the pair index folds to 0
-#define DH_LOAD_SLAB(s_)                                                                   \
-  {                                                                                        \
-    const int pair_ = kOnePair ? 0 : (s_) / nslab_pair;                                    \
-    staged_pair = pair_;                                                                   \
-    const long pbase_ = ((long)((s_) - pair_ * nslab_pair) * g.nchunk + chunk) * 16 + q * 4; \
-    const float* sxp_ = pair_ == 0 ? g.sx[0] : g.sx[1];                                    \
-    if (pair_ == 0) { if (is_y) { DH_FETCH_(g.Y[0]) } else { DH_FETCH_(g.X[0]) } }         \
-    else { if (is_y) { DH_FETCH_(g.Y[1]) } else { DH_FETCH_(g.X[1]) } }                    \
-  }
-#define DH_FINISH_(V_)                                                                     \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                          \
-    Raw4 q_; q_.a = ra[i]; q_.b = rb[i];                                                   \
-    v_[i] = okp[i] ? view_finish4(V_, q_, scol) : z4_;                                     \
-  }
-#define DH_STORE_SLAB(buf_)                                                                \
-  {                                                                                        \
-    const f4 z4_ = {0.f, 0.f, 0.f, 0.f};                                                   \
-    f4 v_[4];                                                                              \
-    if (staged_pair == 0) { if (is_y) { DH_FINISH_(g.Y[0]) } else { DH_FINISH_(g.X[0]) } } \
-    else { if (is_y) { DH_FINISH_(g.Y[1]) } else { DH_FINISH_(g.X[1]) } }                  \
-    if (want_colsum && !is_y && staged_pair == 0) {                                        \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) { csum.x += v_[i].x; csum.y += v_[i].y; csum.z += v_[i].z; csum.w += v_[i].w; } \
-    }                                                                                      \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                        \
-      float f_ = rsx[i];                                                                   \
-      if (is_y) f_ = split_yscale(f_, G);                                                    \
-      v_[i].x *= f_; v_[i].y *= f_; v_[i].z *= f_; v_[i].w *= f_;                          \
-    }                                                                                      \
-    unsigned char* d_ = sdst + (buf_) * DH_BUF;                                            \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {   /* column j of the 4 points */       \
-      const f4 c_ = {v_[0][j], v_[1][j], v_[2][j], v_[3][j]};                              \
-      split_store4(c_, d_ + j * DX_JREG, DX_PLANE);                                        \
-    }                                                                                      \
-  }
-
-  if (nslab > 0) {
-    DH_LOAD_SLAB(0)
-    DH_STORE_SLAB(0)
-    if (is_y && nslab > 1) DH_LOAD_SLAB(1)
-  }
-  cnr_lds_barrier();
-  const int ln = lane & 31, lh = lane >> 5;
-  const int xoff = lh * DX_HALF + (ln & 3) * DX_JREG + (wr * 16 + (ln >> 2)) * 16;
-  const int yoff = DH_OPER + lh * DX_HALF + (ln & 3) * DX_JREG + (wc * 32 + (ln >> 2)) * 16;
-  for (int s = 0; s < nslab; ++s) {
-    const int buf = s & 1;
-    if (!is_y) {
-      if (s + 1 < nslab) DH_LOAD_SLAB(s + 1)
-    } else if (s + 1 < nslab) {
-      DH_STORE_SLAB(buf ^ 1)
-      if (s + 2 < nslab) DH_LOAD_SLAB(s + 2)
-    }
-    const unsigned char* B_ = smem_d + buf * DH_BUF;
-    f16x8 a[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) a[i][p] = *reinterpret_cast<const f16x8*>(B_ + xoff + p * DX_PLANE + i * 128);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f16x8 b[2];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) b[p] = *reinterpret_cast<const f16x8*>(B_ + yoff + p * DX_PLANE + j * 128);
-      f32x16 c0 = acc[0][j], c1 = acc[1][j];
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b[1], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b[1], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][1], b[0], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][1], b[0], c1, 0, 0, 0);
-      c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][0], b[0], c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][0], b[0], c1, 0, 0, 0);
-      acc[0][j] = c0; acc[1][j] = c1;
-    }
-    if (!is_y && s + 1 < nslab) DH_STORE_SLAB(buf ^ 1)
-    cnr_lds_barrier();
-  }
-#undef DH_LOAD_SLAB
-#undef DH_STORE_SLAB
-#undef DH_FETCH_
-#undef DH_FINISH_
-
-  // undo 2^G in two exact steps (G can exceed the fp32 exponent range of a single factor)
-  const SplitPow2 un = split_pow2(-G);
-  dw_store_partial<true>(g.partial + chunk * (long)g.Npad * g.ldk, g, acc, n0 + wr * 64, k0 + wc * 128, lane, un.u1, un.u2);
-  if (want_colsum) {
-    float* cs = reinterpret_cast<float*>(smem_d);
-    if (!is_y) *reinterpret_cast<f4*>(cs + q * 256 + c4 * 4) = csum;
-    cnr_lds_barrier();
-    if (tid < 256 && n0 + tid < g.Npad) g.colsum[chunk * g.Npad + n0 + tid] = ((cs[tid] + cs[256 + tid]) + cs[512 + tid]) + cs[768 + tid];
-  }
-}
-
-template <int XK0, int YK0, int XK1, int YK1>
-static void launch_dw_hx_t(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const size_t lds = (size_t)2 * DH_BUF;
-  const int tn_ = (g.N - n0) < 256 ? (g.N - n0) : 256, tk_ = (g.K - k0) < 256 ? (g.K - k0) : 256;
-  TimingScope ts_("dw_gemm_hx", 1, 4224, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  launch_lds<dw_gemm_hx_kernel<XK0, YK0, XK1, YK1>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
-}
-
-static void launch_dw_hx(const DwGemm& g, int n0, int k0, cnr_stream s) {
-  const DwKinds k = dw_kinds(g);
-  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_DIRECT, -1, -1)
-  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, -1, -1)
-  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT)
-  DW_KINDS_CASE(launch_dw_hx_t, k, VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT)
-  launch_dw_hx_t<-1, -1, -1, -1>(g, n0, k0, s);
+template <class F>
+static void launch_dw_split(const DwGemm& g, int n0, int k0, cnr_stream s) {
+  F::Pins::first_match(g, [&](auto pin) {
+    const size_t lds = (size_t)2 * dw_split_buf<F>;
+    const int tn_ = (g.N - n0) < 256 ? (g.N - n0) : 256, tk_ = (g.K - k0) < 256 ? (g.K - k0) : 256;
+    TimingScope ts_(F::name, 1, 4224, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
+    launch_lds<dw_gemm_split_kernel<F, decltype(pin)>>(dim3(g.nchunk), dim3(512), lds, lds, s, g, n0, k0);
+  });
 }
 
 // ================================================================================================
 // weight-gradient strips with one very narrow side (<= 8 columns): the 3 / 6 extra input columns of the colour and
 // relight nets, the rgb / sdf output rows.  Pure HBM streams (<= 12 FLOP per loaded byte): no matrix cores, no LDS
-// staging.  One workgroup per point chunk, 16 waves, each wave walks its own points (slabs dealt round-robin as in
-// dw_gemm_bx); a lane owns 4 columns of the wide operand x all narrow columns in registers; the 8 waves are folded
+// staging.  One workgroup per point chunk, 16 waves, each wave walks its own points (slabs dealt as DwSlabs says);
+// a lane owns 4 columns of the wide operand x all narrow columns in registers; the 8 waves are folded
 // through LDS in a fixed order.  NARROW_X: the narrow operand is X (rows of dW), otherwise Y (columns of dW).
 // ================================================================================================
 constexpr int SK_WAVES = 8;
+// the pinned launches of the strips: every view VK_DIRECT with scale 1 (4 of the 5 strips of a step; the pin of two such pairs also serves a
+// single one, whose second pair is never read), and the sdf row of the top SDF layer (zbar x softplus(z) + unit vector x qbar)
+typedef DwPin<VK_DIRECT, VK_DIRECT, VK_DIRECT, VK_DIRECT, DW_ONES_ALL> SkDirect;
+typedef DwPin<VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT, 0x9> SkSdfRow;
 
-// KINDS: 0 = interpreted views; 1 = every view VK_DIRECT with scale 1 (4 of the 5 strips of a step); 2 = the sdf row of the top
-// SDF layer (zbar x softplus(z) + unit vector x qbar).  With the kinds pinned the interpreted prologue folds away.
-template <bool NARROW_X, bool NG2, int KINDS>
+template <bool NARROW_X, bool NG2, class PIN>
 __global__ __launch_bounds__(SK_WAVES * 64) void dw_skinny_kernel(const DwGemm g_in, int n0, int k0, int ncnt) {
   DwGemm g = g_in;
-  if (KINDS == 1) {
-    g.X[0].kind = VK_DIRECT; g.Y[0].kind = VK_DIRECT; g.X[1].kind = VK_DIRECT; g.Y[1].kind = VK_DIRECT;
-    g.X[0].scale = 1.0f; g.Y[0].scale = 1.0f; g.X[1].scale = 1.0f; g.Y[1].scale = 1.0f;
-  } else if (KINDS == 2) {
-    g.X[0].kind = VK_DIRECT; g.Y[0].kind = VK_SOFTPLUS; g.X[1].kind = VK_CONST_COL0; g.Y[1].kind = VK_DIRECT;
-    g.X[0].scale = 1.0f; g.Y[1].scale = 1.0f;
-  }
+  PIN::apply(g);
   constexpr int SK_UNROLL = NG2 ? 4 : 8;
   extern __shared__ __attribute__((aligned(16))) float smem_k[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -607,10 +510,9 @@ __global__ __launch_bounds__(SK_WAVES * 64) void dw_skinny_kernel(const DwGemm g
   for (int j = 0; j < 8; ++j) { acc[j].x = 0.f; acc[j].y = 0.f; acc[j].z = 0.f; acc[j].w = 0.f; }
   f4 cs0 = {0.f, 0.f, 0.f, 0.f}, cs1 = {0.f, 0.f, 0.f, 0.f};       // column sums of the narrow X operand (bias gradient)
   const bool want_colsum = NARROW_X && g.colsum != nullptr && k0 == 0;
-  // points of this workgroup: 16-point slabs chunk, chunk + nchunk, ...; wave w takes points w and w + 8 of each slab
-  const long total_slabs = (g.P + 15) / 16;
-  const long my_slabs = chunk < total_slabs ? (total_slabs - chunk + g.nchunk - 1) / g.nchunk : 0;
-  const long my_pts = my_slabs * (16 / SK_WAVES);       // per wave
+  // points of this workgroup: wave w takes points w and w + 8 of each of its slabs
+  const DwSlabs slabs(g.P, chunk, g.nchunk);
+  const long my_pts = slabs.n * (16 / SK_WAVES);   // per wave
   const f4 z4 = {0.f, 0.f, 0.f, 0.f};
   for (int pair = 0; pair < g.npairs; ++pair) {
     const View& Vn = NARROW_X ? (pair == 0 ? g.X[0] : g.X[1]) : (pair == 0 ? g.Y[0] : g.Y[1]);
@@ -622,7 +524,7 @@ __global__ __launch_bounds__(SK_WAVES * 64) void dw_skinny_kernel(const DwGemm g
 #pragma unroll
       for (int u = 0; u < SK_UNROLL; ++u) {
         const long i = i0 + u;
-        const long pt = ((i >> 1) * g.nchunk + chunk) * 16 + wave + SK_WAVES * (i & 1);
+        const long pt = slabs.first_point(i >> 1) + wave + SK_WAVES * (i & 1);
         const bool ok = i < my_pts && pt < g.P;
         okmask |= ok ? (1u << u) : 0u;
         const long ptc = ok ? pt : g.P - 1;
@@ -676,24 +578,20 @@ __global__ __launch_bounds__(SK_WAVES * 64) void dw_skinny_kernel(const DwGemm g
   }
 }
 
-template <bool NARROW_X, bool NG2, int KINDS>
+template <bool NARROW_X, bool NG2, class PIN>
 static void launch_dw_skinny_td(const DwGemm& g, int n0, int k0, int ncnt, cnr_stream s) {
   const size_t lds = ((size_t)SK_WAVES * 8 * 256 + SK_WAVES * 8) * sizeof(float);
   const int wide = NARROW_X ? ((g.K - k0) < 256 ? (g.K - k0) : 256) : ((g.N - n0) < 256 ? (g.N - n0) : 256);
   const int tn_ = NARROW_X ? ncnt : wide, tk_ = NARROW_X ? wide : ncnt;
   TimingScope ts_("dw_skinny", 1, NARROW_X ? 1 : 2, g.P, tn_, tk_, g.npairs, s, dw_gemm_bytes(g, tn_, tk_));
-  launch_lds<dw_skinny_kernel<NARROW_X, NG2, KINDS>>(dim3(g.nchunk), dim3(SK_WAVES * 64), lds, lds, s, g, n0, k0, ncnt);
+  launch_lds<dw_skinny_kernel<NARROW_X, NG2, PIN>>(dim3(g.nchunk), dim3(SK_WAVES * 64), lds, lds, s, g, n0, k0, ncnt);
 }
 
 template <bool NARROW_X, bool NG2>
 static void launch_dw_skinny_t(const DwGemm& g, int n0, int k0, int ncnt, cnr_stream s) {
-  bool direct = true;
-  for (int i = 0; i < g.npairs; ++i) direct = direct && g.X[i].kind == VK_DIRECT && g.Y[i].kind == VK_DIRECT && g.X[i].scale == 1.0f && g.Y[i].scale == 1.0f;
-  const bool sdf_row = NARROW_X && g.npairs == 2 && g.X[0].kind == VK_DIRECT && g.X[0].scale == 1.0f && g.Y[0].kind == VK_SOFTPLUS &&
-                       g.X[1].kind == VK_CONST_COL0 && g.Y[1].kind == VK_DIRECT && g.Y[1].scale == 1.0f;
-  if (direct) launch_dw_skinny_td<NARROW_X, NG2, 1>(g, n0, k0, ncnt, s);
-  else if (sdf_row) launch_dw_skinny_td<NARROW_X, NG2, 2>(g, n0, k0, ncnt, s);
-  else launch_dw_skinny_td<NARROW_X, NG2, 0>(g, n0, k0, ncnt, s);
+  if (SkDirect::matches(g) || DwPin<VK_DIRECT, VK_DIRECT, -1, -1, DW_ONES_ALL>::matches(g)) launch_dw_skinny_td<NARROW_X, NG2, SkDirect>(g, n0, k0, ncnt, s);
+  else if (NARROW_X && SkSdfRow::matches(g)) launch_dw_skinny_td<NARROW_X, NG2, SkSdfRow>(g, n0, k0, ncnt, s);
+  else launch_dw_skinny_td<NARROW_X, NG2, DwInterpreted>(g, n0, k0, ncnt, s);
 }
 
 template <bool NARROW_X>
@@ -713,26 +611,18 @@ void be_dw_gemm(const DwGemm& g, cnr_stream s) {
       if (nrem > 32) {
         if (krem > 64 && g.skip_main) { k0 += 256; continue; }   // main tile formed by the fused layer + weight-gradient launch
         if (krem > 64) {
-          // the gradient-chain pair of the top SDF layer is a unit vector at the sdf row: it adds nothing to other row tiles
+          const DwMainTile t = dw_main_tile(g, n0, dw_fp32, dw_bf16);
           DwGemm gm = g;
-          if (gm.npairs == 2 && gm.X[1].kind == VK_CONST_COL0) {
-            const int hot = gm.X[1].math_split == (1 << 30) ? 0 : gm.X[1].math_split;
-            if (hot < n0 || hot >= n0 + 256) gm.npairs = 1;
-          }
-          bool scaled = !dw_bf16 && gm.split_f16;
-          for (int i = 0; i < gm.npairs; ++i) scaled = scaled && gm.sx[i] != nullptr && gm.sy[i] != nullptr;
-          if (dw_fp32) launch_dw<4, 2, 2, 4>(g, n0, k0, s);
-          else if (scaled) launch_dw_hx(gm, n0, k0, s);
-          else launch_dw_bx(gm, n0, k0, s);
+          gm.npairs = t.npairs;
+          if (t.form == DW_TILE_FP32) launch_dw<4, 2, 2, 4>(gm, n0, k0, s);
+          else if (t.form == DW_TILE_F16) launch_dw_split<DwF16>(gm, n0, k0, s);
+          else launch_dw_split<DwBf16>(gm, n0, k0, s);
           k0 += 256;
         }
         else if (krem <= 8 && !dw_fp32 && !(g.colsum != nullptr && k0 == 0) && (k0 & 3) == 0) { launch_dw_skinny<false>(g, n0, k0, krem, s); k0 += 64; }
         else {   // 9..64-column strips (embedding inputs): FP32-MFMA tile, view kinds pinned for the two shapes of the plan
-          const bool d0 = g.X[0].kind == VK_DIRECT && g.Y[0].kind == VK_DIRECT && g.X[0].scale == 1.0f && g.Y[0].scale == 1.0f;
-          if (g.npairs == 1 && d0) launch_dw<8, 1, 1, 2, 1>(g, n0, k0, s);
-          else if (g.npairs == 2 && d0 && g.X[1].kind == VK_SIGMUL && g.Y[1].kind == VK_DIRECT && g.X[1].scale == 1.0f && g.Y[1].scale == 1.0f)
-            launch_dw<8, 1, 1, 2, 2>(g, n0, k0, s);
-          else launch_dw<8, 1, 1, 2>(g, n0, k0, s);
+          DwPinList<DwPin<VK_DIRECT, VK_DIRECT, -1, -1, DW_ONES_ALL>, DwPin<VK_DIRECT, VK_DIRECT, VK_SIGMUL, VK_DIRECT, DW_ONES_ALL>, DwInterpreted>::first_match(
+              g, [&](auto pin) { launch_dw<8, 1, 1, 2, decltype(pin)>(g, n0, k0, s); });
           k0 += 64;
         }
       } else if (nrem <= 8 && !dw_fp32 && (n0 & 3) == 0) {

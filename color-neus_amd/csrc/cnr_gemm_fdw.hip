@@ -18,7 +18,7 @@
 //                   fragment: fd_tr8 below); 64 x 128 outputs per wave = 128 accumulator registers.
 // Per 32-point tile and SIMD: 48 + 48 MFMAs.  One workgroup barrier per tile; three input-tile buffers (stage t + 1 | product t | dW t - 1).
 //
-// Scaling of the split-f16 weight gradient (same scheme as dw_gemm_hx_kernel): S' = S * ss[pt] are the planes the layer product uses
+// Scaling of the split-f16 weight gradient (same scheme as dw_gemm_split_kernel<DwF16>): S' = S * ss[pt] are the planes the layer product uses
 // anyway; Ep' = Ep * 2^G / ss[pt], so S'^T Ep' = 2^G S^T Ep exactly.  G = 1 + min over the points seen so far of log2(ss * se) (se: the
 // row scale of Ep saved by the forward pass) is a RUNNING minimum: when a tile lowers it the accumulators are rescaled by the exact
 // power of two (wave-uniform, rare after the first tiles).  Fixed summation order per (range, half): bitwise deterministic.

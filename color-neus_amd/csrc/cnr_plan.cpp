@@ -1183,12 +1183,7 @@ static void dw_into_region(const Lin& q, DwGemm& g, const DwRegion& r, int slot0
   g.N = q.n; g.K = kmain > 0 ? kmain : q.k_int;   // (kmain: the columns beyond it are formed by be_strip_bwd)
   g.nchunk = nchunk; g.chunk_pts = round_up((int)((P + nchunk - 1) / nchunk), 16);
   g.partial = r.part + (size_t)slot0 * q.npad * q.ldw; g.Npad = q.npad; g.ldk = q.ldw; g.colsum = with_bias ? r.csum : nullptr;
-  // split-f16 tiles need the row scales of every operand of the 256 x 256 tiles (the top SDF layer's unit-vector pair is dropped there)
-  const int need = (g.npairs == 2 && g.X[1].kind == VK_CONST_COL0) ? 1 : g.npairs;
-  bool scaled = q.n > 32 && q.k_int > 64;
-  for (int i = 0; i < need; ++i) scaled = scaled && g.sx[i] && g.sy[i];
-  g.split_f16 = scaled;
-  be_dw_gemm(g, s);
+  be_dw_gemm(g, s);   // (which of its 256 x 256 tiles run split-f16: dw_main_tile, from the row scales g carries)
 }
 // layer launch + its weight-gradient pair (d.X[0] / d.Y[0]: the pair as a plain weight-gradient GEMM -- what the CPU emulation and the HIP
 // backend's unfused fallback run; se = row scales of the epilogue-side operand) into slots [slot0, slot0 + b.fslots) of a region
@@ -1204,7 +1199,6 @@ static void fused_into_region(const Lin& q, const LayerGemm& g, DwGemm& d, const
   f.transposed = transposed; f.nslots = b.fslots;
   d.npairs = 1; d.P = g.P; d.N = q.n; d.K = kmain > 0 ? kmain : q.k_int; d.nchunk = b.fslots; d.chunk_pts = round_up((int)((g.P + b.fslots - 1) / b.fslots), 16);
   d.partial = f.partial; d.Npad = q.npad; d.ldk = q.ldw; d.colsum = f.colsum;
-  d.split_f16 = q.n > 32 && q.k_int > 64 && d.sx[0] && d.sy[0];
   be_layer_dw_gemm(g, d, f, s);
 }
 
@@ -2016,7 +2010,7 @@ static void layout_nerf_bwd(NerfModel& m, const NerfCtx& x, long n, Arena& a, Ne
   place_slack(a);
 }
 // weight + bias gradient of one background layer: dW = sum_pt X (x) Y, db = column sums of X; queued for one batched finish
-// (no row scales: dw_into_region keeps the tiles off the split-f16 form)
+// (no row scales: dw_main_tile keeps the tiles off the split-f16 form)
 static int nerf_dw(const Lin& q, const float* X, int ldx, const float* Y, int ldy, long n, NerfBwd& b, const float* const* params,
                    float* const* dP, cnr_stream s) {
   DwGemm d;

@@ -394,12 +394,29 @@ struct DwGemm {
   int Npad = 0, ldk = 0;
   float* colsum = nullptr;    // optional [nchunk][Npad]: column sums of X[0] (bias gradient)
   // optional per-point row scales of the operands (LayerGemm::rs_out of the launch that consumed the same view).  With all of them
-  // present (split_f16) the 256 x 256 tiles run as f16 x 3; every workgroup takes the exponent G = 1 + min log2(sx * sy) over its own points
+  // present the 256 x 256 tiles run as f16 x 3 (dw_main_tile); every workgroup takes the exponent G = 1 + min log2(sx * sy) over its own points
   const float* sx[2] = {nullptr, nullptr};
   const float* sy[2] = {nullptr, nullptr};
-  bool split_f16 = false;
   bool skip_main = false;     // leave out the 256 x 256 main tiles (formed elsewhere: the fused layer + weight-gradient launch); strips only
 };
+
+// How the 256 x 256 main tile at rows n0 of a weight-gradient GEMM runs, THE one statement of it: its operand pairs and its arithmetic.
+// The gradient-chain pair of the top SDF layer is a unit vector at the sdf row (VK_CONST_COL0): it adds nothing to the other row tiles and is
+// dropped there.  The tile runs split-f16 when every remaining pair has both row scales, split-bf16 otherwise (a caller keeps a launch on
+// split-bf16 by leaving a scale pointer null); fp32 / bf16: the debugging switches CNR_DW_FP32 (which keeps every pair) / CNR_DW_BF16.
+enum DwTileForm : int { DW_TILE_F16 = 0, DW_TILE_BF16, DW_TILE_FP32 };
+struct DwMainTile { int npairs; DwTileForm form; };
+inline DwMainTile dw_main_tile(const DwGemm& g, int n0, bool fp32, bool bf16) {
+  if (fp32) return {g.npairs, DW_TILE_FP32};
+  int npairs = g.npairs;
+  if (npairs == 2 && g.X[1].kind == VK_CONST_COL0) {
+    const int hot = g.X[1].math_split == (1 << 30) ? 0 : g.X[1].math_split;
+    if (hot < n0 || hot >= n0 + 256) npairs = 1;
+  }
+  bool scaled = !bf16;
+  for (int i = 0; i < npairs; ++i) scaled = scaled && g.sx[i] != nullptr && g.sy[i] != nullptr;
+  return {npairs, scaled ? DW_TILE_F16 : DW_TILE_BF16};
+}
 
 // Algorithmic HBM bytes of one launch: every operand matrix read once, every output written once (weights and bias are
 // noise at these sizes and are left out).  Used only for the roofline figures of the timing records.

@@ -121,6 +121,42 @@ def test_the_layer_tile_steps_have_one_definition():
     assert readback == ["cnr_ws_tile.h"], readback
 
 
+def test_the_weight_gradient_tile_steps_have_one_definition():
+    """cnr_gemm_dw.hip: the split-bf16 and split-f16 256 x 256 tiles are one kernel over a format; the round-robin slab count is written once
+    (DwSlabs); view kinds are pinned in one function (DwPin::apply, whose template arguments also generate the host's DwPin::matches); and no
+    launch carries a split-f16 flag of its own: which form a main tile runs in is dw_main_tile (cnr_views.h) alone."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    code = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h", ".cpp")):
+            code[fn] = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, fn)).read().split("\n"))
+    dw = code["cnr_gemm_dw.hip"]
+    assert not re.search(r"\bdw_gemm_[bh]x_kernel\b", dw)
+    assert len(re.findall(r"\bvoid\s+dw_gemm_split_kernel\s*\(", dw)) == 1
+    slab_count = r"-\s*chunk\w*\s*\+\s*[\w.]*nchunk\w*\s*-\s*1\s*\)\s*/"
+    sites = [(fn, m.start()) for fn, text in code.items() for m in re.finditer(slab_count, text)]
+    assert len(sites) == 1 and sites[0][0] == "cnr_gemm_dw.hip", sites
+    # `.kind =` / `->kind =` on a view: every assignment lies inside the body of DwPin::apply
+    assigns = [m.start() for m in re.finditer(r"(\.|->)kind\s*=[^=]", dw)]
+    body = re.search(r"void\s+apply\s*\(\s*DwGemm\s*&\s*\w+\s*\)\s*\{", dw)
+    assert body and assigns, (body, assigns)
+    depth, end = 0, None
+    for i in range(body.end() - 1, len(dw)):
+        depth += {"{": 1, "}": -1}.get(dw[i], 0)
+        if depth == 0:
+            end = i
+            break
+    assert all(body.end() <= a < end for a in assigns), assigns
+    assert len(re.findall(r"\bvoid\s+apply\s*\(", dw)) == 1
+    # the main-tile decision: one function, its only inputs the launch and the two debugging switches; an assignment to a split_f16 flag
+    # anywhere must take its value from it
+    assert len(re.findall(r"\bDwMainTile\s+dw_main_tile\s*\(", "\n".join(code.values()))) == 1 and "dw_main_tile(" in code["cnr_views.h"]
+    assert "dw_main_tile(" in dw
+    for fn, text in code.items():
+        for m in re.finditer(r"split_f16\s*=[^=][^;]*;", text):
+            assert "dw_main_tile(" in m.group(0), (fn, m.group(0))
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
         _lib.RenderLibrary(str(tmp_path / "libcolorneus_hip.so"))

@@ -1,6 +1,8 @@
 """cnr_linear_forward / cnr_linear_backward (one plain nn.Linear (+ ReLU) on the render library's layer and weight-gradient kernels; the
 shapes are those of the NeRF++ background network, fields.py:192-274, which cnr_background_forward chains internally) against torch.nn.functional.linear (+ ReLU) with autograd: every shape of the NeRF stack and ragged point counts."""
 import os
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -69,12 +71,12 @@ SHAPES += [(128, 128, True), (112, 96, True), (240, 256, True), (48, 160, False)
            (256, 32, False), (256, 33, False)]
 
 
-def _check(library, device, sizes):
+def _check(library, device, sizes, shapes=SHAPES):
     import color_neus_amd as cn
     lib = cn.load_library(library)
     g = torch.Generator().manual_seed(0)
     for n in sizes:
-        for k, n_out, relu in SHAPES:
+        for k, n_out, relu in shapes:
             x = torch.randn(n, k, generator=g)
             w = torch.randn(n_out, k, generator=g) / k ** 0.5
             b = torch.randn(n_out, generator=g) * 0.1
@@ -111,6 +113,37 @@ def test_linear_op_emu():
 @pytest.mark.gpu
 def test_linear_op_hip():
     _check(None, "cuda:0", [1, 33, 1280, 5000])
+
+
+# (k, n_out, relu) whose weight gradient has a 256 x 256 main tile: a full one, a partial one, a second column tile (k0 = 256), the row-tail boundary
+FP32_SHAPES = [(256, 256, True), (80, 80, True), (340, 256, True), (256, 33, False)]
+_FP32_CHILD = r"""
+import sys, os
+root = sys.argv[1]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+import torch
+import color_neus_amd as cn
+import test_linear_op as T
+lib = cn.load_library(None)
+lib.timing_enable(True)
+lib.timing_collect()
+T._check(None, "cuda:0", [1, 33], T.FP32_SHAPES)
+torch.cuda.synchronize()
+names = [(rec[0], rec[2]) for rec in lib.timing_collect()]
+assert ("dw_gemm", 4224) in names, names
+assert not any(nm in ("dw_gemm_bx", "dw_gemm_hx") for nm, _ in names), names
+print("fp32 main tiles:", sum(1 for r in names if r == ("dw_gemm", 4224)))
+"""
+
+
+@pytest.mark.gpu
+def test_linear_op_fp32_main_tiles_hip():
+    """CNR_DW_FP32=1 (read once per process: a child process) sends the 256 x 256 main tiles to dw_gemm_kernel<4, 2, 2, 4> -- the launch records
+    show it -- whose staging and column sums no other test meets at ragged and sub-slab point counts: n = 1 leaves every workgroup but one
+    without a slab, n = 33 ends inside one.  Same check as test_linear_op_hip: y, dx, dW, db against float64 autograd at 2e-5 of the tensor's maximum."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _FP32_CHILD, root], env=dict(os.environ, CNR_DW_FP32="1"), cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
 # (k, n_out): the split-f16 stream form of the layer kernel, a narrow input, K beyond 256
