@@ -1,5 +1,5 @@
 // Kernel launch interface between the host orchestration (cnr_plan.cpp) and the kernels.
-// Implemented twice: cnr_kernels.hip (HIP, gfx950 -- the product) and cnr_kernels_emu.cpp (CPU emulation, tests only).
+// Implemented twice: the .hip translation units (HIP, gfx950 -- the product) and cnr_kernels_emu.cpp (CPU emulation, tests only).
 #pragma once
 #include "cnr_common.h"
 #include "cnr_views.h"
@@ -10,6 +10,26 @@ constexpr int kMaxRaySamples = 256;   // per-ray kernels stage one ray in LDS: M
 constexpr int kMaxOutside = 128;      // background samples per ray (N_OUTSIDE)
 
 struct Segment { int dst, src, len; };   // internal column [dst, dst+len) <- reference column [src, src+len)
+// the column permutation a layer's segments describe: the reference column behind internal column j / the internal column of reference column c
+// (-1: none -- zero padding / a column the layer does not read).  A layer's segments are disjoint in dst and in src (build_model in cnr_plan.cpp, the
+// only place that writes them, deals consecutive pieces of the reference columns to consecutive internal ones), so at most one segment matches
+// and the order of the search does not matter.
+CNR_HD int seg_src_of(const Segment* seg, int nseg, int j) {
+  int src = -1;
+  for (int q = 0; q < nseg; ++q)
+    if (j >= seg[q].dst && j < seg[q].dst + seg[q].len) src = seg[q].src + (j - seg[q].dst);
+  return src;
+}
+CNR_HD int seg_dst_of(const Segment* seg, int nseg, int c) {
+  int dst = -1;
+  for (int q = 0; q < nseg; ++q)
+    if (c >= seg[q].src && c < seg[q].src + seg[q].len) dst = seg[q].dst + (c - seg[q].src);
+  return dst;
+}
+// weight-norm (w = g * v / |v| per row): the row's scale from its sum of squares, and the backward of one entry from the row's dot = <dw, v> and nrm = |v|
+// (d g of the row is dot / nrm).  The sums are the caller's, in double: the row norm is the most rounding-sensitive step (x inv_s downstream)
+CNR_HD float weight_norm_scale(float g, double ss) { return g / (float)sqrt(ss); }
+CNR_HD float weight_norm_dv(float g, float nrm, float dot, float dw, float v) { return (g / nrm) * (dw - dot / (nrm * nrm) * v); }
 
 // effective-weight preparation (weight-norm, column permutation, padding, transpose)
 struct PrepWeight {
@@ -116,7 +136,17 @@ struct PruneGather {
   // index-list form (forward-only render, chain-fused ReLU stacks read their rows through idx): the per-sample outputs of the DROPPED samples
   // are zeroed here instead of by three memsets over the whole buffers
   float* zero_gcol = nullptr; float* zero_relit = nullptr; float* zero_delta = nullptr;   // [P][4], [P][4] or null, [P][3] or null
+  // (zero_gcol and zero_relit are written as whole f4 rows on both backends: 16-byte aligned, as every sub-buffer of the 256-byte arena is)
 };
+// the keep test of a sample, and what a dropped one leaves behind: its per-sample colour outputs read as zero (it contributes nothing)
+CNR_HD bool prune_keep(float weight, float eps) { return weight >= eps; }
+CNR_HD void prune_zero_dropped(const PruneGather& p, long pt) {
+  if (!p.zero_gcol) return;
+  const f4 z4 = {0.f, 0.f, 0.f, 0.f};
+  reinterpret_cast<f4*>(p.zero_gcol)[pt] = z4;
+  if (p.zero_relit) reinterpret_cast<f4*>(p.zero_relit)[pt] = z4;
+  if (p.zero_delta) { p.zero_delta[pt * 3] = 0.f; p.zero_delta[pt * 3 + 1] = 0.f; p.zero_delta[pt * 3 + 2] = 0.f; }
+}
 struct PruneScatter {
   long P; const int* count; const int* idx;
   const float* gcol_c; const float* relit_c; const float* delta_c;   // compact [.][4], [.][4], [.][3] (relit/delta null for plain NeuS)
@@ -200,7 +230,7 @@ void be_query_seed(const QuerySeed& p, cnr_stream s);
 void be_query_out(const QueryOut& p, cnr_stream s);
 
 // ---- chain-fused kernels (cnr_chain.hip): a tile of points goes through all layers of a chain without leaving the CU
-struct PackJob {    // f16 planes [2][rows][ld] (be_split_planes) -> fragment-major planes Wf[8][ld/16][2][64][8] of the fused kernels
+struct PackJob {    // f16 planes [2][rows][ld] (be_split_planes_many) -> fragment-major planes Wf[8][ld/16][2][64][8] of the fused kernels
   const unsigned short* planes; long plane_stride; int rows; int ld; unsigned short* Wf;
 };
 void be_pack_frags_many(const PackJob* jobs, int count, cnr_stream s);
@@ -332,16 +362,13 @@ void be_strip_bwd(const StripBwd& p, cnr_stream s);
 bool be_fdw_enabled();
 bool be_fdw_xrow();          // DwFuse::xrow_mode / LayerGemm::k_extra are available in be_layer_dw_gemm
 void be_layer_dw_gemm(const LayerGemm& g, const DwGemm& d, const DwFuse& f, cnr_stream s);
-void be_prep_weight(const PrepWeight& p, cnr_stream s);
-// fp32 matrix [rows][ld] -> two f16 planes of the row-scaled matrix (x * 2^e = hi + lo, 22 significand bits) + 1/2^e per row,
-// for the weight-stationary f16-split GEMM (cnr_gemm.hip)
-void be_split_planes(const float* src, int rows, int ld, unsigned short* planes, float* inv_scale, cnr_stream s);
 // all layers of a model in two launches (the per-layer launches are latency-bound: 57 launches of a few microseconds each)
+// SplitJob: fp32 matrix [rows][ld] -> two f16 planes of the row-scaled matrix (x * 2^e = hi + lo, 22 significand bits) + 1/2^e per row,
+// for the weight-stationary f16-split GEMM (cnr_gemm.hip)
 struct SplitJob { const float* src; int rows; int ld; unsigned short* planes; float* inv_scale; };
 void be_prep_weights(const PrepWeight* p, int count, cnr_stream s);
 void be_finish_weights(const FinishWeight* f, int count, cnr_stream s);   // every layer keeps its own partial buffer until this launch
 void be_split_planes_many(const SplitJob* jobs, int count, cnr_stream s);
-void be_finish_weight(const FinishWeight& p, cnr_stream s);
 void be_embed_z(const EmbedZ& p, cnr_stream s);
 void be_embed_pts(const EmbedPts& p, cnr_stream s);
 void be_upsample(const UpSample& p, cnr_stream s);
@@ -707,7 +734,6 @@ void be_composite_bg_bwd(const CompositeBgBwd& p, cnr_stream s);
 void be_zero_cols(float* p, int ld, int c0, int c1, long rows, cnr_stream s);
 // dst[row][c] = src[row][c] for c < ncols (two row-major matrices with different row strides): compact <-> padded operand buffers
 void be_copy_cols(float* dst, int ld_dst, const float* src, int ld_src, int ncols, long rows, cnr_stream s);
-void be_grid_points(float* pts /*unused*/, cnr_stream s);
 struct KernelTiming { char name[32]; int kind; int nt; long P; int N, K, pairs; float ms; double bytes; };
 void be_timing_enable(int on);
 int be_timing_collect(KernelTiming* out, int max_records);   // synchronises the recorded events, returns #records, resets

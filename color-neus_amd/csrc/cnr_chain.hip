@@ -35,15 +35,8 @@ namespace cnr {
 // fragment-major weight planes: Wf[cb][kb][plane][lane][8] = plane[n(cb, lane & 31)][kb * 16 + (lane >> 5) * 8 + 0..7]
 // with n(cb, m) = cb * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3): MFMA row m of the transposed product -> layer column
 // ------------------------------------------------------------------------------------------------
-constexpr int kPackBatch = 64;
-struct PackBatch { int count; int blk_start[kPackBatch + 1]; PackJob j[kPackBatch]; };
-static_assert(sizeof(PackBatch) <= 4096, "kernel argument block");
-
-__global__ __launch_bounds__(64) void pack_frags_kernel(const PackBatch b) {
-  int i = 0;
-  while (i + 1 < b.count && (int)blockIdx.x >= b.blk_start[i + 1]) ++i;
-  const PackJob& j = b.j[i];
-  const int blk = (int)blockIdx.x - b.blk_start[i];        // (cb * nkb + kb) * 2 + plane
+// one 64-thread block per 1 KB fragment block blk = (cb * nkb + kb) * 2 + plane of a job
+__device__ __forceinline__ void pack_frags_block(const PackJob& j, const int blk) {
   const int nkb = j.ld / 16;
   const int plane = blk & 1, kb = (blk >> 1) % nkb, cb = (blk >> 1) / nkb;
   const int lane = threadIdx.x, m = lane & 31;
@@ -54,17 +47,10 @@ __global__ __launch_bounds__(64) void pack_frags_kernel(const PackBatch b) {
   *reinterpret_cast<u16x8*>(j.Wf + ((long)blk * 64 + lane) * 8) = v;
 }
 
+using PackBatch = RowBatch<PackJob, 64>;
+__global__ __launch_bounds__(64) void pack_frags_kernel(const PackBatch b) { const auto at = b.locate(blockIdx.x); pack_frags_block(at.job, at.row); }
 void be_pack_frags_many(const PackJob* jobs, int count, cnr_stream s) {
-  for (int i0 = 0; i0 < count; i0 += kPackBatch) {
-    PackBatch b;
-    b.count = count - i0 < kPackBatch ? count - i0 : kPackBatch;
-    int blks = 0;
-    for (int i = 0; i < b.count; ++i) { b.blk_start[i] = blks; b.j[i] = jobs[i0 + i]; blks += 8 * (jobs[i0 + i].ld / 16) * 2; }
-    b.blk_start[b.count] = blks;
-    TimingScope ts_("pack_frags", 2, 0, blks, 0, 0, 0, s);
-    hipLaunchKernelGGL(pack_frags_kernel, dim3(blks), dim3(64), 0, s, b);
-  }
-  CNR_LAUNCH_CHECK("pack_frags");
+  launch_row_batches<PackBatch>(pack_frags_kernel, "pack_frags", jobs, count, 64, s, [](const PackJob& j) { return 8 * (j.ld / 16) * 2; });
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "cnr_hip_util.h"
 #include "cnr_gemm_int.h"
 #include "cnr_split.h"
+#include "cnr_wave.h"
 
 namespace cnr {
 
@@ -333,8 +334,7 @@ __global__ __launch_bounds__(512, 1) void dw_gemm_split_kernel(const DwGemm g_in
     };
     scan(g.sx[0], g.sy[0]);
     if (g.npairs > 1) scan(g.sx[1], g.sy[1]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(G, d); G = o < G ? o : G; }
+    G = wave_min_int(G);
     int* red = reinterpret_cast<int*>(smem_d);
     if (lane == 0) red[wave] = G;
     F::barrier();

@@ -10,6 +10,7 @@
 #include "cnr_gemm_int.h"
 #include "cnr_split.h"
 #include "cnr_ws_tile.h"
+#include "cnr_wave.h"
 
 namespace cnr {
 
@@ -34,10 +35,7 @@ template <int NG>
 struct WsRawSet { Raw4 r[NG]; };
 // the row dot of a staged row (LayerGemm::dot_w; K <= 256 there): this thread's 16 columns, then the 16 threads of the row
 __device__ __forceinline__ float ws_row_dot(const f4* v, const f4 (&dw)[4]) {
-  float dsum = (ws_dot4(v[0], dw[0]) + ws_dot4(v[1], dw[1])) + (ws_dot4(v[2], dw[2]) + ws_dot4(v[3], dw[3]));
-#pragma unroll
-  for (int d = 8; d >= 1; d >>= 1) dsum += __shfl_xor(dsum, d, 16);
-  return dsum;
+  return row16_sum((ws_dot4(v[0], dw[0]) + ws_dot4(v[1], dw[1])) + (ws_dot4(v[2], dw[2]) + ws_dot4(v[3], dw[3])));
 }
 
 // VK / EK >= 0 pin the view / epilogue kind at compile time: the interpreted switches of cnr_views.h fold away and each

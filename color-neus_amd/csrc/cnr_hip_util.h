@@ -131,3 +131,38 @@ __device__ __forceinline__ int cnr_ror8_min(int x) {   // min with the lane 8 fu
       cnr::g_first_error_where = where;                           \
     }                                                             \
   } while (0)
+
+namespace cnr {
+// Batched row jobs: ONE launch works through the rows of up to CAP small jobs (a model's layers: each on its own is a latency-bound launch of a few
+// microseconds).  Workgroup b works on row b - start[i] of job i, the job whose row range [start[i], start[i + 1]) holds b; the batch travels as the
+// kernel's argument block.
+template <class JobT, int CAP>
+struct RowBatch {
+  using Job = JobT;
+  static constexpr int kCap = CAP;
+  int count; int start[CAP + 1]; Job job[CAP];
+  struct At { const Job& job; int row; };
+  __device__ __forceinline__ At locate(int block) const {
+    const RowBatch& b = *this;
+    int i = 0;
+    while (i + 1 < b.count && block >= b.start[i + 1]) ++i;
+    return {b.job[i], block - b.start[i]};
+  }
+};
+// cuts the job list into batches of Batch::kCap and launches `kernel` (one workgroup of `threads` per row, rows_of(job) rows per job) once per batch,
+// each launch under the record `name` with its row count
+template <class Batch, class Rows>
+void launch_row_batches(void (*kernel)(const Batch), const char* name, const typename Batch::Job* jobs, int count, int threads, hipStream_t s, Rows rows_of) {
+  static_assert(sizeof(Batch) <= 4096, "kernel argument block");
+  for (int i0 = 0; i0 < count; i0 += Batch::kCap) {
+    Batch b;
+    b.count = count - i0 < Batch::kCap ? count - i0 : Batch::kCap;
+    int rows = 0;
+    for (int i = 0; i < b.count; ++i) { b.start[i] = rows; b.job[i] = jobs[i0 + i]; rows += rows_of(jobs[i0 + i]); }
+    b.start[b.count] = rows;
+    TimingScope ts_(name, 2, 0, rows, 0, 0, 0, s);
+    hipLaunchKernelGGL(kernel, dim3(rows), dim3(threads), 0, s, b);
+  }
+  CNR_LAUNCH_CHECK(name);
+}
+}  // namespace cnr

@@ -20,6 +20,7 @@
 #include "cnr_bodies.h"
 #include "cnr_hip_util.h"
 #include "cnr_split.h"
+#include "cnr_wave.h"
 
 namespace cnr {
 
@@ -265,29 +266,8 @@ __global__ __launch_bounds__(512) void strip_bwd_kernel(const StripBwd p, long p
         v[u * NT + j] = fmaf(d[u].w, w[j].w, fmaf(d[u].z, w[j].z, fmaf(d[u].y, w[j].y, d[u].x * w[j].x)));
       }
     }
-    // halving exchange.  Steps 32 and 16 by VALU lane swaps: v_permlane32_swap(v[i], v[i + mk]) leaves {(lo of v[i], lo of v[i + mk]), (hi of v[i], hi of v[i + mk])},
-    // i.e. in every lane the value it keeps and the one its partner sends -- their sum is keep + recv of the shuffle form (a + b commutes: same bits)
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-      const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 32]), false, false);
-      v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i]), __float_as_uint(v[i + 16]), false, false);
-      v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-    }
-#pragma unroll
-    for (int mk = 8; mk >= 1; mk >>= 1) {
-      const bool up = (lane & mk) != 0;
-#pragma unroll
-      for (int i = 0; i < mk; ++i) {
-        const float keep = up ? v[i + mk] : v[i];
-        const float send = up ? v[i] : v[i + mk];
-        v[i] = keep + __shfl_xor(send, mk);
-      }
-    }
-    if (p.tail && mine) p.tail[(pt + yu) * p.ldt + yj] = v[0] * p.tail_scale;
+    const float dot = wave_halving_sum64(v);
+    if (p.tail && mine) p.tail[(pt + yu) * p.ldt + yj] = dot * p.tail_scale;
   }
   // fold the 8 waves in a fixed order; a slot row is [ .. 256 main columns (another launch) .. | nt strip columns | zero pad up to ldk ]
 #pragma unroll
@@ -306,7 +286,7 @@ __global__ __launch_bounds__(512) void strip_bwd_kernel(const StripBwd p, long p
   }
 }
 // forward of a narrow head (see HeadFwd): a wave owns 16 points at a time (lane = 4-column group), the 16 x 4 partial dot products of a lane
-// are summed over the 64 lanes by the halving exchange of strip_bwd_kernel; lane L then applies the head's epilogue to point L / 4, column L % 4
+// are summed over the 64 lanes by the same halving exchange (wave_halving_sum64); lane L then applies the head's epilogue to point L / 4, column L % 4
 // (and to the pad columns 4.., which epi_apply zero-fills where the epilogue kind asks for it).
 __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadFwd p) {
   const int lane = threadIdx.x & 63, k = lane * 4;
@@ -328,20 +308,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadFwd p) {
     for (int u = 0; u < 16; ++u)
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[u * 4 + j] = fmaf(d[u].w, w[j].w, fmaf(d[u].z, w[j].z, fmaf(d[u].y, w[j].y, d[u].x * w[j].x)));
-#pragma unroll
-    for (int mk = 32; mk >= 1; mk >>= 1) {
-      const bool up = (lane & mk) != 0;
-#pragma unroll
-      for (int i = 0; i < mk; ++i) {
-        const float keep = up ? v[i + mk] : v[i];
-        const float send = up ? v[i] : v[i + mk];
-        v[i] = keep + __shfl_xor(send, mk);
-      }
-    }
+    const float dot = wave_halving_sum64(v);
     const long row = pt + (lane >> 2);
     if (row < P) {
       const int j = lane & 3;
-      epi_apply(p.E, row, j, v[0]);
+      epi_apply(p.E, row, j, dot);
       epi_apply(p.E, row, j + 4, 0.0f);
       epi_apply(p.E, row, j + 8, 0.0f);
       epi_apply(p.E, row, j + 12, 0.0f);
@@ -359,10 +330,7 @@ void be_head_fwd(const HeadFwd& p, cnr_stream s) {
 
 template <int NT>
 static void launch_strip_bwd(const StripBwd& p, long per, cnr_stream s) {
-  static DeviceOnce attr_once;
-  const size_t lds = (size_t)8 * NT * 256 * sizeof(float);
-  if (attr_once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&strip_bwd_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  hipLaunchKernelGGL((strip_bwd_kernel<NT>), dim3(p.nslots), dim3(512), lds, s, p, per);
+  launch_lds<strip_bwd_kernel<NT>>(dim3(p.nslots), dim3(512), (size_t)8 * NT * 256 * sizeof(float), 64 * 1024, s, p, per);
 }
 void be_strip_bwd(const StripBwd& p, cnr_stream s) {
   const long per = round_up((int)((p.P + p.nslots - 1) / p.nslots), 64);
@@ -457,13 +425,9 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const GradFinish p) {
       else if (is_cos) t = -(f * (e_prev * ce[c]));
       part[c] = t;
     }
-#pragma unroll
-    for (int d = 8; d >= 1; d >>= 1)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) part[c] += __shfl_xor(part[c], d, 16);
     float g[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = part[c] * p.scale;
+    for (int c = 0; c < 3; ++c) g[c] = row16_sum(part[c]) * p.scale;
     if (lane16 == 0) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) { p.grad_out[pt * 3 + c] = g[c]; p.AUX[pt * kAux + 3 + c] = g[c]; }
@@ -550,43 +514,11 @@ void be_gbar_finish(const GbarFinish& p, cnr_stream s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// block reductions
+// weight preparation and finish: all layers of a model in one launch each (RowBatch, cnr_hip_util.h), one workgroup per row
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x = fmaxf(x, __shfl_xor(x, d));
-  return x;
-}
-__device__ __forceinline__ int wave_min_int(int x) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { int y = __shfl_xor(x, d); x = y < x ? y : x; }
-  return x;
-}
-// sum over a 256-thread block; result valid in every thread
-__device__ __forceinline__ float block_sum_256(float x, float* sh4 /*>= 4 floats*/) {
-  x = wave_sum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
-
-__device__ __forceinline__ double block_sum_256d(double x, double* sh4) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
-
 // effective weights: weight-norm, column permutation, zero padding, transpose copy.  One block per padded row.
-__device__ __forceinline__ void prep_weight_row(const PrepWeight& p, const int n, double* redd) {
+__device__ __forceinline__ void prep_weight_row(const PrepWeight& p, const int n) {
+  __shared__ double redd[4];
   const int tid = threadIdx.x;                     // n: internal row
   const bool real = n < p.n;
   const int nr = real ? (n + p.row_rot) % p.n : 0;  // reference row
@@ -595,15 +527,13 @@ __device__ __forceinline__ void prep_weight_row(const PrepWeight& p, const int n
     double ss = 0.0;   // row norm in double: weight_norm is the most rounding-sensitive step (x inv_s downstream)
     if (real)
       for (int c = tid; c < p.k_ref; c += 256) { double x = p.v[(long)nr * p.k_ref + c]; ss += x * x; }
-    ss = block_sum_256d(ss, redd);
-    if (real) scale = p.g[nr] / (float)sqrt(ss);
+    ss = block_sum_256(ss, redd);
+    if (real) scale = weight_norm_scale(p.g[nr], ss);
   }
   for (int j = tid; j < p.kpad; j += 256) {
     float val = 0.0f;
     if (real && j < p.ldw) {
-      int src = -1;
-      for (int q = 0; q < p.nseg; ++q)
-        if (j >= p.seg[q].dst && j < p.seg[q].dst + p.seg[q].len) src = p.seg[q].src + (j - p.seg[q].dst);
+      const int src = seg_src_of(p.seg, p.nseg, j);
       if (src >= 0) val = p.v[(long)nr * p.k_ref + src] * scale;
     }
     if (j < p.ldw) p.W[(long)n * p.ldw + j] = val;
@@ -611,86 +541,40 @@ __device__ __forceinline__ void prep_weight_row(const PrepWeight& p, const int n
   }
   if (tid == 0) p.bias[n] = real && p.b ? p.b[nr] : 0.0f;
 }
-__global__ __launch_bounds__(256) void prep_weight_kernel(const PrepWeight p) {
-  __shared__ double redd[4];
-  prep_weight_row(p, blockIdx.x, redd);
-}
-constexpr int kPrepBatch = 24;
-struct PrepBatch { int count; int row_start[kPrepBatch + 1]; PrepWeight p[kPrepBatch]; };
-static_assert(sizeof(PrepBatch) <= 4096, "kernel argument block");
-__global__ __launch_bounds__(256) void prep_weight_batch_kernel(const PrepBatch b) {
-  __shared__ double redd[4];
-  int i = 0;
-  while (i + 1 < b.count && (int)blockIdx.x >= b.row_start[i + 1]) ++i;
-  prep_weight_row(b.p[i], (int)blockIdx.x - b.row_start[i], redd);
+using PrepBatch = RowBatch<PrepWeight, 24>;
+__global__ __launch_bounds__(256) void prep_weight_batch_kernel(const PrepBatch b) { const auto at = b.locate(blockIdx.x); prep_weight_row(at.job, at.row); }
+void be_prep_weights(const PrepWeight* p, int count, cnr_stream s) {
+  launch_row_batches<PrepBatch>(prep_weight_batch_kernel, "prep_weight", p, count, 256, s, [](const PrepWeight& j) { return j.npad; });
 }
 
 // fp32 matrix -> two f16 planes of the row-scaled matrix: x * 2^e = hi + lo with e chosen per row so that max|x| * 2^e is in
 // [2^13, 2^14) (exact scaling; 11 + 11 significand bits), plus 1 / 2^e per row.  One 64-thread block per row.
-__device__ __forceinline__ void split_planes_row(const float* src, int ld, unsigned short* planes, long plane_stride, float* inv_scale, const int r) {
-  const float* row = src + (long)r * ld;
+__device__ __forceinline__ void split_planes_row(const SplitJob& j, const int r) {
+  const int ld = j.ld;
+  const long plane_stride = (long)j.rows * ld;
+  const float* row = j.src + (long)r * ld;
   float mx = 0.0f;
   for (int k = threadIdx.x; k < ld; k += 64) mx = fmaxf(mx, fabsf(row[k]));
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
+  mx = wave_max(mx);
   const float sc = split_row_scale(mx);
   for (int k = threadIdx.x; k < ld; k += 64) {
     const SplitF16 h = split_f16(row[k] * sc);
-    planes[(long)r * ld + k] = __builtin_bit_cast(unsigned short, h.hi);
-    planes[plane_stride + (long)r * ld + k] = __builtin_bit_cast(unsigned short, h.lo);
+    j.planes[(long)r * ld + k] = __builtin_bit_cast(unsigned short, h.hi);
+    j.planes[plane_stride + (long)r * ld + k] = __builtin_bit_cast(unsigned short, h.lo);
   }
-  if (threadIdx.x == 0) inv_scale[r] = 1.0f / sc;
+  if (threadIdx.x == 0) j.inv_scale[r] = 1.0f / sc;
 }
-__global__ __launch_bounds__(64) void split_planes_kernel(const float* src, int ld, unsigned short* planes, long plane_stride, float* inv_scale) {
-  split_planes_row(src, ld, planes, plane_stride, inv_scale, blockIdx.x);
-}
-constexpr int kSplitBatch = 2 * kPrepBatch;
-struct SplitBatch { int count; int row_start[kSplitBatch + 1]; SplitJob j[kSplitBatch]; };
-static_assert(sizeof(SplitBatch) <= 4096, "kernel argument block");
-__global__ __launch_bounds__(64) void split_planes_batch_kernel(const SplitBatch b) {
-  int i = 0;
-  while (i + 1 < b.count && (int)blockIdx.x >= b.row_start[i + 1]) ++i;
-  const SplitJob& j = b.j[i];
-  split_planes_row(j.src, j.ld, j.planes, (long)j.rows * j.ld, j.inv_scale, (int)blockIdx.x - b.row_start[i]);
-}
+using SplitBatch = RowBatch<SplitJob, 2 * PrepBatch::kCap>;   // (W and Wt of every prepared layer)
+__global__ __launch_bounds__(64) void split_planes_batch_kernel(const SplitBatch b) { const auto at = b.locate(blockIdx.x); split_planes_row(at.job, at.row); }
 void be_split_planes_many(const SplitJob* jobs, int count, cnr_stream s) {
-  for (int i0 = 0; i0 < count; i0 += kSplitBatch) {
-    SplitBatch b;
-    b.count = count - i0 < kSplitBatch ? count - i0 : kSplitBatch;
-    int rows = 0;
-    for (int i = 0; i < b.count; ++i) { b.row_start[i] = rows; b.j[i] = jobs[i0 + i]; rows += jobs[i0 + i].rows; }
-    b.row_start[b.count] = rows;
-    TimingScope ts_("split_planes", 2, 0, rows, 0, 0, 0, s);
-    hipLaunchKernelGGL(split_planes_batch_kernel, dim3(rows), dim3(64), 0, s, b);
-  }
-  CNR_LAUNCH_CHECK("split_planes");
-}
-void be_prep_weights(const PrepWeight* p, int count, cnr_stream s) {
-  for (int i0 = 0; i0 < count; i0 += kPrepBatch) {
-    PrepBatch b;
-    b.count = count - i0 < kPrepBatch ? count - i0 : kPrepBatch;
-    int rows = 0;
-    for (int i = 0; i < b.count; ++i) { b.row_start[i] = rows; b.p[i] = p[i0 + i]; rows += p[i0 + i].npad; }
-    b.row_start[b.count] = rows;
-    TimingScope ts_("prep_weight", 2, 0, rows, 0, 0, 0, s);
-    hipLaunchKernelGGL(prep_weight_batch_kernel, dim3(rows), dim3(256), 0, s, b);
-  }
-  CNR_LAUNCH_CHECK("prep_weight");
-}
-void be_split_planes(const float* src, int rows, int ld, unsigned short* planes, float* inv_scale, cnr_stream s) {
-  TimingScope ts_("split_planes", 2, 0, rows, 0, 0, 0, s);
-  hipLaunchKernelGGL(split_planes_kernel, dim3(rows), dim3(64), 0, s, src, ld, planes, (long)rows * ld, inv_scale);
-  CNR_LAUNCH_CHECK("split_planes");
-}
-
-void be_prep_weight(const PrepWeight& p, cnr_stream s) {
-  TimingScope ts_("prep_weight", 2, 0, p.npad, 0, 0, 0, s);
-  hipLaunchKernelGGL(prep_weight_kernel, dim3(p.npad), dim3(256), 0, s, p);
-  CNR_LAUNCH_CHECK("prep_weight");
+  launch_row_batches<SplitBatch>(split_planes_batch_kernel, "split_planes", jobs, count, 64, s, [](const SplitJob& j) { return j.rows; });
 }
 
 // reduce dW partials, undo the column permutation, weight-norm backward.  One block per output row.
-__device__ __forceinline__ void finish_weight_row(const FinishWeight& p, const int n, float* red, double* redd, float* dwi) {
+__device__ __forceinline__ void finish_weight_row(const FinishWeight& p, const int n) {
+  __shared__ float red[4];
+  __shared__ double redd[4];
+  __shared__ float dwi[512];
   const int tid = threadIdx.x;                        // n: internal row
   const int nr = (n + p.row_rot) % p.n;               // reference row
   for (int j = tid; j < p.ldk; j += 256) {
@@ -716,9 +600,7 @@ __device__ __forceinline__ void finish_weight_row(const FinishWeight& p, const i
   int cref[2] = {-1, -1};
   int cnt = 0;
   for (int c = tid; c < p.k_ref && cnt < 2; c += 256, ++cnt) {
-    int dst = -1;
-    for (int q = 0; q < p.nseg; ++q)
-      if (c >= p.seg[q].src && c < p.seg[q].src + p.seg[q].len) dst = p.seg[q].dst + (c - p.seg[q].src);
+    const int dst = seg_dst_of(p.seg, p.nseg, c);
     cref[cnt] = c;
     dref[cnt] = dst >= 0 ? dwi[dst] : 0.0f;
   }
@@ -726,17 +608,14 @@ __device__ __forceinline__ void finish_weight_row(const FinishWeight& p, const i
     double dotd = 0.0, ssd = 0.0;
     for (int q = 0; q < 2; ++q)
       if (cref[q] >= 0) { double vv = p.v[(long)nr * p.k_ref + cref[q]]; dotd += (double)dref[q] * vv; ssd += vv * vv; }
-    dotd = block_sum_256d(dotd, redd);
-    ssd = block_sum_256d(ssd, redd);
+    dotd = block_sum_256(dotd, redd);
+    ssd = block_sum_256(ssd, redd);
     const float dot = (float)dotd;
     const float nrm = (float)sqrt(ssd);
     const float gg = p.g[nr];
     if (tid == 0) p.dg[nr] = dot / nrm;
     for (int q = 0; q < 2; ++q)
-      if (cref[q] >= 0) {
-        float vv = p.v[(long)nr * p.k_ref + cref[q]];
-        p.dv[(long)nr * p.k_ref + cref[q]] = (gg / nrm) * (dref[q] - dot / (nrm * nrm) * vv);
-      }
+      if (cref[q] >= 0) p.dv[(long)nr * p.k_ref + cref[q]] = weight_norm_dv(gg, nrm, dot, dref[q], p.v[(long)nr * p.k_ref + cref[q]]);
   } else {
     for (int q = 0; q < 2; ++q)
       if (cref[q] >= 0) p.dv[(long)nr * p.k_ref + cref[q]] = dref[q];
@@ -749,39 +628,10 @@ __device__ __forceinline__ void finish_weight_row(const FinishWeight& p, const i
     if (tid == 0) p.db[nr] = s;
   }
 }
-__global__ __launch_bounds__(256) void finish_weight_kernel(const FinishWeight p) {
-  __shared__ float red[4];
-  __shared__ double redd[4];
-  __shared__ float dwi[512];
-  finish_weight_row(p, blockIdx.x, red, redd, dwi);
-}
-constexpr int kFinishBatch = 24;
-struct FinishBatch { int count; int row_start[kFinishBatch + 1]; FinishWeight f[kFinishBatch]; };
-static_assert(sizeof(FinishBatch) <= 4096, "kernel argument block");
-__global__ __launch_bounds__(256) void finish_weight_batch_kernel(const FinishBatch b) {
-  __shared__ float red[4];
-  __shared__ double redd[4];
-  __shared__ float dwi[512];
-  int i = 0;
-  while (i + 1 < b.count && (int)blockIdx.x >= b.row_start[i + 1]) ++i;
-  finish_weight_row(b.f[i], (int)blockIdx.x - b.row_start[i], red, redd, dwi);
-}
+using FinishBatch = RowBatch<FinishWeight, 24>;
+__global__ __launch_bounds__(256) void finish_weight_batch_kernel(const FinishBatch b) { const auto at = b.locate(blockIdx.x); finish_weight_row(at.job, at.row); }
 void be_finish_weights(const FinishWeight* f, int count, cnr_stream s) {
-  for (int i0 = 0; i0 < count; i0 += kFinishBatch) {
-    FinishBatch b;
-    b.count = count - i0 < kFinishBatch ? count - i0 : kFinishBatch;
-    int rows = 0;
-    for (int i = 0; i < b.count; ++i) { b.row_start[i] = rows; b.f[i] = f[i0 + i]; rows += f[i0 + i].n; }
-    b.row_start[b.count] = rows;
-    TimingScope ts_("finish_weight", 2, 0, rows, 0, 0, 0, s);
-    hipLaunchKernelGGL(finish_weight_batch_kernel, dim3(rows), dim3(256), 0, s, b);
-  }
-  CNR_LAUNCH_CHECK("finish_weight");
-}
-void be_finish_weight(const FinishWeight& p, cnr_stream s) {
-  TimingScope ts_("finish_weight", 2, 0, p.n, 0, 0, 0, s);
-  hipLaunchKernelGGL(finish_weight_kernel, dim3(p.n), dim3(256), 0, s, p);
-  CNR_LAUNCH_CHECK("finish_weight");
+  launch_row_batches<FinishBatch>(finish_weight_batch_kernel, "finish_weight", f, count, 256, s, [](const FinishWeight& j) { return j.n; });
 }
 
 // ================================================================================================
@@ -975,33 +825,6 @@ void be_variance_finish(const VarianceFinish& p, cnr_stream s) {
 // ================================================================================================
 // per-ray kernels: one wavefront per ray, 4 rays per workgroup, ray state staged in LDS
 // ================================================================================================
-__device__ __forceinline__ float wave_scan_incl_add(float x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { float y = __shfl_up(x, d); if (lane >= d) x = y + x; }
-  return x;
-}
-__device__ __forceinline__ float wave_scan_incl_mul(float x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { float y = __shfl_up(x, d); if (lane >= d) x = y * x; }
-  return x;
-}
-// exclusive product scan along a ray in chunks of 64: the product of f over the lanes below times the carry of the earlier chunks, which
-// then takes this chunk in
-__device__ __forceinline__ float wave_excl_cumprod(float f, int lane, float& carry) {
-  const float incl = wave_scan_incl_mul(f, lane);
-  float excl = __shfl_up(incl, 1);
-  if (lane == 0) excl = 1.0f;
-  const float T = carry * excl;
-  carry = carry * __shfl(incl, 63);
-  return T;
-}
-// reverse inclusive scan: result[lane] = sum_{l >= lane} x[l]
-__device__ __forceinline__ float wave_scan_incl_add_rev(float x, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { float y = __shfl_down(x, d); if (lane + d < 64) x = x + y; }
-  return x;
-}
-
 // ---- building blocks of the sampler kernels (merge_kernel, upsample_kernel, sampler_step_kernel): one wavefront works on one ray's rows
 // in LDS.  None of them holds a barrier: every kernel places its own between the stages.
 // slope of the sdf along the ray in every section -> cs
@@ -1345,7 +1168,7 @@ __global__ __launch_bounds__(256) void prune_count_kernel(const PruneCount p) {
   int cnt = 0;
   for (int base = 0; base < p.M; base += 64) {
     const int j = base + lane;
-    const bool keep = j < p.M && p.weights[ray * p.M + j] >= p.eps;
+    const bool keep = j < p.M && prune_keep(p.weights[ray * p.M + j], p.eps);
     cnt += __popcll(__ballot(keep));
   }
   if (lane == 0) p.counts[ray] = cnt;
@@ -1358,28 +1181,19 @@ void be_prune_count(const PruneCount& p, cnr_stream s) {
 
 // exclusive scan of the per-ray counts (one workgroup; R is a few thousand)
 __global__ __launch_bounds__(1024) void prune_scan_kernel(const PruneScan p) {
-  __shared__ int wsum[16];
-  __shared__ int carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
+  __shared__ int wsum[1][16];
+  __shared__ int carry[1];
+  const int tid = threadIdx.x;
+  if (tid == 0) carry[0] = 0;
   __syncthreads();
   for (long base = 0; base < p.R; base += 1024) {
     const long i = base + tid;
-    int x = i < p.R ? p.counts[i] : 0;
-    int incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { int y = __shfl_up(incl, d); if (lane >= d) incl += y; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const int carry = carry_s;
-    if (i < p.R) p.offsets[i] = carry + woff + incl - x;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + incl;
-    __syncthreads();
+    const int x[1] = {i < p.R ? p.counts[i] : 0};
+    int excl[1];
+    block_excl_scan<16, 1, int>(x, excl, wsum, carry);
+    if (i < p.R) p.offsets[i] = excl[0];
   }
-  if (tid == 0) p.offsets[p.R] = carry_s;
+  if (tid == 0) p.offsets[p.R] = carry[0];
 }
 void be_prune_scan(const PruneScan& p, cnr_stream s) {
   TimingScope ts_("prune_scan", 2, 0, p.R, 0, 0, 0, s);
@@ -1395,18 +1209,12 @@ __global__ __launch_bounds__(256) void prune_gather_kernel(const PruneGather p) 
   int carry = 0;
   for (int base = 0; base < p.M; base += 64) {
     const int j = base + lane;
-    const bool keep = j < p.M && p.weights[ray * p.M + j] >= p.eps;
+    const bool keep = j < p.M && prune_keep(p.weights[ray * p.M + j], p.eps);
     const unsigned long long mask = __ballot(keep);
     const int pos = carry + __popcll(mask & ((1ull << lane) - 1ull));
     if (keep) list[wave][pos] = j;
     carry += __popcll(mask);
-    if (j < p.M && !keep && p.zero_gcol) {   // a dropped sample contributes nothing: its colour outputs read as zero
-      const long pt = ray * p.M + j;
-      const f4 z4 = {0.f, 0.f, 0.f, 0.f};
-      reinterpret_cast<f4*>(p.zero_gcol)[pt] = z4;
-      if (p.zero_relit) reinterpret_cast<f4*>(p.zero_relit)[pt] = z4;
-      if (p.zero_delta) { p.zero_delta[pt * 3] = 0.f; p.zero_delta[pt * 3 + 1] = 0.f; p.zero_delta[pt * 3 + 2] = 0.f; }
-    }
+    if (j < p.M && !keep) prune_zero_dropped(p, ray * p.M + j);
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -1591,150 +1399,5 @@ void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream s) {
   hipLaunchKernelGGL(gen_rays_focal_fold_kernel, dim3(1), dim3(64), 0, s, q);
   CNR_LAUNCH_CHECK("gen_rays_bwd");
 }
-
-// learnable cameras: one thread per slot (forward) / per camera (backward, which folds that camera's slots in slot order); one launch each
-
-// ------------------------------------------------------------------------------------------------
-// marching cubes on the device lattice: the 512^3 volume never leaves HBM between extract_fields and the mesh
-// ------------------------------------------------------------------------------------------------
-}  // namespace cnr
-#define CNR_MC_QUAL static __constant__ const
-#include "cnr_mc_table.h"
-namespace cnr {
-
-__global__ __launch_bounds__(256) void mc_count_kernel(const McVolume m) {
-  const long n = (long)m.res * m.res * m.res;
-  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long)gridDim.x * 256) {
-    const int z = (int)(v % m.res), y = (int)((v / m.res) % m.res), x = (int)(v / ((long)m.res * m.res));
-    unsigned char fl;
-    const int idx = mc_cell(m.u, m.res, m.thr, x, y, z, &fl);
-    m.flags[v] = fl;
-    m.counts[v * 2] = mc_popcount3(fl);
-    m.counts[v * 2 + 1] = idx >= 0 ? kMcNumTris[idx] : 0;
-  }
-}
-// exclusive scan of the two count channels: per-block sums, one workgroup scans the block sums, blocks rescan with their offset
-__global__ __launch_bounds__(256) void mc_block_sum_kernel(const McVolume m, long n) {
-  __shared__ int red[2][4];
-  const long base = (long)blockIdx.x * kMcScanBlock;
-  int a = 0, b = 0;
-  for (int j = threadIdx.x; j < kMcScanBlock; j += 256) { const long v = base + j; if (v < n) { a += m.counts[v * 2]; b += m.counts[v * 2 + 1]; } }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { a += __shfl_xor(a, d); b += __shfl_xor(b, d); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m.block_sums[blockIdx.x * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    m.block_sums[blockIdx.x * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-  }
-}
-__global__ __launch_bounds__(1024) void mc_scan_sums_kernel(const McVolume m, int nblocks) {
-  __shared__ int wsum[2][16];
-  __shared__ int carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 2) carry[tid] = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int i = base + tid;
-    int x[2] = {i < nblocks ? m.block_sums[i * 2] : 0, i < nblocks ? m.block_sums[i * 2 + 1] : 0};
-    int incl[2] = {x[0], x[1]};
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int y0 = __shfl_up(incl[0], d), y1 = __shfl_up(incl[1], d);
-      if (lane >= d) { incl[0] += y0; incl[1] += y1; }
-    }
-    if (lane == 63) { wsum[0][wave] = incl[0]; wsum[1][wave] = incl[1]; }
-    __syncthreads();
-    int woff[2] = {0, 0};
-    for (int w = 0; w < wave; ++w) { woff[0] += wsum[0][w]; woff[1] += wsum[1][w]; }
-    const int c0 = carry[0], c1 = carry[1];
-    if (i < nblocks) { m.block_sums[i * 2] = c0 + woff[0] + incl[0] - x[0]; m.block_sums[i * 2 + 1] = c1 + woff[1] + incl[1] - x[1]; }
-    __syncthreads();
-    if (tid == 1023) { carry[0] = c0 + woff[0] + incl[0]; carry[1] = c1 + woff[1] + incl[1]; }
-    __syncthreads();
-  }
-  if (tid == 0) { m.totals[0] = carry[0]; m.totals[1] = carry[1]; }
-}
-__global__ __launch_bounds__(256) void mc_scan_apply_kernel(const McVolume m, long n) {
-  // one workgroup rescans its 2048-element chunk: 8 elements per thread, wave scan, wave offsets through LDS
-  __shared__ int wsum[2][4];
-  const long base = (long)blockIdx.x * kMcScanBlock + (long)threadIdx.x * 8;
-  int a[8], b[8], sa = 0, sb = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { const long v = base + j; a[j] = v < n ? m.counts[v * 2] : 0; b[j] = v < n ? m.counts[v * 2 + 1] : 0; sa += a[j]; sb += b[j]; }
-  int ia = sa, ib = sb;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const int ya = __shfl_up(ia, d), yb = __shfl_up(ib, d); if (lane >= d) { ia += ya; ib += yb; } }
-  if (lane == 63) { wsum[0][wave] = ia; wsum[1][wave] = ib; }
-  __syncthreads();
-  int oa = m.block_sums[blockIdx.x * 2] + ia - sa, ob = m.block_sums[blockIdx.x * 2 + 1] + ib - sb;
-  for (int w = 0; w < wave; ++w) { oa += wsum[0][w]; ob += wsum[1][w]; }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { const long v = base + j; if (v < n) { m.counts[v * 2] = oa; m.counts[v * 2 + 1] = ob; } oa += a[j]; ob += b[j]; }
-}
-void be_mc_count(const McVolume& m, cnr_stream s) {
-  const long n = (long)m.res * m.res * m.res;
-  const int nblocks = (int)((n + kMcScanBlock - 1) / kMcScanBlock);
-  TimingScope ts_("mc_count_scan", 2, 0, n, 0, 0, 0, s, (double)n * (4.0 * 4.0 + 1.0 + 8.0 * 3.0));
-  long cb = (n + 255) / 256; if (cb > 65535 * 4) cb = 65535 * 4;
-  hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)cb), dim3(256), 0, s, m);
-  hipLaunchKernelGGL(mc_block_sum_kernel, dim3(nblocks), dim3(256), 0, s, m, n);
-  hipLaunchKernelGGL(mc_scan_sums_kernel, dim3(1), dim3(1024), 0, s, m, nblocks);
-  hipLaunchKernelGGL(mc_scan_apply_kernel, dim3(nblocks), dim3(256), 0, s, m, n);
-  CNR_LAUNCH_CHECK("mc_count");
-}
-
-struct McEmit { McVolume m; float bmin[3], bmax[3]; float* verts; int* tris; };
-__global__ __launch_bounds__(256) void mc_emit_kernel(const McEmit e) {
-  const McVolume& m = e.m;
-  const int res = m.res;
-  const long r2 = (long)res * res, n = r2 * res;
-  const long stride[3] = {r2, (long)res, 1};
-  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long)gridDim.x * 256) {
-    const unsigned fl = m.flags[v];
-    const int xyz[3] = {(int)(v / r2), (int)((v / res) % res), (int)(v % res)};
-    if (fl) {   // the vertices on the (up to three) level-crossing edges this voxel owns
-      int k = m.counts[v * 2];
-      const float u0 = m.u[v];
-      for (int a = 0; a < 3; ++a) {
-        if (!((fl >> a) & 1)) continue;
-        const float u1 = m.u[v + stride[a]];
-        const float t = (m.thr - u0) / (u1 - u0);
-        for (int c = 0; c < 3; ++c) {
-          const float g = (float)xyz[c] + (c == a ? t : 0.0f);      // lattice index coordinates, like mcubes' vertices
-          e.verts[(long)k * 3 + c] = g / ((float)res - 1.0f) * (e.bmax[c] - e.bmin[c]) + e.bmin[c];   // NeuS.py:36-39
-        }
-        ++k;
-      }
-    }
-    if (xyz[0] + 1 < res && xyz[1] + 1 < res && xyz[2] + 1 < res) {
-      int idx = 0;
-      for (int c = 0; c < 8; ++c) idx |= (m.u[v + (c & 1) * r2 + ((c >> 1) & 1) * res + ((c >> 2) & 1)] > m.thr ? 1 : 0) << c;
-      const int nt = kMcNumTris[idx];
-      int t0 = m.counts[v * 2 + 1];
-      for (int t = 0; t < nt; ++t) {
-        for (int q = 0; q < 3; ++q) {
-          const int ed = kMcTris[idx][t * 3 + q], a = ed >> 2, kk = ed & 3;
-          const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;       // the two other axes in increasing order
-          const long vo = v + (kk & 1) * stride[o0] + (kk >> 1) * stride[o1];
-          e.tris[(long)(t0 + t) * 3 + q] = m.counts[vo * 2] + mc_popcount3(m.flags[vo] & ((1u << a) - 1u));
-        }
-      }
-    }
-  }
-}
-void be_mc_emit(const McVolume& m, const float* bmin, const float* bmax, float* verts, int* tris, cnr_stream s) {
-  McEmit e;
-  e.m = m; e.verts = verts; e.tris = tris;
-  for (int c = 0; c < 3; ++c) { e.bmin[c] = bmin[c]; e.bmax[c] = bmax[c]; }
-  const long n = (long)m.res * m.res * m.res;
-  TimingScope ts_("mc_emit", 2, 0, n, 0, 0, 0, s);
-  long cb = (n + 255) / 256; if (cb > 65535 * 4) cb = 65535 * 4;
-  hipLaunchKernelGGL(mc_emit_kernel, dim3((unsigned)cb), dim3(256), 0, s, e);
-  CNR_LAUNCH_CHECK("mc_emit");
-}
-
-void be_grid_points(float*, cnr_stream) {}
 
 }  // namespace cnr

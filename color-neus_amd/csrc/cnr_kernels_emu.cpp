@@ -9,17 +9,14 @@
 #include <vector>
 
 #include "cnr_backend.h"
-#include "cnr_mc_table.h"
+#include "cnr_mc.h"
 #include "cnr_loss.h"
 #include "cnr_bodies.h"
 
 namespace cnr {
 
 const char* be_name() { return "cpu-emu"; }
-void be_split_planes(const float*, int, int, unsigned short*, float*, cnr_stream) {}
 void be_split_planes_many(const SplitJob*, int, cnr_stream) {}
-void be_prep_weights(const PrepWeight* p, int count, cnr_stream s) { for (int i = 0; i < count; ++i) be_prep_weight(p[i], s); }
-void be_finish_weights(const FinishWeight* f, int count, cnr_stream s) { for (int i = 0; i < count; ++i) be_finish_weight(f[i], s); }
 void be_timing_enable(int) {}
 int be_timing_collect(KernelTiming*, int) { return 0; }
 int be_check_last_error(char*, size_t) { return 0; }
@@ -68,7 +65,6 @@ void be_loss_grads(const LossArgs& a, const float* coef, float* d_color, float* 
 void be_zero_cols(float* p, int ld, int c0, int c1, long rows, cnr_stream) {
   for (long r = 0; r < rows; ++r) for (int c = c0; c < c1; ++c) p[r * ld + c] = 0.0f;
 }
-void be_grid_points(float*, cnr_stream) {}
 void be_copy_cols(float* dst, int ld_dst, const float* src, int ld_src, int ncols, long rows, cnr_stream) {
   for (long r = 0; r < rows; ++r) memcpy(dst + r * ld_dst, src + r * ld_src, (size_t)ncols * sizeof(float));
 }
@@ -234,13 +230,7 @@ void be_layer_dw_gemm(const LayerGemm& g, const DwGemm& d, const DwFuse& f, cnr_
     }
 }
 
-static int seg_src_of(const Segment* seg, int nseg, int j) {
-  for (int q = 0; q < nseg; ++q)
-    if (j >= seg[q].dst && j < seg[q].dst + seg[q].len) return seg[q].src + (j - seg[q].dst);
-  return -1;
-}
-
-void be_prep_weight(const PrepWeight& p, cnr_stream) {
+static void prep_weight(const PrepWeight& p) {
   for (int n = 0; n < p.npad; ++n) {
     const bool real = n < p.n;
     const int nr = real ? (n + p.row_rot) % p.n : 0;
@@ -248,7 +238,7 @@ void be_prep_weight(const PrepWeight& p, cnr_stream) {
     if (p.g && real) {
       double ss = 0.0;   // row norm accumulated in double (weight_norm is the most rounding-sensitive step: x inv_s downstream)
       for (int c = 0; c < p.k_ref; ++c) { double x = p.v[(long)nr * p.k_ref + c]; ss += x * x; }
-      scale = p.g[nr] / (float)sqrt(ss);
+      scale = weight_norm_scale(p.g[nr], ss);
     }
     for (int j = 0; j < p.kpad; ++j) {
       float val = 0.0f;
@@ -262,8 +252,9 @@ void be_prep_weight(const PrepWeight& p, cnr_stream) {
     p.bias[n] = real && p.b ? p.b[nr] : 0.0f;
   }
 }
+void be_prep_weights(const PrepWeight* p, int count, cnr_stream) { for (int i = 0; i < count; ++i) prep_weight(p[i]); }
 
-void be_finish_weight(const FinishWeight& p, cnr_stream) {
+static void finish_weight(const FinishWeight& p) {
   std::vector<float> dwi(p.ldk), dref(p.k_ref);
   for (int n = 0; n < p.n; ++n) {
     const int nr = (n + p.row_rot) % p.n;
@@ -274,9 +265,7 @@ void be_finish_weight(const FinishWeight& p, cnr_stream) {
       dwi[j] = s;
     }
     for (int c = 0; c < p.k_ref; ++c) {
-      int dst = -1;
-      for (int q = 0; q < p.nseg; ++q)
-        if (c >= p.seg[q].src && c < p.seg[q].src + p.seg[q].len) dst = p.seg[q].dst + (c - p.seg[q].src);
+      const int dst = seg_dst_of(p.seg, p.nseg, c);
       dref[c] = dst >= 0 ? dwi[dst] : 0.0f;
     }
     if (p.g) {
@@ -284,10 +273,7 @@ void be_finish_weight(const FinishWeight& p, cnr_stream) {
       for (int c = 0; c < p.k_ref; ++c) { double vv = p.v[(long)nr * p.k_ref + c]; dotd += (double)dref[c] * vv; ssd += vv * vv; }
       float dot = (float)dotd, nrm = (float)sqrt(ssd), gg = p.g[nr];
       p.dg[nr] = dot / nrm;
-      for (int c = 0; c < p.k_ref; ++c) {
-        float vv = p.v[(long)nr * p.k_ref + c];
-        p.dv[(long)nr * p.k_ref + c] = (gg / nrm) * (dref[c] - dot / (nrm * nrm) * vv);
-      }
+      for (int c = 0; c < p.k_ref; ++c) p.dv[(long)nr * p.k_ref + c] = weight_norm_dv(gg, nrm, dot, dref[c], p.v[(long)nr * p.k_ref + c]);
     } else {
       for (int c = 0; c < p.k_ref; ++c) p.dv[(long)nr * p.k_ref + c] = dref[c];
     }
@@ -298,6 +284,7 @@ void be_finish_weight(const FinishWeight& p, cnr_stream) {
     }
   }
 }
+void be_finish_weights(const FinishWeight* f, int count, cnr_stream) { for (int i = 0; i < count; ++i) finish_weight(f[i]); }
 
 void be_reduce_eik(const ReduceEik& p, cnr_stream) {
   float a = 0.0f, b = 0.0f;
@@ -329,35 +316,8 @@ void be_mc_count(const McVolume& m, cnr_stream) {
   m.totals[0] = vo; m.totals[1] = to;
 }
 void be_mc_emit(const McVolume& m, const float* bmin, const float* bmax, float* verts, int* tris, cnr_stream) {
-  const int res = m.res;
-  const long r2 = (long)res * res, n = r2 * res;
-  const long stride[3] = {r2, (long)res, 1};
-  for (long v = 0; v < n; ++v) {
-    const unsigned fl = m.flags[v];
-    const int xyz[3] = {(int)(v / r2), (int)((v / res) % res), (int)(v % res)};
-    int k = m.counts[v * 2];
-    for (int a = 0; a < 3; ++a) {
-      if (!((fl >> a) & 1)) continue;
-      const float u0 = m.u[v], u1 = m.u[v + stride[a]];
-      const float t = (m.thr - u0) / (u1 - u0);
-      for (int c = 0; c < 3; ++c) {
-        const float g = (float)xyz[c] + (c == a ? t : 0.0f);
-        verts[(long)k * 3 + c] = g / ((float)res - 1.0f) * (bmax[c] - bmin[c]) + bmin[c];
-      }
-      ++k;
-    }
-    unsigned char dummy;
-    const int idx = mc_cell(m.u, res, m.thr, xyz[0], xyz[1], xyz[2], &dummy);
-    if (idx < 0) continue;
-    const int t0 = m.counts[v * 2 + 1];
-    for (int t = 0; t < kMcNumTris[idx]; ++t)
-      for (int q = 0; q < 3; ++q) {
-        const int ed = kMcTris[idx][t * 3 + q], a = ed >> 2, kk = ed & 3;
-        const int o0 = a == 0 ? 1 : 0, o1 = a == 2 ? 1 : 2;
-        const long vo = v + (kk & 1) * stride[o0] + (kk >> 1) * stride[o1];
-        tris[(long)(t0 + t) * 3 + q] = m.counts[vo * 2] + mc_popcount3(m.flags[vo] & ((1u << a) - 1u));
-      }
-  }
+  const long n = (long)m.res * m.res * m.res;
+  for (long v = 0; v < n; ++v) mc_emit_voxel(m, v, bmin, bmax, verts, tris);
 }
 
 // twin of nn_search_kernel / nn_unpack_kernel: the same nn_dist2 / nn_update / nn_key on the whole target range, one query per iteration
@@ -687,7 +647,7 @@ namespace cnr {
 void be_prune_count(const PruneCount& p, cnr_stream) {
   for (long r = 0; r < p.R; ++r) {
     int c = 0;
-    for (int j = 0; j < p.M; ++j) c += p.weights[r * p.M + j] >= p.eps ? 1 : 0;
+    for (int j = 0; j < p.M; ++j) c += prune_keep(p.weights[r * p.M + j], p.eps) ? 1 : 0;
     p.counts[r] = c;
   }
 }
@@ -701,13 +661,7 @@ void be_prune_gather(const PruneGather& p, cnr_stream) {
     int k = p.offsets[r];
     for (int j = 0; j < p.M; ++j) {
       long pt = r * p.M + j;
-      if (!(p.weights[pt] >= p.eps)) {
-        if (p.zero_gcol) {
-          for (int c = 0; c < 4; ++c) { p.zero_gcol[pt * 4 + c] = 0.f; if (p.zero_relit) p.zero_relit[pt * 4 + c] = 0.f; }
-          if (p.zero_delta) for (int c = 0; c < 3; ++c) p.zero_delta[pt * 3 + c] = 0.f;
-        }
-        continue;
-      }
+      if (!prune_keep(p.weights[pt], p.eps)) { prune_zero_dropped(p, pt); continue; }
       p.idx[k] = (int)pt;
       if (p.featx_c) {
         memcpy(p.featx_c + (long)k * p.ldfx, p.featx + pt * p.ldfx, sizeof(float) * p.ldfx);

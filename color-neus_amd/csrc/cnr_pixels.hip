@@ -18,6 +18,7 @@
 #include "cnr_backend.h"
 #include "cnr_bodies.h"
 #include "cnr_hip_util.h"
+#include "cnr_wave.h"
 
 namespace cnr {
 
@@ -71,31 +72,20 @@ __global__ __launch_bounds__(kPixThreads) void pixel_count_kernel(const PixelTab
   }
 }
 
-// per image: tile counts -> exclusive offsets, totals (the scan of mc_scan_sums_kernel on 256 threads)
+// per image: tile counts -> exclusive offsets, totals
 __global__ __launch_bounds__(kPixThreads) void pixel_scan_kernel(const PixelTable t) {
   __shared__ int wsum[2][kPixWaves];
   __shared__ int carry[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   int* counts = t.tile_counts + (long)blockIdx.x * t.tiles * 2;
   if (tid < 2) carry[tid] = 0;
   __syncthreads();
   for (long base = 0; base < t.tiles; base += kPixThreads) {
     const long i = base + tid;
-    const int x0 = i < t.tiles ? counts[i * 2] : 0, x1 = i < t.tiles ? counts[i * 2 + 1] : 0;
-    int i0 = x0, i1 = x1;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int y0 = __shfl_up(i0, d), y1 = __shfl_up(i1, d);
-      if (lane >= d) { i0 += y0; i1 += y1; }
-    }
-    if (lane == 63) { wsum[0][wave] = i0; wsum[1][wave] = i1; }
-    __syncthreads();
-    int o0 = carry[0], o1 = carry[1];
-    for (int w = 0; w < wave; ++w) { o0 += wsum[0][w]; o1 += wsum[1][w]; }
-    if (i < t.tiles) { counts[i * 2] = o0 + i0 - x0; counts[i * 2 + 1] = o1 + i1 - x1; }
-    __syncthreads();
-    if (tid == kPixThreads - 1) { carry[0] = o0 + i0; carry[1] = o1 + i1; }
-    __syncthreads();
+    const int x[2] = {i < t.tiles ? counts[i * 2] : 0, i < t.tiles ? counts[i * 2 + 1] : 0};
+    int excl[2];
+    block_excl_scan<kPixWaves, 2, int>(x, excl, wsum, carry);
+    if (i < t.tiles) { counts[i * 2] = excl[0]; counts[i * 2 + 1] = excl[1]; }
   }
   if (tid == 0) { t.fg_count[blockIdx.x] = carry[0]; t.bg_count[blockIdx.x] = carry[1]; }
 }
@@ -176,27 +166,20 @@ __global__ __launch_bounds__(kDrawThreads) void choose_pixels_kernel(const Pixel
   __shared__ unsigned pf[kPixMaxSlots], pb[kPixMaxSlots];       // inclusive slot-order prefixes of the foreground / background counts
   __shared__ int cams[kPixMaxSlots];
   __shared__ unsigned wsum[2][kDrawThreads / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long seed = p.state[0], step = p.state[1];              // every thread reads the state in front of the barriers; thread 0 writes it behind them
   const PixKey k = pix_key(seed, step);
   const unsigned want = (unsigned)pix_want_fg(p);
-  unsigned f = 0, g = 0;
+  unsigned fg[2] = {0, 0};
   if (tid < p.B) {
     const int cam = pix_slot_image(p, k, tid);
-    pix_slot_counts(p, cam, &f, &g);
+    pix_slot_counts(p, cam, &fg[0], &fg[1]);
     cams[tid] = cam;
     if (p.cams_out) p.cams_out[tid] = cam;
   }
-  unsigned i0 = f, i1 = g;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned y0 = (unsigned)__shfl_up((int)i0, d), y1 = (unsigned)__shfl_up((int)i1, d);
-    if (lane >= d) { i0 += y0; i1 += y1; }
-  }
-  if (lane == 63) { wsum[0][wave] = i0; wsum[1][wave] = i1; }
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) { i0 += wsum[0][w]; i1 += wsum[1][w]; }
-  if (tid < p.B) { pf[tid] = i0; pb[tid] = i1; }
+  unsigned excl[2];
+  block_excl_scan<kDrawThreads / 64, 2, unsigned>(fg, excl, wsum, nullptr);
+  if (tid < p.B) { pf[tid] = excl[0] + fg[0]; pb[tid] = excl[1] + fg[1]; }
   __syncthreads();
   const unsigned F = pf[p.B - 1], G = pb[p.B - 1];
   const unsigned kfg = want < F ? want : F;

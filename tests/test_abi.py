@@ -106,8 +106,7 @@ def test_the_layer_tile_steps_have_one_definition():
     """The opt-in to a CU's whole LDS is made by launch_lds (cnr_hip_util.h) alone: no launcher calls hipFuncSetAttribute itself.  The read-back
     of an accumulator block from a wave's transposition tile (row scale times column scale undone) is ws_tile_row4 (cnr_ws_tile.h) alone."""
     csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
-    # cnr_kernels.hip: launch_strip_bwd, a file the tile-step change left alone (64 KiB for strip_bwd_kernel)
-    attr_allowed = {"cnr_hip_util.h", "cnr_chain_util.h", "cnr_kernels.hip"}
+    attr_allowed = {"cnr_hip_util.h", "cnr_chain_util.h"}
     attr, readback = [], []
     for fn in sorted(os.listdir(csrc)):
         if not fn.endswith((".hip", ".h", ".cpp")):
@@ -155,6 +154,38 @@ def test_the_weight_gradient_tile_steps_have_one_definition():
     for fn, text in code.items():
         for m in re.finditer(r"split_f16\s*=[^=][^;]*;", text):
             assert "dw_main_tile(" in m.group(0), (fn, m.group(0))
+
+
+def test_the_wave_primitives_have_one_definition():
+    """Wave folds, scans and the halving exchange by shuffle are written in cnr_wave.h (and the DPP / lane-swap forms in cnr_hip_util.h) alone: no
+    other source of csrc/ holds a shuffle inside a doubling or halving loop.  The batched row-job launch (RowBatch, cnr_hip_util.h) is the one place
+    that searches a batch for a workgroup's job, and hipFuncSetAttribute is called by the util headers only."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    # sites that keep their own loop, each a different operation from every primitive of cnr_wave.h:
+    #   cnr_image.hip     img_block_sum: two doubles by __shfl_down, valid in thread 0 only, the waves folded in wave order (its documented order);
+    #                     depth_range_kernel: the minimum of two UNSIGNED keys at once
+    #   cnr_gemm_fdw.hip  the extra row: a fold over the 8 row lanes only (d = 8, 16, 32: lanes 0..7 keep the result), five values at once
+    own_loops = {"cnr_image.hip": 2, "cnr_gemm_fdw.hip": 1}
+    step = re.compile(r"<<= 1|>>= 1")
+    loops, search, attr = {}, [], []
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h", ".cpp")):
+            continue
+        lines = [line.split("//")[0] for line in open(os.path.join(csrc, fn)).read().split("\n")]
+        code = "\n".join(lines)
+        search += [fn] * len(re.findall(r">= \w+\.\w*start\[i \+ 1\]", code))
+        if "hipFuncSetAttribute(" in code:
+            attr.append(fn)
+        if fn in ("cnr_wave.h", "cnr_hip_util.h"):
+            continue
+        for i, line in enumerate(lines):
+            in_for = "__shfl" in line and step.search(line)
+            after_for = "__shfl" in line and i > 0 and re.search(r"\bfor\s*\(", lines[i - 1]) and step.search(lines[i - 1])
+            if in_for or after_for:
+                loops[fn] = loops.get(fn, 0) + 1
+    assert loops == own_loops, loops
+    assert search == ["cnr_hip_util.h"], search
+    assert attr and set(attr) <= {"cnr_hip_util.h", "cnr_chain_util.h"}, attr
 
 
 def test_missing_library_fails_loudly(tmp_path):

@@ -102,6 +102,21 @@ def test_marching_cubes_hip_matches_emulation_and_properties():
             assert np.abs(got[k][0] - ref[k][0]).max() < 1e-6, k
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("res", [13, 129])
+def test_marching_cubes_scan_blocks_hip_matches_emulation(res):
+    """The scan of the per-voxel counts works in blocks of 2048 voxels whose sums ONE workgroup scans in trips of 1024: 13^3 = 2197 voxels are two
+    ragged blocks, 129^3 = 2 146 689 voxels are 1049 blocks, i.e. a second trip with its carry.  The sphere of _run: totals, triangles and vertices
+    of the HIP build against the emulation's, as the test above asserts them."""
+    sphere = lambda x, y, z: 0.6 - torch.sqrt(x * x + y * y + z * z)
+    (v, t), (rv, rt) = ((a.cpu().numpy(), b.cpu().numpy()) for a, b in (
+        _renderer(library, device).marching_cubes(_lattice(res, sphere, device), [-1, -1, -1], [1, 1, 1], 0.0)
+        for library, device in ((None, "cuda:0"), (N.EMU_LIB, "cpu"))))
+    assert len(t) > 0 and (len(v), len(t)) == (len(rv), len(rt))
+    assert np.array_equal(t, rt)
+    assert np.abs(v - rv).max() < 1e-6
+
+
 def test_ply_round_trip(tmp_path):
     from color_neus_amd import meshio
     g = np.random.default_rng(0)

@@ -4,7 +4,8 @@ layer 2..257 wide), skip layers of width d_hidden - embedding.  All fused fast p
 general layer / weight-gradient kernels in instantiations no other GPU test launches (weight-stationary kernel with 96..224 weight rows or an
 odd number of k16 blocks, the 3-tile general kernel, tail fill behind a 9- or 89-wide skip layer, partial weight-gradient tiles and their row
 tails).  Eight configurations x two batch shapes through the product route against the float64 oracle run live, under the project's own
-gates (tests/_golden.py: nothing new); CPU: emulation build (loose rule, as everywhere), GPU (-m gpu): HIP build (strict rule).
+gates (tests/_golden.py: nothing new); CPU: emulation build (loose rule, as everywhere), GPU (-m gpu): HIP build (strict rule).  A ninth
+configuration, `deep`, adds depth instead of a width: 29 linear layers, more than one batch of the batched weight launches holds; shape B only.
 
 Batch shapes: (A) 64 rays x (16 + 16) samples, 4 up-sampling steps: 2048 points, all tiles full; (B) 67 rays x (12 + 9), 3 steps: 1407
 points, P % 32 = 31, a ragged last tile in every kernel.
@@ -55,15 +56,19 @@ CONFIGS = {
     "thresh": lambda: _cfg("Color_NeuS", (160, 3, [2]), 95, ("no_view_dir", 0, 96, 2), (192, 2, 1), multires=4),
     # top layer exactly one 32-column tile (the boundary of the weight-gradient row tails)
     "f31": lambda: _cfg("NeuS", (64, 2, []), 31, ("idr", 2, 48, 1), None),
+    # 13 + 9 + 7 = 29 linear layers: more than the 24 jobs of one batched weight-preparation / weight-gradient finish launch, so both take a second
+    # batch (shape B only: the depth, not the widths, is what this row adds)
+    "deep": lambda: _cfg("Color_NeuS", (48, 12, [4]), 20, ("no_view_dir", 0, 16, 8), (16, 6, 1)),
 }
+ONLY_SHAPE = {"deep": "B"}        # configurations that run at one batch shape
 
 # Seeds (see the module docstring): 7 wherever the float32 oracle passes the strict gate at 7.  Rejected: f255 / A at 7 and w208 / B at 7
 # and 8 -- on those draws only deviation_network.variance fails, the one-entry cancelling sum (tests/_golden.py scalar_tolerance), where the
 # float32 oracle itself sits beyond 5e-4 of the float64 value.
-SEEDS = {(name, shape): 7 for name in CONFIGS for shape in SHAPES}
+CASES = [(name, shape) for name in CONFIGS for shape in SHAPES if ONLY_SHAPE.get(name, shape) == shape]
+SEEDS = {case: 7 for case in CASES}
 SEEDS["f255", "A"] = 8
 SEEDS["w208", "B"] = 9
-CASES = [(name, shape) for name in CONFIGS for shape in SHAPES]
 MAX_SENSITIVE_RAYS = 8
 
 
@@ -267,7 +272,7 @@ def test_width_lattice_hip(name, shape):
 
 @pytest.mark.gpu
 def test_width_lattice_error_table():
-    """The per-tensor error table of the HIP build on all 16 cases (what the gate above condenses: error against float64, bulk error, distance
+    """The per-tensor error table of the HIP build on all 17 cases (what the gate above condenses: error against float64, bulk error, distance
     from the float32 oracle, tolerance), written to profiles/width_lattice_error_table.txt: the measured numbers live there, not in the gates."""
     lines = []
     for name, shape in CASES:
@@ -328,14 +333,15 @@ CENSUS = [
 
 @pytest.mark.gpu
 def test_width_lattice_launch_census():
-    """Shape A of all eight configurations (forward + backward) under the library's per-launch records: the union of launches contains the
-    general-kernel instantiations named in the module docstring."""
+    """Shape A of the eight width configurations and shape B of `deep` (forward + backward) under the library's per-launch records: the union of
+    launches contains the general-kernel instantiations named in the module docstring, and `deep`, with its 29 layers, takes a second batch of the
+    batched row-job launches (24 jobs each: prep_weight, finish_weight; split_planes holds 48, W and Wt of a layer, and splits with prep_weight)."""
     import color_neus_amd as cn
     lib = cn.load_library()
     dev = torch.device(DEV)
-    seen = set()
+    seen, batches = set(), {}
     for name in CONFIGS:
-        ref = _reference(name, "A")
+        ref = _reference(name, ONLY_SHAPE.get(name, "A"))
         o, d, near, far, t_rand, gt, mask = [t.to(dev) for t in ref["batch"]]
         r = N.make_renderer(ref["ocfg"], ref["P"], None, dev)
         lib.timing_enable(True)
@@ -349,6 +355,10 @@ def test_width_lattice_launch_census():
         finally:
             lib.timing_enable(False)
         seen |= {(rec[0], rec[2], rec[4], rec[5]) for rec in recs if rec[0].startswith(("layer_gemm", "dw_"))}
+        batches[name] = {k: [rec[3] for rec in recs if rec[0] == k] for k in ("prep_weight", "finish_weight")}      # rows of each launch
+        print("%s batched row-job launches (rows): %r" % (name, batches[name]))
+    for k in ("prep_weight", "finish_weight"):      # every step of <= 24 layers launches each once per pass that needs it, `deep` twice
+        assert len(batches["w48"][k]) > 0 and len(batches["deep"][k]) == 2 * len(batches["w48"][k]) and min(batches["deep"][k]) > 0, (k, batches)
     print("width lattice launch census:")
     for rec in sorted(seen):
         print("    %r," % (rec,))
