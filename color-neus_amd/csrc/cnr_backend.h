@@ -1,4 +1,4 @@
-// Kernel launch interface between the host orchestration (cnr_plan.cpp) and the kernels.
+// Kernel launch interface between the host orchestration (the host units listed in cnr_plan.cpp, sharing cnr_plan.h) and the kernels.
 // Implemented twice: the .hip translation units (HIP, gfx950 -- the product) and cnr_kernels_emu.cpp (CPU emulation, tests only).
 #pragma once
 #include "cnr_common.h"
@@ -11,7 +11,7 @@ constexpr int kMaxOutside = 128;      // background samples per ray (N_OUTSIDE)
 
 struct Segment { int dst, src, len; };   // internal column [dst, dst+len) <- reference column [src, src+len)
 // the column permutation a layer's segments describe: the reference column behind internal column j / the internal column of reference column c
-// (-1: none -- zero padding / a column the layer does not read).  A layer's segments are disjoint in dst and in src (build_model in cnr_plan.cpp, the
+// (-1: none -- zero padding / a column the layer does not read).  A layer's segments are disjoint in dst and in src (build_model in cnr_model.cpp, the
 // only place that writes them, deals consecutive pieces of the reference columns to consecutive internal ones), so at most one segment matches
 // and the order of the search does not matter.
 CNR_HD int seg_src_of(const Segment* seg, int nseg, int j) {

@@ -1,4 +1,4 @@
-// Debug / fallback switches of the render library: ONE place reads the environment (debug_flags(), cnr_plan.cpp), once per process, on first
+// Debug / fallback switches of the render library: ONE place reads the environment (debug_flags(), cnr_plan.cpp: the core host unit), once per process, on first
 // use; every other file reads the parsed struct.  Nothing here changes a result beyond what the selected kernel form's own round-off
 // changes -- except the ablation words of the CNR_TUNING build, which are documented as wrong-result timing aids.
 //
@@ -53,7 +53,7 @@ struct DebugFlags {
 #endif
 };
 
-// parsed on first use (thread-safe function-local static); defined in cnr_plan.cpp -- the library's only getenv site
+// parsed on first use (thread-safe function-local static); defined in cnr_plan.cpp (the core host unit; the others only read the struct) -- the library's only getenv site
 const DebugFlags& debug_flags();
 
 // an ablation word inside a kernel: the kernel argument in the tuning build, the constant 0 (branches fold away) in the product build

@@ -278,7 +278,7 @@ struct DwBf16 {
     c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b[0], c0, 0, 0, 0);
     c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b[0], c1, 0, 0, 0);
   }
-  // the operand combinations of the render plan (cnr_plan.cpp): MLP layers, SDF value + gradient-chain pairs
+  // the operand combinations of the render plan (cnr_render_bwd.cpp, cnr_background.cpp): MLP layers, SDF value + gradient-chain pairs
   typedef DwPinList<DwPin<VK_DIRECT, VK_DIRECT>, DwPin<VK_DIRECT, VK_SOFTPLUS>, DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL, VK_DIRECT>,
                     DwPin<VK_DIRECT, VK_SOFTPLUS, VK_SIGMUL_ROW, VK_DIRECT>, DwPin<VK_DIRECT, VK_SOFTPLUS, VK_CONST_COL0, VK_DIRECT>, DwInterpreted> Pins;
 };

@@ -72,7 +72,7 @@ __device__ __forceinline__ f4 fd_ep4(const Epi& e, const EpiRaw4& raw) {
 
 // NKB: k16 blocks of the layer product (16; 14 for the 217-wide SDF layer in front of the skip connection, whose pad columns are zero)
 // XR: DwFuse::xrow_mode (0 none; 1 column sums of the o2 output of an EK_SWEEP launch; 2 EK_VBACK launch with k_extra: rank-one update of the
-// product by A column 256 and the row of that column's products with Ep) -- the sdf row of the 257-wide top SDF layer, see cnr_plan.cpp
+// product by A column 256 and the row of that column's products with Ep) -- the sdf row of the 257-wide top SDF layer, see plan_sdf_backward in cnr_render_bwd.cpp
 // TAILF: the epilogue keeps its tail fill (sweep launch of the layer below a skip connection) and runs the general 16-byte epilogue code
 // SPLITF: the value-backward epilogue keeps its split point (layer fed by a skip connection; see fdw_shape_ok), general 16-byte epilogue code
 template <int EK, int NKB = 16, int XR = 0, bool TAILF = false, bool SPLITF = false>

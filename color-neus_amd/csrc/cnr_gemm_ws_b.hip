@@ -34,7 +34,7 @@ void launch_layer_gemm_ws(const LayerGemm& g_in, int wrows, cnr_stream s) {
     else launch_ws_t<V_, E_, false>(g, wrows, s);                    \
     return;                                                          \
   }
-  // the combinations the render plan issues on 256-wide layers (cnr_plan.cpp)
+  // the combinations the render plan issues on 256-wide layers (cnr_render_fwd.cpp, cnr_render_bwd.cpp)
   WS_CASE(VK_DIRECT, EK_RELU) WS_CASE(VK_DIRECT, EK_RELU_MASK) WS_CASE(VK_DIRECT, EK_SPLIT)
   WS_CASE(VK_DIRECT, EK_SWEEP) WS_CASE(VK_DIRECT, EK_VBACK)
 #undef WS_CASE

@@ -62,8 +62,8 @@ def test_unsupported_configurations_are_rejected_with_a_message():
 
 
 def test_the_library_reads_the_environment_in_one_place():
-    """Debug / fallback switches: one parsed-once struct (csrc/cnr_debug.h, debug_flags() in cnr_plan.cpp), one getenv call site; the tuning and
-    ablation words exist only in the -DCNR_TUNING build (tools), as compile-time constants in the product."""
+    """Debug / fallback switches: one parsed-once struct (csrc/cnr_debug.h, debug_flags() in cnr_plan.cpp, the core of the host units), one
+    getenv call site; the tuning and ablation words exist only in the -DCNR_TUNING build (tools), as compile-time constants in the product."""
     csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
     sites = []
     for fn in sorted(os.listdir(csrc)):
@@ -75,6 +75,25 @@ def test_the_library_reads_the_environment_in_one_place():
     assert len(sites) == 1 and sites[0][0] == "cnr_plan.cpp", sites
     hdr = open(os.path.join(csrc, "cnr_debug.h")).read()
     assert "static constexpr int ws_kinds" in hdr and "#ifdef CNR_TUNING" in hdr
+
+
+def test_every_entry_point_has_one_definition():
+    """Every cnr_* function that include/colorneus_render.h declares is defined exactly once across the host units csrc/*.cpp (an unindented
+    line `int|size_t|void|const char* cnr_name(`: the entry point is the implementation, no shell over a static twin); no .hip or .h file of
+    csrc/ defines one, and the private header the units share (cnr_plan.h) has no extern "C" part."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    definition = re.compile(r"^(?:int|size_t|void|const char\s*\*)\s*(cnr_[a-z_0-9]+)\s*\(", re.M)
+    found = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".cpp", ".hip", ".h")):
+            code = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, fn)).read().split("\n"))
+            for name in definition.findall(code):
+                found.setdefault(name, []).append(fn)
+    declared = declared_symbols()
+    assert {s: found.get(s, []) for s in declared if len(found.get(s, [])) != 1} == {}
+    assert sorted(found) == declared, set(found) ^ set(declared)
+    assert all(fn.endswith(".cpp") for fns in found.values() for fn in fns), found
+    assert 'extern "C"' not in open(os.path.join(csrc, "cnr_plan.h")).read()
 
 
 def test_the_split_f16_rule_has_one_definition():

@@ -229,5 +229,5 @@ def test_eval_edge_sizes_emu():
 
 @pytest.mark.gpu
 def test_eval_edge_sizes_hip():
-    # 262144 = one evaluation chunk (cnr_plan.cpp kEvalChunk): one point more starts a second pass
+    # 262144 = one evaluation chunk (cnr_points.cpp kEvalChunk): one point more starts a second pass
     _check_eval_sizes(None, torch.device("cuda:0"), "dtu", [0, 1, 31, 33, 127, 129, 4097, 262144, 262145])

@@ -54,7 +54,7 @@ def _pruned_forward(library, device, n_rays, eps):
     """The forward-only render of tiny_sharp with and without prune_eps on n_rays rays (the fixture's 32 rays repeated, every origin moved by up
     to 0.01 so that the rays keep different numbers of samples), and the compaction's index list and offsets as the library left them.  They are
     read from the scratch buffer: the forward-only layout ends with index list [P], counts [R], offsets [R + 1] and the slack of 1024 floats,
-    each rounded to 256 bytes (layout_ctx_infer / place_compaction in csrc/cnr_plan.cpp)."""
+    each rounded to 256 bytes (layout_ctx_infer / place_compaction in csrc/cnr_model.cpp)."""
     fx = G.load("tiny_sharp")
     ocfg, P = G.weights_of("tiny_sharp", fx)
     r = N.make_renderer(ocfg, P, library, device)

@@ -260,7 +260,7 @@ def _case(name, shape, library, device, strict):
 
 @pytest.mark.parametrize("name,shape", CASES)
 def test_width_lattice_emu(name, shape):
-    """CPU emulation build: shares the plan (cnr_plan.cpp), none of the HIP kernels; loose gradient rule as everywhere."""
+    """CPU emulation build: shares the host units (cnr_plan.h), none of the HIP kernels; loose gradient rule as everywhere."""
     _case(name, shape, N.EMU_LIB, torch.device("cpu"), strict=False)
 
 
@@ -775,3 +775,108 @@ def test_backward_launch_sequence_per_switch(setting, tmp_path):
         recs = [tuple(rec) for rec in got[case]]
         print("%s / %s: %d launches" % (setting, case, len(recs)))
         assert recs == want, (setting, case, [(i, a, b) for i, (a, b) in enumerate(zip(recs, want)) if a != b][:3], len(recs), len(want))
+
+
+# Ordered launch records of the entry points that test_backward_launch_sequence_per_switch does not cover, under the default environment:
+# recorded with tests/_entry_sequence_child.py on the library of the commit before the host plan was split into units (cnr_plan.h).
+ENTRY_SEQUENCES = {
+    'background_forward': [
+        ('prep_weight', 2, 0, 2496, 0, 0, 0), ('split_planes', 2, 0, 5408, 0, 0, 0), ('bg_embed', 2, 0, 640, 0, 0, 0),
+        ('layer_gemm_ws', 0, 108, 640, 256, 84, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm', 0, 8, 640, 256, 340, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm', 0, 1, 640, 1, 256, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('layer_gemm', 0, 4, 640, 128, 283, 1), ('layer_gemm', 0, 1, 640, 3, 128, 1),
+        ('bg_alpha', 2, 0, 640, 0, 0, 0),
+    ],
+    'background_backward': [
+        ('bg_heads_bwd', 2, 0, 640, 0, 0, 0), ('dw_skinny', 1, 1, 640, 3, 128, 1), ('layer_gemm', 0, 4, 640, 128, 3, 1),
+        ('dw_gemm_bx', 1, 4224, 640, 128, 256, 1), ('dw_gemm', 1, 8112, 640, 128, 27, 1), ('layer_gemm_ws', 0, 108, 640, 256, 128, 1),
+        ('layer_gemm', 0, 1, 640, 27, 128, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('dw_skinny', 1, 1, 640, 1, 256, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('bg_join', 2, 0, 163840, 0, 0, 0), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1),
+        ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 84, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1),
+        ('layer_gemm', 0, 3, 640, 84, 256, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1),
+        ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1),
+        ('layer_gemm_ws', 0, 108, 640, 256, 256, 1), ('dw_gemm_bx', 1, 4224, 640, 256, 256, 1), ('layer_gemm_ws', 0, 108, 640, 256, 256, 1),
+        ('dw_gemm_bx', 1, 4224, 640, 256, 84, 1), ('layer_gemm', 0, 3, 640, 84, 256, 1), ('finish_weight', 2, 0, 2436, 0, 0, 0),
+        ('bg_embed_bwd', 2, 0, 640, 0, 0, 0), ('bg_rays_bwd', 2, 0, 16, 0, 0, 0),
+    ],
+    'forward_only_prune_tiny_sharp': [
+        ('prep_weight', 2, 0, 544, 0, 0, 0), ('split_planes', 2, 0, 1184, 0, 0, 0), ('pack_frags', 2, 0, 176, 0, 0, 0),
+        ('embed_z', 2, 0, 256, 0, 0, 0), ('layer_gemm', 0, 2, 256, 64, 39, 1), ('layer_gemm', 0, 2, 256, 64, 64, 1),
+        ('layer_gemm', 0, 1, 256, 1, 64, 1), ('sampler_step', 2, 0, 16, 0, 0, 0), ('layer_gemm', 0, 2, 64, 64, 39, 1),
+        ('layer_gemm', 0, 2, 64, 64, 64, 1), ('layer_gemm', 0, 1, 64, 1, 64, 1), ('sampler_step', 2, 0, 16, 0, 0, 0),
+        ('layer_gemm', 0, 2, 64, 64, 39, 1), ('layer_gemm', 0, 2, 64, 64, 64, 1), ('layer_gemm', 0, 1, 64, 1, 64, 1),
+        ('sampler_step', 2, 0, 16, 0, 0, 0), ('layer_gemm', 0, 2, 64, 64, 39, 1), ('layer_gemm', 0, 2, 64, 64, 64, 1),
+        ('layer_gemm', 0, 1, 64, 1, 64, 1), ('sampler_step', 2, 0, 16, 0, 0, 0), ('merge', 2, 0, 16, 0, 0, 0), ('fine_setup', 2, 0, 512, 0, 0, 0),
+        ('layer_gemm', 0, 2, 512, 64, 39, 1), ('layer_gemm', 0, 2, 512, 64, 64, 1), ('layer_gemm', 0, 1, 512, 1, 64, 1),
+        ('layer_gemm', 0, 2, 512, 64, 64, 1), ('layer_gemm', 0, 2, 512, 64, 64, 1), ('layer_gemm', 0, 2, 512, 39, 64, 1),
+        ('grad_finish', 2, 0, 512, 0, 0, 0), ('composite_fwd', 2, 0, 16, 0, 0, 0), ('prune_count', 2, 0, 16, 0, 0, 0),
+        ('prune_scan', 2, 0, 16, 0, 0, 0), ('prune_gather', 2, 0, 16, 0, 0, 0), ('layer_gemm', 0, 2, 512, 64, 70, 1),
+        ('layer_gemm', 0, 2, 512, 64, 64, 1), ('layer_gemm', 0, 1, 512, 3, 64, 1), ('layer_gemm', 0, 2, 512, 64, 33, 1),
+        ('layer_gemm', 0, 2, 512, 64, 67, 1), ('layer_gemm', 0, 1, 512, 3, 64, 1), ('prune_scatter', 2, 0, 512, 0, 0, 0),
+        ('composite_fwd', 2, 0, 16, 0, 0, 0), ('reduce_eik', 2, 0, 16, 0, 0, 0),
+    ],
+    'forward_only_prune_dtu_sharp': [
+        ('prep_weight', 2, 0, 4448, 0, 0, 0), ('split_planes', 2, 0, 8992, 0, 0, 0), ('pack_frags', 2, 0, 3968, 0, 0, 0),
+        ('embed_z', 2, 0, 1024, 0, 0, 0), ('chain_sdf_value', 3, 12, 1024, 1840, 256, 1), ('sampler_step', 2, 0, 16, 0, 0, 0),
+        ('chain_sdf_value', 3, 12, 256, 1840, 256, 1), ('sampler_step', 2, 0, 16, 0, 0, 0), ('chain_sdf_value', 3, 12, 256, 1840, 256, 1),
+        ('sampler_step', 2, 0, 16, 0, 0, 0), ('chain_sdf_value', 3, 12, 256, 1840, 256, 1), ('sampler_step', 2, 0, 16, 0, 0, 0),
+        ('merge', 2, 0, 16, 0, 0, 0), ('fine_setup', 2, 0, 2048, 0, 0, 0), ('chain_sdf_fwd', 3, 11, 2048, 2096, 256, 1),
+        ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+        ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 217, 1), ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1),
+        ('layer_gemm_ws', 0, 108, 2048, 256, 256, 1), ('narrow_dx', 0, 301, 2048, 39, 256, 1), ('grad_finish', 2, 0, 2048, 0, 0, 0),
+        ('composite_fwd', 2, 0, 16, 0, 0, 0), ('prune_count', 2, 0, 16, 0, 0, 0), ('prune_scan', 2, 0, 16, 0, 0, 0),
+        ('prune_gather', 2, 0, 16, 0, 0, 0), ('chain_fwd', 3, 11, 2048, 1872, 256, 1), ('composite_fwd', 2, 0, 16, 0, 0, 0),
+        ('reduce_eik', 2, 0, 16, 0, 0, 0),
+    ],
+    'extract_color': [
+        ('prep_weight', 2, 0, 544, 0, 0, 0), ('split_planes', 2, 0, 1184, 0, 0, 0), ('pack_frags', 2, 0, 176, 0, 0, 0),
+        ('embed_pts', 2, 0, 37, 0, 0, 0), ('layer_gemm', 0, 2, 37, 64, 39, 1), ('layer_gemm', 0, 2, 37, 64, 64, 1),
+        ('layer_gemm', 0, 1, 37, 1, 64, 1), ('layer_gemm', 0, 2, 37, 64, 64, 1), ('layer_gemm', 0, 2, 37, 64, 64, 1),
+        ('layer_gemm', 0, 2, 37, 39, 64, 1), ('grad_finish', 2, 0, 37, 0, 0, 0), ('layer_gemm', 0, 2, 37, 64, 70, 1),
+        ('layer_gemm', 0, 2, 37, 64, 64, 1), ('layer_gemm', 0, 1, 37, 3, 64, 1),
+    ],
+    'extract_fields': [
+        ('prep_weight', 2, 0, 224, 0, 0, 0), ('split_planes', 2, 0, 416, 0, 0, 0), ('pack_frags', 2, 0, 176, 0, 0, 0),
+        ('embed_pts', 2, 0, 512, 0, 0, 0), ('layer_gemm', 0, 2, 512, 64, 39, 1), ('layer_gemm', 0, 2, 512, 64, 64, 1),
+        ('layer_gemm', 0, 1, 512, 1, 64, 1),
+    ],
+    'query_forward': [
+        ('prep_weight', 2, 0, 224, 0, 0, 0), ('split_planes', 2, 0, 416, 0, 0, 0), ('pack_frags', 2, 0, 176, 0, 0, 0),
+        ('query_in', 2, 0, 384, 0, 0, 0), ('embed_pts', 2, 0, 128, 0, 0, 0), ('layer_gemm', 0, 2, 128, 64, 39, 1),
+        ('layer_gemm', 0, 2, 128, 64, 64, 1), ('layer_gemm', 0, 1, 128, 1, 64, 1), ('layer_gemm', 0, 2, 128, 64, 64, 1),
+        ('layer_gemm', 0, 2, 128, 64, 64, 1), ('layer_gemm', 0, 2, 128, 39, 64, 1), ('grad_finish', 2, 0, 128, 0, 0, 0),
+        ('query_out', 2, 0, 148, 0, 0, 0),
+    ],
+    'query_backward': [
+        ('query_seed', 2, 0, 2688, 0, 0, 0), ('gbar_finish', 2, 0, 128, 0, 0, 0), ('layer_gemm', 0, 2, 128, 64, 39, 1),
+        ('layer_gemm', 0, 2, 128, 64, 64, 1), ('layer_gemm', 0, 2, 128, 64, 65, 1), ('layer_gemm', 0, 2, 128, 64, 64, 1),
+        ('layer_gemm', 0, 2, 128, 39, 64, 1), ('dw_gemm', 1, 8112, 128, 64, 39, 2), ('dw_gemm', 1, 8112, 128, 64, 64, 2),
+        ('dw_gemm', 1, 8112, 128, 65, 64, 2), ('finish_weight', 2, 0, 193, 0, 0, 0), ('pbar_finish', 2, 0, 128, 0, 0, 0),
+        ('query_out', 2, 0, 111, 0, 0, 0),
+    ],
+}
+
+
+@pytest.mark.gpu
+def test_entry_point_launch_sequences(tmp_path):
+    """Background forward + backward (tiny_outside, 16 rays), a forward-only render with prune_eps > 0 in both forms (tiny_sharp: compact
+    copies + per-layer chains; dtu_sharp: the chain-fused launch through the index list; 16 rays each), extract_color on 37 vertices,
+    extract_fields at resolution 8 and a point-query forward + backward with want_grad at 37 points, in one child process: the whole
+    ordered list of launch records of every call equals the recorded one.  (The CPU emulation records no launches: GPU only.)"""
+    import json
+    import subprocess
+    import sys
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_entry_sequence_child.py")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("CNR_")}
+    out = os.path.join(str(tmp_path), "entries.json")
+    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stdout[-1500:] + r.stderr[-3000:])
+    with open(out) as f:
+        got = json.load(f)
+    assert set(got) == set(ENTRY_SEQUENCES), sorted(got)
+    for case, want in ENTRY_SEQUENCES.items():
+        recs = [tuple(rec) for rec in got[case]]
+        print("%s: %d launches" % (case, len(recs)))
+        assert recs == want, (case, [(i, a, b) for i, (a, b) in enumerate(zip(recs, want)) if a != b][:3], len(recs), len(want))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Host orchestration (cnr_plan.cpp: arena layout, descriptors, slot bookkeeping) + the CPU twin of the kernels under AddressSanitizer and
+# Host orchestration (the host units of csrc/, cnr_plan.h: arena layout, descriptors, slot bookkeeping) + the CPU twin of the kernels under AddressSanitizer and
 # UndefinedBehaviorSanitizer.  CPU only (GPU sanitizers are not available on the pool).  Writes profiles/<tag>_sanitizer_log.txt.
 #   bash tools/run_sanitizers.sh r03
 set -u
