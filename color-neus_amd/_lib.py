@@ -174,6 +174,9 @@ SIGNATURES = {
     "cnr_image_panel": (_int, [_FP, _FP, _FP, _int, _int, _FP, _FP, _FP, _size, _FP]),
     "cnr_vertex_color_scratch_bytes": (_size, [_cfg, _i64]),
     "cnr_vertex_color": (_int, [_cfg, _PP, _FP, _i64, _FP, _FP, _size, _FP]),
+    # mesh rasteriser
+    "cnr_mesh_raster_scratch_bytes": (_size, [_i64, _i64, _i32, _i32]),
+    "cnr_mesh_raster": (_int, [_FP, _i64, _FP, _i64, _FP, _FP, _FP, _i32, _i32, _i32, _FP, _f32, _f32, _F3, _FP, _FP, _FP, _FP, _FP, _size, _FP]),
     # one plain fully-connected layer
     "cnr_linear_scratch_bytes": (_size, [_i64, _i32, _i32, _i32]),
     "cnr_linear_forward": (_int, [_FP, _i64, _i32, _FP, _FP, _i32, _i32, _FP, _FP, _size, _FP]),

@@ -664,6 +664,11 @@ CNR_HD unsigned char img_panel_byte(const ImagePanel& p, int row, int col, float
   return img_hot(img_depth_level(p.depth[(long)row * p.W + c / 3], vmin, vmax), c % 3);
 }
 
+// ---- mesh rasteriser (cnr_mesh_raster): MeshRaster, be_mesh_raster and the per-element functions both builds share are in cnr_raster.h
+}  // namespace cnr
+#include "cnr_raster.h"
+namespace cnr {
+
 // ---- N_OUTSIDE > 0: the NeRF++ background of NeuS (NeuS.py:95-134, 313-369; NeRF, fields.py:192-274) -----------------------------------
 // No shipped configuration enables it; these kernels favour plain code over speed (one thread per ray / per point).
 struct OutsideZ {       // background sample positions (NeuS.py:315-338) merged with the sorted foreground samples (NeuS.py:353-355)

@@ -402,6 +402,39 @@ void be_image_panel(const ImagePanel& p, cnr_stream) {
     for (int col = 0; col < rowb; ++col) p.panel[(long)row * rowb + col] = img_panel_byte(p, row, col, vmin, vmax);
 }
 
+// twin of the four raster_*_kernel launches: the same raster_* functions; triangles one after the other (the minimum of the keys does not
+// depend on the order), each over its clipped box, the large ones through the list like the HIP build
+void be_mesh_raster(const MeshRaster& p, cnr_stream) {
+  const long hw = (long)p.H * p.W;
+  p.dropped[0] = 0; p.dropped[1] = 0; *p.n_large = 0;
+  for (long i = 0; i < hw; ++i) p.keys[i] = kRasterNoKey;
+  if (p.V > 0) {
+    const RasterCam cam = raster_cam(p);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < p.V; ++i) p.pv[i] = raster_project(cam, p.vertices + i * 3, p.opengl, p.z_near);
+  }
+  auto draw = [&](const RasterTri& t, int f) {
+    for (int j = t.j0; j <= t.j1; ++j)
+      for (int i = t.i0; i <= t.i1; ++i) {
+        unsigned long long& k = p.keys[(long)j * p.W + i];
+        k = std::min(k, raster_pixel_key(t, f, i, j));
+      }
+  };
+  if (p.V > 0)
+    for (long f = 0; f < p.F; ++f) {
+      const RasterTri t = raster_setup(p.triangles + f * 3, p.V, p.pv, p.H, p.W);
+      if (t.status == 1) ++p.dropped[0];
+      if (t.status == 2) ++p.dropped[1];
+      if (t.status != 0) continue;
+      if (raster_is_small(t)) draw(t, (int)f);
+      else p.large[(*p.n_large)++] = (int)f;
+    }
+  for (int l = 0; l < *p.n_large; ++l) draw(raster_setup(p.triangles + (long)p.large[l] * 3, p.V, p.pv, p.H, p.W), p.large[l]);
+#pragma omp parallel for schedule(static)
+  for (int j = 0; j < p.H; ++j)
+    for (int i = 0; i < p.W; ++i) raster_resolve(p, i, j);
+}
+
 void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
   for (int cam = 0; cam < q.f.n_cams; ++cam) {
     double acc[14] = {0};   // (the HIP kernel sums in float in a fixed tree order; the tests compare both with autograd)

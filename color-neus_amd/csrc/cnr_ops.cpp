@@ -441,4 +441,48 @@ int cnr_image_panel(const float* gt, const float* render, const float* depth, in
   return check_backend("image_panel");
 }
 
+// the one layout of the rasteriser's scratch: projected vertices | z-buffer keys | large-triangle list | its length.  Returns the size; with a
+// base pointer it also places the four parts.
+static size_t raster_layout(int64_t V, int64_t F, int64_t hw, char* base, MeshRaster* p) {
+  const size_t pv = round_up_sz((size_t)V * sizeof(RasterVert), 256), keys = round_up_sz((size_t)hw * sizeof(unsigned long long), 256);
+  const size_t large = round_up_sz((size_t)F * sizeof(int), 256);
+  if (p) {
+    p->pv = reinterpret_cast<RasterVert*>(base);
+    p->keys = reinterpret_cast<unsigned long long*>(base + pv);
+    p->large = reinterpret_cast<int*>(base + pv + keys);
+    p->n_large = reinterpret_cast<int*>(base + pv + keys + large);
+  }
+  return pv + keys + large + 256;
+}
+static bool raster_sizes_ok(int64_t V, int64_t F, int32_t H, int32_t W) {
+  return V >= 0 && F >= 0 && V < (int64_t)1 << 31 && F < (int64_t)1 << 31 && H >= 1 && W >= 1 && (int64_t)H * W < (int64_t)1 << 31;
+}
+size_t cnr_mesh_raster_scratch_bytes(int64_t n_vertices, int64_t n_triangles, int32_t H, int32_t W) {
+  if (!raster_sizes_ok(n_vertices, n_triangles, H, W)) return 0;
+  return raster_layout(n_vertices, n_triangles, (int64_t)H * W, nullptr, nullptr);
+}
+
+int cnr_mesh_raster(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const float* colors, const float* c2w,
+                    const float* focal, int32_t H, int32_t W, int32_t opengl, const float* origin, float radius, float z_near,
+                    const float* background, float* rgb, float* depth, int32_t* tri_id, int32_t* dropped, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+  if (H < 1 || W < 1) return fail("mesh_raster: H and W must be at least 1 (got %d x %d)", H, W);
+  if ((int64_t)H * W >= (int64_t)1 << 31) return fail("mesh_raster: the image must have fewer than 2^31 pixels");
+  if (n_vertices < 0 || n_triangles < 0) return fail("mesh_raster: n_vertices and n_triangles must not be negative");
+  if (n_vertices >= (int64_t)1 << 31 || n_triangles >= (int64_t)1 << 31)
+    return fail("mesh_raster: n_vertices and n_triangles must be below 2^31 (the indices are int32)");
+  if ((n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles) || !c2w || !focal || !depth || !tri_id || !dropped || !scratch)
+    return fail("mesh_raster: null argument");
+  if ((rgb == nullptr) != (colors == nullptr)) return fail("mesh_raster: rgb and colors must be given together or be null together");
+  if (scratch_bytes < raster_layout(n_vertices, n_triangles, (int64_t)H * W, nullptr, nullptr)) return fail("mesh_raster scratch too small");
+  MeshRaster p;
+  p.vertices = vertices; p.V = (long)n_vertices; p.triangles = triangles; p.F = (long)n_triangles; p.colors = colors;
+  p.c2w = c2w; p.focal = focal; p.origin = origin; p.radius = radius; p.z_near = z_near; p.H = H; p.W = W; p.opengl = opengl;
+  for (int k = 0; k < 3; ++k) p.background[k] = background ? background[k] : 0.0f;
+  p.rgb = rgb; p.depth = depth; p.tri_id = tri_id; p.dropped = dropped;
+  raster_layout(n_vertices, n_triangles, (int64_t)H * W, static_cast<char*>(scratch), &p);
+  be_mesh_raster(p, (cnr_stream)stream);
+  return check_backend("mesh_raster");
+}
+
 }  // extern "C"

@@ -115,6 +115,19 @@ __device__ __forceinline__ void block_excl_scan(const T (&x)[CH], T (&excl)[CH],
   }
 }
 
+// ---- appending to a list in global memory ------------------------------------------------------------------------------------------------------
+// The lanes of the wave with `flag` take consecutive places behind *counter: ballot + popcount, ONE atomic add per wave (by the first flagged
+// lane, none when no lane is flagged).  Returns this lane's place (meaningful in the flagged lanes).  The whole wave must arrive.
+__device__ __forceinline__ int wave_append(bool flag, int* counter) {
+  const unsigned long long mask = __ballot(flag);
+  if (mask == 0) return 0;
+  const int lane = threadIdx.x & 63, first = __ffsll((long long)mask) - 1;
+  int base = 0;
+  if (lane == first) base = atomicAdd(counter, __popcll(mask));
+  base = __shfl(base, first);
+  return base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
 // ---- 64 sums over the wave at once -----------------------------------------------------------------------------------------------------------
 // Halving exchange: every lane brings 64 partial values, lane L gets back the sum of part[L] over the 64 lanes (63 exchanges for 64 sums).  In
 // step mk a lane keeps the half of its values that belongs to its side of the mask and adds the partner's.  Steps 32 and 16 by VALU lane swaps:

@@ -7,15 +7,20 @@ squared-error and SSIM sums are one kernel (``cnr_image_metrics``) and the pictu
 where the arithmetic is specified); the image stays on the device from ray generation to the bytes of the file.  kornia, cv2 and imageio
 are not dependencies of this package.
 
+``rasterize_mesh`` and ``mesh_view_metrics`` look at the product of a run, the extracted mesh with its vertex colours, from a camera
+(``cnr_mesh_raster``): the reference has no counterpart, it shows its meshes in third-party viewers.
+
 Inputs of any float dtype and any strides are detached and converted to contiguous float32 on their own device, and the work goes to the
 current stream.  CUDA tensors go through the HIP library; CPU tensors only with an explicitly passed emulation ``library=`` (there is no CPU
 fallback).  NOTHING HERE IS DIFFERENTIABLE."""
+import numpy as np
 import torch
 
 from . import _lib, meshio, parallel, rays
 from ._lib import ptr, stream_of
 
-__all__ = ["image_metrics", "psnr", "ssim", "mse2psnr", "PSNR", "SSIM", "AverageMeter", "cmap", "panel", "validate_image"]
+__all__ = ["image_metrics", "psnr", "ssim", "mse2psnr", "PSNR", "SSIM", "AverageMeter", "cmap", "panel", "validate_image", "rasterize_mesh",
+           "mesh_view_metrics"]
 
 
 def _library(library, dev):
@@ -238,3 +243,105 @@ def validate_image(renderer, c2w, focal, image_gt, origin, radius, normalize=Tru
     if path is not None:
         meshio.write_png(path, pic)
     return {"color_fine": color, "depth": depth, "psnr": float(m["psnr"]), "ssim": float(m["ssim"]), "panel": pic}
+
+
+def _on(x, dtype, dev, name, shape):
+    """``x`` (tensor, numpy array or sequence) as a contiguous ``dtype`` tensor of ``shape`` (-1: any) on ``dev``."""
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x))
+    x = x.detach().to(device=dev, dtype=dtype).contiguous()
+    if x.dim() != len(shape) or any(want not in (-1, have) for want, have in zip(shape, x.shape)):
+        raise ValueError(f"{name}: expected shape {list(shape)} (-1: any), got {list(x.shape)}")
+    return x
+
+
+def rasterize_mesh(vertices, triangles, c2w, focal, H, W, colors=None, opengl=False, origin=None, radius=1.0, z_near=1e-3, background=None,
+                   library=None):
+    """The mesh seen from one camera (``cnr_mesh_raster``, include/colorneus_render.h, where the arithmetic is specified): a z-buffer of
+    opaque triangles with per-vertex colours, pixel ``(i, j)`` sampled where the ray of ``rays.get_rays_at`` leaves the camera.
+
+    ``vertices`` [V, 3], ``triangles`` [F, 3], ``colors`` [V, 3] or None: tensors or numpy arrays of any float / integer dtype
+    (``extract_geometry`` and ``extract_color`` return float64 / int64 numpy), converted to contiguous float32 / int32.  The device is that
+    of ``vertices`` when it is a tensor, else that of ``c2w`` when it is one, else the CPU; everything else is moved there.  ``c2w`` [4, 4],
+    ``focal`` [2]; ``origin`` [3] / ``radius`` move the camera centre into the mesh's frame, ``(c2w[:3, 3] - origin) / radius``, as the
+    trainer normalises its rays (without ``origin``, ``radius`` must be 1).  The rotation of ``c2w`` is taken as orthonormal.  A triangle with
+    a vertex at or behind ``z_near`` (or projected beyond 2^21 pixels) is dropped whole: there is no polygon clipping.
+
+    Returns ``{"rgb" [H, W, 3] (only with colors), "depth" [H, W] (camera depth; NaN where nothing is covered), "tri_id" [H, W] int64 (-1:
+    nothing), "mask" [H, W] bool, "dropped": {"behind_or_far": int, "bad_index": int}}``; uncovered pixels of ``rgb`` are ``background``
+    (3 floats, default black).  Reading ``dropped`` is the call's one host synchronisation.  Results are bitwise reproducible.
+    CUDA tensors use the HIP library; CPU tensors need an explicit emulation ``library=``.  Not differentiable."""
+    dev = vertices.device if torch.is_tensor(vertices) else (c2w.device if torch.is_tensor(c2w) else torch.device("cpu"))
+    lib = _lib.library_for(library, dev, ("a mesh", "rasterised"))
+    H, W = int(H), int(W)
+    v = _on(vertices, torch.float32, dev, "vertices", (-1, 3))
+    idx = torch.as_tensor(np.asarray(triangles)) if not torch.is_tensor(triangles) else triangles
+    if idx.is_floating_point() or idx.dtype == torch.bool:
+        raise ValueError(f"triangles: expected an integer dtype, got {idx.dtype}")
+    t = _on(idx, torch.int32, dev, "triangles", (-1, 3))
+    col = _on(colors, torch.float32, dev, "colors", (v.shape[0], 3)) if colors is not None else None
+    if col is not None and col.shape[0] == 0:      # (an empty tensor has no address; colors / rgb are NULL together in the ABI)
+        col = torch.zeros(1, 3, dtype=torch.float32, device=dev)
+    cam = _on(c2w, torch.float32, dev, "c2w", (4, 4))
+    foc = _on(torch.as_tensor(focal).reshape(-1) if torch.is_tensor(focal) else np.asarray(focal).reshape(-1), torch.float32, dev, "focal", (2,))
+    org = _on(origin, torch.float32, dev, "origin", (3,)) if origin is not None else None
+    if org is None and float(radius) != 1.0:
+        raise ValueError("rasterize_mesh: radius without origin (pass origin=[0, 0, 0] to scale only)")
+    if H < 1 or W < 1:
+        raise ValueError(f"rasterize_mesh: H and W must be at least 1 (got {H} x {W})")
+    rgb = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if col is not None else None
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    tri_id = torch.empty(H, W, dtype=torch.int32, device=dev)
+    dropped = torch.empty(2, dtype=torch.int32, device=dev)
+    bg = _lib.float3(background) if background is not None else None
+    scratch, nb = lib.scratch("cnr_mesh_raster_scratch_bytes", dev, v.shape[0], t.shape[0], H, W, at_least=1)
+    lib.call("cnr_mesh_raster", ptr(v if v.shape[0] else None), v.shape[0], ptr(t if t.shape[0] else None), t.shape[0], ptr(col), ptr(cam),
+             ptr(foc), H, W, int(bool(opengl)), ptr(org), float(radius), float(z_near), bg, ptr(rgb), ptr(depth), ptr(tri_id), ptr(dropped),
+             ptr(scratch), nb, stream_of(dev))
+    out = {}
+    if col is not None:
+        out["rgb"] = rgb
+    out["depth"] = depth
+    out["tri_id"] = tri_id.to(torch.int64)
+    out["mask"] = tri_id >= 0
+    n_far, n_bad = (int(x) for x in dropped.tolist())      # the one host read, last
+    out["dropped"] = {"behind_or_far": n_far, "bad_index": n_bad}
+    return out
+
+
+def mesh_view_metrics(vertices, triangles, colors, c2w, focal, image_gt, mask=None, opengl=False, origin=None, radius=1.0, background=None,
+                      path=None, library=None):
+    """The product (mesh and vertex colours) scored against one image: ``rasterize_mesh`` into the image's size, then ``image_metrics``
+    against ``image_gt`` (``[H, W, 3]`` or ``[3, H, W]``), so PSNR and SSIM have the definitions of ``validate_image``.
+
+    With a ``mask`` ``[H, W]`` the ground truth is composited onto ``background`` (default black) outside ``mask > 0`` before scoring, and
+    ``iou`` is added: intersection over union of ``mask > 0`` with the raster's mask, from integer counts (1.0 when both are empty).  With
+    ``path`` the picture ``gt | mesh render | mesh depth`` is saved through ``panel`` and ``meshio.write_png``.  Returns a dict of Python
+    floats ``{"psnr", "ssim"[, "iou"]}``.  Not differentiable."""
+    gt = _float32(image_gt, "image_gt")
+    if gt.dim() != 3 or 3 not in (gt.shape[0], gt.shape[2]):
+        raise ValueError(f"image_gt: expected [H, W, 3] or [3, H, W], got {tuple(gt.shape)}")
+    if gt.shape[2] != 3:
+        gt = gt.permute(1, 2, 0)
+    h, w = gt.shape[0], gt.shape[1]
+    if colors is None:
+        raise ValueError("mesh_view_metrics: colors are required")
+    r = rasterize_mesh(vertices, triangles, c2w, focal, h, w, colors=colors, opengl=opengl, origin=origin, radius=radius, background=background,
+                       library=library)
+    dev = r["depth"].device
+    gt = gt.to(dev).contiguous()
+    out = {}
+    if mask is not None:
+        m = (mask if torch.is_tensor(mask) else torch.as_tensor(np.asarray(mask))).to(dev)
+        if tuple(m.shape) != (h, w):
+            raise ValueError(f"mask: expected [{h}, {w}], got {tuple(m.shape)}")
+        m = m > 0
+        bg = torch.tensor([float(x) for x in background] if background is not None else [0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+        gt = torch.where(m[..., None], gt, bg.expand(h, w, 3)).contiguous()
+        inter, union = int((m & r["mask"]).sum()), int((m | r["mask"]).sum())
+        out["iou"] = inter / union if union else 1.0
+    s = image_metrics(r["rgb"], gt, library=library)
+    out["psnr"], out["ssim"] = float(s["psnr"]), float(s["ssim"])
+    if path is not None:
+        meshio.write_png(path, panel(gt, r["rgb"], r["depth"], library=library))
+    return out

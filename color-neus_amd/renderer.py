@@ -714,17 +714,36 @@ class NeuSRenderer(nn.Module):
         verts, tris = self.marching_cubes(u, bound_min, bound_max, threshold)
         return verts.cpu().numpy().astype(np.float64), tris.cpu().numpy().astype(np.int64)
 
-    def extract_color(self, vertices, device):
-        """Per-vertex colour = color_network(pts, g, -g, feat) (NeuS.py:44-64); returns np (V,3)."""
-        pts = torch.as_tensor(np.asarray(vertices), dtype=torch.float32, device=torch.device(device)).reshape(-1, 3).contiguous()
+    def vertex_colors(self, vertices):
+        """extract_color on device tensors: ``vertices`` [V, 3] on the renderer's device -> rgb [V, 3] float32 there, no host round trip."""
+        pts = vertices.detach().to(torch.float32).reshape(-1, 3).contiguous()
         n = pts.shape[0]
         rgb = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
         if n == 0:
-            return rgb.cpu().numpy()
+            return rgb
         plist, parr = self._param_array()
         scratch, nb = self._lib.scratch("cnr_vertex_color_scratch_bytes", pts.device, C.byref(self._ccfg), n)
         self._lib.call("cnr_vertex_color", C.byref(self._ccfg), parr, ptr(pts), n, ptr(rgb), ptr(scratch), nb, stream_of(pts))
-        return rgb.cpu().numpy()
+        return rgb
+
+    def extract_color(self, vertices, device):
+        """Per-vertex colour = color_network(pts, g, -g, feat) (NeuS.py:44-64); returns np (V,3)."""
+        pts = torch.as_tensor(np.asarray(vertices), dtype=torch.float32, device=torch.device(device))
+        return self.vertex_colors(pts).cpu().numpy()
+
+    def render_mesh_view(self, bound_min, bound_max, resolution, c2w, focal, H, W, threshold=0.0, opengl=False, origin=None, radius=1.0,
+                         z_near=1e-3, background=None):
+        """The extracted, coloured mesh seen from a camera without leaving the device: extract_fields -> marching_cubes -> vertex colours
+        (cnr_vertex_color) -> imaging.rasterize_mesh.  ``c2w`` [4, 4] on the renderer's device decides the device.  Returns rasterize_mesh's
+        dict plus ``"vertices"``, ``"triangles"`` and ``"colors"`` (device tensors).  Not differentiable."""
+        from . import imaging
+        u = self.extract_fields(bound_min, bound_max, c2w.device, resolution)
+        verts, tris = self.marching_cubes(u, bound_min, bound_max, threshold)
+        colors = self.vertex_colors(verts)
+        out = imaging.rasterize_mesh(verts, tris, c2w, focal, H, W, colors=colors, opengl=opengl, origin=origin, radius=radius, z_near=z_near,
+                                     background=background, library=self._lib)
+        out.update(vertices=verts, triangles=tris, colors=colors)
+        return out
 
 
 class ColorNeuSRenderer(NeuSRenderer):

@@ -488,6 +488,46 @@ size_t cnr_vertex_color_scratch_bytes(const cnr_config* cfg, int64_t n_points);
 int cnr_vertex_color(const cnr_config* cfg, const float* const* params, const float* verts, int64_t n_points,
                      float* rgb, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- mesh rasteriser: the coloured mesh (cnr_mc_emit's vertices and triangles, cnr_vertex_color's colours) seen from a camera, as a z-buffer
+ * of opaque triangles: rgb [H][W][3], depth [H][W] (camera depth, the ray parameter of get_rays_at(normalize=False)) and tri_id [H][W].
+ * Cameras are device pointers as for cnr_gen_rays, and origin / radius normalise the camera centre as there: t = (c2w[:3,3] - origin) / radius
+ * (origin NULL: t = c2w[:3,3]); the vertices are in that normalised frame (where extract_geometry leaves them).
+ * Every float operation below is one rounded fp32 operation, in the order written (no FMA; `/` is the correctly rounded IEEE quotient); the
+ * integer operations are exact (int64).
+ *   vertex    d = p - t;  xc = (R00*d0 + R10*d1) + R20*d2, yc and zc likewise with columns 1 and 2 of R = c2w[:3,:3].  This is R^T d: the
+ *             rotation is taken as orthonormal (it is in every dataset of the reference); a c2w with scale or shear is not inverted.
+ *             opengl != 0: yc = -yc, zc = -zc.   u = (fx*xc)/zc + W*0.5f,  v = (fy*yc)/zc + H*0.5f: the inverse of get_rays_at, pixel (i, j)
+ *             is sampled at integer (i, j), so a pixel is covered exactly when its ray hits the triangle.
+ *             X = (int)rintf(u*256.0f), Y = (int)rintf(v*256.0f): 1/256-pixel fixed point, round half to even.
+ *             A vertex is usable iff zc > z_near (a NaN fails) and |u| < 2^21 and |v| < 2^21.
+ *   triangle  dropped whole when an index is outside [0, n_vertices) (counted in dropped[1]; the vertex array is never read out of bounds) or
+ *             when a vertex is not usable (counted in dropped[0]).  THERE IS NO POLYGON CLIPPING: a triangle that reaches behind z_near is not
+ *             drawn in part.  The cameras of every shipped configuration sit outside the unit sphere that holds the mesh.
+ *             A = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0).  A == 0 is skipped silently.  A < 0: vertices 1 and 2 are swapped for what follows (both
+ *             facings are drawn, no culling).
+ *   coverage  E0 = edge(1,2), E1 = edge(2,0), E2 = edge(0,1), edge(p,q) = (Xq-Xp)*(256 j - Yp) - (Yq-Yp)*(256 i - Xp), at pixel column i, row j.
+ *             Covered iff all three are >= 0: edges are inclusive and there is no top-left rule.  A pixel on a shared edge is covered by both
+ *             neighbours and the depth key decides its owner, so two triangles that share an edge leave no hole.
+ *   pixel     b_k = (float)E_k / (float)A;  q_k = b_k / z_k (z_k = zc of vertex k);  s = (q0 + q1) + q2;  depth = 1.0f / s.  A depth that is not
+ *             > 0 is skipped.  key = (uint64)bits(depth) << 32 | (uint32)triangle index; the z-buffer keeps the MINIMUM key per pixel (a 64-bit
+ *             integer min, no float atomics): the nearest depth wins, of equal depths the lowest triangle index.  The result does not depend on
+ *             the order in which triangles arrive or on how the work is split: two calls give the same bits.
+ *   resolve   for the winning triangle E_k, b_k, q_k and s are recomputed from the same integers (the same bits); w_k = q_k / s;
+ *             rgb = (w0*c0 + w1*c1) + w2*c2 per channel (c_k the colour of vertex k after the swap); depth comes from the key, tri_id is the index.
+ *             A pixel no triangle covers gets tri_id = -1, depth = NaN, rgb = background (cnr_image_panel leaves NaN depths out of its range and
+ *             draws them as level 0).
+ * No anti-aliasing, culling, textures, shading or gradients.  colors and rgb are NULL together (then only depth and tri_id are written).
+ * dropped: device int32 [2], overwritten.  n_triangles == 0 or n_vertices == 0 succeeds and writes an all-background image.
+ * Errors: H or W < 1; H*W >= 2^31; n_vertices or n_triangles >= 2^31 (or negative); a null required pointer; rgb and colors not null together;
+ * scratch too small.  scratch: cnr_mesh_raster_scratch_bytes, contents need not be initialised (0 for sizes the entry point refuses). */
+size_t cnr_mesh_raster_scratch_bytes(int64_t n_vertices, int64_t n_triangles, int32_t H, int32_t W);
+int cnr_mesh_raster(const float* vertices /* [V][3] */, int64_t n_vertices, const int32_t* triangles /* [F][3] */, int64_t n_triangles,
+                    const float* colors /* [V][3] or NULL */, const float* c2w /* device [4][4] */, const float* focal /* device [2] */,
+                    int32_t H, int32_t W, int32_t opengl, const float* origin /* device [3] or NULL */, float radius, float z_near,
+                    const float* background /* host [3] or NULL = 0,0,0 */, float* rgb /* [H][W][3]; NULL iff colors NULL */,
+                    float* depth /* [H][W] */, int32_t* tri_id /* [H][W] */, int32_t* dropped /* device [2] */,
+                    void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- one plain fully-connected layer on the layer / weight-gradient kernels of the render path: y = act(x W^T + b), act = ReLU or none.
  * The NeRF++ background network of NeuS (NeRF, fields.py:192-274; N_OUTSIDE > 0, NeuS.py:95-134) is a chain of nn.Linear (+ ReLU) layers;
  * color-neus_amd/background.py evaluates each of them through these two entry points.  x [n][k], y / dy [n][n_out], W [n_out][k] and b [n_out]
