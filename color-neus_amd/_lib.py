@@ -225,11 +225,15 @@ class RenderLibrary:
         if getattr(self.lib, name)(*args) != 0:
             raise RuntimeError(f"{name} failed: {self.lib.cnr_last_error().decode()}")
 
-    def scratch(self, bytes_fn, device, *args, at_least=0):
+    def scratch(self, bytes_fn, device, *args, at_least=0, zero=False, nbytes=None):
         """(uninitialised uint8 tensor on ``device``, nbytes) for the size function ``bytes_fn(*args)``; the tensor holds at least
-        ``at_least`` bytes (a valid pointer where the size can be 0), nbytes is what the size function said."""
-        nb = getattr(self.lib, bytes_fn)(*args)
-        return torch.empty(max(nb, at_least), dtype=torch.uint8, device=device), nb
+        ``at_least`` bytes (a valid pointer where the size can be 0), nbytes is what the size function said.  ``nbytes``: the byte count
+        itself, for an entry point whose scratch size the header states as a formula (``bytes_fn`` then names that entry point).
+        ``zero``: the buffer comes zero-filled (the loss scratch's contract: zero before the first use, left zero by every call).
+        Every context / scratch buffer of the package is allocated here (tests/_guard.py substitutes this one method)."""
+        nb = getattr(self.lib, bytes_fn)(*args) if nbytes is None else int(nbytes)
+        alloc = torch.zeros if zero else torch.empty
+        return alloc(max(nb, at_least), dtype=torch.uint8, device=device), nb
 
     def timing_enable(self, on: bool):
         self.lib.cnr_timing_enable(1 if on else 0)

@@ -675,6 +675,7 @@ void be_loss_sums(const LossArgs& a, float* partial, float* sums, cnr_stream s) 
 // partials in the fixed order of loss_fold_kernel and runs the scalar tail (loss_combine).  Which block is last does not matter: bitwise the same
 // sums as the two-launch form.  The ticket counter is a 4-byte slot of the CALLER's scratch (zero before the first use of the buffer; the last
 // block leaves it zero): calls on one stream may share a buffer, calls that may overlap (other streams, other threads) bring their own.
+// The last block also clears the partial sums it has folded, so an all-zero scratch is all zero again after the call.
 // shard != 0 (ray-sharded runs): no scalar tail; the last block writes the rank's statistics for the all-reduce instead:
 // stats[0..2] = the three sums, stats[3..4] = the rank's eikonal sums, stats[5] = a second copy of stats[4] that the all-reduce leaves alone.
 __global__ __launch_bounds__(256) void loss_forward_kernel(const LossArgs a, float* partial, unsigned* ticket, const LossScalars c, const float* gerr, float* sums,
@@ -711,6 +712,7 @@ __global__ __launch_bounds__(256) void loss_forward_kernel(const LossArgs a, flo
     v[0] += __hip_atomic_load(partial + k * 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     v[1] += __hip_atomic_load(partial + k * 4 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     v[2] += __hip_atomic_load(partial + k * 4 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    partial[k * 4] = 0.f; partial[k * 4 + 1] = 0.f; partial[k * 4 + 2] = 0.f;   // (slot 3 was written as 0: the scratch is left all zero)
   }
   __shared__ float tot[4];
   for (int j = 0; j < 3; ++j) { const float sj = block_sum_256(v[j], red); if (tid == 0) tot[j] = sj; }

@@ -90,7 +90,13 @@ template <class Layout> static size_t layout_size(void* buf, Layout&& layout) {
   layout(a);
   return a.off;
 }
+// A base must be kBaseAlign-aligned (include/colorneus_render.h): the Arena places every sub-buffer at a multiple of 256 bytes FROM the base,
+// and the kernels access those sub-buffers with 16-byte vectors and 8-byte atomics.  (Entry points that do not lay out through
+// layout_checked -- cnr_ops.cpp, cnr_composite_background_* -- do not check their base: the header says which.)
+constexpr size_t kBaseAlign = 16;
 template <class Layout> static int layout_checked(const char* what, void* buf, size_t bytes, Layout&& layout) {
+  if ((uintptr_t)buf % kBaseAlign != 0)
+    return fail("%s misaligned: its address must be a multiple of %zu bytes, got %p", what, kBaseAlign, buf);
   const size_t need = layout_size(buf, layout);
   return need > bytes ? fail("%s too small: need %zu bytes, got %zu", what, need, bytes) : 0;
 }

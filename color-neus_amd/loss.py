@@ -46,13 +46,13 @@ _SCRATCH = {}   # (library path, device, stream) -> the loss scratch of that str
 
 def _loss_scratch(lib, dev, R):
     """The scratch of the loss kernels for the current stream of ``dev``.  Its tail holds the completion counter of the one-launch forms
-    (include/colorneus_render.h: zero before the first use, left zero by every call), so the buffer is created zeroed ONCE per stream and
+    (include/colorneus_render.h: zero before the first use, left zero by every call, like the rest of the buffer), so it is created zeroed ONCE per stream and
     reused: calls on one stream are ordered, calls on different streams get different buffers."""
     nb = lib.lib.cnr_loss_scratch_bytes(R)
     key = (lib.path, str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
     t = _SCRATCH.get(key)
     if t is None or t.numel() < nb:
-        t = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        t, nb = lib.scratch("cnr_loss_scratch_bytes", dev, R, zero=True)
         _SCRATCH[key] = t
     return t, nb
 

@@ -156,7 +156,7 @@ class ClipAdam(torch.optim.Optimizer):
                 nb = self._lib.lib.cnr_clip_adam_scratch_bytes(n, sz)
                 key = (gi, str(dev))
                 if key not in self._scratch or self._scratch[key].numel() < nb:   # scratch is not optimiser state: kept out of state_dict
-                    self._scratch[key] = torch.empty(nb, dtype=torch.uint8, device=dev)
+                    self._scratch[key] = self._lib.scratch("cnr_clip_adam_scratch_bytes", dev, n, sz)[0]
                 self._lib.call("cnr_clip_adam_step", C.byref(cfg), n, sz, pw, pg, C.c_void_p(st["exp_avg"].data_ptr() + 4 * offs[i]),
                                C.c_void_p(st["exp_avg_sq"].data_ptr() + 4 * offs[i]), ptr(self._scratch[key]), nb, stream)
                 i = j + 1

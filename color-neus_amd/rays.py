@@ -250,10 +250,10 @@ class _GenRays(torch.autograd.Function):
         d_far = z3(d_far) if has_nf else None
         d_c2w = torch.empty_like(c2w_c)
         d_focal = torch.empty(2, dtype=torch.float32, device=dev)
-        scratch = torch.empty(c2w_c.shape[0] * 2, dtype=torch.float32, device=dev)
+        scratch, nb = ctx.lib.scratch("cnr_gen_rays_backward", dev, nbytes=c2w_c.shape[0] * 2 * 4)   # n_cams * 2 floats: the header's formula
         ctx.lib.call("cnr_gen_rays_backward", ptr(idx if idx.numel() else None), n, ptr(c2w_c), c2w_c.shape[0], ptr(focal_c), H, W, normalize, opengl,
                      ptr(org if org.numel() else None), radius, ptr(d_o), ptr(d_d), ptr(d_near), ptr(d_far), ptr(d_c2w), ptr(d_focal),
-                     ptr(scratch), scratch.numel() * 4, stream_of(c2w_c))
+                     ptr(scratch), nb, stream_of(c2w_c))
         return (None, None, None, d_c2w.reshape(c2w_shape) if need[3] else None, d_focal.reshape(focal_shape) if need[4] else None,
                 None, None, None, None, None, None, None, None, None)
 

@@ -15,6 +15,13 @@
  *     process does keep: the first-error latch behind cnr_last_error(), the optional timing records (cnr_timing_enable), debug
  *     switches read once from the environment (CNR_*), the per-(kernel, device) "dynamic LDS opt-in applied" flags, and an
  *     atomic launch counter whose parity only picks the order in which a layer launch walks its tiles (speed, never a value)
+ *   - alignment: the render, evaluation (sdf_eval, sdf_grid, vertex_color), point-query, linear and background-network
+ *     entry points place sub-buffers at multiples of 256 bytes from the address of their `void* ctx` / `void* scratch`
+ *     and access them with 16-byte vector loads / stores and 8-byte atomics: that address must be a multiple of 16 bytes,
+ *     and these entry points refuse one that is not ("... misaligned: its address must be a multiple of 16 bytes")
+ *     before anything is launched.  The other entry points with a scratch buffer (loss, clip_adam, pixel table, mc, nn,
+ *     image, mesh raster, composite_background, gen_rays_backward) do not check its address: give them, like every
+ *     buffer, what hipMalloc gives (256-byte aligned)
  *   - all work is enqueued on the given hipStream_t (passed as void*); no internal synchronisation
  *   - return value: 0 on success, negative on error; cnr_last_error() returns a message for the calling thread
  *   - parameters are passed as an array of device pointers in the canonical order reported by cnr_param_info()
@@ -163,8 +170,10 @@ int cnr_loss_coef(const cnr_loss_config* cfg, const float* g_loss /* device [1] 
  *   cnr_loss_forward : cnr_loss_sums (delta_per_ray == 0: delta_relight is [R][M][3]; != 0: the per-ray sums [R]) + cnr_loss_combine; the block that
  *                      finishes last folds the partial sums in the fixed order of cnr_loss_sums -- bitwise the same sums and scalars.  Its completion
  *                      counter is the 4 bytes at offset cnr_loss_scratch_bytes() - 16 of the CALLER's scratch: zero before the first call that uses
- *                      the buffer, left zero by every call.  A buffer may be reused call after call on one stream; calls that may overlap (other
- *                      streams or threads) need buffers of their own.  cnr_loss_sums / cnr_loss_sums_ray never touch the counter.
+ *                      the buffer, left zero by every call.  So is the rest of the buffer: the folding block clears the partial sums it has read,
+ *                      and a scratch that was all zero before a call is all zero after it.  A buffer may be reused call after call on one
+ *                      stream; calls that may overlap (other streams or threads) need buffers of their own.  cnr_loss_sums / cnr_loss_sums_ray
+ *                      never touch the counter.
  *   cnr_loss_backward: cnr_loss_coef (also written to coef[4] for the caller: coef[2] * mask is d / d delta_relight, coef[3] is d / d gradient_error)
  *                      + cnr_loss_grads for d_color_fine / d_weight_sum.  eik_factor (device [1] or NULL = 1): coef[3] = g * lambda_eikonal * eik_factor
  *                      (ray-sharded runs, below). */

@@ -517,6 +517,8 @@ def test_abi_scratch_and_errors(backend):
 
 
 def test_cpu_tensors_need_an_explicit_library():
+    if not os.path.isfile(cn.library_path()):
+        pytest.skip("HIP library not built")
     V, Fc, col = _sphere()
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         cn.rasterize_mesh(torch.from_numpy(V.copy()), torch.from_numpy(Fc.copy()), torch.from_numpy(_camera(0)), torch.tensor([F0, F0]), H0, W0)

@@ -163,7 +163,8 @@ def _check(name, shape, library, device, strict):
     R, M = o.shape[0], ocfg.n_samples + ocfg.n_importance
     r = N.make_renderer(ocfg, P, library, device)
     dv = lambda t: t.to(device)
-    og, dg = dv(o).requires_grad_(True), dv(d).requires_grad_(True)
+    # (clone: on the CPU .to() returns the shared reference's own tensor, whose .grad a second _check of the case would add to)
+    og, dg = dv(o).clone().requires_grad_(True), dv(d).clone().requires_grad_(True)
     out = r(og, dg, dv(near), dv(far), z_vals=dv(ref["z32"]))
     loss, _ = cn.compute_loss(out, dv(gt), dv(mask))
     loss.backward()
