@@ -177,6 +177,10 @@ SIGNATURES = {
     # mesh rasteriser
     "cnr_mesh_raster_scratch_bytes": (_size, [_i64, _i64, _i32, _i32]),
     "cnr_mesh_raster": (_int, [_FP, _i64, _FP, _i64, _FP, _FP, _FP, _i32, _i32, _i32, _FP, _f32, _f32, _F3, _FP, _FP, _FP, _FP, _FP, _size, _FP]),
+    # mesh connected components, selection, compaction
+    "cnr_mesh_components": (_int, [_FP, _i64, _i64, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "cnr_mesh_select": (_int, [_FP, _i64, _i64, _FP, _FP, _FP, _i32, _i32, _f32, _FP, _FP, _FP, _FP, _FP, _FP]),
+    "cnr_mesh_compact": (_int, [_FP, _FP, _FP, _i64, _i64, _FP, _FP, _FP, _FP, _FP, _FP]),
     # one plain fully-connected layer
     "cnr_linear_scratch_bytes": (_size, [_i64, _i32, _i32, _i32]),
     "cnr_linear_forward": (_int, [_FP, _i64, _i32, _FP, _FP, _i32, _i32, _FP, _FP, _size, _FP]),

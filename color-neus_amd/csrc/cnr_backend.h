@@ -667,6 +667,8 @@ CNR_HD unsigned char img_panel_byte(const ImagePanel& p, int row, int col, float
 // ---- mesh rasteriser (cnr_mesh_raster): MeshRaster, be_mesh_raster and the per-element functions both builds share are in cnr_raster.h
 }  // namespace cnr
 #include "cnr_raster.h"
+// ---- mesh connected components, selection, compaction (cnr_mesh_components / _select / _compact): descriptors and shared functions in cnr_meshcc.h
+#include "cnr_meshcc.h"
 namespace cnr {
 
 // ---- N_OUTSIDE > 0: the NeRF++ background of NeuS (NeuS.py:95-134, 313-369; NeRF, fields.py:192-274) -----------------------------------

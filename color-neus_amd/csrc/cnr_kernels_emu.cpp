@@ -435,6 +435,55 @@ void be_mesh_raster(const MeshRaster& p, cnr_stream) {
     for (int i = 0; i < p.W; ++i) raster_resolve(p, i, j);
 }
 
+// twins of the meshcc_*_kernel launches: the same meshcc_* functions, one triangle / vertex after the other.  The union-find runs with the
+// plain accessor; hooking the larger root under the smaller gives the same roots as every order of the HIP build's hooks.
+void be_mesh_components(const MeshComponents& p, cnr_stream) {
+  for (int k = 0; k < 4; ++k) p.summary[k] = 0;
+  p.dropped[0] = 0;
+  for (long v = 0; v < p.V; ++v) { p.labels[v] = (int)v; p.face_count[v] = 0; p.vertex_count[v] = 0; }
+  for (long f = 0; f < p.F; ++f) {
+    const int* t = p.triangles + f * 3;
+    if (!meshcc_valid(t, p.V)) { ++p.dropped[0]; continue; }
+    meshcc_unite<MeshccPlain>(p.labels, t[0], t[1]);
+    meshcc_unite<MeshccPlain>(p.labels, t[0], t[2]);
+  }
+  for (long v = 0; v < p.V; ++v) {
+    const int root = meshcc_root(p.labels, (int)v);
+    p.labels[v] = root;
+    ++p.vertex_count[root];
+    if (root == (int)v) ++p.summary[0];
+  }
+  for (long f = 0; f < p.F; ++f) {
+    const int* t = p.triangles + f * 3;
+    if (meshcc_valid(t, p.V)) ++p.face_count[p.labels[t[0]]];
+  }
+  unsigned long long best = 0;
+  for (long v = 0; v < p.V; ++v)
+    if (p.labels[v] == (int)v && p.face_count[v] > 0) {
+      ++p.summary[1];
+      best = std::max(best, meshcc_key(p.face_count[v], (int)v));
+    }
+  meshcc_unkey(best, &p.summary[2], &p.summary[3]);
+}
+
+void be_mesh_select(const MeshSelect& p, cnr_stream) {
+  const int thr = meshcc_threshold(p.min_faces, p.min_ratio, p.summary[3]);
+  p.totals[0] = p.totals[1] = 0;
+  for (long v = 0; v < p.V; ++v) {
+    p.keep_vertex[v] = meshcc_keep_vertex(p, v, thr);
+    p.vertex_map[v] = p.keep_vertex[v] ? p.totals[0]++ : -1;
+  }
+  for (long f = 0; f < p.F; ++f) {
+    p.keep_face[f] = meshcc_keep_face(p, f, thr);
+    p.face_map[f] = p.keep_face[f] ? p.totals[1]++ : -1;
+  }
+}
+
+void be_mesh_compact(const MeshCompact& p, cnr_stream) {
+  for (long v = 0; v < p.V; ++v) meshcc_compact_vertex(p, v);
+  for (long f = 0; f < p.F; ++f) meshcc_compact_face(p, f);
+}
+
 void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
   for (int cam = 0; cam < q.f.n_cams; ++cam) {
     double acc[14] = {0};   // (the HIP kernel sums in float in a fixed tree order; the tests compare both with autograd)

@@ -485,4 +485,56 @@ int cnr_mesh_raster(const float* vertices, int64_t n_vertices, const int32_t* tr
   return check_backend("mesh_raster");
 }
 
+// the three mesh-cleaning entries share the size rule: indices and counts are int32
+static int mesh_sizes(const char* what, int64_t F, int64_t V) {
+  if (F < 0 || V < 0) return fail("%s: n_triangles and n_vertices must not be negative", what);
+  if (F > INT32_MAX || V > INT32_MAX)
+    return fail("%s: n_triangles and n_vertices must not exceed 2^31 - 1 (indices and counts are int32; got %lld and %lld)", what, (long long)F, (long long)V);
+  return 0;
+}
+
+int cnr_mesh_components(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, int32_t* labels, int32_t* face_count,
+                        int32_t* vertex_count, int32_t* summary, int32_t* dropped, void* stream) {
+  if (mesh_sizes("mesh_components", n_triangles, n_vertices)) return -1;
+  if ((n_triangles > 0 && !triangles) || (n_vertices > 0 && (!labels || !face_count || !vertex_count)) || !summary || !dropped)
+    return fail("mesh_components: null argument");
+  if (reinterpret_cast<uintptr_t>(summary) % 8 != 0) return fail("mesh_components: summary must be 8-byte aligned");
+  MeshComponents p;
+  p.triangles = triangles; p.F = (long)n_triangles; p.V = (long)n_vertices;
+  p.labels = labels; p.face_count = face_count; p.vertex_count = vertex_count; p.summary = summary; p.dropped = dropped;
+  be_mesh_components(p, (cnr_stream)stream);
+  return check_backend("mesh_components");
+}
+
+int cnr_mesh_select(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* labels, const int32_t* face_count,
+                    const int32_t* summary, int32_t mode, int32_t min_faces, float min_ratio, uint8_t* keep_vertex, uint8_t* keep_face,
+                    int32_t* vertex_map, int32_t* face_map, int32_t* totals, void* stream) {
+  if (mesh_sizes("mesh_select", n_triangles, n_vertices)) return -1;
+  if (mode != CNR_MESH_KEEP_LARGEST && mode != CNR_MESH_KEEP_THRESHOLD) return fail("mesh_select: mode must be 0 (largest) or 1 (threshold), got %d", mode);
+  if (min_faces < 0 || !(min_ratio >= 0.0f)) return fail("mesh_select: min_faces and min_ratio must not be negative (or NaN)");
+  if ((n_triangles > 0 && (!triangles || !keep_face || !face_map)) || (n_vertices > 0 && (!labels || !face_count || !keep_vertex || !vertex_map)) ||
+      !summary || !totals)
+    return fail("mesh_select: null argument");
+  MeshSelect p;
+  p.triangles = triangles; p.F = (long)n_triangles; p.V = (long)n_vertices; p.labels = labels; p.face_count = face_count; p.summary = summary;
+  p.mode = mode; p.min_faces = min_faces; p.min_ratio = min_ratio;
+  p.keep_vertex = keep_vertex; p.keep_face = keep_face; p.vertex_map = vertex_map; p.face_map = face_map; p.totals = totals;
+  be_mesh_select(p, (cnr_stream)stream);
+  return check_backend("mesh_select");
+}
+
+int cnr_mesh_compact(const float* vertices, const float* colors, const int32_t* triangles, int64_t n_triangles, int64_t n_vertices,
+                     const int32_t* vertex_map, const int32_t* face_map, float* out_vertices, float* out_colors, int32_t* out_triangles,
+                     void* stream) {
+  if (mesh_sizes("mesh_compact", n_triangles, n_vertices)) return -1;
+  // (an output array is empty, and may be NULL, when its map keeps nothing: V' and F' are the caller's knowledge, from cnr_mesh_select's totals)
+  if ((n_triangles > 0 && (!triangles || !face_map)) || (n_vertices > 0 && (!vertices || !vertex_map))) return fail("mesh_compact: null argument");
+  if ((colors == nullptr) != (out_colors == nullptr)) return fail("mesh_compact: colors and out_colors must be given together or be null together");
+  MeshCompact p;
+  p.vertices = vertices; p.colors = colors; p.triangles = triangles; p.F = (long)n_triangles; p.V = (long)n_vertices;
+  p.vertex_map = vertex_map; p.face_map = face_map; p.out_vertices = out_vertices; p.out_colors = out_colors; p.out_triangles = out_triangles;
+  be_mesh_compact(p, (cnr_stream)stream);
+  return check_backend("mesh_compact");
+}
+
 }  // extern "C"

@@ -1,0 +1,119 @@
+"""Mesh clean-up on the device library: connected components of an indexed triangle mesh and removal of the small ones ("floaters").
+
+The iso-surface of a NeuS-style SDF almost always carries small closed shells away from the object and fragments near the bounding box;
+evaluation scripts remove them before scoring (``trimesh.split`` and "keep the largest" in the reference's environment).  Here that is
+three entry points of the C ABI (include/colorneus_render.h, where the definitions are): ``cnr_mesh_components`` labels the components with a
+lock-free union-find, ``cnr_mesh_select`` marks what to keep and scans the marks into index maps, ``cnr_mesh_compact`` writes the kept
+vertices, colours and triangles in their original order.  Everything is integer work: the results are exact and the same bits on every run.
+
+``triangles`` may be a tensor or a numpy array of any integer dtype and any strides, ``vertices`` / ``colors`` of any float dtype; they are
+converted to contiguous int32 / float32 on the device of ``vertices`` (``connected_components``: of ``triangles``).  CUDA tensors go through
+the HIP library; CPU tensors only with an explicitly passed emulation ``library=`` (there is no CPU fallback).  NOTHING HERE IS
+DIFFERENTIABLE: inputs are detached and results carry no graph."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr, stream_of
+
+__all__ = ["connected_components", "clean_mesh"]
+
+_MODES = {"largest": 0, "threshold": 1}
+
+
+def _triangles(t, dev=None):
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.asarray(t))
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"triangles: expected an integer dtype, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"triangles: expected an (F, 3) tensor, got {tuple(t.shape)}")
+    t = t.detach()
+    if t.numel() and t.dtype == torch.int64:
+        # an index that does not fit int32 is outside [0, V) for every V the library takes: it stays invalid (-1) instead of wrapping
+        t = torch.where((t < 0) | (t > 2 ** 31 - 1), torch.full_like(t, -1), t)
+    return t.to(device=dev if dev is not None else t.device, dtype=torch.int32).contiguous()
+
+
+def _floats(x, name, dev, rows=None):
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x))
+    if x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
+        raise ValueError(f"{name}: expected a floating-point (N, 3) tensor, got {tuple(x.shape)} {x.dtype}")
+    if rows is not None and x.shape[0] != rows:
+        raise ValueError(f"{name}: expected {rows} rows, got {x.shape[0]}")
+    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _components(t, n_vertices, lib):
+    """t: contiguous int32 (F, 3) -> (labels, face_count, vertex_count, summary [4], dropped [1]), all device int32, nothing read back."""
+    dev, V = t.device, int(n_vertices)
+    labels, face_count, vertex_count = (torch.empty(V, dtype=torch.int32, device=dev) for _ in range(3))
+    summary = torch.empty(4, dtype=torch.int32, device=dev)
+    dropped = torch.empty(1, dtype=torch.int32, device=dev)
+    lib.call("cnr_mesh_components", ptr(t), t.shape[0], V, ptr(labels), ptr(face_count), ptr(vertex_count), ptr(summary), ptr(dropped),
+             stream_of(dev))
+    return labels, face_count, vertex_count, summary, dropped
+
+
+def connected_components(triangles, n_vertices, library=None):
+    """The connected components of the mesh ``triangles`` [F, 3] over ``n_vertices`` vertices (``cnr_mesh_components``).
+
+    Returns a dict: device int32 tensors ``labels`` [V] (the smallest vertex index of each vertex's component), ``face_count`` [V] and
+    ``vertex_count`` [V] (a component's totals at its root ``r``, where ``labels[r] == r``; 0 elsewhere), and Python ints ``n_components``,
+    ``n_components_with_faces``, ``largest_label`` (most faces, ties to the lowest label; -1 without a valid triangle),
+    ``largest_face_count`` and ``dropped`` (triangles with an index outside ``[0, n_vertices)``: they connect nothing).  A vertex no valid
+    triangle names is a component of its own with zero faces.  Reading the five ints is the call's one host synchronisation."""
+    n_vertices = int(n_vertices)
+    if n_vertices < 0:
+        raise ValueError(f"connected_components: n_vertices must not be negative (got {n_vertices})")
+    t = _triangles(triangles)
+    lib = _lib.library_for(library, t.device, ("a mesh", "labelled"))
+    labels, face_count, vertex_count, summary, dropped = _components(t, n_vertices, lib)
+    s = torch.cat([summary, dropped]).tolist()
+    return {"labels": labels, "face_count": face_count, "vertex_count": vertex_count, "n_components": s[0], "n_components_with_faces": s[1],
+            "largest_label": s[2], "largest_face_count": s[3], "dropped": s[4]}
+
+
+def clean_mesh(vertices, triangles, colors=None, keep="largest", min_faces=0, min_ratio=0.0, library=None):
+    """Remove components from a mesh: ``(vertices', triangles', colors' or None, info)``, device tensors (float32 [V', 3], int32 [F', 3],
+    float32 [V', 3]) in the ORIGINAL order of the kept vertices and faces, the indices of ``triangles'`` renumbered.
+
+    ``keep="largest"`` keeps the component with the most faces (ties: the one with the lowest vertex index) and takes no thresholds;
+    ``keep="threshold"`` keeps every component with at least ``max(min_faces, ceil(min_ratio * largest_face_count))`` faces (the product and
+    the ceiling in float32).  Triangles with an index outside ``[0, V)`` and vertices that no kept triangle's component holds -- unreferenced
+    vertices included -- are removed.  ``info``: the ints of ``connected_components`` plus ``n_vertices`` / ``n_faces`` (of the result) and the
+    device tensors ``labels``, ``face_count``, ``vertex_count``, ``keep_vertex`` / ``keep_face`` (bool) and ``vertex_map`` [V] / ``face_map`` [F]
+    (int32: the new index, -1 for what was removed).  One host read (the summary and the two totals) sizes the outputs, as in
+    ``marching_cubes``.  Not differentiable."""
+    if keep not in _MODES:
+        raise ValueError(f"clean_mesh: keep must be 'largest' or 'threshold', got {keep!r}")
+    min_faces, min_ratio = int(min_faces), float(min_ratio)
+    if min_faces < 0 or not min_ratio >= 0.0:
+        raise ValueError(f"clean_mesh: min_faces and min_ratio must not be negative (got {min_faces}, {min_ratio})")
+    if keep == "largest" and (min_faces or min_ratio):
+        raise ValueError("clean_mesh: keep='largest' takes no min_faces / min_ratio (use keep='threshold')")
+    dev = vertices.device if torch.is_tensor(vertices) else (triangles.device if torch.is_tensor(triangles) else torch.device("cpu"))
+    lib = _lib.library_for(library, dev, ("a mesh", "cleaned"))
+    v = _floats(vertices, "vertices", dev)
+    t = _triangles(triangles, dev)
+    col = _floats(colors, "colors", dev, v.shape[0]) if colors is not None else None
+    V, F = v.shape[0], t.shape[0]
+    labels, face_count, vertex_count, summary, dropped = _components(t, V, lib)
+    keep_vertex, keep_face = torch.empty(V, dtype=torch.uint8, device=dev), torch.empty(F, dtype=torch.uint8, device=dev)
+    vertex_map, face_map = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev)
+    totals = torch.empty(2, dtype=torch.int32, device=dev)
+    lib.call("cnr_mesh_select", ptr(t), F, V, ptr(labels), ptr(face_count), ptr(summary), _MODES[keep], min_faces, min_ratio, ptr(keep_vertex),
+             ptr(keep_face), ptr(vertex_map), ptr(face_map), ptr(totals), stream_of(dev))
+    s = torch.cat([summary, dropped, totals]).tolist()      # the one host round trip: the caller owns the output buffers
+    nv, nf = s[5], s[6]
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_t = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    out_c = torch.empty(nv, 3, dtype=torch.float32, device=dev) if col is not None else None
+    if nv > 0:      # (a kept vertex has a kept face and the other way round: both are empty together, and empty tensors have no address)
+        lib.call("cnr_mesh_compact", ptr(v), ptr(col), ptr(t), F, V, ptr(vertex_map), ptr(face_map), ptr(out_v), ptr(out_c), ptr(out_t),
+                 stream_of(dev))
+    info = {"n_components": s[0], "n_components_with_faces": s[1], "largest_label": s[2], "largest_face_count": s[3], "dropped": s[4],
+            "n_vertices": nv, "n_faces": nf, "labels": labels, "face_count": face_count, "vertex_count": vertex_count,
+            "keep_vertex": keep_vertex.bool(), "keep_face": keep_face.bool(), "vertex_map": vertex_map, "face_map": face_map}
+    return out_v, out_t, out_c, info

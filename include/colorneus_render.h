@@ -537,6 +537,43 @@ int cnr_mesh_raster(const float* vertices /* [V][3] */, int64_t n_vertices, cons
                     float* depth /* [H][W] */, int32_t* tri_id /* [H][W] */, int32_t* dropped /* device [2] */,
                     void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- mesh connected components and floater removal: label the components of an indexed triangle mesh (cnr_mc_emit's welded vertices make face
+ * connectivity vertex connectivity), choose the ones to keep, and compact vertices, colours and triangles in their original order.  All of it is
+ * integer work: every result is exact and the same bits for every face order, launch order and build.
+ * Definitions:
+ *   valid       a triangle whose three indices lie in [0, n_vertices).  An invalid one connects nothing, belongs to no component, is counted in
+ *               dropped[0] and is never kept (cnr_mesh_raster's rule for dropped[1]; the vertex arrays are never read out of bounds).
+ *   connected   two vertices are connected when a valid triangle contains both.  Degenerate (a, a, b) and duplicate triangles are valid.  A vertex
+ *               in no valid triangle is a component of its own with zero faces.
+ *   labels[v]   the smallest vertex index of v's component; the component's root is the vertex r with labels[r] == r.
+ *   face_count[r], vertex_count[r]   the component's totals at its root, 0 at every other index.  A valid triangle counts for labels[t[0]].
+ *   summary     {n_components, n_components_with_faces, largest_label, largest_face_count}: "largest" = most faces, ties to the lowest label,
+ *               zero-face components are no candidates; without a valid triangle largest_label = -1 and largest_face_count = 0.
+ * There is no size query and no scratch: the working storage is the typed arrays themselves, device memory owned by the caller, all overwritten:
+ *   cnr_mesh_components   labels, face_count, vertex_count: int32 [n_vertices] each (labels holds the union-find's parent array while the call
+ *                         runs); summary: int32 [4], 8-BYTE ALIGNED (its second half holds a 64-bit key while the call runs); dropped: int32 [1]
+ *   cnr_mesh_select       keep_vertex: uint8 [n_vertices], keep_face: uint8 [n_triangles] (0 or 1); vertex_map: int32 [n_vertices], face_map:
+ *                         int32 [n_triangles]: the element's index after compaction (the number of kept elements before it), -1 when it goes;
+ *                         totals: int32 [2] = {V', F'}.  labels, face_count and summary are cnr_mesh_components' results for the same mesh.
+ *   cnr_mesh_compact      out_vertices, out_colors: float [V'][3], out_triangles: int32 [F'][3], exactly that long (the caller reads totals
+ *                         first; an array of length 0 may be NULL); out_triangles[face_map[f]][k] = vertex_map[triangles[f][k]].  vertex_map
+ *                         and face_map are cnr_mesh_select's for the same mesh.
+ * Selection: mode 0 (largest) keeps the faces of component largest_label and nothing else (min_faces and min_ratio are not used); mode 1
+ * (threshold) keeps face f iff it is valid and face_count[labels[t[0]]] >= max(min_faces, ceil(min_ratio * largest_face_count)), the product
+ * and the ceiling in fp32.  A vertex is kept iff its component is kept AND has at least one face: unreferenced vertices go.
+ * n_triangles == 0 and n_vertices == 0 are legal (with n_vertices == 0 every triangle is invalid): launches over an empty range are left out,
+ * summary, dropped and totals are still written.  Errors: n_triangles or n_vertices negative or above 2^31 - 1; a null pointer to an array
+ * that is not empty; summary not 8-byte aligned; a mode other than 0 / 1; min_faces < 0; min_ratio < 0 or NaN; colors and out_colors not
+ * null together.  Nothing is differentiable. */
+int cnr_mesh_components(const int32_t* triangles /* [F][3] */, int64_t n_triangles, int64_t n_vertices, int32_t* labels, int32_t* face_count,
+                        int32_t* vertex_count, int32_t* summary /* [4] */, int32_t* dropped /* [1] */, void* stream);
+int cnr_mesh_select(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* labels, const int32_t* face_count,
+                    const int32_t* summary, int32_t mode, int32_t min_faces, float min_ratio, uint8_t* keep_vertex, uint8_t* keep_face,
+                    int32_t* vertex_map, int32_t* face_map, int32_t* totals /* [2] */, void* stream);
+int cnr_mesh_compact(const float* vertices /* [V][3] */, const float* colors /* [V][3] or NULL */, const int32_t* triangles, int64_t n_triangles,
+                     int64_t n_vertices, const int32_t* vertex_map, const int32_t* face_map, float* out_vertices, float* out_colors /* NULL iff colors NULL */,
+                     int32_t* out_triangles, void* stream);
+
 /* ---- one plain fully-connected layer on the layer / weight-gradient kernels of the render path: y = act(x W^T + b), act = ReLU or none.
  * The NeRF++ background network of NeuS (NeRF, fields.py:192-274; N_OUTSIDE > 0, NeuS.py:95-134) is a chain of nn.Linear (+ ReLU) layers;
  * color-neus_amd/background.py evaluates each of them through these two entry points.  x [n][k], y / dy [n][n_out], W [n_out][k] and b [n_out]
