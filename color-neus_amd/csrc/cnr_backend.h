@@ -1,4 +1,7 @@
-// Kernel launch interface between the host orchestration (the host units listed in cnr_plan.cpp, sharing cnr_plan.h) and the kernels.
+// Kernel launch interface of the render path between the host orchestration (the host units listed in cnr_plan.cpp, sharing cnr_plan.h) and the
+// kernels: weight preparation, the layer / chain / narrow / head / strip launches, sampler, compositor and prune, the *_finish kernels and the
+// point-query rows, the memset / column helpers, timing, ranges and the error check.  Every stand-alone family (loss, optimiser, rays, pixels,
+// cameras, marching cubes, nearest neighbour, image metrics, background, mesh raster, mesh components) has a header of its own: cnr_<family>.h.
 // Implemented twice: the .hip translation units (HIP, gfx950 -- the product) and cnr_kernels_emu.cpp (CPU emulation, tests only).
 #pragma once
 #include "cnr_common.h"
@@ -7,7 +10,6 @@
 namespace cnr {
 
 constexpr int kMaxRaySamples = 256;   // per-ray kernels stage one ray in LDS: M <= 256
-constexpr int kMaxOutside = 128;      // background samples per ray (N_OUTSIDE)
 
 struct Segment { int dst, src, len; };   // internal column [dst, dst+len) <- reference column [src, src+len)
 // the column permutation a layer's segments describe: the reference column behind internal column j / the internal column of reference column c
@@ -388,354 +390,6 @@ void be_variance_finish(const VarianceFinish& p, cnr_stream s);
 void be_pbar_finish(const PbarFinish& p, cnr_stream s);
 void be_rays_grad_finish(const RaysGradFinish& p, cnr_stream s);
 void be_memset_zero(void* p, size_t bytes, cnr_stream s);
-
-// training loss (include/colorneus_render.h, cnr_loss_*): partial sums [nblk][4] -> sums[4]; gradients w.r.t. the renderer outputs
-struct LossArgs {
-  const float* color; const float* wsum; const float* drel; const float* gt; const float* mask;
-  long R; int M; int rgb_l1; int include_mask;
-  int drel_per_ray = 0;   // 1: drel is [R], the per-ray sums over samples and rgb (CompositeFwd::delta_ray_sum)
-};
-constexpr int kLossBlocks = 256;
-void be_loss_sums(const LossArgs& a, float* partial /* [kLossBlocks][4] */, float* sums /* [4] */, cnr_stream s);
-void be_loss_grads(const LossArgs& a, const float* coef, float* d_color, float* d_wsum, float* d_drel, cnr_stream s);
-struct LossScalars {   // see cnr_loss_combine / cnr_loss_coef in the ABI header; the constants are formed in double on the host and rounded once
-  float lf, le, lm, lr;                 // lambdas
-  float Rg, den_rgb, den_rel;           // n_rays_global, 3 Rg, 3 Rg M
-  float c_rgb, c_bce, c_rel;            // lambda_fine * (1 | 2) / (3 Rg), lambda_mask / Rg, lambda_relight * 2 / (3 Rg M)
-  int use_mask, use_relight;
-};
-void be_loss_combine(const LossScalars& c, const float* sums, const float* gerr, float* out6, cnr_stream s);
-void be_loss_coef(const LossScalars& c, const float* g_loss, const float* mean_rel, float* coef4, cnr_stream s);
-// the forward side (partial sums, their fold, the scalar tail) and the backward side (coefficients + element-wise gradients) as ONE launch each
-// (ticket: a zero-initialised 4-byte completion counter in the caller's scratch, left zero)
-void be_loss_forward(const LossArgs& a, float* partial, unsigned* ticket, const LossScalars& c, const float* gerr, float* sums, float* out6, cnr_stream s);
-void be_loss_backward(const LossArgs& a, const LossScalars& c, const float* g_loss, const float* mean_rel, const float* eik_factor /* or null */, float* coef4,
-                      float* d_color, float* d_wsum, float* d_drel_ray /* [R] or null */, cnr_stream s);
-// ray-sharded runs: this rank's statistics for the one all-reduce of the objective (one launch), and the scalar tail on the reduced statistics
-void be_loss_shard_stats(const LossArgs& a, float* partial, unsigned* ticket, const float* eik_sums /* [2] */, float* stats8, cnr_stream s);
-void be_loss_shard_combine(const LossScalars& c, const float* stats8, float* out8, cnr_stream s);
-// per-parameter gradient clip + Adam over up to kAdamBatch tensors per launch (clip_gradient + torch.optim.Adam, net_utils.py:174-184, :88)
-constexpr int kAdamBatch = 64;
-constexpr int kAdamChunk = 4096;   // elements per workgroup: a tensor is cut into ceil(n / kAdamChunk) chunks
-struct AdamTensor { float* w; const float* g; long off; long n; int chunk0; };   // off: offset of this tensor's moments in the flat m / v buffers; chunk0: its first chunk
-struct AdamArgs {
-  int count; AdamTensor t[kAdamBatch];
-  int nchunks; float* partial;         // [nchunks] per-chunk sums of squared gradient entries (scratch)
-  float* m; float* v;                  // flat exp_avg / exp_avg_sq
-  float lr, beta1, beta2, eps, max_norm;   // max_norm <= 0: no clipping
-  float bc1, bc2_sqrt;                 // 1 - beta1^step, sqrt(1 - beta2^step)
-  const float* hyper;                  // device [3] = {lr, bc1, bc2_sqrt} or null: read instead of the three members above (graph replay)
-};
-// one tensor's update; norm2 = the tensor's sum of squared gradient entries (fixed-order reduction by the caller)
-CNR_HD float adam_clip_coef(float norm2, float max_norm) {
-  if (!(max_norm > 0.0f)) return 1.0f;
-  const float c = max_norm / (sqrtf(norm2) + 1e-6f);    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-  return c < 1.0f ? c : 1.0f;
-}
-CNR_HD void adam_update1(const AdamArgs& a, float* w, float g, float* m, float* v) {
-  const float m1 = *m + (g - *m) * (1.0f - a.beta1);               // exp_avg.lerp_(grad, 1 - beta1)
-  const float v1 = *v * a.beta2 + (1.0f - a.beta2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  *m = m1; *v = v1;
-  const float lr = a.hyper ? a.hyper[0] : a.lr, bc1 = a.hyper ? a.hyper[1] : a.bc1, bc2_sqrt = a.hyper ? a.hyper[2] : a.bc2_sqrt;
-  const float denom = sqrtf(v1) / bc2_sqrt + a.eps;
-  *w = *w - (lr / bc1) * (m1 / denom);                         // param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1)
-}
-void be_clip_adam(const AdamArgs& a, cnr_stream s);   // a.partial must hold a.nchunks floats
-
-// ---- ray generation for the selected pixels (the producer right in front of the path): get_rays_multicam / get_rays_at
-// (lib/models/tools/ray_utils.py:16-119) with the trainer's origin / radius normalisation and near_far_from_sphere
-// (NeuS_Trainer.py:117-119, ray_utils.py:7-13) folded in, and its backward to the camera poses and the focal lengths
-struct GenRays {
-  const long* pix_idx; long n;          // flat index over (camera, row, column); null: pixel i of camera 0 (get_rays_at)
-  const float* c2w; int n_cams;         // [n_cams][4][4]
-  const float* focal;                   // [2] (device)
-  int H, W, normalize, opengl;
-  const float* image; const float* mask;    // [n_cams][H][W][3] / [n_cams][H][W] or null
-  const float* origin; float radius;        // rays_o = (rays_o - origin) / radius when origin != null
-  float* rays_o; float* rays_d; float* rgb; float* mask_sel; float* near_; float* far_;   // any of rgb / mask_sel / near_ / far_ may be null
-  int* bad_count = nullptr;             // device counter or null: +1 per pixel index outside [0, n_cams * H * W) (an error flag, not arithmetic)
-};
-struct GenRaysBwd {
-  GenRays f;                            // the forward arguments (outputs unused)
-  const float* d_rays_o; const float* d_rays_d; const float* d_near; const float* d_far;   // upstream gradients (d_near / d_far may be null)
-  float* d_c2w;                         // [n_cams][4][4] (bottom row zero)
-  float* d_focal_partial;               // [n_cams][2] per-camera contributions, folded in camera order into d_focal
-  float* d_focal;                       // [2]
-};
-void be_gen_rays(const GenRays& p, cnr_stream s);
-void be_gen_rays_bwd(const GenRaysBwd& p, cnr_stream s);
-
-// ---- on-device pixel choice (cnr_pixel_table_build / cnr_choose_pixels; specified in include/colorneus_render.h): the sampling semantics of
-// get_rays_multicam's pixel choice (ray_utils.py:57-76) on a Philox stream keyed by a device {seed, step}.  The arithmetic (pix_* in cnr_bodies.h)
-// is shared by the HIP kernels and the emulation; all of it is integer arithmetic.
-constexpr int kPixTile = 4096;            // pixels of one image that one workgroup counts / scatters (16 wave-chunks of 256: 64 lanes x one 16-byte load)
-constexpr int kPixMaxSlots = 1024;        // images per draw: the slot prefixes live in LDS
-struct PixelTable {
-  const float* masks; int n_images; long hw;   // [n_images][hw]
-  int* order;                             // [n_images][hw]: foreground pixels ascending, then background pixels ascending
-  int* fg_count; int* bg_count;           // [n_images]
-  int* tile_counts; long tiles;           // [n_images][tiles][2] scratch: per-tile {fg, bg} counts -> exclusive offsets within the image
-};
-void be_pixel_table(const PixelTable& t, cnr_stream s);
-struct PixelDraw {
-  long* state;                            // device {seed, step}; the step is advanced behind the draw
-  long n; int want_fg; const int* want_fg_dev;
-  const int* cam_ids; int B, n_images; long hw;
-  const int* order; const int* fg_count; const int* bg_count;   // all null: draws with replacement over [0, span)
-  unsigned long long span;
-  long* idx; int* cams_out; int* counts_out; float* t_rand;
-};
-void be_choose_pixels(const PixelDraw& p, cnr_stream s);
-
-// ---- learnable cameras (camera_net.py:8-109): the producer of c2w / focal in front of the ray generator
-struct Camera {
-  const float* r; const float* t;       // [num_cams][6 or 3], [num_cams][3]; null: no pose part
-  const float* init_c2w;                // [num_cams][4][4] or null
-  const float* fx; const float* fy;     // [1] each; fy null with fx_only; fx null: no focal part
-  const long* cam_ids; long B;          // [B] or null: slot i is camera i (B == num_cams)
-  int num_cams, six_d, focal_order, fx_only, H, W;
-  float* c2w; float* focal;             // [B][4][4] (null: no pose part), [2] (null: no focal part)
-};
-struct CameraBwd {
-  Camera f;                             // the forward arguments (outputs unused)
-  const float* d_c2w; const float* d_focal;           // [B][4][4], [2]
-  float* d_r; float* d_t; float* d_fx; float* d_fy;   // dense [num_cams][6 or 3], [num_cams][3], [1], [1]; any may be null
-};
-void be_camera_fwd(const Camera& p, cnr_stream s);
-void be_camera_bwd(const CameraBwd& q, cnr_stream s);
-
-// ---- iso-surface extraction on the device-resident SDF lattice (replaces the CPU mcubes.marching_cubes call of extract_geometry,
-// NeuS.py:31-40): cell classification + edge ownership, two exclusive scans, vertex / triangle emission
-struct McVolume {
-  const float* u; int res; float thr;      // u[x][y][z], surface where u crosses thr, "inside" = u > thr
-  unsigned char* flags;                    // [res^3] bit a: the edge from this voxel along +axis a crosses the level
-  int* counts;                             // [res^3][2] -> exclusive offsets {vertex, triangle} after mc_scan
-  int* block_sums;                         // [nblocks][2]
-  int* totals;                             // [2] device: number of vertices, number of triangles
-};
-constexpr int kMcScanBlock = 2048;
-void be_mc_count(const McVolume& v, cnr_stream s);    // flags + per-voxel {vertex, triangle} counts, scanned into offsets; totals written
-void be_mc_emit(const McVolume& v, const float* bmin, const float* bmax, float* verts, int* tris, cnr_stream s);
-// shared per-voxel logic (host + device)
-CNR_HD int mc_cell(const float* u, int res, float thr, int x, int y, int z, unsigned char* flags_out) {   // returns the cube index or -1 (no cell)
-  const long r2 = (long)res * res, v = ((long)x * res + y) * res + z;
-  const bool f0 = u[v] > thr;
-  unsigned char fl = 0;
-  if (x + 1 < res && (u[v + r2] > thr) != f0) fl |= 1;
-  if (y + 1 < res && (u[v + res] > thr) != f0) fl |= 2;
-  if (z + 1 < res && (u[v + 1] > thr) != f0) fl |= 4;
-  *flags_out = fl;
-  if (x + 1 >= res || y + 1 >= res || z + 1 >= res) return -1;
-  int idx = 0;
-  for (int c = 0; c < 8; ++c) {
-    const long vc = v + (c & 1) * r2 + ((c >> 1) & 1) * res + ((c >> 2) & 1);
-    idx |= (u[vc] > thr ? 1 : 0) << c;
-  }
-  return idx;
-}
-CNR_HD int mc_popcount3(unsigned x) { return (int)((x & 1) + ((x >> 1) & 1) + ((x >> 2) & 1)); }
-
-// ---- exact brute-force nearest neighbour of 3-D points (cnr_nn_search): the search behind the Chamfer / F-score mesh metrics
-// (lib/utils/mesh_tools.py:59-70 calls pytorch3d.loss.chamfer_distance on the vertices of two meshes).
-// For query i: the minimum over the targets j of d2(i, j) and the LOWEST j that attains it.  Candidates are ordered by the 64-bit key
-// (bits(d2) << 32) | j: d2 >= 0, so its bit pattern orders like its value, and the minimum key is the answer with the tie-break included.
-// A split of the target range folds its best keys with an integer min: the result does not depend on the number of splits or their order.
-struct NnSearch {
-  const float* query; long n;           // [n][3]
-  const float* target; long m;          // [m][3], 0 < m < 2^31
-  float* dist2; int* idx;               // [n]; a query whose every d2 is NaN gets NaN / -1
-  unsigned long long* keys;             // [n] scratch
-};
-void be_nn_search(const NnSearch& p, cnr_stream s);
-constexpr unsigned long long kNnNoKey = ~0ull;   // "no candidate": above every key, and it unpacks to {NaN, -1}
-// every operation a separately rounded fp32 operation in this order (the build passes -ffp-contract=off: no FMA)
-CNR_HD float nn_dist2(float qx, float qy, float qz, float tx, float ty, float tz) {
-  const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-// The scan over ascending j keeps {best, besti}, starting from {+inf, -1}: a strictly smaller d2 wins, so the lowest j of equal minima stays and
-// a NaN never wins.  The one candidate this misses is d2 == +inf itself (overflowing differences) while nothing has been taken yet: nn_update_inf,
-// run over a range whose nn_update pass left besti < 0, takes the first of those.
-CNR_HD void nn_update(float d2, int j, float& best, int& besti) {
-  if (d2 < best) { best = d2; besti = j; }
-}
-CNR_HD void nn_update_inf(float d2, int j, float best, int& besti) {
-  if (besti < 0 && d2 == best) besti = j;   // best is still +inf here
-}
-CNR_HD unsigned long long nn_key(float best, int besti) {
-  if (besti < 0) return kNnNoKey;
-  unsigned bits;
-  memcpy(&bits, &best, sizeof bits);
-  return ((unsigned long long)bits << 32) | (unsigned)besti;
-}
-CNR_HD void nn_unpack(unsigned long long key, float* dist2, int* idx) {
-  const unsigned bits = (unsigned)(key >> 32);
-  memcpy(dist2, &bits, sizeof bits);
-  *idx = (int)(unsigned)(key & 0xffffffffull);
-}
-
-// ---- image evaluation (cnr_image_metrics / cnr_image_panel): what NeuS_Trainer.validate_image does behind its render loop
-// (NeuS_Trainer.py:250-277): squared error (PSNR), the window-3 SSIM of lib/metrics/similarity.py:55, and the gt | render | depth picture.
-// The arithmetic is specified in include/colorneus_render.h; every operation below is a separately rounded fp32 operation in the order
-// written (the build passes -ffp-contract=off), so the HIP kernel and the emulation produce the same bits per pixel.
-// Both layouts are one picture of `planes` planes of H rows of `rowlen` floats whose horizontal neighbours are `cs` floats apart:
-//   [B][C][H][W]  planes = B*C, rowlen = W,   cs = 1          [B][H][W][C]  planes = B, rowlen = W*C, cs = C
-struct ImageStats {
-  const float* x; const float* y;      // the two images
-  long planes; int H, W, cs;           // rowlen = W * cs
-  float* map;                          // SSIM per element, the inputs' layout, or null
-  double* partials; long nblocks;      // [nblocks][2] scratch: per-block {sum d*d, sum ssim}
-  double* sums;                        // [2]
-};
-void be_image_stats(const ImageStats& p, cnr_stream s);
-struct ImagePanel {
-  const float* gt; const float* render;   // [H][W][3], or both null: the panel is the depth map alone, [H][W][3]
-  const float* depth;                     // [H][W]
-  int H, W, nsec;                         // nsec = 3 (gt | render | depth) or 1
-  unsigned char* panel;                   // [H][nsec*W][3]
-  float* range;                           // [2] vmin, vmax over the non-NaN depths ({0, 0} when there is none)
-  unsigned* keys;                         // [2] scratch: min of img_depth_key, min of ~img_depth_key
-};
-void be_image_panel(const ImagePanel& p, cnr_stream s);
-constexpr int kImgMaxCs = 32;             // channels-last form: at most this many channels (the halo of a staged row is cs floats each side)
-constexpr int kImgTileW = 64, kImgTileH = 16;   // floats x rows of one block's tile
-CNR_HD long img_tiles_x(int W, int cs) { return ((long)W * cs + kImgTileW - 1) / kImgTileW; }
-CNR_HD long img_tiles_y(int H) { return (H + kImgTileH - 1) / kImgTileH; }
-// reflection without repeating the edge: -1 -> 1, n -> n - 2 (only called with i in [-1, n], n >= 2)
-CNR_HD int img_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-// one pass of the normalised 3-tap Gaussian (sigma 1.5, as float32 torch evaluates it): outer taps w1, centre w0
-CNR_HD float img_tap3(float a, float b, float c) {
-  const float w1 = 0x1.3b3046p-2f, w0 = 0x1.899f76p-2f;
-  return (w1 * a + w0 * b) + w1 * c;
-}
-CNR_HD float img_ssim(float mu1, float mu2, float e11, float e22, float e12) {
-  const float m11 = mu1 * mu1, m22 = mu2 * mu2, m12 = mu1 * mu2;
-  const float s1 = e11 - m11, s2 = e22 - m22, s12 = e12 - m12;
-  const float num = (2.0f * m12 + 1e-4f) * (2.0f * s12 + 9e-4f);
-  const float den = ((m11 + m22) + 1e-4f) * ((s1 + s2) + 9e-4f);
-  return num / (den + 1e-12f);
-}
-CNR_HD float img_sqerr(float x, float y) {
-  const float d = x - y;
-  return d * d;
-}
-// clamp to [lo, hi] that sends NaN to lo
-CNR_HD float img_clamp(float v, float lo, float hi) {
-  v = v > lo ? v : lo;
-  return v < hi ? v : hi;
-}
-// rgb.mul(255.0).astype(np.uint8) (NeuS_Trainer.py:252-256): truncation; out-of-range values are clamped (numpy wraps them), NaN gives 0
-CNR_HD unsigned char img_quant(float v) { return (unsigned char)(int)img_clamp(v * 255.0f, 0.0f, 255.0f); }
-// order-preserving key of a non-NaN float (negative values: all bits flipped, others: sign bit set)
-CNR_HD unsigned img_depth_key(float d) {
-  unsigned b;
-  memcpy(&b, &d, sizeof b);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-CNR_HD float img_depth_unkey(unsigned k) {
-  const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float d;
-  memcpy(&d, &b, sizeof d);
-  return d;
-}
-// keys = {min key, min ~key} as be_image_panel's range pass leaves them -> vmin, vmax ({0, 0} when no depth was a number)
-CNR_HD void img_depth_range(const unsigned* keys, float* vmin, float* vmax) {
-  const unsigned kmin = keys[0], kmax = ~keys[1];
-  if (kmin > kmax) { *vmin = 0.0f; *vmax = 0.0f; return; }
-  *vmin = img_depth_unkey(kmin); *vmax = img_depth_unkey(kmax);
-}
-// image_float_to_uint8 (viztools.py:145-155): level 0..255 of a depth in [vmin, vmax]; a range below 1e-10 or a NaN depth gives 0
-CNR_HD int img_depth_level(float d, float vmin, float vmax) {
-  const float range = vmax - vmin;
-  if (!(range >= 1e-10f)) return 0;
-  const float t = (d - vmin) / range;
-  return (int)img_clamp(t * 255.0f, 0.0f, 255.0f);
-}
-// channel ch (0 blue, 1 green, 2 red: cv2's order) of the HOT ramp at level v
-CNR_HD unsigned char img_hot(int v, int ch) {
-  const float u = (float)v / 255.0f;
-  const float c = ch == 2 ? 2.5f * u : (ch == 1 ? 2.5f * u - 1.0f : 5.0f * u - 4.0f);
-  return (unsigned char)(int)(255.0f * img_clamp(c, 0.0f, 1.0f) + 0.5f);
-}
-// byte `col` (0 .. nsec*3W) of panel row `row`
-CNR_HD unsigned char img_panel_byte(const ImagePanel& p, int row, int col, float vmin, float vmax) {
-  const int w3 = 3 * p.W, sec = col / w3, c = col - sec * w3;
-  if (sec < p.nsec - 1) return img_quant((sec == 0 ? p.gt : p.render)[(long)row * w3 + c]);
-  return img_hot(img_depth_level(p.depth[(long)row * p.W + c / 3], vmin, vmax), c % 3);
-}
-
-// ---- mesh rasteriser (cnr_mesh_raster): MeshRaster, be_mesh_raster and the per-element functions both builds share are in cnr_raster.h
-}  // namespace cnr
-#include "cnr_raster.h"
-// ---- mesh connected components, selection, compaction (cnr_mesh_components / _select / _compact): descriptors and shared functions in cnr_meshcc.h
-#include "cnr_meshcc.h"
-namespace cnr {
-
-// ---- N_OUTSIDE > 0: the NeRF++ background of NeuS (NeuS.py:95-134, 313-369; NeRF, fields.py:192-274) -----------------------------------
-// No shipped configuration enables it; these kernels favour plain code over speed (one thread per ray / per point).
-struct OutsideZ {       // background sample positions (NeuS.py:315-338) merged with the sorted foreground samples (NeuS.py:353-355)
-  long R; int M, n_out, n_samples;
-  const float* far_; const float* t_rand /* [R][n_out] uniform draws (NeuS.py:335) or null: no perturbation */; const float* z /* [R][M], ascending */;
-  float* z_feed;        // [R][M + n_out] ascending
-  int* src;             // [R][M + n_out]: j >= 0: z[j];  -1 - k: background sample k
-};
-struct OutsideZBwd {    // d far (z_out[k] = far / zz[n_out - 1 - k] + 1 / n_samples) and, for the copies of z in z_feed, d z
-  long R; int M, n_out, n_samples; const float* t_rand; const int* src; const float* d_z_feed;
-  float* d_far;         // [R]
-  float* d_z;           // [R][M] or null
-};
-struct BgEmbed {        // render_core_outside's inputs (NeuS.py:102-115): section length, mid point, [p / r, 1 / r], PE-multires of it, PE-multires_view of the direction
-  const float* o; const float* d; const float* z_feed; long R; int MF; float sample_dist; int multires, multires_view;
-  float* E; int lde;               // [n][lde]: PE row (4 + 8 multires live columns, zero padded)
-  float* XH; int ldxh, xh_off;     // optional second copy of the PE row: XH[pt][xh_off + c] (the skip layer's input tail, zero padded up to ldxh)
-  float* FV; int ldfv, fv_off;     // PE of the view direction: FV[pt][fv_off + c] (the view layer's input tail, zero padded up to ldfv)
-  float* dist;                     // [n] section lengths
-};
-struct BgAlpha {        // alpha = 1 - exp(-softplus(density) dist) (NeuS.py:119-120)
-  long n; const float* density; const float* dist; float* alpha;
-};
-struct BgHeadsBwd {     // cotangents of the two heads' pre-activations: d density (through alpha) and d rgb_pre (through the sigmoid), d dist
-  long n; const float* density; const float* dist; const float* rgb /* [n][3] post-sigmoid */; const float* d_alpha; const float* d_rgb /* [n][3] */;
-  float* d_density /* [n][ldd], column 0 live, the rest zero */; int ldd; float* d_rgb_pre /* [n][ldr], 3 live */; int ldr; float* d_dist /* [n] */;
-};
-struct BgJoin {         // dZ[pt][c] = H[pt][c] > 0 ? T[pt][c] + d_density[pt] * w_alpha[c] : 0: the last hidden layer feeds the feature layer AND the density head
-  long n; int W; const float* T; const float* H; const float* d_density; int ldd; const float* w_alpha; float* dZ;
-};
-struct BgEmbedBwd {     // per point: cotangent of the sample point p and of the view direction from the PE cotangents
-  const float* o; const float* d; const float* z_feed; long R; int MF; float sample_dist; int multires, multires_view;
-  const float* dE0; int lde0; const float* dE1; int lde1 /* second PE cotangent (skip layer) or null */; const float* dVE; int ldve;
-  float* dp;            // [n][8]: {dp.x, dp.y, dp.z, dview.x, dview.y, dview.z, 0, 0}
-};
-struct BgRaysBwd {      // per ray: d rays_o, d rays_d, d z_feed from the per-point cotangents
-  const float* d; const float* z_feed; long R; int MF; float sample_dist; const float* dp; const float* d_dist;
-  float* d_o; float* d_d; float* d_z_feed;   // [R][3], [R][3], [R][MF] (d_z_feed is ADDED to: the compositor's depth term lands there first)
-};
-struct CompositeBg {    // render_core with a background (NeuS.py:236-292, Color_NeuS.py:66-138): S-density alpha, inside / outside mixing, compositing over M + n_out samples
-  const float* o; const float* d; const float* z; const float* z_feed; long R; int M, MF; float sample_dist;
-  const float* sdf; const float* g /* [R][M][3] */; const float* color /* [R][M][3] */; const float* gcolor /* [R][M][3] or null */;
-  const float* bg_alpha /* [R][MF] */; const float* bg_color /* [R][MF][3] */;
-  const float* variance; float cos_anneal; const float* background_rgb;
-  float* color_fine; float* s_val; float* cdf_fine; float* weight_sum; float* weight_max; float* weights /* [R][MF] */; float* inside_sphere;
-  float* depth; float* global_color; float* eik_partial /* [R][2] */;
-};
-struct CompositeBgBwd {
-  CompositeBg f;        // the forward arguments (outputs unused except weights)
-  const float* d_color_fine; const float* d_s_val; const float* d_cdf; const float* d_weight_sum; const float* d_weight_max; const float* d_weights;
-  const float* d_gradient_error; const float* d_depth; const float* d_global_color; const float* d_gradients /* [R][M][3] or null */;
-  const float* eik_sums;   // [2] of the forward pass
-  float* d_sdf; float* d_g; float* d_color; float* d_gcolor; float* d_bg_alpha; float* d_bg_color;
-  float* d_inv_s_partial /* [R] */; float* d_rays_d /* [R][3] */; float* d_z /* [R][M] */; float* d_z_feed /* [R][MF] */;
-};
-void be_outside_z(const OutsideZ& p, cnr_stream s);
-void be_outside_z_bwd(const OutsideZBwd& p, cnr_stream s);
-void be_bg_embed(const BgEmbed& p, cnr_stream s);
-void be_bg_alpha(const BgAlpha& p, cnr_stream s);
-void be_bg_heads_bwd(const BgHeadsBwd& p, cnr_stream s);
-void be_bg_join(const BgJoin& p, cnr_stream s);
-void be_bg_embed_bwd(const BgEmbedBwd& p, cnr_stream s);
-void be_bg_rays_bwd(const BgRaysBwd& p, cnr_stream s);
-void be_composite_bg(const CompositeBg& p, cnr_stream s);
-void be_composite_bg_bwd(const CompositeBgBwd& p, cnr_stream s);
 
 // p[row][c] = 0 for c in [c0, c1), row < rows: zero the pad columns a GEMM reads without touching the rest of a wide buffer
 void be_zero_cols(float* p, int ld, int c0, int c1, long rows, cnr_stream s);

@@ -1,6 +1,7 @@
 // The plain linear op and the NeRF++ background network built from the same layer launches, with the sampling and compositing of the
 // samples outside the unit sphere (cnr_outside_z*, cnr_composite_background_*).  Nothing here uses the render model or its contexts.
 #include "cnr_plan.h"
+#include "cnr_bg.h"
 
 namespace cnr {
 

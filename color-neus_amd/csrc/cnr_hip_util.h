@@ -132,6 +132,24 @@ __device__ __forceinline__ int cnr_ror8_min(int x) {   // min with the lane 8 fu
     }                                                             \
   } while (0)
 
+// The one point-wise launch: a row X(name, parameter struct, body, element count) of a point-wise table (CNR_POINTWISE_KERNELS in cnr_bodies.h,
+// CNR_RAYS_KERNELS, CNR_CAMERA_KERNELS, CNR_BG_KERNELS in their family headers) becomes the grid-stride kernel over the body and be_<name>, which
+// launches it on the row's element count.  Expanded inside namespace cnr by the unit that holds the table's kernels.
+#define CNR_PW_KERNEL(NAME, PARAM, BODY, COUNT)                                              \
+  __global__ __launch_bounds__(256) void NAME##_kernel(const PARAM p, long n) {              \
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)   \
+      BODY(p, i);                                                                            \
+  }                                                                                          \
+  void be_##NAME(const PARAM& p, cnr_stream s) {                                             \
+    const long n = (COUNT);                                                                  \
+    if (n <= 0) return;                                                                      \
+    long blocks = (n + 255) / 256;                                                           \
+    if (blocks > 8192) blocks = 8192;                                                        \
+    TimingScope ts_(#NAME, 2, 0, n, 0, 0, 0, s);                                             \
+    hipLaunchKernelGGL(NAME##_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, n);        \
+    CNR_LAUNCH_CHECK(#NAME);                                                                 \
+  }
+
 namespace cnr {
 // Batched row jobs: ONE launch works through the rows of up to CAP small jobs (a model's layers: each on its own is a latency-bound launch of a few
 // microseconds).  Workgroup b works on row b - start[i] of job i, the job whose row range [start[i], start[i + 1]) holds b; the batch travels as the

@@ -1,8 +1,8 @@
 // Image evaluation for gfx950 (cnr_image_metrics / cnr_image_panel): squared error and window-3 SSIM sums of two images, and the
-// gt | render | depth picture of validate_image as bytes.  The per-pixel arithmetic is the img_* functions of cnr_backend.h, shared with
+// gt | render | depth picture of validate_image as bytes.  The per-pixel arithmetic is the img_* functions of cnr_image.h, shared with
 // the CPU emulation; the kernels only decide who computes what.
 //
-//   image_stats_kernel         one block = one tile of kImgTileH rows x kImgTileW floats of one plane (cnr_backend.h: both layouts are
+//   image_stats_kernel         one block = one tile of kImgTileH rows x kImgTileW floats of one plane (cnr_image.h: both layouts are
 //                              planes of rows whose horizontal neighbours are cs floats apart, so a channels-last tile is a contiguous
 //                              piece of every row with all channels in it).  The tile of both images and a halo of one row / cs floats
 //                              (reflected at the image border) goes to LDS with row-contiguous loads, once; the row pass of the five
@@ -16,7 +16,7 @@
 
 #include <cstdint>
 
-#include "cnr_backend.h"
+#include "cnr_image.h"
 #include "cnr_hip_util.h"
 
 namespace cnr {

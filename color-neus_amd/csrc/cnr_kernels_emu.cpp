@@ -9,59 +9,29 @@
 #include <vector>
 
 #include "cnr_backend.h"
-#include "cnr_mc.h"
-#include "cnr_loss.h"
 #include "cnr_bodies.h"
+#include "cnr_loss.h"
+#include "cnr_optim.h"
+#include "cnr_rays.h"
+#include "cnr_cameras.h"
+#include "cnr_bg.h"
+#include "cnr_mc.h"
+#include "cnr_nn.h"
+#include "cnr_image.h"
+#include "cnr_pixels.h"
+#include "cnr_raster.h"
+#include "cnr_meshcc.h"
 
 namespace cnr {
 
+// ---- cnr_runtime.hip
 const char* be_name() { return "cpu-emu"; }
-void be_split_planes_many(const SplitJob*, int, cnr_stream) {}
 void be_timing_enable(int) {}
 int be_timing_collect(KernelTiming*, int) { return 0; }
 int be_check_last_error(char*, size_t) { return 0; }
 void be_range_push(const char*) {}
 void be_range_pop() {}
 void be_memset_zero(void* p, size_t bytes, cnr_stream) { memset(p, 0, bytes); }
-void be_loss_sums(const LossArgs& a, float* partial, float* sums, cnr_stream) {
-  (void)partial;
-  double s_rgb = 0, s_bce = 0, s_rel = 0;   // (the emulation only has to agree with the oracle to test tolerance, not bitwise with the GPU)
-  for (long i = 0; i < a.R * 3; ++i) s_rgb += loss_rgb_term(a.color[i], a.gt[i], a.rgb_l1);
-  if (a.mask) for (long r = 0; r < a.R; ++r) s_bce += loss_bce_term(a.wsum[r], a.mask[r]);
-  if (a.drel) {
-    const long per_ray = a.drel_per_ray ? 1 : (long)a.M * 3;
-    for (long i = 0; i < a.R * per_ray; ++i) s_rel += a.drel[i] * ((a.include_mask && a.mask) ? a.mask[i / per_ray] : 1.0f);
-  }
-  sums[0] = (float)s_rgb; sums[1] = (float)s_bce; sums[2] = (float)s_rel; sums[3] = 0.f;
-}
-void be_loss_combine(const LossScalars& c, const float* sums, const float* gerr, float* out6, cnr_stream) { loss_combine(c, sums, gerr, out6); }
-void be_loss_forward(const LossArgs& a, float* partial, unsigned* ticket, const LossScalars& c, const float* gerr, float* sums, float* out6, cnr_stream s) {
-  (void)ticket;
-  be_loss_sums(a, partial, sums, s);
-  loss_combine(c, sums, gerr, out6);
-}
-void be_loss_shard_stats(const LossArgs& a, float* partial, unsigned* ticket, const float* eik_sums, float* stats8, cnr_stream s) {
-  (void)ticket;
-  float sums[4];
-  be_loss_sums(a, partial, sums, s);
-  stats8[0] = sums[0]; stats8[1] = sums[1]; stats8[2] = sums[2]; stats8[3] = eik_sums[0]; stats8[4] = eik_sums[1]; stats8[5] = eik_sums[1]; stats8[6] = stats8[7] = 0.0f;
-}
-void be_loss_shard_combine(const LossScalars& c, const float* stats8, float* out8, cnr_stream) { loss_shard_combine(c, stats8, out8); }
-void be_loss_backward(const LossArgs& a, const LossScalars& c, const float* g_loss, const float* mean_rel, const float* eik_factor, float* coef4, float* d_color,
-                      float* d_wsum, float* d_drel_ray, cnr_stream s) {
-  loss_coef(c, g_loss, c.use_relight ? mean_rel : g_loss, eik_factor, coef4);
-  be_loss_grads(a, coef4, d_color, d_wsum, nullptr, s);
-  if (d_drel_ray) for (long r = 0; r < a.R; ++r) d_drel_ray[r] = (a.include_mask && a.mask) ? coef4[2] * a.mask[r] : coef4[2];
-}
-void be_loss_coef(const LossScalars& c, const float* g_loss, const float* mean_rel, float* coef4, cnr_stream) { loss_coef(c, g_loss, mean_rel, nullptr, coef4); }
-void be_loss_grads(const LossArgs& a, const float* coef, float* d_color, float* d_wsum, float* d_drel, cnr_stream) {
-  for (long i = 0; i < a.R * 3; ++i) d_color[i] = coef[0] * loss_rgb_grad(a.color[i], a.gt[i], a.rgb_l1);
-  if (d_wsum) for (long r = 0; r < a.R; ++r) d_wsum[r] = a.mask ? coef[1] * loss_bce_grad(a.wsum[r], a.mask[r]) : 0.0f;
-  if (d_drel) {
-    const long per_ray = (long)a.M * 3;
-    for (long i = 0; i < a.R * per_ray; ++i) d_drel[i] = coef[2] * ((a.include_mask && a.mask) ? a.mask[i / per_ray] : 1.0f);
-  }
-}
 void be_zero_cols(float* p, int ld, int c0, int c1, long rows, cnr_stream) {
   for (long r = 0; r < rows; ++r) for (int c = c0; c < c1; ++c) p[r * ld + c] = 0.0f;
 }
@@ -69,6 +39,7 @@ void be_copy_cols(float* dst, int ld_dst, const float* src, int ld_src, int ncol
   for (long r = 0; r < rows; ++r) memcpy(dst + r * ld_dst, src + r * ld_src, (size_t)ncols * sizeof(float));
 }
 
+// ---- the layer launches (cnr_gemm*.hip) and what only the HIP build has (cnr_chain*.hip, cnr_sweep0.hip, cnr_narrow_bwd.hip)
 void be_layer_gemm(const LayerGemm& g0, cnr_stream) {
   LayerGemm g = g0;
   if (g.P_dev) g.P = *g.P_dev;
@@ -126,6 +97,46 @@ void be_dw_gemm(const DwGemm& g, cnr_stream) {
   }
 }
 
+bool be_fdw_enabled() { return !debug_flags().no_fdw; }
+bool be_fdw_xrow() { return be_fdw_enabled(); }
+void be_layer_dw_gemm(const LayerGemm& g, const DwGemm& d, const DwFuse& f, cnr_stream s) {
+  // xrow_mode 2: the plain weight-gradient GEMM below forms the extra row itself (d.N covers it) but zero-fills the slots first: keep what
+  // the mode-1 launch left there and add it back
+  std::vector<float> keep;
+  if (f.xrow_mode == 2) {
+    keep.resize((size_t)f.nslots * 256);
+    for (int c = 0; c < f.nslots; ++c) memcpy(&keep[(size_t)c * 256], f.xrow + (long)c * f.xrow_stride, 256 * sizeof(float));
+  }
+  be_dw_gemm(d, s);      // (first: EK_VBACK updates o1 in place, but neither dW operand is an output of this launch, so the order is free)
+  be_layer_gemm(g, s);
+  if (f.xrow_mode == 2)
+    for (int c = 0; c < f.nslots; ++c)
+      for (int k = 0; k < 256; ++k) f.xrow[(long)c * f.xrow_stride + k] += keep[(size_t)c * 256 + k];
+  if (f.xrow_mode == 1)   // column sums of the o2 output over the point slices of d
+    for (int c = 0; c < f.nslots; ++c) {
+      const long p0 = c * d.chunk_pts, p1 = std::min(d.P, p0 + d.chunk_pts);
+      for (int k = 0; k < 256; ++k) {
+        float sum = 0.0f;
+        for (long pt = p0; pt < p1; ++pt) sum += g.E.o2[pt * g.E.ld2 + k];
+        f.xrow[(long)c * f.xrow_stride + k] = sum * f.xrow_scale;
+      }
+    }
+}
+
+// the CPU emulation has no chain-fused kernels: the host orchestration falls back to the per-layer sequence
+void be_pack_frags_many(const PackJob*, int, cnr_stream) {}
+bool be_sdf_value_chain(const SdfValueChain&, cnr_stream) { return false; }
+bool be_relu_chain_fwd(const ReluChainFwd&, cnr_stream) { return false; }
+bool be_relu_chain_fwd_enabled() { return false; }
+bool be_sdf_save_chain(const SdfSaveChain&, cnr_stream) { return false; }
+bool be_sweep0_ok(const LayerGemm&) { return false; }   // (nor the sweep launch that forms its layer's weight-gradient pair)
+int be_sweep0_slots(long) { return 0; }
+void be_sweep0_dw(const LayerGemm&, float*, int, cnr_stream) {}
+bool be_narrow_bwd_ok(const NarrowBwd&) { return false; }   // (nor the one-pass backward of a narrow-input layer)
+int be_narrow_bwd_slots(long) { return 0; }
+void be_narrow_bwd(const NarrowBwd&, cnr_stream) {}
+
+// ---- cnr_kernels.hip
 #define CNR_PW(NAME, PARAM, BODY, COUNT)                \
   void be_##NAME(const PARAM& p, cnr_stream) {          \
     const long n_ = (COUNT);                            \
@@ -173,16 +184,6 @@ void be_head_fwd(const HeadFwd& p, cnr_stream) {
       epi_apply(p.E, row, j, acc);
     }
 }
-void be_sampler_step(const SamplerStep& p, cnr_stream s) {   // the three steps one after the other (the fused launch is a speed matter)
-  if (p.do_merge) be_merge(p.g, s);
-  be_upsample(p.u, s);
-  if (p.do_embed) {
-    EmbedZ e;
-    e.o = p.u.o; e.d = p.u.d; e.R = p.u.R; e.m = p.u.m; e.z = p.u.new_z; e.ldz = p.u.m; e.make_z = 0;
-    e.near_ = nullptr; e.far_ = nullptr; e.t_rand = nullptr; e.scale = p.scale; e.multires = p.multires; e.E = p.E;
-    be_embed_z(e, s);
-  }
-}
 void be_strip_bwd(const StripBwd& p, cnr_stream) {
   const long per = round_up((int)((p.P + p.nslots - 1) / p.nslots), 64);
 #pragma omp parallel for
@@ -204,31 +205,7 @@ void be_strip_bwd(const StripBwd& p, cnr_stream) {
       }
   }
 }
-bool be_fdw_enabled() { return !debug_flags().no_fdw; }
-bool be_fdw_xrow() { return be_fdw_enabled(); }
-void be_layer_dw_gemm(const LayerGemm& g, const DwGemm& d, const DwFuse& f, cnr_stream s) {
-  // xrow_mode 2: the plain weight-gradient GEMM below forms the extra row itself (d.N covers it) but zero-fills the slots first: keep what
-  // the mode-1 launch left there and add it back
-  std::vector<float> keep;
-  if (f.xrow_mode == 2) {
-    keep.resize((size_t)f.nslots * 256);
-    for (int c = 0; c < f.nslots; ++c) memcpy(&keep[(size_t)c * 256], f.xrow + (long)c * f.xrow_stride, 256 * sizeof(float));
-  }
-  be_dw_gemm(d, s);      // (first: EK_VBACK updates o1 in place, but neither dW operand is an output of this launch, so the order is free)
-  be_layer_gemm(g, s);
-  if (f.xrow_mode == 2)
-    for (int c = 0; c < f.nslots; ++c)
-      for (int k = 0; k < 256; ++k) f.xrow[(long)c * f.xrow_stride + k] += keep[(size_t)c * 256 + k];
-  if (f.xrow_mode == 1)   // column sums of the o2 output over the point slices of d
-    for (int c = 0; c < f.nslots; ++c) {
-      const long p0 = c * d.chunk_pts, p1 = std::min(d.P, p0 + d.chunk_pts);
-      for (int k = 0; k < 256; ++k) {
-        float sum = 0.0f;
-        for (long pt = p0; pt < p1; ++pt) sum += g.E.o2[pt * g.E.ld2 + k];
-        f.xrow[(long)c * f.xrow_stride + k] = sum * f.xrow_scale;
-      }
-    }
-}
+void be_split_planes_many(const SplitJob*, int, cnr_stream) {}
 
 static void prep_weight(const PrepWeight& p) {
   for (int n = 0; n < p.npad; ++n) {
@@ -300,278 +277,17 @@ void be_variance_finish(const VarianceFinish& p, cnr_stream) {
   *p.d_variance = inv_s_backward(p.variance[0], a);
 }
 
-void be_mc_count(const McVolume& m, cnr_stream) {
-  const int res = m.res;
-  const long n = (long)res * res * res;
-  int vo = 0, to = 0;
-  for (long v = 0; v < n; ++v) {
-    const int z = (int)(v % res), y = (int)((v / res) % res), x = (int)(v / ((long)res * res));
-    unsigned char fl;
-    const int idx = mc_cell(m.u, res, m.thr, x, y, z, &fl);
-    m.flags[v] = fl;
-    m.counts[v * 2] = vo; m.counts[v * 2 + 1] = to;
-    vo += mc_popcount3(fl);
-    to += idx >= 0 ? kMcNumTris[idx] : 0;
-  }
-  m.totals[0] = vo; m.totals[1] = to;
-}
-void be_mc_emit(const McVolume& m, const float* bmin, const float* bmax, float* verts, int* tris, cnr_stream) {
-  const long n = (long)m.res * m.res * m.res;
-  for (long v = 0; v < n; ++v) mc_emit_voxel(m, v, bmin, bmax, verts, tris);
-}
-
-// twin of nn_search_kernel / nn_unpack_kernel: the same nn_dist2 / nn_update / nn_key on the whole target range, one query per iteration
-void be_nn_search(const NnSearch& p, cnr_stream) {
-#pragma omp parallel for schedule(static)
-  for (long i = 0; i < p.n; ++i) {
-    const float qx = p.query[i * 3], qy = p.query[i * 3 + 1], qz = p.query[i * 3 + 2];
-    float best = INFINITY;
-    int besti = -1;
-    for (long j = 0; j < p.m; ++j)
-      nn_update(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
-    if (besti < 0)
-      for (long j = 0; j < p.m; ++j)
-        nn_update_inf(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
-    p.keys[i] = nn_key(best, besti);
-    nn_unpack(p.keys[i], &p.dist2[i], &p.idx[i]);
+// ---- cnr_perray.hip
+void be_sampler_step(const SamplerStep& p, cnr_stream s) {   // the three steps one after the other (the fused launch is a speed matter)
+  if (p.do_merge) be_merge(p.g, s);
+  be_upsample(p.u, s);
+  if (p.do_embed) {
+    EmbedZ e;
+    e.o = p.u.o; e.d = p.u.d; e.R = p.u.R; e.m = p.u.m; e.z = p.u.new_z; e.ldz = p.u.m; e.make_z = 0;
+    e.near_ = nullptr; e.far_ = nullptr; e.t_rand = nullptr; e.scale = p.scale; e.multires = p.multires; e.E = p.E;
+    be_embed_z(e, s);
   }
 }
-
-// twin of image_stats_kernel / image_stats_finish_kernel: the same img_* functions, one element per iteration, the row pass of the three
-// rows recomputed per element; float64 sums per image row, then the rows in index order (a fixed order, not the HIP build's: DESIGN 5)
-void be_image_stats(const ImageStats& p, cnr_stream) {
-  const int cs = p.cs;
-  const long rowlen = (long)p.W * cs, nrows = p.planes * p.H;
-  std::vector<double> part((size_t)nrows * 2);
-#pragma omp parallel for schedule(static)
-  for (long pr = 0; pr < nrows; ++pr) {
-    const long plane = pr / p.H;
-    const int r = (int)(pr - plane * p.H);
-    const float* px = p.x + plane * p.H * rowlen;
-    const float* py = p.y + plane * p.H * rowlen;
-    double sum_d = 0.0, sum_s = 0.0;
-    for (long g = 0; g < rowlen; ++g) {
-      const int pix = (int)(g / cs), ch = (int)(g - (long)pix * cs);
-      const long gl = (long)img_reflect(pix - 1, p.W) * cs + ch, gr = (long)img_reflect(pix + 1, p.W) * cs + ch;
-      float h[5][3];
-      for (int k = 0; k < 3; ++k) {
-        const long row = (long)img_reflect(r - 1 + k, p.H) * rowlen;
-        const float xl = px[row + gl], xc = px[row + g], xr = px[row + gr];
-        const float yl = py[row + gl], yc = py[row + g], yr = py[row + gr];
-        h[0][k] = img_tap3(xl, xc, xr);
-        h[1][k] = img_tap3(yl, yc, yr);
-        h[2][k] = img_tap3(xl * xl, xc * xc, xr * xr);
-        h[3][k] = img_tap3(yl * yl, yc * yc, yr * yr);
-        h[4][k] = img_tap3(xl * yl, xc * yc, xr * yr);
-      }
-      float m[5];
-      for (int q = 0; q < 5; ++q) m[q] = img_tap3(h[q][0], h[q][1], h[q][2]);
-      const float s = img_ssim(m[0], m[1], m[2], m[3], m[4]);
-      const long at = (long)r * rowlen + g;
-      if (p.map) p.map[plane * p.H * rowlen + at] = s;
-      sum_d += (double)img_sqerr(px[at], py[at]);
-      sum_s += (double)s;
-    }
-    part[2 * pr] = sum_d;
-    part[2 * pr + 1] = sum_s;
-  }
-  double a = 0.0, b = 0.0;
-  for (long pr = 0; pr < nrows; ++pr) { a += part[2 * pr]; b += part[2 * pr + 1]; }
-  p.sums[0] = a;
-  p.sums[1] = b;
-}
-
-// twin of depth_range_kernel / image_panel_kernel
-void be_image_panel(const ImagePanel& p, cnr_stream) {
-  p.keys[0] = p.keys[1] = 0xffffffffu;
-  for (long i = 0; i < (long)p.H * p.W; ++i) {
-    const float d = p.depth[i];
-    if (d == d) {
-      const unsigned k = img_depth_key(d);
-      p.keys[0] = std::min(p.keys[0], k);
-      p.keys[1] = std::min(p.keys[1], ~k);
-    }
-  }
-  float vmin, vmax;
-  img_depth_range(p.keys, &vmin, &vmax);
-  p.range[0] = vmin;
-  p.range[1] = vmax;
-  const int rowb = p.nsec * 3 * p.W;
-#pragma omp parallel for schedule(static)
-  for (int row = 0; row < p.H; ++row)
-    for (int col = 0; col < rowb; ++col) p.panel[(long)row * rowb + col] = img_panel_byte(p, row, col, vmin, vmax);
-}
-
-// twin of the four raster_*_kernel launches: the same raster_* functions; triangles one after the other (the minimum of the keys does not
-// depend on the order), each over its clipped box, the large ones through the list like the HIP build
-void be_mesh_raster(const MeshRaster& p, cnr_stream) {
-  const long hw = (long)p.H * p.W;
-  p.dropped[0] = 0; p.dropped[1] = 0; *p.n_large = 0;
-  for (long i = 0; i < hw; ++i) p.keys[i] = kRasterNoKey;
-  if (p.V > 0) {
-    const RasterCam cam = raster_cam(p);
-#pragma omp parallel for schedule(static)
-    for (long i = 0; i < p.V; ++i) p.pv[i] = raster_project(cam, p.vertices + i * 3, p.opengl, p.z_near);
-  }
-  auto draw = [&](const RasterTri& t, int f) {
-    for (int j = t.j0; j <= t.j1; ++j)
-      for (int i = t.i0; i <= t.i1; ++i) {
-        unsigned long long& k = p.keys[(long)j * p.W + i];
-        k = std::min(k, raster_pixel_key(t, f, i, j));
-      }
-  };
-  if (p.V > 0)
-    for (long f = 0; f < p.F; ++f) {
-      const RasterTri t = raster_setup(p.triangles + f * 3, p.V, p.pv, p.H, p.W);
-      if (t.status == 1) ++p.dropped[0];
-      if (t.status == 2) ++p.dropped[1];
-      if (t.status != 0) continue;
-      if (raster_is_small(t)) draw(t, (int)f);
-      else p.large[(*p.n_large)++] = (int)f;
-    }
-  for (int l = 0; l < *p.n_large; ++l) draw(raster_setup(p.triangles + (long)p.large[l] * 3, p.V, p.pv, p.H, p.W), p.large[l]);
-#pragma omp parallel for schedule(static)
-  for (int j = 0; j < p.H; ++j)
-    for (int i = 0; i < p.W; ++i) raster_resolve(p, i, j);
-}
-
-// twins of the meshcc_*_kernel launches: the same meshcc_* functions, one triangle / vertex after the other.  The union-find runs with the
-// plain accessor; hooking the larger root under the smaller gives the same roots as every order of the HIP build's hooks.
-void be_mesh_components(const MeshComponents& p, cnr_stream) {
-  for (int k = 0; k < 4; ++k) p.summary[k] = 0;
-  p.dropped[0] = 0;
-  for (long v = 0; v < p.V; ++v) { p.labels[v] = (int)v; p.face_count[v] = 0; p.vertex_count[v] = 0; }
-  for (long f = 0; f < p.F; ++f) {
-    const int* t = p.triangles + f * 3;
-    if (!meshcc_valid(t, p.V)) { ++p.dropped[0]; continue; }
-    meshcc_unite<MeshccPlain>(p.labels, t[0], t[1]);
-    meshcc_unite<MeshccPlain>(p.labels, t[0], t[2]);
-  }
-  for (long v = 0; v < p.V; ++v) {
-    const int root = meshcc_root(p.labels, (int)v);
-    p.labels[v] = root;
-    ++p.vertex_count[root];
-    if (root == (int)v) ++p.summary[0];
-  }
-  for (long f = 0; f < p.F; ++f) {
-    const int* t = p.triangles + f * 3;
-    if (meshcc_valid(t, p.V)) ++p.face_count[p.labels[t[0]]];
-  }
-  unsigned long long best = 0;
-  for (long v = 0; v < p.V; ++v)
-    if (p.labels[v] == (int)v && p.face_count[v] > 0) {
-      ++p.summary[1];
-      best = std::max(best, meshcc_key(p.face_count[v], (int)v));
-    }
-  meshcc_unkey(best, &p.summary[2], &p.summary[3]);
-}
-
-void be_mesh_select(const MeshSelect& p, cnr_stream) {
-  const int thr = meshcc_threshold(p.min_faces, p.min_ratio, p.summary[3]);
-  p.totals[0] = p.totals[1] = 0;
-  for (long v = 0; v < p.V; ++v) {
-    p.keep_vertex[v] = meshcc_keep_vertex(p, v, thr);
-    p.vertex_map[v] = p.keep_vertex[v] ? p.totals[0]++ : -1;
-  }
-  for (long f = 0; f < p.F; ++f) {
-    p.keep_face[f] = meshcc_keep_face(p, f, thr);
-    p.face_map[f] = p.keep_face[f] ? p.totals[1]++ : -1;
-  }
-}
-
-void be_mesh_compact(const MeshCompact& p, cnr_stream) {
-  for (long v = 0; v < p.V; ++v) meshcc_compact_vertex(p, v);
-  for (long f = 0; f < p.F; ++f) meshcc_compact_face(p, f);
-}
-
-void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
-  for (int cam = 0; cam < q.f.n_cams; ++cam) {
-    double acc[14] = {0};   // (the HIP kernel sums in float in a fixed tree order; the tests compare both with autograd)
-    for (long i = 0; i < q.f.n; ++i) {
-      int c; float out[14];
-      body_gen_rays_bwd1(q, i, &c, out);
-      if (c == cam) for (int k = 0; k < 14; ++k) acc[k] += out[k];
-    }
-    for (int k = 0; k < 12; ++k) q.d_c2w[cam * 16 + k] = (float)acc[k];
-    for (int k = 12; k < 16; ++k) q.d_c2w[cam * 16 + k] = 0.0f;
-    q.d_focal_partial[cam * 2] = (float)acc[12]; q.d_focal_partial[cam * 2 + 1] = (float)acc[13];
-  }
-  for (int j = 0; j < 2; ++j) {
-    float s = 0.0f;
-    for (int c = 0; c < q.f.n_cams; ++c) s += q.d_focal_partial[c * 2 + j];
-    q.d_focal[j] = s;
-  }
-}
-
-void be_pixel_table(const PixelTable& t, cnr_stream) {
-#pragma omp parallel for schedule(static)
-  for (int n = 0; n < t.n_images; ++n) {
-    const float* m = t.masks + (long)n * t.hw;
-    int* row = t.order + (long)n * t.hw;
-    int f = 0, g = 0;
-    for (long i = 0; i < t.hw; ++i) f += pix_class(m[i]) == 1;
-    for (long i = 0, a = 0; i < t.hw; ++i) {
-      const int c = pix_class(m[i]);
-      if (c == 1) row[a++] = (int)i;
-      else if (c == 2) row[f + g++] = (int)i;
-    }
-    t.fg_count[n] = f; t.bg_count[n] = g;
-  }
-}
-
-void be_choose_pixels(const PixelDraw& p, cnr_stream) {
-  const PixKey k = pix_key(p.state[0], p.state[1]);
-  std::vector<unsigned> pf(p.B), pb(p.B);
-  std::vector<int> cams(p.B);
-  unsigned F = 0, G = 0;
-  for (int b = 0; b < p.B; ++b) {
-    unsigned f, g;
-    cams[b] = pix_slot_image(p, k, b);
-    pix_slot_counts(p, cams[b], &f, &g);
-    pf[b] = F += f; pb[b] = G += g;
-    if (p.cams_out) p.cams_out[b] = cams[b];
-  }
-  const unsigned want = (unsigned)pix_want_fg(p), kfg = want < F ? want : F;
-  const unsigned long long m = (unsigned long long)p.n - kfg;
-  if (p.counts_out) { p.counts_out[0] = p.order ? (int)kfg : 0; p.counts_out[1] = p.order ? (int)(m < G ? m : G) : 0; }
-#pragma omp parallel for schedule(static)
-  for (long j = 0; j < p.n; ++j) {
-    if (p.order) pix_draw_masked(p, k, j, pf.data(), pb.data(), cams.data(), kfg);
-    else p.idx[j] = pix_draw_replace(p, k, j);
-    if (p.t_rand) p.t_rand[j] = pix_jitter(k, j);
-  }
-  p.state[1] = (long)((unsigned long long)p.state[1] + 1ull);
-}
-
-void be_clip_adam(const AdamArgs& a, cnr_stream) {
-  for (int k = 0; k < a.count; ++k) {
-    const AdamTensor& t = a.t[k];
-    float coef = 1.0f;
-    if (a.max_norm > 0.0f) {
-      float tot = 0.0f;   // per-chunk sums, then the chunks (the summation order differs from the HIP kernels': round-off level)
-      for (long c0 = 0; c0 < t.n; c0 += kAdamChunk) {
-        float ss = 0.0f;
-        for (long i = c0; i < t.n && i < c0 + kAdamChunk; ++i) ss += t.g[i] * t.g[i];
-        tot += ss;
-      }
-      coef = adam_clip_coef(tot, a.max_norm);
-    }
-    for (long i = 0; i < t.n; ++i) adam_update1(a, t.w + i, t.g[i] * coef, a.m + t.off + i, a.v + t.off + i);
-  }
-}
-
-// the CPU emulation has no chain-fused kernels: the host orchestration falls back to the per-layer sequence
-void be_pack_frags_many(const PackJob*, int, cnr_stream) {}
-bool be_sdf_value_chain(const SdfValueChain&, cnr_stream) { return false; }
-bool be_relu_chain_fwd(const ReluChainFwd&, cnr_stream) { return false; }
-bool be_relu_chain_fwd_enabled() { return false; }
-bool be_sdf_save_chain(const SdfSaveChain&, cnr_stream) { return false; }
-bool be_sweep0_ok(const LayerGemm&) { return false; }   // (nor the sweep launch that forms its layer's weight-gradient pair)
-int be_sweep0_slots(long) { return 0; }
-void be_sweep0_dw(const LayerGemm&, float*, int, cnr_stream) {}
-bool be_narrow_bwd_ok(const NarrowBwd&) { return false; }   // (nor the one-pass backward of a narrow-input layer)
-int be_narrow_bwd_slots(long) { return 0; }
-void be_narrow_bwd(const NarrowBwd&, cnr_stream) {}
 
 void be_upsample(const UpSample& p, cnr_stream) {
 #pragma omp parallel for
@@ -683,6 +399,42 @@ void be_composite_bwd(const CompositeBwd& p, cnr_stream) {
   }
 }
 
+void be_prune_count(const PruneCount& p, cnr_stream) {
+  for (long r = 0; r < p.R; ++r) {
+    int c = 0;
+    for (int j = 0; j < p.M; ++j) c += prune_keep(p.weights[r * p.M + j], p.eps) ? 1 : 0;
+    p.counts[r] = c;
+  }
+}
+void be_prune_scan(const PruneScan& p, cnr_stream) {
+  int run = 0;
+  for (long r = 0; r < p.R; ++r) { p.offsets[r] = run; run += p.counts[r]; }
+  p.offsets[p.R] = run;
+}
+void be_prune_gather(const PruneGather& p, cnr_stream) {
+  for (long r = 0; r < p.R; ++r) {
+    int k = p.offsets[r];
+    for (int j = 0; j < p.M; ++j) {
+      long pt = r * p.M + j;
+      if (!prune_keep(p.weights[pt], p.eps)) { prune_zero_dropped(p, pt); continue; }
+      p.idx[k] = (int)pt;
+      if (p.featx_c) {
+        memcpy(p.featx_c + (long)k * p.ldfx, p.featx + pt * p.ldfx, sizeof(float) * p.ldfx);
+        memcpy(p.aux_c + (long)k * kAux, p.aux + pt * kAux, sizeof(float) * kAux);
+      }
+      ++k;
+    }
+  }
+}
+void be_prune_scatter(const PruneScatter& p, cnr_stream) {
+  for (long i = 0; i < *p.count; ++i) {
+    long pt = p.idx[i];
+    for (int c = 0; c < 4; ++c) p.gcol[pt * 4 + c] = p.gcol_c[i * 4 + c];
+    if (p.relit) for (int c = 0; c < 4; ++c) p.relit[pt * 4 + c] = p.relit_c[i * 4 + c];
+    if (p.delta) for (int c = 0; c < 3; ++c) p.delta[pt * 3 + c] = p.delta_c[i * 3 + c];
+  }
+}
+
 void be_rays_grad_finish(const RaysGradFinish& p, cnr_stream) {
   const int npe = p.multires_view > 0 ? 3 + 6 * p.multires_view : 3;
   for (long ray = 0; ray < p.R; ++ray) {
@@ -723,42 +475,317 @@ void be_rays_grad_finish(const RaysGradFinish& p, cnr_stream) {
   }
 }
 
-}  // namespace cnr
-
-namespace cnr {
-void be_prune_count(const PruneCount& p, cnr_stream) {
-  for (long r = 0; r < p.R; ++r) {
-    int c = 0;
-    for (int j = 0; j < p.M; ++j) c += prune_keep(p.weights[r * p.M + j], p.eps) ? 1 : 0;
-    p.counts[r] = c;
+// ---- cnr_loss.hip
+void be_loss_sums(const LossArgs& a, float* partial, float* sums, cnr_stream) {
+  (void)partial;
+  double s_rgb = 0, s_bce = 0, s_rel = 0;   // (the emulation only has to agree with the oracle to test tolerance, not bitwise with the GPU)
+  for (long i = 0; i < a.R * 3; ++i) s_rgb += loss_rgb_term(a.color[i], a.gt[i], a.rgb_l1);
+  if (a.mask) for (long r = 0; r < a.R; ++r) s_bce += loss_bce_term(a.wsum[r], a.mask[r]);
+  if (a.drel) {
+    const long per_ray = a.drel_per_ray ? 1 : (long)a.M * 3;
+    for (long i = 0; i < a.R * per_ray; ++i) s_rel += a.drel[i] * ((a.include_mask && a.mask) ? a.mask[i / per_ray] : 1.0f);
+  }
+  sums[0] = (float)s_rgb; sums[1] = (float)s_bce; sums[2] = (float)s_rel; sums[3] = 0.f;
+}
+void be_loss_combine(const LossScalars& c, const float* sums, const float* gerr, float* out6, cnr_stream) { loss_combine(c, sums, gerr, out6); }
+void be_loss_forward(const LossArgs& a, float* partial, unsigned* ticket, const LossScalars& c, const float* gerr, float* sums, float* out6, cnr_stream s) {
+  (void)ticket;
+  be_loss_sums(a, partial, sums, s);
+  loss_combine(c, sums, gerr, out6);
+}
+void be_loss_shard_stats(const LossArgs& a, float* partial, unsigned* ticket, const float* eik_sums, float* stats8, cnr_stream s) {
+  (void)ticket;
+  float sums[4];
+  be_loss_sums(a, partial, sums, s);
+  stats8[0] = sums[0]; stats8[1] = sums[1]; stats8[2] = sums[2]; stats8[3] = eik_sums[0]; stats8[4] = eik_sums[1]; stats8[5] = eik_sums[1]; stats8[6] = stats8[7] = 0.0f;
+}
+void be_loss_shard_combine(const LossScalars& c, const float* stats8, float* out8, cnr_stream) { loss_shard_combine(c, stats8, out8); }
+void be_loss_backward(const LossArgs& a, const LossScalars& c, const float* g_loss, const float* mean_rel, const float* eik_factor, float* coef4, float* d_color,
+                      float* d_wsum, float* d_drel_ray, cnr_stream s) {
+  loss_coef(c, g_loss, c.use_relight ? mean_rel : g_loss, eik_factor, coef4);
+  be_loss_grads(a, coef4, d_color, d_wsum, nullptr, s);
+  if (d_drel_ray) for (long r = 0; r < a.R; ++r) d_drel_ray[r] = (a.include_mask && a.mask) ? coef4[2] * a.mask[r] : coef4[2];
+}
+void be_loss_coef(const LossScalars& c, const float* g_loss, const float* mean_rel, float* coef4, cnr_stream) { loss_coef(c, g_loss, mean_rel, nullptr, coef4); }
+void be_loss_grads(const LossArgs& a, const float* coef, float* d_color, float* d_wsum, float* d_drel, cnr_stream) {
+  for (long i = 0; i < a.R * 3; ++i) d_color[i] = coef[0] * loss_rgb_grad(a.color[i], a.gt[i], a.rgb_l1);
+  if (d_wsum) for (long r = 0; r < a.R; ++r) d_wsum[r] = a.mask ? coef[1] * loss_bce_grad(a.wsum[r], a.mask[r]) : 0.0f;
+  if (d_drel) {
+    const long per_ray = (long)a.M * 3;
+    for (long i = 0; i < a.R * per_ray; ++i) d_drel[i] = coef[2] * ((a.include_mask && a.mask) ? a.mask[i / per_ray] : 1.0f);
   }
 }
-void be_prune_scan(const PruneScan& p, cnr_stream) {
-  int run = 0;
-  for (long r = 0; r < p.R; ++r) { p.offsets[r] = run; run += p.counts[r]; }
-  p.offsets[p.R] = run;
-}
-void be_prune_gather(const PruneGather& p, cnr_stream) {
-  for (long r = 0; r < p.R; ++r) {
-    int k = p.offsets[r];
-    for (int j = 0; j < p.M; ++j) {
-      long pt = r * p.M + j;
-      if (!prune_keep(p.weights[pt], p.eps)) { prune_zero_dropped(p, pt); continue; }
-      p.idx[k] = (int)pt;
-      if (p.featx_c) {
-        memcpy(p.featx_c + (long)k * p.ldfx, p.featx + pt * p.ldfx, sizeof(float) * p.ldfx);
-        memcpy(p.aux_c + (long)k * kAux, p.aux + pt * kAux, sizeof(float) * kAux);
+
+// ---- cnr_optim.hip
+void be_clip_adam(const AdamArgs& a, cnr_stream) {
+  for (int k = 0; k < a.count; ++k) {
+    const AdamTensor& t = a.t[k];
+    float coef = 1.0f;
+    if (a.max_norm > 0.0f) {
+      float tot = 0.0f;   // per-chunk sums, then the chunks (the summation order differs from the HIP kernels': round-off level)
+      for (long c0 = 0; c0 < t.n; c0 += kAdamChunk) {
+        float ss = 0.0f;
+        for (long i = c0; i < t.n && i < c0 + kAdamChunk; ++i) ss += t.g[i] * t.g[i];
+        tot += ss;
       }
-      ++k;
+      coef = adam_clip_coef(tot, a.max_norm);
+    }
+    for (long i = 0; i < t.n; ++i) adam_update1(a, t.w + i, t.g[i] * coef, a.m + t.off + i, a.v + t.off + i);
+  }
+}
+
+// ---- cnr_rays.hip, cnr_cameras.hip, cnr_bg.hip
+CNR_RAYS_KERNELS(CNR_PW)
+CNR_CAMERA_KERNELS(CNR_PW)
+CNR_BG_KERNELS(CNR_PW)
+
+void be_gen_rays_bwd(const GenRaysBwd& q, cnr_stream) {
+  for (int cam = 0; cam < q.f.n_cams; ++cam) {
+    double acc[14] = {0};   // (the HIP kernel sums in float in a fixed tree order; the tests compare both with autograd)
+    for (long i = 0; i < q.f.n; ++i) {
+      int c; float out[14];
+      body_gen_rays_bwd1(q, i, &c, out);
+      if (c == cam) for (int k = 0; k < 14; ++k) acc[k] += out[k];
+    }
+    for (int k = 0; k < 12; ++k) q.d_c2w[cam * 16 + k] = (float)acc[k];
+    for (int k = 12; k < 16; ++k) q.d_c2w[cam * 16 + k] = 0.0f;
+    q.d_focal_partial[cam * 2] = (float)acc[12]; q.d_focal_partial[cam * 2 + 1] = (float)acc[13];
+  }
+  for (int j = 0; j < 2; ++j) {
+    float s = 0.0f;
+    for (int c = 0; c < q.f.n_cams; ++c) s += q.d_focal_partial[c * 2 + j];
+    q.d_focal[j] = s;
+  }
+}
+
+// ---- cnr_mc.hip
+void be_mc_count(const McVolume& m, cnr_stream) {
+  const int res = m.res;
+  const long n = (long)res * res * res;
+  int vo = 0, to = 0;
+  for (long v = 0; v < n; ++v) {
+    const int z = (int)(v % res), y = (int)((v / res) % res), x = (int)(v / ((long)res * res));
+    unsigned char fl;
+    const int idx = mc_cell(m.u, res, m.thr, x, y, z, &fl);
+    m.flags[v] = fl;
+    m.counts[v * 2] = vo; m.counts[v * 2 + 1] = to;
+    vo += mc_popcount3(fl);
+    to += idx >= 0 ? kMcNumTris[idx] : 0;
+  }
+  m.totals[0] = vo; m.totals[1] = to;
+}
+void be_mc_emit(const McVolume& m, const float* bmin, const float* bmax, float* verts, int* tris, cnr_stream) {
+  const long n = (long)m.res * m.res * m.res;
+  for (long v = 0; v < n; ++v) mc_emit_voxel(m, v, bmin, bmax, verts, tris);
+}
+
+// ---- cnr_nn.hip
+// twin of nn_search_kernel / nn_unpack_kernel: the same nn_dist2 / nn_update / nn_key on the whole target range, one query per iteration
+void be_nn_search(const NnSearch& p, cnr_stream) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < p.n; ++i) {
+    const float qx = p.query[i * 3], qy = p.query[i * 3 + 1], qz = p.query[i * 3 + 2];
+    float best = INFINITY;
+    int besti = -1;
+    for (long j = 0; j < p.m; ++j)
+      nn_update(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
+    if (besti < 0)
+      for (long j = 0; j < p.m; ++j)
+        nn_update_inf(nn_dist2(qx, qy, qz, p.target[j * 3], p.target[j * 3 + 1], p.target[j * 3 + 2]), (int)j, best, besti);
+    p.keys[i] = nn_key(best, besti);
+    nn_unpack(p.keys[i], &p.dist2[i], &p.idx[i]);
+  }
+}
+
+// ---- cnr_image.hip
+// twin of image_stats_kernel / image_stats_finish_kernel: the same img_* functions, one element per iteration, the row pass of the three
+// rows recomputed per element; float64 sums per image row, then the rows in index order (a fixed order, not the HIP build's: DESIGN 5)
+void be_image_stats(const ImageStats& p, cnr_stream) {
+  const int cs = p.cs;
+  const long rowlen = (long)p.W * cs, nrows = p.planes * p.H;
+  std::vector<double> part((size_t)nrows * 2);
+#pragma omp parallel for schedule(static)
+  for (long pr = 0; pr < nrows; ++pr) {
+    const long plane = pr / p.H;
+    const int r = (int)(pr - plane * p.H);
+    const float* px = p.x + plane * p.H * rowlen;
+    const float* py = p.y + plane * p.H * rowlen;
+    double sum_d = 0.0, sum_s = 0.0;
+    for (long g = 0; g < rowlen; ++g) {
+      const int pix = (int)(g / cs), ch = (int)(g - (long)pix * cs);
+      const long gl = (long)img_reflect(pix - 1, p.W) * cs + ch, gr = (long)img_reflect(pix + 1, p.W) * cs + ch;
+      float h[5][3];
+      for (int k = 0; k < 3; ++k) {
+        const long row = (long)img_reflect(r - 1 + k, p.H) * rowlen;
+        const float xl = px[row + gl], xc = px[row + g], xr = px[row + gr];
+        const float yl = py[row + gl], yc = py[row + g], yr = py[row + gr];
+        h[0][k] = img_tap3(xl, xc, xr);
+        h[1][k] = img_tap3(yl, yc, yr);
+        h[2][k] = img_tap3(xl * xl, xc * xc, xr * xr);
+        h[3][k] = img_tap3(yl * yl, yc * yc, yr * yr);
+        h[4][k] = img_tap3(xl * yl, xc * yc, xr * yr);
+      }
+      float m[5];
+      for (int q = 0; q < 5; ++q) m[q] = img_tap3(h[q][0], h[q][1], h[q][2]);
+      const float s = img_ssim(m[0], m[1], m[2], m[3], m[4]);
+      const long at = (long)r * rowlen + g;
+      if (p.map) p.map[plane * p.H * rowlen + at] = s;
+      sum_d += (double)img_sqerr(px[at], py[at]);
+      sum_s += (double)s;
+    }
+    part[2 * pr] = sum_d;
+    part[2 * pr + 1] = sum_s;
+  }
+  double a = 0.0, b = 0.0;
+  for (long pr = 0; pr < nrows; ++pr) { a += part[2 * pr]; b += part[2 * pr + 1]; }
+  p.sums[0] = a;
+  p.sums[1] = b;
+}
+
+// twin of depth_range_kernel / image_panel_kernel
+void be_image_panel(const ImagePanel& p, cnr_stream) {
+  p.keys[0] = p.keys[1] = 0xffffffffu;
+  for (long i = 0; i < (long)p.H * p.W; ++i) {
+    const float d = p.depth[i];
+    if (d == d) {
+      const unsigned k = img_depth_key(d);
+      p.keys[0] = std::min(p.keys[0], k);
+      p.keys[1] = std::min(p.keys[1], ~k);
     }
   }
+  float vmin, vmax;
+  img_depth_range(p.keys, &vmin, &vmax);
+  p.range[0] = vmin;
+  p.range[1] = vmax;
+  const int rowb = p.nsec * 3 * p.W;
+#pragma omp parallel for schedule(static)
+  for (int row = 0; row < p.H; ++row)
+    for (int col = 0; col < rowb; ++col) p.panel[(long)row * rowb + col] = img_panel_byte(p, row, col, vmin, vmax);
 }
-void be_prune_scatter(const PruneScatter& p, cnr_stream) {
-  for (long i = 0; i < *p.count; ++i) {
-    long pt = p.idx[i];
-    for (int c = 0; c < 4; ++c) p.gcol[pt * 4 + c] = p.gcol_c[i * 4 + c];
-    if (p.relit) for (int c = 0; c < 4; ++c) p.relit[pt * 4 + c] = p.relit_c[i * 4 + c];
-    if (p.delta) for (int c = 0; c < 3; ++c) p.delta[pt * 3 + c] = p.delta_c[i * 3 + c];
+
+// ---- cnr_pixels.hip
+void be_pixel_table(const PixelTable& t, cnr_stream) {
+#pragma omp parallel for schedule(static)
+  for (int n = 0; n < t.n_images; ++n) {
+    const float* m = t.masks + (long)n * t.hw;
+    int* row = t.order + (long)n * t.hw;
+    int f = 0, g = 0;
+    for (long i = 0; i < t.hw; ++i) f += pix_class(m[i]) == 1;
+    for (long i = 0, a = 0; i < t.hw; ++i) {
+      const int c = pix_class(m[i]);
+      if (c == 1) row[a++] = (int)i;
+      else if (c == 2) row[f + g++] = (int)i;
+    }
+    t.fg_count[n] = f; t.bg_count[n] = g;
   }
 }
+
+void be_choose_pixels(const PixelDraw& p, cnr_stream) {
+  const PixKey k = pix_key(p.state[0], p.state[1]);
+  std::vector<unsigned> pf(p.B), pb(p.B);
+  std::vector<int> cams(p.B);
+  unsigned F = 0, G = 0;
+  for (int b = 0; b < p.B; ++b) {
+    unsigned f, g;
+    cams[b] = pix_slot_image(p, k, b);
+    pix_slot_counts(p, cams[b], &f, &g);
+    pf[b] = F += f; pb[b] = G += g;
+    if (p.cams_out) p.cams_out[b] = cams[b];
+  }
+  const unsigned want = (unsigned)pix_want_fg(p), kfg = want < F ? want : F;
+  const unsigned long long m = (unsigned long long)p.n - kfg;
+  if (p.counts_out) { p.counts_out[0] = p.order ? (int)kfg : 0; p.counts_out[1] = p.order ? (int)(m < G ? m : G) : 0; }
+#pragma omp parallel for schedule(static)
+  for (long j = 0; j < p.n; ++j) {
+    if (p.order) pix_draw_masked(p, k, j, pf.data(), pb.data(), cams.data(), kfg);
+    else p.idx[j] = pix_draw_replace(p, k, j);
+    if (p.t_rand) p.t_rand[j] = pix_jitter(k, j);
+  }
+  p.state[1] = (long)((unsigned long long)p.state[1] + 1ull);
+}
+
+// ---- cnr_raster.hip
+// twin of the four raster_*_kernel launches: the same raster_* functions; triangles one after the other (the minimum of the keys does not
+// depend on the order), each over its clipped box, the large ones through the list like the HIP build
+void be_mesh_raster(const MeshRaster& p, cnr_stream) {
+  const long hw = (long)p.H * p.W;
+  p.dropped[0] = 0; p.dropped[1] = 0; *p.n_large = 0;
+  for (long i = 0; i < hw; ++i) p.keys[i] = kRasterNoKey;
+  if (p.V > 0) {
+    const RasterCam cam = raster_cam(p);
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < p.V; ++i) p.pv[i] = raster_project(cam, p.vertices + i * 3, p.opengl, p.z_near);
+  }
+  auto draw = [&](const RasterTri& t, int f) {
+    for (int j = t.j0; j <= t.j1; ++j)
+      for (int i = t.i0; i <= t.i1; ++i) {
+        unsigned long long& k = p.keys[(long)j * p.W + i];
+        k = std::min(k, raster_pixel_key(t, f, i, j));
+      }
+  };
+  if (p.V > 0)
+    for (long f = 0; f < p.F; ++f) {
+      const RasterTri t = raster_setup(p.triangles + f * 3, p.V, p.pv, p.H, p.W);
+      if (t.status == 1) ++p.dropped[0];
+      if (t.status == 2) ++p.dropped[1];
+      if (t.status != 0) continue;
+      if (raster_is_small(t)) draw(t, (int)f);
+      else p.large[(*p.n_large)++] = (int)f;
+    }
+  for (int l = 0; l < *p.n_large; ++l) draw(raster_setup(p.triangles + (long)p.large[l] * 3, p.V, p.pv, p.H, p.W), p.large[l]);
+#pragma omp parallel for schedule(static)
+  for (int j = 0; j < p.H; ++j)
+    for (int i = 0; i < p.W; ++i) raster_resolve(p, i, j);
+}
+
+// ---- cnr_meshcc.hip
+// twins of the meshcc_*_kernel launches: the same meshcc_* functions, one triangle / vertex after the other.  The union-find runs with the
+// plain accessor; hooking the larger root under the smaller gives the same roots as every order of the HIP build's hooks.
+void be_mesh_components(const MeshComponents& p, cnr_stream) {
+  for (int k = 0; k < 4; ++k) p.summary[k] = 0;
+  p.dropped[0] = 0;
+  for (long v = 0; v < p.V; ++v) { p.labels[v] = (int)v; p.face_count[v] = 0; p.vertex_count[v] = 0; }
+  for (long f = 0; f < p.F; ++f) {
+    const int* t = p.triangles + f * 3;
+    if (!meshcc_valid(t, p.V)) { ++p.dropped[0]; continue; }
+    meshcc_unite<MeshccPlain>(p.labels, t[0], t[1]);
+    meshcc_unite<MeshccPlain>(p.labels, t[0], t[2]);
+  }
+  for (long v = 0; v < p.V; ++v) {
+    const int root = meshcc_root(p.labels, (int)v);
+    p.labels[v] = root;
+    ++p.vertex_count[root];
+    if (root == (int)v) ++p.summary[0];
+  }
+  for (long f = 0; f < p.F; ++f) {
+    const int* t = p.triangles + f * 3;
+    if (meshcc_valid(t, p.V)) ++p.face_count[p.labels[t[0]]];
+  }
+  unsigned long long best = 0;
+  for (long v = 0; v < p.V; ++v)
+    if (p.labels[v] == (int)v && p.face_count[v] > 0) {
+      ++p.summary[1];
+      best = std::max(best, meshcc_key(p.face_count[v], (int)v));
+    }
+  meshcc_unkey(best, &p.summary[2], &p.summary[3]);
+}
+
+void be_mesh_select(const MeshSelect& p, cnr_stream) {
+  const int thr = meshcc_threshold(p.min_faces, p.min_ratio, p.summary[3]);
+  p.totals[0] = p.totals[1] = 0;
+  for (long v = 0; v < p.V; ++v) {
+    p.keep_vertex[v] = meshcc_keep_vertex(p, v, thr);
+    p.vertex_map[v] = p.keep_vertex[v] ? p.totals[0]++ : -1;
+  }
+  for (long f = 0; f < p.F; ++f) {
+    p.keep_face[f] = meshcc_keep_face(p, f, thr);
+    p.face_map[f] = p.keep_face[f] ? p.totals[1]++ : -1;
+  }
+}
+
+void be_mesh_compact(const MeshCompact& p, cnr_stream) {
+  for (long v = 0; v < p.V; ++v) meshcc_compact_vertex(p, v);
+  for (long f = 0; f < p.F; ++f) meshcc_compact_face(p, f);
+}
+
 }  // namespace cnr

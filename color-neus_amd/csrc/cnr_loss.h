@@ -1,9 +1,35 @@
 // Per-element pieces of the training loss (NeuS_Trainer.compute_loss, NeuS_Trainer.py:129-171), shared by the HIP kernels and the CPU
 // emulation used in the tests.
 #pragma once
-#include "cnr_backend.h"
+#include "cnr_common.h"
 
 namespace cnr {
+
+// training loss (include/colorneus_render.h, cnr_loss_*): partial sums [nblk][4] -> sums[4]; gradients w.r.t. the renderer outputs
+struct LossArgs {
+  const float* color; const float* wsum; const float* drel; const float* gt; const float* mask;
+  long R; int M; int rgb_l1; int include_mask;
+  int drel_per_ray = 0;   // 1: drel is [R], the per-ray sums over samples and rgb (CompositeFwd::delta_ray_sum)
+};
+constexpr int kLossBlocks = 256;
+void be_loss_sums(const LossArgs& a, float* partial /* [kLossBlocks][4] */, float* sums /* [4] */, cnr_stream s);
+void be_loss_grads(const LossArgs& a, const float* coef, float* d_color, float* d_wsum, float* d_drel, cnr_stream s);
+struct LossScalars {   // see cnr_loss_combine / cnr_loss_coef in the ABI header; the constants are formed in double on the host and rounded once
+  float lf, le, lm, lr;                 // lambdas
+  float Rg, den_rgb, den_rel;           // n_rays_global, 3 Rg, 3 Rg M
+  float c_rgb, c_bce, c_rel;            // lambda_fine * (1 | 2) / (3 Rg), lambda_mask / Rg, lambda_relight * 2 / (3 Rg M)
+  int use_mask, use_relight;
+};
+void be_loss_combine(const LossScalars& c, const float* sums, const float* gerr, float* out6, cnr_stream s);
+void be_loss_coef(const LossScalars& c, const float* g_loss, const float* mean_rel, float* coef4, cnr_stream s);
+// the forward side (partial sums, their fold, the scalar tail) and the backward side (coefficients + element-wise gradients) as ONE launch each
+// (ticket: a zero-initialised 4-byte completion counter in the caller's scratch, left zero)
+void be_loss_forward(const LossArgs& a, float* partial, unsigned* ticket, const LossScalars& c, const float* gerr, float* sums, float* out6, cnr_stream s);
+void be_loss_backward(const LossArgs& a, const LossScalars& c, const float* g_loss, const float* mean_rel, const float* eik_factor /* or null */, float* coef4,
+                      float* d_color, float* d_wsum, float* d_drel_ray /* [R] or null */, cnr_stream s);
+// ray-sharded runs: this rank's statistics for the one all-reduce of the objective (one launch), and the scalar tail on the reduced statistics
+void be_loss_shard_stats(const LossArgs& a, float* partial, unsigned* ticket, const float* eik_sums /* [2] */, float* stats8, cnr_stream s);
+void be_loss_shard_combine(const LossScalars& c, const float* stats8, float* out8, cnr_stream s);
 
 CNR_HD float loss_rgb_term(float c, float gt, int l1) { const float e = c - gt; return l1 ? fabsf(e) : e * e; }
 CNR_HD float loss_rgb_grad(float c, float gt, int l1) { const float e = c - gt; return l1 ? (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) : e; }

@@ -20,7 +20,7 @@
 // with one add per lane.  What remains is the adds on the one address of the main component, about 0.1 us each.
 #include <hip/hip_runtime.h>
 
-#include "cnr_backend.h"
+#include "cnr_meshcc.h"
 #include "cnr_hip_util.h"
 #include "cnr_wave.h"
 

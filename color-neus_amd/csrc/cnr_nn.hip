@@ -3,13 +3,13 @@
 //   nn_search_kernel   256 threads, every lane keeps kNnQ queries in registers; the block's part of the target range goes tile by tile through LDS as
 //                      float4 and is read back by all lanes at the same address (a broadcast: one ds_read_b128 serves 64 lanes x kNnQ distance
 //                      evaluations).  The pair loop is VALU work only: 3 subtractions, 3 multiplications, 2 additions, 1 compare, 2 selects -- no FMA,
-//                      so that the distance is the separately rounded fp32 expression the CPU emulation evaluates (nn_dist2 in cnr_backend.h).
+//                      so that the distance is the separately rounded fp32 expression the CPU emulation evaluates (nn_dist2 in cnr_nn.h).
 //                      blockIdx.y splits the target range, so that few queries against many targets still fill the chip; every block folds its
 //                      best keys into keys[query] with a 64-bit unsigned integer atomic min (order-independent: DESIGN 5).
 //   nn_unpack_kernel   keys -> dist2 / idx
 #include <hip/hip_runtime.h>
 
-#include "cnr_backend.h"
+#include "cnr_nn.h"
 #include "cnr_hip_util.h"
 
 namespace cnr {

@@ -1,6 +1,16 @@
 // The stand-alone ops of the ABI: each checks its arguments, fills one descriptor and enqueues its kernels.  None uses the render model, a
 // context or the arena: this unit takes only fail / check_backend from cnr_plan.h.
 #include "cnr_plan.h"
+#include "cnr_loss.h"
+#include "cnr_optim.h"
+#include "cnr_rays.h"
+#include "cnr_pixels.h"
+#include "cnr_cameras.h"
+#include "cnr_mc.h"
+#include "cnr_nn.h"
+#include "cnr_image.h"
+#include "cnr_raster.h"
+#include "cnr_meshcc.h"
 
 using namespace cnr;
 

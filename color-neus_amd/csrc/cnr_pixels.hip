@@ -1,5 +1,5 @@
 // On-device pixel choice for gfx950 (cnr_pixel_table_build / cnr_choose_pixels; specified in include/colorneus_render.h).  The arithmetic --
-// Philox4x32-10, the keyed bijection, the classification of a mask value, one draw -- is the pix_* functions of cnr_bodies.h, shared with the
+// Philox4x32-10, the keyed bijection, the classification of a mask value, one draw -- is the pix_* functions of cnr_pixels.h, shared with the
 // CPU emulation; the kernels only decide who computes what.  Integer arithmetic only, plain C++, vector stores.
 //
 //   pixel_count_kernel    one block = one tile of kPixTile pixels of one image.  A wave reads a chunk of 256 pixels with one 16-byte load per
@@ -15,8 +15,7 @@
 
 #include <cstdint>
 
-#include "cnr_backend.h"
-#include "cnr_bodies.h"
+#include "cnr_pixels.h"
 #include "cnr_hip_util.h"
 #include "cnr_wave.h"
 

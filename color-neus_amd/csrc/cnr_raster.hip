@@ -11,7 +11,7 @@
 //   raster_resolve_kernel   one pixel per lane: decode the key, gather the winner's vertices and colours, write rgb / depth / tri_id
 #include <hip/hip_runtime.h>
 
-#include "cnr_backend.h"
+#include "cnr_raster.h"
 #include "cnr_hip_util.h"
 #include "cnr_wave.h"
 
