@@ -11,9 +11,10 @@ from .renderer import ColorNeuSRenderer, NeuSRenderer, RENDERER, build_renderer,
 from .loss import compute_loss, compute_loss_fused  # noqa: F401
 from . import parallel, rays, synthetic, optim, meshio, metrics, imaging, cameras, meshops  # noqa: F401
 from .meshio import write_ply, write_png  # noqa: F401
-from .metrics import nearest_neighbors, chamfer_distance, mesh_metrics, compute_chamfer_distance  # noqa: F401
+from .metrics import (nearest_neighbors, chamfer_distance, mesh_metrics, compute_chamfer_distance, point_mesh_distance, surface_metrics,  # noqa: F401
+                      compute_surface_metrics)  # noqa: F401
 from .imaging import image_metrics, psnr, ssim, mse2psnr, PSNR, SSIM, cmap, panel, validate_image, rasterize_mesh, mesh_view_metrics  # noqa: F401
-from .meshops import connected_components, clean_mesh  # noqa: F401
+from .meshops import connected_components, clean_mesh, sample_surface  # noqa: F401
 from .rays import PixelSampler  # noqa: F401
 from .cameras import FocalNet, PoseNet, Cameras, cameras_from_state_dict  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
@@ -21,5 +22,6 @@ from .optim import ClipAdam  # noqa: F401
 __all__ = ["RenderConfig", "config_from_node", "load_library", "library_path", "RenderLibrary", "ColorNeuSRenderer",
            "NeuSRenderer", "RENDERER", "build_renderer", "register_into", "compute_loss", "compute_loss_fused", "parallel", "rays", "synthetic", "sample_pdf", "optim", "ClipAdam", "meshio", "write_ply",
            "metrics", "nearest_neighbors", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance",
+           "point_mesh_distance", "surface_metrics", "compute_surface_metrics", "sample_surface",
            "imaging", "image_metrics", "psnr", "ssim", "mse2psnr", "PSNR", "SSIM", "cmap", "panel", "validate_image", "rasterize_mesh", "mesh_view_metrics", "write_png",
            "meshops", "connected_components", "clean_mesh", "PixelSampler", "cameras", "FocalNet", "PoseNet", "Cameras", "cameras_from_state_dict"]

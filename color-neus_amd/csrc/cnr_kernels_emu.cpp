@@ -21,6 +21,7 @@
 #include "cnr_pixels.h"
 #include "cnr_raster.h"
 #include "cnr_meshcc.h"
+#include "cnr_surface.h"
 
 namespace cnr {
 
@@ -786,6 +787,43 @@ void be_mesh_select(const MeshSelect& p, cnr_stream) {
 void be_mesh_compact(const MeshCompact& p, cnr_stream) {
   for (long v = 0; v < p.V; ++v) meshcc_compact_vertex(p, v);
   for (long f = 0; f < p.F; ++f) meshcc_compact_face(p, f);
+}
+
+// ---- cnr_surface.hip
+// twins of surf_area_kernel / surf_cdf_scan_kernel: the same surf_area_bits / surf_weight, the integer max and the prefix sums in face order
+void be_mesh_area_cdf(const MeshAreaCdf& p, cnr_stream) {
+  unsigned long long amax = 0ull, total = 0ull;
+  long long zero = 0, invalid = 0;
+  for (long f = 0; f < p.F; ++f) {
+    p.cdf[f] = surf_area_bits(p, f);
+    if (p.cdf[f] != kSurfInvalid) amax = std::max(amax, p.cdf[f]);
+  }
+  for (long f = 0; f < p.F; ++f) {
+    const unsigned long long bits = p.cdf[f], w = surf_weight(bits, (unsigned)amax);
+    total += w; zero += w == 0ull; invalid += bits == kSurfInvalid;
+    p.cdf[f] = total;
+  }
+  p.summary[0] = (long long)total; p.summary[1] = zero; p.summary[2] = invalid; p.summary[3] = (long long)amax;
+}
+void be_mesh_sample(const MeshSample& p, cnr_stream) {
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < p.n; ++i) surf_sample(p, i);
+}
+// twin of surf_dist_kernel / surf_finish_kernel: the records of all faces once, then the same surf_dist2 / nn_update / nn_key over the whole
+// face range in ascending order, one query per iteration
+void be_point_mesh_distance(const PointMeshDist& p, cnr_stream) {
+  std::vector<SurfTri> rec((size_t)p.F);
+#pragma omp parallel for schedule(static)
+  for (long f = 0; f < p.F; ++f) rec[(size_t)f] = surf_record(p.vertices, p.V, p.triangles + f * 3);
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < p.n; ++i) {
+    const float qx = p.query[i * 3], qy = p.query[i * 3 + 1], qz = p.query[i * 3 + 2];
+    float best = INFINITY;
+    int besti = -1;
+    for (long f = 0; f < p.F; ++f) nn_update(surf_dist2(rec[(size_t)f], qx, qy, qz), (int)f, best, besti);
+    p.keys[i] = nn_key(best, besti);
+    surf_finish(p, i);
+  }
 }
 
 }  // namespace cnr

@@ -11,6 +11,7 @@
 #include "cnr_image.h"
 #include "cnr_raster.h"
 #include "cnr_meshcc.h"
+#include "cnr_surface.h"
 
 using namespace cnr;
 
@@ -545,6 +546,58 @@ int cnr_mesh_compact(const float* vertices, const float* colors, const int32_t* 
   p.vertex_map = vertex_map; p.face_map = face_map; p.out_vertices = out_vertices; p.out_colors = out_colors; p.out_triangles = out_triangles;
   be_mesh_compact(p, (cnr_stream)stream);
   return check_backend("mesh_compact");
+}
+
+// the three surface entries share the mesh's size rule: at least one face, indices and face numbers are int32
+static int surface_sizes(const char* what, int64_t F, int64_t V) {
+  if (F <= 0) return fail("%s: the mesh has no faces (n_triangles = %lld)", what, (long long)F);
+  if (V < 0) return fail("%s: n_vertices must not be negative", what);
+  if (F >= (int64_t)1 << 31 || V >= (int64_t)1 << 31)
+    return fail("%s: n_triangles and n_vertices must be below 2^31 (indices and face numbers are int32; got %lld and %lld)", what, (long long)F, (long long)V);
+  return 0;
+}
+
+int cnr_mesh_area_cdf(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, uint64_t* cdf, int64_t* summary,
+                      void* stream) {
+  if (surface_sizes("mesh_area_cdf", n_triangles, n_vertices)) return -1;
+  if ((n_vertices > 0 && !vertices) || !triangles || !cdf || !summary) return fail("mesh_area_cdf: null argument");
+  if (reinterpret_cast<uintptr_t>(cdf) % 8 != 0 || reinterpret_cast<uintptr_t>(summary) % 8 != 0)
+    return fail("mesh_area_cdf: cdf and summary must be 8-byte aligned");
+  MeshAreaCdf p;
+  p.vertices = vertices; p.V = (long)n_vertices; p.triangles = triangles; p.F = (long)n_triangles;
+  p.cdf = reinterpret_cast<unsigned long long*>(cdf); p.summary = reinterpret_cast<long long*>(summary);
+  be_mesh_area_cdf(p, (cnr_stream)stream);
+  return check_backend("mesh_area_cdf");
+}
+
+int cnr_mesh_sample(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const uint64_t* cdf, int64_t n_samples,
+                    int64_t seed, float* points, int32_t* faces, float* bary, void* stream) {
+  if (n_samples < 0) return fail("mesh_sample: n_samples < 0");
+  if (surface_sizes("mesh_sample", n_triangles, n_vertices)) return -1;
+  if (n_samples == 0) return 0;
+  if ((n_vertices > 0 && !vertices) || !triangles || !cdf || !points || !faces) return fail("mesh_sample: null argument");
+  if (reinterpret_cast<uintptr_t>(cdf) % 8 != 0) return fail("mesh_sample: cdf must be 8-byte aligned");
+  MeshSample p;
+  p.vertices = vertices; p.V = (long)n_vertices; p.triangles = triangles; p.F = (long)n_triangles;
+  p.cdf = reinterpret_cast<const unsigned long long*>(cdf); p.n = (long)n_samples;
+  p.seed_lo = (unsigned)((uint64_t)seed & 0xffffffffull); p.seed_hi = (unsigned)((uint64_t)seed >> 32);
+  p.points = points; p.faces = faces; p.bary = bary;
+  be_mesh_sample(p, (cnr_stream)stream);
+  return check_backend("mesh_sample");
+}
+
+int cnr_point_mesh_distance(const float* query, int64_t n_query, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                            int64_t n_triangles, float* dist2, int32_t* face, float* closest, uint64_t* keys, void* stream) {
+  if (n_query < 0) return fail("point_mesh_distance: n_query < 0");
+  if (surface_sizes("point_mesh_distance", n_triangles, n_vertices)) return -1;
+  if (n_query == 0) return 0;
+  if (!query || (n_vertices > 0 && !vertices) || !triangles || !dist2 || !face || !keys) return fail("point_mesh_distance: null argument");
+  if (reinterpret_cast<uintptr_t>(keys) % 8 != 0) return fail("point_mesh_distance: keys must be 8-byte aligned");
+  PointMeshDist p;
+  p.query = query; p.n = (long)n_query; p.vertices = vertices; p.V = (long)n_vertices; p.triangles = triangles; p.F = (long)n_triangles;
+  p.dist2 = dist2; p.face = face; p.closest = closest; p.keys = reinterpret_cast<unsigned long long*>(keys);
+  be_point_mesh_distance(p, (cnr_stream)stream);
+  return check_backend("point_mesh_distance");
 }
 
 }  // extern "C"

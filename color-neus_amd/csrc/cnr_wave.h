@@ -68,7 +68,7 @@ __device__ __forceinline__ float wave_scan_incl_add_rev(float x, int lane) {
   return x;
 }
 
-// ---- integer scans (int or unsigned; exact whatever the order) -----------------------------------------------------------------------------
+// ---- integer scans (int or unsigned, or their 64-bit forms; exact whatever the order) -------------------------------------------------------
 // inclusive scan of CH channels along the wave, the channels' shuffles interleaved
 template <int CH, class T>
 __device__ __forceinline__ void wave_incl_scan_int(T (&x)[CH], int lane) {
@@ -76,7 +76,7 @@ __device__ __forceinline__ void wave_incl_scan_int(T (&x)[CH], int lane) {
   for (int d = 1; d < 64; d <<= 1) {
     T y[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) y[c] = (T)__shfl_up((int)x[c], d);
+    for (int c = 0; c < CH; ++c) y[c] = sizeof(T) == 8 ? (T)__shfl_up((long long)x[c], d) : (T)__shfl_up((int)x[c], d);
 #pragma unroll
     for (int c = 0; c < CH; ++c) if (lane >= d) x[c] += y[c];
   }

@@ -5,6 +5,7 @@ evaluation scripts remove them before scoring (``trimesh.split`` and "keep the l
 three entry points of the C ABI (include/colorneus_render.h, where the definitions are): ``cnr_mesh_components`` labels the components with a
 lock-free union-find, ``cnr_mesh_select`` marks what to keep and scans the marks into index maps, ``cnr_mesh_compact`` writes the kept
 vertices, colours and triangles in their original order.  Everything is integer work: the results are exact and the same bits on every run.
+``sample_surface`` draws points uniformly by area on a mesh (``cnr_mesh_area_cdf``, ``cnr_mesh_sample``): the input of the surface metrics.
 
 ``triangles`` may be a tensor or a numpy array of any integer dtype and any strides, ``vertices`` / ``colors`` of any float dtype; they are
 converted to contiguous int32 / float32 on the device of ``vertices`` (``connected_components``: of ``triangles``).  CUDA tensors go through
@@ -16,7 +17,7 @@ import torch
 from . import _lib
 from ._lib import ptr, stream_of
 
-__all__ = ["connected_components", "clean_mesh"]
+__all__ = ["connected_components", "clean_mesh", "sample_surface"]
 
 _MODES = {"largest": 0, "threshold": 1}
 
@@ -117,3 +118,58 @@ def clean_mesh(vertices, triangles, colors=None, keep="largest", min_faces=0, mi
             "n_vertices": nv, "n_faces": nf, "labels": labels, "face_count": face_count, "vertex_count": vertex_count,
             "keep_vertex": keep_vertex.bool(), "keep_face": keep_face.bool(), "vertex_map": vertex_map, "face_map": face_map}
     return out_v, out_t, out_c, info
+
+
+def _area_cdf(v, t, lib):
+    """v: contiguous float32 (V, 3), t: contiguous int32 (F, 3), F > 0 -> (cdf uint64-as-int64 [F], summary int64 [4]), device tensors."""
+    cdf = torch.empty(t.shape[0], dtype=torch.int64, device=v.device)       # (the library's uint64 prefix sums: below 2^63, so int64 reads them)
+    summary = torch.empty(4, dtype=torch.int64, device=v.device)
+    lib.call("cnr_mesh_area_cdf", ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(cdf), ptr(summary), stream_of(v.device))
+    return cdf, summary
+
+
+def _sample(v, t, cdf, n, seed, lib):
+    """n samples of the mesh (v, t) with the prefix sums cdf -> (points float32 [n, 3], faces int32 [n], bary float32 [n, 2])."""
+    dev = v.device
+    points = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(n, dtype=torch.int32, device=dev)
+    bary = torch.empty(n, 2, dtype=torch.float32, device=dev)
+    if n > 0:
+        lib.call("cnr_mesh_sample", ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(cdf), n, seed, ptr(points), ptr(faces), ptr(bary), stream_of(dev))
+    return points, faces, bary
+
+
+def sample_surface(vertices, triangles, n_samples, seed=0, colors=None, library=None):
+    """``n_samples`` points drawn uniformly by area on the mesh (``cnr_mesh_area_cdf`` + ``cnr_mesh_sample``): ``(points, faces, bary)``, device
+    tensors float32 [n, 3], int64 [n] (the face each point lies on) and float32 [n, 3] (the barycentric weights of the face's three corners, in
+    [0, 1], the first one ``1 - u - v``); with ``colors`` [V, 3] a fourth result, the colours interpolated with those weights (float32 [n, 3]).
+
+    The draw is counter based (Philox under ``seed``, a 64-bit integer): the same seed gives the same bits on every run and build, and the
+    first k samples of a longer draw are the k samples of a shorter one.  Faces are weighted by integer weights of 32 bits relative to the largest
+    face: a face below 2^-32 of the largest area, a face with an index outside ``[0, V)`` and one with a non-finite area are never drawn.  A
+    mesh on which nothing can be drawn (no faces, or no face of positive weight) raises ValueError; reading that total is the call's one host
+    synchronisation.  Not differentiable."""
+    n, seed = int(n_samples), int(seed)
+    if n < 0:
+        raise ValueError(f"sample_surface: n_samples must not be negative (got {n})")
+    if not -2 ** 63 <= seed < 2 ** 64:
+        raise ValueError(f"sample_surface: seed must fit 64 bits (got {seed})")
+    seed = seed - 2 ** 64 if seed >= 2 ** 63 else seed
+    dev = vertices.device if torch.is_tensor(vertices) else (triangles.device if torch.is_tensor(triangles) else torch.device("cpu"))
+    lib = _lib.library_for(library, dev, ("a mesh", "sampled"))
+    v = _floats(vertices, "vertices", dev)
+    t = _triangles(triangles, dev)
+    col = _floats(colors, "colors", dev, v.shape[0]) if colors is not None else None
+    if t.shape[0] == 0:
+        raise ValueError("sample_surface: the mesh has no faces")
+    cdf, summary = _area_cdf(v, t, lib)
+    total, zero, invalid, _ = summary.tolist()
+    if total <= 0:
+        raise ValueError(f"sample_surface: no face can be drawn ({t.shape[0]} faces, {zero} of weight 0, {invalid} of them invalid)")
+    points, faces, uv = _sample(v, t, cdf, n, seed, lib)
+    faces = faces.to(torch.int64)
+    bary = torch.cat([(1.0 - uv[:, :1]) - uv[:, 1:], uv], dim=1)      # exact: u, v and u + v are multiples of 2^-24 in [0, 1]
+    if col is None:
+        return points, faces, bary
+    corners = col[t.to(torch.int64)[faces]]                            # [n, 3 corners, 3 channels]
+    return points, faces, bary, (corners * bary[:, :, None]).sum(dim=1)

@@ -3,17 +3,20 @@
 The reference scores an extracted mesh with ``compute_chamfer_distance`` (lib/utils/mesh_tools.py:59-70): the vertices of two mesh files,
 optionally normalised (``normalize_point_cloud``, :43-56), handed to ``pytorch3d.loss.chamfer_distance``.  Here the all-pairs search behind
 it is one exact brute-force kernel (``cnr_nn_search``, include/colorneus_render.h); the reductions on its per-point results are a few torch
-calls in float64.
+calls in float64.  That is the vertex-cloud parity route.  Vertex density is not surface density -- two tessellations of one surface have a
+non-zero vertex Chamfer -- so ``surface_metrics`` measures the same figures between surfaces: points drawn uniformly by area
+(``meshops.sample_surface``) and the exact closest triangle of a mesh for every point (``point_mesh_distance``, ``cnr_point_mesh_distance``).
 
 Every function takes ``(N, 3)`` tensors of any float dtype and any strides, converts them to contiguous float32 on their own device and runs on
 the current stream.  CUDA tensors go through the HIP library; CPU tensors only with an explicitly passed emulation ``library=`` (there is no
 CPU fallback).  NOTHING HERE IS DIFFERENTIABLE: inputs are detached and results carry no graph."""
 import torch
 
-from . import _lib, meshio
+from . import _lib, meshio, meshops
 from ._lib import ptr, stream_of
 
-__all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance"]
+__all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance", "point_mesh_distance",
+           "surface_metrics", "compute_surface_metrics"]
 
 
 def _library(library, dev):
@@ -114,6 +117,108 @@ def mesh_metrics(pred, gt, thresholds=(0.01, 0.02, 0.05), library=None):
         out[f"precision@{t:g}"], out[f"recall@{t:g}"] = prec, rec
         out[f"fscore@{t:g}"] = 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
     return out
+
+
+def _mesh(mesh, name, dev=None):
+    """``(vertices, triangles)`` -> contiguous float32 (V, 3) and int32 (F, 3) on the vertices' device; F == 0 raises ValueError."""
+    if not isinstance(mesh, (tuple, list)) or len(mesh) != 2:
+        raise ValueError(f"{name}: expected a (vertices, triangles) pair")
+    v = _points(mesh[0], f"{name} vertices")
+    v = v if dev is None else v.to(dev)
+    t = meshops._triangles(mesh[1], v.device)
+    if t.shape[0] == 0:
+        raise ValueError(f"{name}: the mesh has no faces")
+    return v, t
+
+
+def _closest_face(q, v, t, lib, want_closest=False):
+    """q (n,3), v (V,3) float32, t (F,3) int32, contiguous on one device, F > 0 -> dist2 float32 (n,), face int32 (n,), closest (n,3) or None."""
+    n, dev = q.shape[0], q.device
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_closest else None
+    if n > 0:
+        keys = torch.empty(n, dtype=torch.int64, device=dev)      # the library's uint64 candidate keys: scratch, never read here
+        lib.call("cnr_point_mesh_distance", ptr(q), n, ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(dist2), ptr(face), ptr(closest), ptr(keys),
+                 stream_of(dev))
+    return dist2, face, closest
+
+
+def point_mesh_distance(points, vertices, triangles, return_closest=False, library=None):
+    """For every point the squared distance to the mesh SURFACE and the face that attains it (``cnr_point_mesh_distance``):
+    ``(dist2 float32 (N,), face int64 (N,))``, with ``return_closest=True`` also the closest point on that face, float32 (N, 3).
+
+    Exact brute force over all point / triangle pairs in float32, the closest point of each closed triangle by Ericson's region classification
+    (include/colorneus_render.h writes the order of operations down); of several faces at the minimal distance the one with the LOWEST index is
+    returned.  A face with an index outside ``[0, V)`` or a non-finite distance never wins; a point with a NaN coordinate gets ``face = -1`` and
+    NaN.  A mesh without faces raises ValueError; no points gives empty tensors.  Not differentiable."""
+    q = _points(points, "points")
+    v, t = _mesh((vertices, triangles), "mesh", q.device)
+    lib = _lib.library_for(library, q.device, ("points", "measured"))
+    dist2, face, closest = _closest_face(q, v, t, lib, return_closest)
+    return (dist2, face.to(torch.int64), closest) if return_closest else (dist2, face.to(torch.int64))
+
+
+def _figures(d2_pg, d2_gp, thresholds, max_dist):
+    """mesh_metrics' dict from the two directions' float32 squared distances (float64 reductions; ``max_dist`` clamps the distances)."""
+    d2_pg, d2_gp = d2_pg.to(torch.float64), d2_gp.to(torch.float64)
+    d_pg, d_gp = d2_pg.sqrt(), d2_gp.sqrt()
+    if max_dist is not None:
+        m = float(max_dist)
+        d_pg, d_gp, d2_pg, d2_gp = d_pg.clamp(max=m), d_gp.clamp(max=m), d2_pg.clamp(max=m * m), d2_gp.clamp(max=m * m)
+    acc, comp = d_pg.mean(), d_gp.mean()
+    out = {"accuracy": float(acc), "completeness": float(comp), "chamfer_l1": float((acc + comp) * 0.5), "chamfer_l2": float(d2_pg.mean() + d2_gp.mean())}
+    for t in thresholds:
+        prec = float((d_pg < float(t)).sum()) / d_pg.shape[0]
+        rec = float((d_gp < float(t)).sum()) / d_gp.shape[0]
+        out[f"precision@{t:g}"], out[f"recall@{t:g}"] = prec, rec
+        out[f"fscore@{t:g}"] = 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
+    return out
+
+
+def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 0.05), exact=True, max_dist=None, library=None):
+    """The figures of ``mesh_metrics`` -- same keys, same definitions, float64 reductions -- measured between SURFACES instead of vertex clouds,
+    so that they do not move with the tessellation.  ``pred`` is ``(vertices, triangles)``; ``gt`` is ``(vertices, triangles)`` or a bare
+    ``(N, 3)`` cloud (a scanned ground truth, as DTU's).
+
+    Each mesh is sampled by area (``meshops.sample_surface``: ``n_samples`` points, pred under ``seed``, gt under ``seed + 1``).  Accuracy is
+    measured from the pred samples, completeness from the gt samples (or the gt cloud).  ``exact=True``: each point to the other SURFACE
+    (``point_mesh_distance``; to the gt cloud's nearest point when gt is a cloud).  ``exact=False``: point to the other side's SAMPLES through
+    ``cnr_nn_search`` -- ``mesh_metrics`` of the two sample sets.  ``max_dist`` clamps every distance before the means and thresholds (the DTU
+    protocol's outlier cap); ``chamfer_l2`` then clamps the squared distances at ``max_dist ** 2``.  Not differentiable."""
+    n_samples = int(n_samples)
+    if n_samples <= 0:
+        raise ValueError(f"surface_metrics: n_samples must be positive (got {n_samples})")
+    if max_dist is not None and not float(max_dist) > 0.0:
+        raise ValueError(f"surface_metrics: max_dist must be positive (got {max_dist})")
+    pv, pt = _mesh(pred, "pred")
+    dev = pv.device
+    lib = _lib.library_for(library, dev, ("meshes", "compared"))
+    ps = meshops.sample_surface(pv, pt, n_samples, seed=seed, library=lib)[0]
+    if isinstance(gt, (tuple, list)):
+        gv, gtri = _mesh(gt, "gt", dev)
+        gs = meshops.sample_surface(gv, gtri, n_samples, seed=int(seed) + 1, library=lib)[0]
+        d2_pg = _closest_face(ps, gv, gtri, lib)[0] if exact else _search(ps, gs, lib)[0]
+    else:
+        gs = _points(gt, "gt").to(dev)
+        if gs.shape[0] == 0:
+            raise ValueError("surface_metrics: the gt cloud is empty")
+        d2_pg = _search(ps, gs, lib)[0]
+    d2_gp = _closest_face(gs, pv, pt, lib)[0] if exact else _search(gs, ps, lib)[0]
+    return _figures(d2_pg, d2_gp, thresholds, max_dist)
+
+
+def compute_surface_metrics(path_pred, path_gt, device="cuda", n_samples=100000, seed=0, thresholds=(0.01, 0.02, 0.05), exact=True, max_dist=None,
+                            library=None):
+    """``surface_metrics`` on two PLY files (``meshio.read_ply_mesh``): ``path_pred`` must hold triangles; a ``path_gt`` without a face element
+    (or with an empty one) is taken as a cloud."""
+    pv, pt = meshio.read_ply_mesh(path_pred)
+    gv, gt = meshio.read_ply_mesh(path_gt)
+    if pt is None:
+        raise ValueError(f"{path_pred}: the predicted mesh has no face element")
+    pred = (torch.from_numpy(pv).to(device), torch.from_numpy(pt).to(device))
+    gt = (torch.from_numpy(gv).to(device), torch.from_numpy(gt).to(device)) if gt is not None and gt.shape[0] else torch.from_numpy(gv).to(device)
+    return surface_metrics(pred, gt, n_samples=n_samples, seed=seed, thresholds=thresholds, exact=exact, max_dist=max_dist, library=library)
 
 
 def compute_chamfer_distance(path_source, path_target, device="cuda", norm=False, library=None):

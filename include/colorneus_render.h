@@ -574,6 +574,61 @@ int cnr_mesh_compact(const float* vertices /* [V][3] */, const float* colors /* 
                      int64_t n_vertices, const int32_t* vertex_map, const int32_t* face_map, float* out_vertices, float* out_colors /* NULL iff colors NULL */,
                      int32_t* out_triangles, void* stream);
 
+/* ---- mesh surface sampling and exact point-to-mesh distance: points drawn uniformly by area on an indexed triangle mesh, and for every query
+ * point the closest triangle of a mesh -- what surface-to-surface accuracy / completeness / Chamfer / F-score need (the vertex clouds that
+ * cnr_nn_search scores depend on the tessellation).  vertices: float [n_vertices][3]; triangles: int32 [n_triangles][3], 0 < n_triangles < 2^31,
+ * 0 <= n_vertices < 2^31.  Every float operation below is ONE rounded fp32 operation in the written order (no FMA; sqrt and / correctly rounded),
+ * everything else is integer arithmetic: results are the same bits on every run, launch shape and build.  There is no size query and no scratch:
+ * cdf, summary and keys are typed device arrays owned by the caller (8-byte aligned), contents need not be initialised.  Nothing is differentiable.
+ * A face is INVALID when one of its indices lies outside [0, n_vertices): it is never read through, has weight 0 and is never the closest face.
+ *
+ * cnr_mesh_area_cdf: integer sampling weights and their prefix sums.  For face f = (a, b, c): e1 = b - a, e2 = c - a,
+ *     n = ((e1y*e2z) - (e1z*e2y), (e1z*e2x) - (e1x*e2z), (e1x*e2y) - (e1y*e2x)),   A_f = sqrtf((nx*nx + ny*ny) + nz*nz)   (the doubled area).
+ *   A face whose A_f is NaN or +inf counts as invalid too.  amax = the largest A_f of the valid faces (an integer max of the bit patterns);
+ *     w_f = (uint64)((A_f / amax) * 4294967296.0f)  (truncated; at most 2^32),   w_f = 0 for an invalid face and when amax == 0.
+ *   A face below 2^-32 of the largest area has weight 0 and is never drawn: that is the resolution of the weights, not an error.
+ *   cdf[f] = w_0 + ... + w_f (uint64 [n_triangles], exact);  summary (int64 [4]) = {total = cdf[F - 1], the number of faces with w_f == 0
+ *   (the invalid ones included), the number of invalid faces, the bit pattern of amax}.
+ *
+ * cnr_mesh_sample: n_samples points uniform by area, counter based: sample i depends on (seed, i) alone, not on n_samples.
+ *     (w0, w1, w2, w3) = Philox4x32-10 of the counter (lo32(i), hi32(i), 0, 0) under the key (lo32(seed), hi32(seed))   (cnr_choose_pixels' generator)
+ *     r = the high 64 bits of ((w0 << 32) | w1) * total;   face = the first f with cdf[f] > r   (a face of weight 0 is never drawn)
+ *     iu = w2 >> 8, iv = w3 >> 8;  if iu + iv > 2^24 (that is u + v > 1):  iu = 2^24 - iu, iv = 2^24 - iv;   u = iu * 2^-24, v = iv * 2^-24   (exact)
+ *     point = (a + u * e1) + v * e2 per component, e1 = b - a, e2 = c - a  (the barycentric weights of a, b, c are 1 - u - v, u, v)
+ *   points: float [n][3], faces: int32 [n], bary: float [n][2] = (u, v) or NULL.  total == 0 gives face = -1 and NaN in points and bary.
+ *   cdf is cnr_mesh_area_cdf's for the same mesh.  n_samples == 0 is a successful no-op.
+ *
+ * cnr_point_mesh_distance: for query i, dist2[i] = the minimum over the faces of the squared distance to the CLOSED triangle, face[i] = the
+ *   LOWEST face index that attains it, closest[i] (float [n][3] or NULL) = the closest point on that face.  Brute force over all pairs, exact.
+ *   Per face: ab = b - a, ac = c - a, abab = ab.ab, abac = ab.ac, acac = ac.ac, every dot product (x*x' + y*y') + z*z'.  Per pair:
+ *     ap = q - a;  d1 = ab.ap, d2 = ac.ap;  d3 = d1 - abab, d4 = d2 - abac;  d5 = d1 - abac, d6 = d2 - acac
+ *     vc = d1*d4 - d3*d2,  vb = d5*d2 - d1*d6,  va = d3*d6 - d5*d4;   e43 = d4 - d3,  e56 = d5 - d6
+ *   the FIRST of these regions that holds sets (n1, n2, den):
+ *     vertex a   d1 <= 0 and d2 <= 0                  (0, 0, 1)
+ *     vertex b   d3 >= 0 and d4 <= d3                 (1, 0, 1)
+ *     edge ab    vc <= 0 and d1 >= 0 and d3 <= 0      (d1, 0, d1 - d3)
+ *     vertex c   d6 >= 0 and d5 <= d6                 (0, 1, 1)
+ *     edge ac    vb <= 0 and d2 >= 0 and d6 <= 0      (0, d2, d2 - d6)
+ *     edge bc    va <= 0 and e43 >= 0 and e56 >= 0    (e56, e43, e43 + e56)
+ *     interior   otherwise                            (vb, vc, (va + vb) + vc)
+ *   inv = 1 / den,  v = n1 * inv,  w = n2 * inv,  closest = (a + v * ab) + w * ac per component,
+ *     d2(i, f) = (dx*dx + dy*dy) + dz*dz,  dx = q.x - closest.x, ...   (cnr_nn_search's expression).
+ *   Candidates are ordered by the 64-bit key (bits(d2) << 32) | f, folded with an integer min.  A d2 that is NaN or +inf never wins, nor does an
+ *   invalid face; a query without a candidate (a NaN query, only invalid faces) gets dist2 = NaN, face = -1 and NaN in closest.  A triangle
+ *   collapsed to one point (a == b == c) is "vertex a" for every query: it behaves as that point.  Any other degenerate triangle can reach
+ *   den == 0 and then a non-finite d2, which never wins.  keys: uint64 [n_query] scratch.  n_query == 0 is a successful no-op.
+ *
+ * Errors (a negative status, the text in cnr_last_error): n_triangles <= 0 or >= 2^31; n_vertices < 0 or >= 2^31; a negative n_samples / n_query; a
+ * null pointer other than bary / closest (vertices may be NULL when n_vertices == 0); cdf, summary or keys not 8-byte aligned. */
+int cnr_mesh_area_cdf(const float* vertices /* [V][3] */, int64_t n_vertices, const int32_t* triangles /* [F][3] */, int64_t n_triangles,
+                      uint64_t* cdf /* [F] */, int64_t* summary /* [4] */, void* stream);
+int cnr_mesh_sample(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const uint64_t* cdf /* [F] */,
+                    int64_t n_samples, int64_t seed, float* points /* [n][3] */, int32_t* faces /* [n] */, float* bary /* [n][2] or NULL */,
+                    void* stream);
+int cnr_point_mesh_distance(const float* query /* [n][3] */, int64_t n_query, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                            int64_t n_triangles, float* dist2 /* [n] */, int32_t* face /* [n] */, float* closest /* [n][3] or NULL */,
+                            uint64_t* keys /* [n] */, void* stream);
+
 /* ---- one plain fully-connected layer on the layer / weight-gradient kernels of the render path: y = act(x W^T + b), act = ReLU or none.
  * The NeRF++ background network of NeuS (NeRF, fields.py:192-274; N_OUTSIDE > 0, NeuS.py:95-134) is a chain of nn.Linear (+ ReLU) layers;
  * color-neus_amd/background.py evaluates each of them through these two entry points.  x [n][k], y / dy [n][n_out], W [n_out][k] and b [n_out]
