@@ -5,6 +5,7 @@ The product library is ``libcolorneus_hip.so`` next to this file (built by ``__g
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -277,6 +278,18 @@ def stream_of(x):
     """The current stream of a tensor's device, or of a torch.device, as the ABI's stream argument (NULL on the CPU)."""
     dev = x if isinstance(x, torch.device) else x.device
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else C.c_void_p(0)
+
+
+def points3(x, name, dev=None, rows=None):
+    """``x`` (a tensor, or anything numpy reads as an array) of shape (N, 3) and any float dtype and strides as a detached contiguous float32
+    tensor on ``dev`` (its own device when None); ``rows``: the N it must have.  Anything else raises ValueError under ``name``."""
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.asarray(x))
+    if x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
+        raise ValueError(f"{name}: expected a floating-point (N, 3) tensor, got {tuple(x.shape)} {x.dtype}")
+    if rows is not None and x.shape[0] != rows:
+        raise ValueError(f"{name}: expected {rows} rows, got {x.shape[0]}")
+    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
 def param_array(tensors, n=None):

@@ -4,6 +4,8 @@
 namespace cnr {
 extern hipError_t g_first_error;
 extern const char* g_first_error_where;
+// the one fill of device memory: `byte` into `bytes` bytes at p on the stream; a failure is recorded as the first error under `where`
+void device_fill(void* p, int byte, size_t bytes, hipStream_t s, const char* where);
 // optional per-launch timing with HIP events on the launch stream (bench / profiling only; off by default)
 void timing_begin(const char* name, int kind, int nt, long P, int N, int K, int pairs, hipStream_t s, double bytes);
 void timing_end(hipStream_t s);

@@ -181,13 +181,9 @@ __global__ __launch_bounds__(kImgThreads) void image_panel_kernel(const ImagePan
   }
 }
 
-static void note_error(hipError_t e, const char* where) {
-  if (e != hipSuccess && g_first_error == hipSuccess) { g_first_error = e; g_first_error_where = where; }
-}
-
 void be_image_stats(const ImageStats& p, cnr_stream s) {
   if (p.nblocks == 0) {
-    note_error(hipMemsetAsync(p.sums, 0, 2 * sizeof(double), s), "image_stats memset");
+    device_fill(p.sums, 0, 2 * sizeof(double), s, "image_stats memset");
     return;
   }
   const long tx = img_tiles_x(p.W, p.cs), ty = img_tiles_y(p.H);
@@ -206,7 +202,7 @@ void be_image_stats(const ImageStats& p, cnr_stream s) {
 
 void be_image_panel(const ImagePanel& p, cnr_stream s) {
   const long n = (long)p.H * p.W;
-  note_error(hipMemsetAsync(p.keys, 0xff, 2 * sizeof(unsigned), s), "image_panel memset");
+  device_fill(p.keys, 0xff, 2 * sizeof(unsigned), s, "image_panel memset");
   {
     long blocks = (n + kImgThreads * 4 - 1) / (kImgThreads * 4);
     if (blocks > 1024) blocks = 1024;

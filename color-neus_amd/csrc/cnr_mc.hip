@@ -38,17 +38,10 @@ __global__ __launch_bounds__(256) void mc_block_sum_kernel(const McVolume m, lon
 __global__ __launch_bounds__(1024) void mc_scan_sums_kernel(const McVolume m, int nblocks) {
   __shared__ int wsum[2][16];
   __shared__ int carry[2];
-  const int tid = threadIdx.x;
-  if (tid < 2) carry[tid] = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int i = base + tid;
-    const int x[2] = {i < nblocks ? m.block_sums[i * 2] : 0, i < nblocks ? m.block_sums[i * 2 + 1] : 0};
-    int excl[2];
-    block_excl_scan<16, 2, int>(x, excl, wsum, carry);
-    if (i < nblocks) { m.block_sums[i * 2] = excl[0]; m.block_sums[i * 2 + 1] = excl[1]; }
-  }
-  if (tid == 0) { m.totals[0] = carry[0]; m.totals[1] = carry[1]; }
+  block_carried_scan<16, 1, 2, int>(nblocks, wsum, carry,
+                                    [&](int i, int (&x)[2]) { x[0] += m.block_sums[i * 2]; x[1] += m.block_sums[i * 2 + 1]; },
+                                    [&](int i, const int (&at)[2]) { m.block_sums[i * 2] = at[0]; m.block_sums[i * 2 + 1] = at[1]; });
+  if (threadIdx.x == 0) { m.totals[0] = carry[0]; m.totals[1] = carry[1]; }
 }
 __global__ __launch_bounds__(256) void mc_scan_apply_kernel(const McVolume m, long n) {
   // one workgroup rescans its 2048-element chunk: 8 elements per thread, wave scan of their sums, wave offsets through LDS.  (block_excl_scan's steps

@@ -17,9 +17,15 @@ using namespace cnr;
 
 extern "C" {
 
-// [kLossBlocks][4] partial sums + 16 bytes whose first 4 are the completion counter of the one-launch forms
-constexpr size_t kLossTicketOff = (size_t)kLossBlocks * 4 * sizeof(float);
-size_t cnr_loss_scratch_bytes(int64_t n_rays) { (void)n_rays; return kLossTicketOff + 16; }
+// the one layout of the loss scratch: [kLossBlocks][4] partial sums | 16 bytes whose first 4 are the completion counter of the one-launch forms.
+// Returns the size; with a base pointer it also places the two parts.
+struct LossScratch { float* partial; unsigned* ticket; };
+static size_t loss_layout(void* base, LossScratch* p) {
+  const size_t partial = (size_t)kLossBlocks * 4 * sizeof(float);
+  if (p) { p->partial = static_cast<float*>(base); p->ticket = reinterpret_cast<unsigned*>(static_cast<char*>(base) + partial); }
+  return partial + 16;
+}
+size_t cnr_loss_scratch_bytes(int64_t n_rays) { (void)n_rays; return loss_layout(nullptr, nullptr); }
 
 static int loss_args(const cnr_loss_config* cfg, const float* color, const float* wsum, const float* drel, const float* gt, const float* mask,
                      int64_t n_rays, int32_t n_samples, LossArgs& a) {
@@ -32,25 +38,25 @@ static int loss_args(const cnr_loss_config* cfg, const float* color, const float
 
 int cnr_loss_sums(const cnr_loss_config* cfg, const float* color_fine, const float* weight_sum, const float* delta_relight, const float* rgb_gt,
                   const float* mask, int64_t n_rays, int32_t n_samples, float* sums, void* scratch, size_t scratch_bytes, void* stream) {
-  LossArgs a;
+  LossArgs a; LossScratch w;
   if (loss_args(cfg, color_fine, weight_sum, delta_relight, rgb_gt, mask, n_rays, n_samples, a)) return -1;
   if (!sums || !scratch) return fail("null argument");
   if (mask && !weight_sum) return fail("weight_sum is required with a mask");
-  if (scratch_bytes < cnr_loss_scratch_bytes(n_rays)) return fail("loss scratch too small");
-  be_loss_sums(a, static_cast<float*>(scratch), sums, (cnr_stream)stream);
+  if (scratch_bytes < loss_layout(scratch, &w)) return fail("loss scratch too small");
+  be_loss_sums(a, w.partial, sums, (cnr_stream)stream);
   return check_backend("loss_sums");
 }
 
 int cnr_loss_sums_ray(const cnr_loss_config* cfg, const float* color_fine, const float* weight_sum, const float* delta_relight_ray_sum,
                       const float* rgb_gt, const float* mask, int64_t n_rays, int32_t n_samples, float* sums, void* scratch, size_t scratch_bytes,
                       void* stream) {
-  LossArgs a;
+  LossArgs a; LossScratch w;
   if (loss_args(cfg, color_fine, weight_sum, delta_relight_ray_sum, rgb_gt, mask, n_rays, n_samples, a)) return -1;
   if (!sums || !scratch) return fail("null argument");
   if (mask && !weight_sum) return fail("weight_sum is required with a mask");
-  if (scratch_bytes < cnr_loss_scratch_bytes(n_rays)) return fail("loss scratch too small");
+  if (scratch_bytes < loss_layout(scratch, &w)) return fail("loss scratch too small");
   a.drel_per_ray = 1;
-  be_loss_sums(a, static_cast<float*>(scratch), sums, (cnr_stream)stream);
+  be_loss_sums(a, w.partial, sums, (cnr_stream)stream);
   return check_backend("loss_sums_ray");
 }
 
@@ -99,28 +105,28 @@ int cnr_loss_coef(const cnr_loss_config* cfg, const float* g_loss, const float* 
 int cnr_loss_forward(const cnr_loss_config* cfg, const float* color_fine, const float* weight_sum, const float* delta_relight, int32_t delta_per_ray,
                      const float* rgb_gt, const float* mask, const float* gradient_error, int64_t n_rays, int32_t n_samples, float n_rays_global,
                      int32_t use_mask, int32_t use_relight, float* sums, float* out, void* scratch, size_t scratch_bytes, void* stream) {
-  LossArgs a;
+  LossArgs a; LossScratch w;
   LossScalars c;
   if (loss_args(cfg, color_fine, weight_sum, delta_relight, rgb_gt, mask, n_rays, n_samples, a)) return -1;
   if (loss_scalars(cfg, n_rays_global, n_samples, use_mask, use_relight, c)) return -1;
   if (!sums || !out || !scratch || !gradient_error) return fail("null argument");
   if (mask && !weight_sum) return fail("weight_sum is required with a mask");
-  if (scratch_bytes < cnr_loss_scratch_bytes(n_rays)) return fail("loss scratch too small");
+  if (scratch_bytes < loss_layout(scratch, &w)) return fail("loss scratch too small");
   a.drel_per_ray = delta_per_ray != 0;
-  be_loss_forward(a, static_cast<float*>(scratch), reinterpret_cast<unsigned*>(static_cast<char*>(scratch) + kLossTicketOff), c, gradient_error, sums, out, (cnr_stream)stream);
+  be_loss_forward(a, w.partial, w.ticket, c, gradient_error, sums, out, (cnr_stream)stream);
   return check_backend("loss_forward");
 }
 
 int cnr_loss_shard_stats(const cnr_loss_config* cfg, const float* color_fine, const float* weight_sum, const float* delta_relight, int32_t delta_per_ray,
                          const float* rgb_gt, const float* mask, const float* eik_sums, int64_t n_rays, int32_t n_samples, float* stats, void* scratch,
                          size_t scratch_bytes, void* stream) {
-  LossArgs a;
+  LossArgs a; LossScratch w;
   if (loss_args(cfg, color_fine, weight_sum, delta_relight, rgb_gt, mask, n_rays, n_samples, a)) return -1;
   if (!stats || !scratch || !eik_sums) return fail("null argument");
   if (mask && !weight_sum) return fail("weight_sum is required with a mask");
-  if (scratch_bytes < cnr_loss_scratch_bytes(n_rays)) return fail("loss scratch too small");
+  if (scratch_bytes < loss_layout(scratch, &w)) return fail("loss scratch too small");
   a.drel_per_ray = delta_per_ray != 0;
-  be_loss_shard_stats(a, static_cast<float*>(scratch), reinterpret_cast<unsigned*>(static_cast<char*>(scratch) + kLossTicketOff), eik_sums, stats, (cnr_stream)stream);
+  be_loss_shard_stats(a, w.partial, w.ticket, eik_sums, stats, (cnr_stream)stream);
   return check_backend("loss_shard_stats");
 }
 
@@ -194,19 +200,23 @@ static int pixel_table_dims(const char* who, int32_t n_images, int64_t hw) {
   if ((double)n_images * (double)hw >= 4294967296.0) return fail("%s: n_images * pixels_per_image must be below 2^32", who);
   return 0;
 }
+// the one layout of the pixel table's scratch (loss_layout's form): a {foreground, background} count pair per image and tile
+static size_t pixel_table_layout(int32_t n_images, int64_t hw, void* base, PixelTable* t) {
+  const long tiles = pixel_tiles(hw);
+  if (t) { t->tile_counts = static_cast<int*>(base); t->tiles = tiles; }
+  return round_up_sz((size_t)n_images * (size_t)tiles * 2 * sizeof(int), 256);
+}
 size_t cnr_pixel_table_scratch_bytes(int32_t n_images, int64_t pixels_per_image) {
-  if (n_images <= 0 || pixels_per_image <= 0) return 0;
-  return round_up_sz((size_t)n_images * (size_t)pixel_tiles(pixels_per_image) * 2 * sizeof(int), 256);
+  return n_images <= 0 || pixels_per_image <= 0 ? 0 : pixel_table_layout(n_images, pixels_per_image, nullptr, nullptr);
 }
 
 int cnr_pixel_table_build(const float* masks, int32_t n_images, int64_t pixels_per_image, int32_t* order, int32_t* fg_count, int32_t* bg_count,
                           void* scratch, size_t scratch_bytes, void* stream) {
   if (pixel_table_dims("pixel_table_build", n_images, pixels_per_image)) return -1;
   if (!masks || !order || !fg_count || !bg_count || !scratch) return fail("pixel_table_build: null argument");
-  if (scratch_bytes < cnr_pixel_table_scratch_bytes(n_images, pixels_per_image)) return fail("pixel_table_build scratch too small");
   PixelTable t;
+  if (scratch_bytes < pixel_table_layout(n_images, pixels_per_image, scratch, &t)) return fail("pixel_table_build scratch too small");
   t.masks = masks; t.n_images = n_images; t.hw = (long)pixels_per_image; t.order = order; t.fg_count = fg_count; t.bg_count = bg_count;
-  t.tile_counts = static_cast<int*>(scratch); t.tiles = pixel_tiles(pixels_per_image);
   if ((double)n_images * (double)t.tiles >= 2147483648.0) return fail("pixel_table_build: too many tiles (n_images * ceil(pixels_per_image / %d) must be below 2^31)", kPixTile);
   be_pixel_table(t, (cnr_stream)stream);
   return check_backend("pixel_table_build");
@@ -348,31 +358,27 @@ int cnr_up_sample(const float* rays_o, const float* rays_d, const float* z_vals,
   return check_backend("up_sample");
 }
 
-static int mc_layout(int32_t res, float thr, const float* u, void* scratch, size_t scratch_bytes, McVolume& v) {
-  if (!u || !scratch) return fail("null argument");
-  if (res < 2 || res > 1290) return fail("marching cubes: resolution must be in [2, 1290]");   // res^3 voxel ids and 2 * res^3 counts stay below 2^31
-  if (scratch_bytes < cnr_mc_scratch_bytes(res)) return fail("marching cubes scratch too small");
+// the one layout of the marching-cubes scratch (loss_layout's form): counts [n][2] | block sums [nblocks][2] | flags [n], n = res^3 voxels
+static size_t mc_layout(int32_t res, char* base, McVolume* v) {
   const size_t n = (size_t)res * res * res;
   const size_t nblocks = (n + kMcScanBlock - 1) / kMcScanBlock;
-  char* p = static_cast<char*>(scratch);
-  v.u = u; v.res = res; v.thr = thr;
-  v.counts = reinterpret_cast<int*>(p); p += round_up_sz(n * 2 * sizeof(int), 256);
-  v.block_sums = reinterpret_cast<int*>(p); p += round_up_sz(nblocks * 2 * sizeof(int), 256);
-  v.flags = reinterpret_cast<unsigned char*>(p);
-  v.totals = nullptr;
-  return 0;
+  const size_t counts = round_up_sz(n * 2 * sizeof(int), 256), sums = round_up_sz(nblocks * 2 * sizeof(int), 256);
+  if (v) { v->counts = reinterpret_cast<int*>(base); v->block_sums = reinterpret_cast<int*>(base + counts); v->flags = reinterpret_cast<unsigned char*>(base + counts + sums); }
+  return counts + sums + round_up_sz(n, 256);
 }
+size_t cnr_mc_scratch_bytes(int32_t resolution) { return resolution < 2 ? 0 : mc_layout(resolution, nullptr, nullptr); }
 
-size_t cnr_mc_scratch_bytes(int32_t resolution) {
-  if (resolution < 2) return 0;
-  const size_t n = (size_t)resolution * resolution * resolution;
-  const size_t nblocks = (n + kMcScanBlock - 1) / kMcScanBlock;
-  return round_up_sz(n * 2 * sizeof(int), 256) + round_up_sz(nblocks * 2 * sizeof(int), 256) + round_up_sz(n, 256);
+static int mc_volume(int32_t res, float thr, const float* u, void* scratch, size_t scratch_bytes, McVolume& v) {
+  if (!u || !scratch) return fail("null argument");
+  if (res < 2 || res > 1290) return fail("marching cubes: resolution must be in [2, 1290]");   // res^3 voxel ids and 2 * res^3 counts stay below 2^31
+  if (scratch_bytes < mc_layout(res, static_cast<char*>(scratch), &v)) return fail("marching cubes scratch too small");
+  v.u = u; v.res = res; v.thr = thr; v.totals = nullptr;
+  return 0;
 }
 
 int cnr_mc_count(const float* u, int32_t resolution, float threshold, void* scratch, size_t scratch_bytes, int32_t* totals, void* stream) {
   McVolume v;
-  if (mc_layout(resolution, threshold, u, scratch, scratch_bytes, v)) return -1;
+  if (mc_volume(resolution, threshold, u, scratch, scratch_bytes, v)) return -1;
   if (!totals) return fail("null argument");
   v.totals = totals;
   be_mc_count(v, (cnr_stream)stream);
@@ -382,7 +388,7 @@ int cnr_mc_count(const float* u, int32_t resolution, float threshold, void* scra
 int cnr_mc_emit(const float* u, int32_t resolution, float threshold, const float* bound_min, const float* bound_max, void* scratch,
                 size_t scratch_bytes, float* vertices, int32_t* triangles, void* stream) {
   McVolume v;
-  if (mc_layout(resolution, threshold, u, scratch, scratch_bytes, v)) return -1;
+  if (mc_volume(resolution, threshold, u, scratch, scratch_bytes, v)) return -1;
   if (!bound_min || !bound_max || !vertices || !triangles) return fail("null argument");
   be_mc_emit(v, bound_min, bound_max, vertices, triangles, (cnr_stream)stream);
   return check_backend("mc_emit");
@@ -409,12 +415,16 @@ int cnr_nn_search(const float* query, int64_t n_query, const float* target, int6
   return check_backend("nn_search");
 }
 
-// one {sum d*d, sum ssim} pair of doubles per tile of the [B][C][H][W] form (the channels-last form of the same image never has more tiles),
-// and 256 bytes for the two range keys of cnr_image_panel
 static long image_blocks(int64_t planes, int H, int W, int cs) { return (long)planes * img_tiles_y(H) * img_tiles_x(W, cs); }
-size_t cnr_image_scratch_bytes(int64_t n_images, int channels, int H, int W) {
-  if (n_images <= 0 || channels < 1 || H < 1 || W < 1) return 0;
+// the one layout of the image scratch (loss_layout's form), which serves one call at a time: cnr_image_metrics' {sum d*d, sum ssim} pair of doubles
+// per tile of the [B][C][H][W] form (the channels-last form never has more tiles) and 256 bytes, or cnr_image_panel's two range keys at its start
+static size_t image_layout(int64_t n_images, int channels, int H, int W, void* base, double** partials, unsigned** keys) {
+  if (partials) *partials = static_cast<double*>(base);
+  if (keys) *keys = static_cast<unsigned*>(base);
   return round_up_sz((size_t)image_blocks(n_images * channels, H, W, 1) * 2 * sizeof(double), 256) + 256;
+}
+size_t cnr_image_scratch_bytes(int64_t n_images, int channels, int H, int W) {
+  return n_images <= 0 || channels < 1 || H < 1 || W < 1 ? 0 : image_layout(n_images, channels, H, W, nullptr, nullptr, nullptr);
 }
 
 int cnr_image_metrics(const float* img0, const float* img1, int64_t n_images, int channels, int H, int W, int channels_last, float* ssim_map,
@@ -429,11 +439,10 @@ int cnr_image_metrics(const float* img0, const float* img1, int64_t n_images, in
     if ((double)n_images * channels * H * W >= 2147483648.0) return fail("image_metrics: the element count must be below 2^31");
     if (channels_last && channels > kImgMaxCs) return fail("image_metrics: the channels-last form takes at most %d channels (got %d)", kImgMaxCs, channels);
     if (!img0 || !img1 || !scratch) return fail("image_metrics: null argument");
-    if (scratch_bytes < cnr_image_scratch_bytes(n_images, channels, H, W)) return fail("image_metrics scratch too small");
+    if (scratch_bytes < image_layout(n_images, channels, H, W, scratch, &p.partials, nullptr)) return fail("image_metrics scratch too small");
     p.cs = channels_last ? channels : 1;
     p.planes = channels_last ? (long)n_images : (long)n_images * channels;
     p.nblocks = image_blocks(p.planes, H, W, p.cs);
-    p.partials = static_cast<double*>(scratch);
   }
   be_image_stats(p, (cnr_stream)stream);
   return check_backend("image_metrics");
@@ -447,7 +456,7 @@ int cnr_image_panel(const float* gt, const float* render, const float* depth, in
   if (scratch_bytes < 2 * sizeof(unsigned)) return fail("image_panel scratch too small");
   ImagePanel p;
   p.gt = gt; p.render = render; p.depth = depth; p.H = H; p.W = W; p.nsec = gt ? 3 : 1; p.panel = panel; p.range = range;
-  p.keys = static_cast<unsigned*>(scratch);
+  image_layout(1, 3, H, W, scratch, nullptr, &p.keys);
   be_image_panel(p, (cnr_stream)stream);
   return check_backend("image_panel");
 }

@@ -369,17 +369,10 @@ void be_prune_count(const PruneCount& p, cnr_stream s) {
 __global__ __launch_bounds__(1024) void prune_scan_kernel(const PruneScan p) {
   __shared__ int wsum[1][16];
   __shared__ int carry[1];
-  const int tid = threadIdx.x;
-  if (tid == 0) carry[0] = 0;
-  __syncthreads();
-  for (long base = 0; base < p.R; base += 1024) {
-    const long i = base + tid;
-    const int x[1] = {i < p.R ? p.counts[i] : 0};
-    int excl[1];
-    block_excl_scan<16, 1, int>(x, excl, wsum, carry);
-    if (i < p.R) p.offsets[i] = excl[0];
-  }
-  if (tid == 0) p.offsets[p.R] = carry[0];
+  block_carried_scan<16, 1, 1, int>(p.R, wsum, carry,
+                                    [&](long i, int (&x)[1]) { x[0] += p.counts[i]; },
+                                    [&](long i, const int (&at)[1]) { p.offsets[i] = at[0]; });
+  if (threadIdx.x == 0) p.offsets[p.R] = carry[0];
 }
 void be_prune_scan(const PruneScan& p, cnr_stream s) {
   TimingScope ts_("prune_scan", 2, 0, p.R, 0, 0, 0, s);

@@ -75,18 +75,11 @@ __global__ __launch_bounds__(kPixThreads) void pixel_count_kernel(const PixelTab
 __global__ __launch_bounds__(kPixThreads) void pixel_scan_kernel(const PixelTable t) {
   __shared__ int wsum[2][kPixWaves];
   __shared__ int carry[2];
-  const int tid = threadIdx.x;
   int* counts = t.tile_counts + (long)blockIdx.x * t.tiles * 2;
-  if (tid < 2) carry[tid] = 0;
-  __syncthreads();
-  for (long base = 0; base < t.tiles; base += kPixThreads) {
-    const long i = base + tid;
-    const int x[2] = {i < t.tiles ? counts[i * 2] : 0, i < t.tiles ? counts[i * 2 + 1] : 0};
-    int excl[2];
-    block_excl_scan<kPixWaves, 2, int>(x, excl, wsum, carry);
-    if (i < t.tiles) { counts[i * 2] = excl[0]; counts[i * 2 + 1] = excl[1]; }
-  }
-  if (tid == 0) { t.fg_count[blockIdx.x] = carry[0]; t.bg_count[blockIdx.x] = carry[1]; }
+  block_carried_scan<kPixWaves, 1, 2, int>(t.tiles, wsum, carry,
+                                           [&](long i, int (&x)[2]) { x[0] += counts[i * 2]; x[1] += counts[i * 2 + 1]; },
+                                           [&](long i, const int (&at)[2]) { counts[i * 2] = at[0]; counts[i * 2 + 1] = at[1]; });
+  if (threadIdx.x == 0) { t.fg_count[blockIdx.x] = carry[0]; t.bg_count[blockIdx.x] = carry[1]; }
 }
 
 __global__ __launch_bounds__(kPixThreads) void pixel_scatter_kernel(const PixelTable t) {

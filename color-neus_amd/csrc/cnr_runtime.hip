@@ -84,10 +84,11 @@ int be_check_last_error(char* msg, size_t n) {
   return -1;
 }
 
-void be_memset_zero(void* p, size_t bytes, cnr_stream s) {
-  hipError_t e = hipMemsetAsync(p, 0, bytes, s);
-  if (e != hipSuccess && g_first_error == hipSuccess) { g_first_error = e; g_first_error_where = "memset"; }
+void device_fill(void* p, int byte, size_t bytes, hipStream_t s, const char* where) {
+  hipError_t e = hipMemsetAsync(p, byte, bytes, s);
+  if (e != hipSuccess && g_first_error == hipSuccess) { g_first_error = e; g_first_error_where = where; }
 }
+void be_memset_zero(void* p, size_t bytes, cnr_stream s) { device_fill(p, 0, bytes, s, "memset"); }
 
 __global__ void zero_cols_kernel(float* p, int ld, int c0, int c1, long rows) {
   const int w = c1 - c0;

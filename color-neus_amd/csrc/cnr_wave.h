@@ -3,6 +3,7 @@
 // Float folds have ONE order (results are compared bit for bit between launches and builds); the integer ones are exact in any order.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace cnr {
 
@@ -113,6 +114,36 @@ __device__ __forceinline__ void block_excl_scan(const T (&x)[CH], T (&excl)[CH],
     }
     __syncthreads();
   }
+}
+
+// The carried scan of ONE workgroup of NWAVES waves through n elements: an exclusive scan of CH channels in trips of NWAVES * 64 * PER elements,
+// thread t of a trip owning PER consecutive ones.  read(i, x) adds element i's contribution to the channel sums x[CH] and may return a small
+// payload, kept in registers until the write-back; write(i, at, payload) -- write(i, at) when read returns nothing -- stores element i from the
+// running offsets at[CH] (the exclusive values on arrival at the thread's first element) and moves them past the element when PER > 1.  Neither
+// is called for i >= n.  wsum and carry are the caller's, as with block_excl_scan; the carry is zeroed here and holds the grand totals on return
+// (visible to every thread: the last trip ends behind a barrier).  The whole workgroup must arrive.
+template <int NWAVES, int PER, int CH, class T, class I, class Read, class Write>
+__device__ __forceinline__ void block_carried_scan(I n, T (*wsum)[NWAVES], T* carry, Read read, Write write) {
+  using P = decltype(read(n, *static_cast<T (*)[CH]>(nullptr)));   // the payload's type; void: read keeps nothing
+  constexpr bool kKeeps = !std::is_void_v<P>;
+  if (threadIdx.x < CH) carry[threadIdx.x] = (T)0;
+  __syncthreads();
+  for (I base = 0; base < n; base += NWAVES * 64 * PER) {
+    const I i0 = base + (I)threadIdx.x * PER;
+    T x[CH] = {}, at[CH];
+    std::conditional_t<kKeeps, P, char> keep[PER] = {};
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (i0 + j < n) { if constexpr (kKeeps) keep[j] = read(i0 + j, x); else read(i0 + j, x); }
+    block_excl_scan<NWAVES, CH, T>(x, at, wsum, carry);
+#pragma unroll
+    for (int j = 0; j < PER; ++j) if (i0 + j < n) { if constexpr (kKeeps) write(i0 + j, at, keep[j]); else write(i0 + j, at); }
+  }
+}
+
+// A bid for the largest 64-bit key in *best.  Bid only when you can win: a key not above the best so far (a relaxed agent-scope load) cannot
+// change it, and its atomic on the one word would only make the others wait.
+__device__ __forceinline__ void bid_max(unsigned long long* best, unsigned long long key) {
+  if (key > __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(best, key);
 }
 
 // ---- appending to a list in global memory ------------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ptr, stream_of
+from ._lib import points3, ptr, stream_of
 
 __all__ = ["connected_components", "clean_mesh", "sample_surface"]
 
@@ -34,16 +34,6 @@ def _triangles(t, dev=None):
         # an index that does not fit int32 is outside [0, V) for every V the library takes: it stays invalid (-1) instead of wrapping
         t = torch.where((t < 0) | (t > 2 ** 31 - 1), torch.full_like(t, -1), t)
     return t.to(device=dev if dev is not None else t.device, dtype=torch.int32).contiguous()
-
-
-def _floats(x, name, dev, rows=None):
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(np.asarray(x))
-    if x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
-        raise ValueError(f"{name}: expected a floating-point (N, 3) tensor, got {tuple(x.shape)} {x.dtype}")
-    if rows is not None and x.shape[0] != rows:
-        raise ValueError(f"{name}: expected {rows} rows, got {x.shape[0]}")
-    return x.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
 def _components(t, n_vertices, lib):
@@ -96,9 +86,9 @@ def clean_mesh(vertices, triangles, colors=None, keep="largest", min_faces=0, mi
         raise ValueError("clean_mesh: keep='largest' takes no min_faces / min_ratio (use keep='threshold')")
     dev = vertices.device if torch.is_tensor(vertices) else (triangles.device if torch.is_tensor(triangles) else torch.device("cpu"))
     lib = _lib.library_for(library, dev, ("a mesh", "cleaned"))
-    v = _floats(vertices, "vertices", dev)
+    v = points3(vertices, "vertices", dev)
     t = _triangles(triangles, dev)
-    col = _floats(colors, "colors", dev, v.shape[0]) if colors is not None else None
+    col = points3(colors, "colors", dev, v.shape[0]) if colors is not None else None
     V, F = v.shape[0], t.shape[0]
     labels, face_count, vertex_count, summary, dropped = _components(t, V, lib)
     keep_vertex, keep_face = torch.empty(V, dtype=torch.uint8, device=dev), torch.empty(F, dtype=torch.uint8, device=dev)
@@ -157,9 +147,9 @@ def sample_surface(vertices, triangles, n_samples, seed=0, colors=None, library=
     seed = seed - 2 ** 64 if seed >= 2 ** 63 else seed
     dev = vertices.device if torch.is_tensor(vertices) else (triangles.device if torch.is_tensor(triangles) else torch.device("cpu"))
     lib = _lib.library_for(library, dev, ("a mesh", "sampled"))
-    v = _floats(vertices, "vertices", dev)
+    v = points3(vertices, "vertices", dev)
     t = _triangles(triangles, dev)
-    col = _floats(colors, "colors", dev, v.shape[0]) if colors is not None else None
+    col = points3(colors, "colors", dev, v.shape[0]) if colors is not None else None
     if t.shape[0] == 0:
         raise ValueError("sample_surface: the mesh has no faces")
     cdf, summary = _area_cdf(v, t, lib)

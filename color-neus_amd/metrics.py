@@ -13,7 +13,7 @@ CPU fallback).  NOTHING HERE IS DIFFERENTIABLE: inputs are detached and results 
 import torch
 
 from . import _lib, meshio, meshops
-from ._lib import ptr, stream_of
+from ._lib import points3, ptr, stream_of
 
 __all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance", "point_mesh_distance",
            "surface_metrics", "compute_surface_metrics"]
@@ -21,14 +21,6 @@ __all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "me
 
 def _library(library, dev):
     return _lib.library_for(library, dev, ("points", "searched"))
-
-
-def _points(x, name):
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(x)
-    if x.dim() != 2 or x.shape[1] != 3 or not x.is_floating_point():
-        raise ValueError(f"{name}: expected a floating-point (N, 3) tensor, got {tuple(x.shape)} {x.dtype}")
-    return x.detach().to(torch.float32).contiguous()
 
 
 def _search(q, t, lib):
@@ -46,7 +38,7 @@ def _search(q, t, lib):
 
 
 def _pair(x, y, names, library):
-    x, y = _points(x, names[0]), _points(y, names[1])
+    x, y = points3(x, names[0]), points3(y, names[1])
     if x.device != y.device:
         raise ValueError(f"{names[0]} is on {x.device}, {names[1]} on {y.device}")
     return x, y, _library(library, x.device)
@@ -72,10 +64,6 @@ def normalize_point_cloud(pc):
     return pc / m, centroid, m
 
 
-def _mean64(d):
-    return d.to(torch.float64).mean()
-
-
 def chamfer_distance(x, y, norm=False, library=None):
     """``mean_i min_j |x_i - y_j|^2 + mean_j min_i |x_i - y_j|^2`` as a 0-dim float64 tensor on the inputs' device: squared distances, the mean
     over the points of each direction, the two directions added.
@@ -92,7 +80,7 @@ def chamfer_distance(x, y, norm=False, library=None):
         x, y = normalize_point_cloud(x)[0].contiguous(), normalize_point_cloud(y)[0].contiguous()
     dxy, _ = _search(x, y, lib)
     dyx, _ = _search(y, x, lib)
-    return _mean64(dxy) + _mean64(dyx)
+    return dxy.to(torch.float64).mean() + dyx.to(torch.float64).mean()
 
 
 def mesh_metrics(pred, gt, thresholds=(0.01, 0.02, 0.05), library=None):
@@ -107,24 +95,14 @@ def mesh_metrics(pred, gt, thresholds=(0.01, 0.02, 0.05), library=None):
         raise ValueError("mesh_metrics: empty point cloud")
     d2_pg, _ = _search(p, g, lib)
     d2_gp, _ = _search(g, p, lib)
-    d_pg, d_gp = d2_pg.to(torch.float64).sqrt(), d2_gp.to(torch.float64).sqrt()
-    acc, comp = d_pg.mean(), d_gp.mean()
-    out = {"accuracy": float(acc), "completeness": float(comp), "chamfer_l1": float((acc + comp) * 0.5),
-           "chamfer_l2": float(_mean64(d2_pg) + _mean64(d2_gp))}
-    for t in thresholds:
-        prec = float((d_pg < float(t)).sum()) / p.shape[0]
-        rec = float((d_gp < float(t)).sum()) / g.shape[0]
-        out[f"precision@{t:g}"], out[f"recall@{t:g}"] = prec, rec
-        out[f"fscore@{t:g}"] = 2.0 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0
-    return out
+    return _figures(d2_pg, d2_gp, thresholds, None)
 
 
 def _mesh(mesh, name, dev=None):
     """``(vertices, triangles)`` -> contiguous float32 (V, 3) and int32 (F, 3) on the vertices' device; F == 0 raises ValueError."""
     if not isinstance(mesh, (tuple, list)) or len(mesh) != 2:
         raise ValueError(f"{name}: expected a (vertices, triangles) pair")
-    v = _points(mesh[0], f"{name} vertices")
-    v = v if dev is None else v.to(dev)
+    v = points3(mesh[0], f"{name} vertices", dev)
     t = meshops._triangles(mesh[1], v.device)
     if t.shape[0] == 0:
         raise ValueError(f"{name}: the mesh has no faces")
@@ -138,7 +116,7 @@ def _closest_face(q, v, t, lib, want_closest=False):
     face = torch.empty(n, dtype=torch.int32, device=dev)
     closest = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_closest else None
     if n > 0:
-        keys = torch.empty(n, dtype=torch.int64, device=dev)      # the library's uint64 candidate keys: scratch, never read here
+        keys, _ = lib.scratch("cnr_point_mesh_distance", dev, nbytes=8 * n)      # the library's uint64 candidate keys, one per query
         lib.call("cnr_point_mesh_distance", ptr(q), n, ptr(v), v.shape[0], ptr(t), t.shape[0], ptr(dist2), ptr(face), ptr(closest), ptr(keys),
                  stream_of(dev))
     return dist2, face, closest
@@ -152,7 +130,7 @@ def point_mesh_distance(points, vertices, triangles, return_closest=False, libra
     (include/colorneus_render.h writes the order of operations down); of several faces at the minimal distance the one with the LOWEST index is
     returned.  A face with an index outside ``[0, V)`` or a non-finite distance never wins; a point with a NaN coordinate gets ``face = -1`` and
     NaN.  A mesh without faces raises ValueError; no points gives empty tensors.  Not differentiable."""
-    q = _points(points, "points")
+    q = points3(points, "points")
     v, t = _mesh((vertices, triangles), "mesh", q.device)
     lib = _lib.library_for(library, q.device, ("points", "measured"))
     dist2, face, closest = _closest_face(q, v, t, lib, return_closest)
@@ -200,7 +178,7 @@ def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 
         gs = meshops.sample_surface(gv, gtri, n_samples, seed=int(seed) + 1, library=lib)[0]
         d2_pg = _closest_face(ps, gv, gtri, lib)[0] if exact else _search(ps, gs, lib)[0]
     else:
-        gs = _points(gt, "gt").to(dev)
+        gs = points3(gt, "gt", dev)
         if gs.shape[0] == 0:
             raise ValueError("surface_metrics: the gt cloud is empty")
         d2_pg = _search(ps, gs, lib)[0]

@@ -207,6 +207,39 @@ def test_the_wave_primitives_have_one_definition():
     assert attr and set(attr) <= {"cnr_hip_util.h", "cnr_chain_util.h"}, attr
 
 
+def test_the_search_scan_and_fill_steps_have_one_definition():
+    """The evaluation kernels' shared steps: hipMemsetAsync is called by device_fill (cnr_runtime.hip) alone; the trip loop around a carried
+    block_excl_scan is block_carried_scan (cnr_wave.h) alone -- every other call of block_excl_scan is the single trip without a carry, but for
+    the one named site below; the
+    fold of a lane's best key into keys[] and the split of the candidate range ("BlocksWanted") are closest_search / search_split
+    (cnr_search.h) alone; the bid in front of a 64-bit atomicMax is bid_max (cnr_wave.h) alone; and the marching-cubes scratch has its round-ups
+    in one layout function of cnr_ops.cpp."""
+    csrc = os.path.join(ROOT, "color-neus_amd", "csrc")
+    code = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h", ".cpp")):
+            code[fn] = "\n".join(line.split("//")[0] for line in open(os.path.join(csrc, fn)).read().split("\n"))
+    assert [fn for fn, text in code.items() if "hipMemsetAsync(" in text] == ["cnr_runtime.hip"]
+    # the one site that keeps its own trip loop, as the issue provides for a kernel whose shared form misses the parent's time:
+    #   cnr_meshcc.hip  meshcc_scan_kernel: its flags are summed behind the bounds branches, so a thread's eight loads are in flight together; through
+    #                   block_carried_scan every load is waited for inside its branch (same registers, 0.711 ms against 0.698 ms: its comment, and
+    #                   profiles/eval_steps_refactor_ab.txt)
+    own_trips = {"cnr_meshcc.hip": 1}
+    calls = [(fn, m.group(0)) for fn, text in code.items() if fn != "cnr_wave.h" for m in re.finditer(r"block_excl_scan<[^;]*;", text)]
+    carried = {}
+    for fn, c in calls:
+        if not re.search(r"nullptr\)\s*;$", c):
+            carried[fn] = carried.get(fn, 0) + 1
+    assert calls and carried == own_trips, carried
+    lines = [(fn, line) for fn, text in code.items() for line in text.split("\n")]
+    folds = [fn for fn, line in lines if "atomicMin(" in line and "nn_key(" in line]
+    assert folds == ["cnr_search.h"], folds
+    assert [fn for fn, text in code.items() if "BlocksWanted" in text] == ["cnr_search.h"]
+    bids = [fn for fn, line in lines if "__hip_atomic_load(" in line and "atomicMax(" in line]
+    assert bids == ["cnr_wave.h"], bids
+    assert code["cnr_ops.cpp"].count("round_up_sz(n * 2 * sizeof(int), 256)") == 1
+
+
 def test_missing_library_fails_loudly(tmp_path):
     with pytest.raises(RuntimeError, match="no CPU/PyTorch fallback"):
         _lib.RenderLibrary(str(tmp_path / "libcolorneus_hip.so"))

@@ -121,6 +121,25 @@ def test_few_queries_many_targets(backend):
     _assert_bitwise_r32(q, t, dist2, idx)
 
 
+# query counts at one workgroup's load (256 threads x 4 queries) and that +- 1; target counts at one LDS tile (1024) and that +- 1
+# (test_edges runs 1 x 1 and 300 x 400: no pair of these)
+QUERIES_PER_WORKGROUP = TARGETS_PER_TILE = 1024
+SHAPES = [(QUERIES_PER_WORKGROUP - 1, 1500), (QUERIES_PER_WORKGROUP, 1500), (QUERIES_PER_WORKGROUP + 1, 1500),
+          (100, TARGETS_PER_TILE - 1), (100, TARGETS_PER_TILE), (100, TARGETS_PER_TILE + 1)]
+
+
+@pytest.mark.parametrize("n,m", SHAPES)
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_launch_shapes(backend, n, m):
+    """R32, bitwise."""
+    lib, dev = _lib_and_dev(backend)
+    g = torch.Generator().manual_seed(1000 * n + m)
+    q = torch.rand(n, 3, generator=g) * 2 - 1
+    t = torch.rand(m, 3, generator=g) * 2 - 1
+    dist2, idx = cn.metrics.nearest_neighbors(q.to(dev), t.to(dev), library=lib)
+    _assert_bitwise_r32(q, t, dist2, idx)
+
+
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_edges(backend):
     lib, dev = _lib_and_dev(backend)

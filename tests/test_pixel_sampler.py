@@ -153,7 +153,8 @@ def _f32bits(a):
 
 # ---- 1. the table ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("backend", BACKENDS)
-@pytest.mark.parametrize("H,W,special", [(1, 1, False), (67, 129, False), (97, 131, False), (67, 129, True)])   # 97 * 131 = 3.1 tiles of 4096 pixels
+# 97 * 131 = 3.1 tiles of 4096 pixels; 1025 * 1024 = 257 tiles: the scan of the tile counts (256 threads, one tile each) makes a second trip
+@pytest.mark.parametrize("H,W,special", [(1, 1, False), (67, 129, False), (97, 131, False), (67, 129, True), (1025, 1024, False)])
 def test_table_against_nonzero(backend, H, W, special):
     library, dev = _lib_and_dev(backend)
     masks = _masks(H, W, special)

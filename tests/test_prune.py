@@ -9,13 +9,12 @@ import _golden as G
 import _native as N
 
 
-def _check(library, device, name):
+def _check(library, device, name, repeat=1):
+    """``repeat``: the fixture's rays tiled that many times."""
     fx = G.load(name)
     ocfg, P = G.weights_of(name, fx)
     r = N.make_renderer(ocfg, P, library, device)
-    o, d = torch.from_numpy(fx["rays_o"]).to(device), torch.from_numpy(fx["rays_d"]).to(device)
-    near, far = torch.from_numpy(fx["jit:near"]).to(device), torch.from_numpy(fx["jit:far"]).to(device)
-    z = torch.from_numpy(fx["jit:z_vals"]).to(device)
+    o, d, near, far, z = (torch.cat([torch.from_numpy(fx[k])] * repeat).to(device) for k in ("rays_o", "rays_d", "jit:near", "jit:far", "jit:z_vals"))
     eps = 1e-3
     with torch.no_grad():
         full = r(o, d, near, far, z_vals=z)
@@ -48,6 +47,16 @@ def test_prune_emu(name):
 @pytest.mark.parametrize("name", ["tiny_sharp", "tiny_neus_sharp", "dtu_sharp"])
 def test_prune_hip(name):
     _check(None, "cuda:0", name)
+
+
+@pytest.mark.gpu
+def test_prune_hip_second_trip_of_the_scan():
+    """prune_scan_kernel walks the rays in trips of 1024: the fixture's rays tiled to the smallest count that is at least 1025 and no multiple
+    of 1024, under _check's assertions."""
+    R = G.load("tiny_sharp")["rays_o"].shape[0]
+    repeat = next(k for k in range(1, 2048) if k * R >= 1025 and k * R % 1024)
+    assert repeat * R == 1056
+    _check(None, "cuda:0", "tiny_sharp", repeat)
 
 
 def _pruned_forward(library, device, n_rays, eps):
