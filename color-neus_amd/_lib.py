@@ -292,6 +292,37 @@ def points3(x, name, dev=None, rows=None):
     return x.detach().to(device=dev, dtype=torch.float32).contiguous()
 
 
+def dense_f32(t, *shape):
+    """``t`` as the detached contiguous float32 tensor the library reads, reshaped to ``shape`` when one is given; None stays None.  For a
+    contiguous float32 tensor that is the same storage and no launch.  It does not move ``t``: a ``.to(device)`` stays with the caller."""
+    if t is None:
+        return None
+    t = t.detach()
+    return (t.reshape(*shape) if shape else t).contiguous().float()
+
+
+def grad_f32(g):
+    """A backward pass's incoming gradient as a contiguous float32 tensor (dense_f32 without the detach); None (unused output) stays None."""
+    return g.contiguous().float() if g is not None else None
+
+
+def save_named(ctx, tail=(), **tensors):
+    """ctx.save_for_backward of the named tensors that are not None, then of the list ``tail`` (the parameters).  Which names are present
+    is recorded on ``ctx``, so that an absent tensor needs no placeholder and a real zero-element tensor is not taken for one.  Everything
+    goes through save_for_backward: a tensor held in a plain ctx attribute would form an uncollectable tensor -> grad_fn -> ctx -> tensor
+    cycle."""
+    ctx.saved_names = tuple(tensors)
+    ctx.saved_present = tuple(t is not None for t in tensors.values())
+    ctx.save_for_backward(*[t for t in tensors.values() if t is not None], *tail)
+
+
+def saved_named(ctx):
+    """What save_named saved: ({name: tensor, or None for an absent one}, tail list)."""
+    it = iter(ctx.saved_tensors)
+    named = {k: (next(it) if here else None) for k, here in zip(ctx.saved_names, ctx.saved_present)}
+    return named, list(it)
+
+
 def param_array(tensors, n=None):
     """The addresses of ``tensors`` as a ``void*[n]`` (n: len(tensors) unless given); a None entry and every slot past the list are NULL."""
     return (C.c_void_p * (len(tensors) if n is None else n))(*[t.data_ptr() if t is not None else None for t in tensors])

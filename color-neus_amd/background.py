@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import param_array, ptr, stream_of
+from ._lib import dense_f32, grad_f32, param_array, ptr, save_named, saved_named, stream_of
 
 
 class NeRF(nn.Module):
@@ -60,27 +60,25 @@ class OutsideZ(torch.autograd.Function):
     def forward(ctx, lib, far, t_rand, z_vals, n_samples, n_outside):
         R, M = z_vals.shape
         dev = z_vals.device
-        far_c = far.detach().reshape(-1).contiguous().float()
-        z_c = z_vals.detach().contiguous().float()
-        t_c = t_rand.detach().to(dev).contiguous().float() if t_rand is not None else None
+        far_c, z_c = dense_f32(far, -1), dense_f32(z_vals)
+        t_c = dense_f32(t_rand.to(dev)) if t_rand is not None else None
         z_feed = torch.empty(R, M + n_outside, dtype=torch.float32, device=dev)
         src = torch.empty(R, M + n_outside, dtype=torch.int32, device=dev)
         lib.call("cnr_outside_z", ptr(far_c), ptr(t_c), ptr(z_c), R, M, n_outside, n_samples, ptr(z_feed), ptr(src), stream_of(z_c))
-        ctx.lib, ctx.meta = lib, (R, M, n_samples, n_outside, far.shape, t_c is not None)
-        ctx.save_for_backward(src, t_c if t_c is not None else torch.empty(0, device=dev))
+        ctx.lib, ctx.meta = lib, (R, M, n_samples, n_outside, far.shape)
+        save_named(ctx, src=src, t_rand=t_c)
         ctx.mark_non_differentiable(src)
         return z_feed, src
 
     @staticmethod
     def backward(ctx, d_z_feed, _d_src):
-        src, t_c = ctx.saved_tensors
-        R, M, n_samples, n_outside, far_shape, has_t = ctx.meta
-        lib = ctx.lib
-        dz = d_z_feed.contiguous().float()
+        sv, _ = saved_named(ctx)
+        R, M, n_samples, n_outside, far_shape = ctx.meta
+        dz = grad_f32(d_z_feed)
         d_far = torch.empty(R, dtype=torch.float32, device=dz.device)
         d_z = torch.empty(R, M, dtype=torch.float32, device=dz.device) if ctx.needs_input_grad[3] else None
-        lib.call("cnr_outside_z_backward", ptr(t_c if has_t else None), ptr(src), ptr(dz), R, M, n_outside, n_samples, ptr(d_far), ptr(d_z),
-                 stream_of(dz))
+        ctx.lib.call("cnr_outside_z_backward", ptr(sv["t_rand"]), ptr(sv["src"]), ptr(dz), R, M, n_outside, n_samples, ptr(d_far), ptr(d_z),
+                     stream_of(dz))
         return None, d_far.reshape(far_shape), None, d_z, None, None
 
 
@@ -91,28 +89,26 @@ class Background(torch.autograd.Function):
     def forward(ctx, lib, ncfg, sample_dist, rays_o, rays_d, z_feed, *params):
         R, MF = z_feed.shape
         dev = z_feed.device
-        o, d, zf = rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float(), z_feed.detach().contiguous().float()
-        plist = [p.detach().contiguous().float() for p in params]
+        o, d, zf = dense_f32(rays_o), dense_f32(rays_d), dense_f32(z_feed)
+        plist = [dense_f32(p) for p in params]
         alpha = torch.empty(R, MF, dtype=torch.float32, device=dev)
         color = torch.empty(R, MF, 3, dtype=torch.float32, device=dev)
         buf, nb = lib.scratch("cnr_background_ctx_bytes", dev, C.byref(ncfg), R, MF)
         lib.call("cnr_background_forward", C.byref(ncfg), param_array(plist), ptr(o), ptr(d), ptr(zf), R, MF, float(sample_dist), ptr(alpha),
                  ptr(color), ptr(buf), nb, stream_of(zf))
-        ctx.lib, ctx.ncfg, ctx.meta = lib, ncfg, (R, MF, float(sample_dist), len(plist))
-        ctx.save_for_backward(o, d, zf, color, buf, *plist)
+        ctx.lib, ctx.ncfg, ctx.meta = lib, ncfg, (R, MF, float(sample_dist))
+        save_named(ctx, plist, o=o, d=d, zf=zf, color=color, buf=buf)
         ctx.set_materialize_grads(False)
         return alpha, color
 
     @staticmethod
     def backward(ctx, d_alpha, d_color):
         lib, ncfg = ctx.lib, ctx.ncfg
-        R, MF, sample_dist, npar = ctx.meta
-        sv = ctx.saved_tensors
-        o, d, zf, color, buf = sv[:5]
-        plist = list(sv[5:])
+        R, MF, sample_dist = ctx.meta
+        sv, plist = saved_named(ctx)
+        o, d, zf, color, buf = (sv[k] for k in ("o", "d", "zf", "color", "buf"))
         dev = zf.device
-        da = d_alpha.contiguous().float() if d_alpha is not None else None
-        dc = d_color.contiguous().float() if d_color is not None else None
+        da, dc = grad_f32(d_alpha), grad_f32(d_color)
         flat, gviews, garr = _lib.flat_grads(plist, dev)
         d_o, d_d = torch.empty(R, 3, dtype=torch.float32, device=dev), torch.empty(R, 3, dtype=torch.float32, device=dev)
         d_zf = torch.empty(R, MF, dtype=torch.float32, device=dev)
@@ -127,6 +123,12 @@ class Background(torch.autograd.Function):
 _COMP_OUT = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "weights", "gradient_error", "depth", "global_color"]
 
 
+def composite_output_names(has_gc):
+    """(differentiable names, non-differentiable names) of the tuple CompositeBg returns, in its order; ``has_gc``: global_color_samples were
+    given (Color_NeuS).  The one place that order is stated: forward, backward and the renderer all name the tuple through it."""
+    return [k for k in _COMP_OUT if has_gc or k != "global_color"], ["inside_sphere", "eik_sums"]
+
+
 class CompositeBg(torch.autograd.Function):
     """The tail of render_core with a background: S-density alpha, inside / outside mixing, compositing over M + N_OUTSIDE samples."""
 
@@ -137,9 +139,9 @@ class CompositeBg(torch.autograd.Function):
         MF = z_feed.shape[1]
         dev = z_vals.device
         f32 = dict(dtype=torch.float32, device=dev)
-        c = lambda t: t.detach().contiguous().float() if t is not None else None
+        c = dense_f32
         t = dict(rays_o=c(rays_o), rays_d=c(rays_d), z_vals=c(z_vals), z_feed=c(z_feed), sdf=c(sdf), grads=c(grads), color=c(color), gcolor=c(gcolor),
-                 bg_alpha=c(bg_alpha), bg_color=c(bg_color), variance=c(variance).reshape(-1), bg=c(background_rgb))
+                 bg_alpha=c(bg_alpha), bg_color=c(bg_color), variance=c(variance, -1), bg=c(background_rgb))
         out = dict(color_fine=torch.empty(R, 3, **f32), s_val=torch.empty(R, 1, **f32), cdf_fine=torch.empty(R, M, **f32), weight_sum=torch.empty(R, 1, **f32),
                    weight_max=torch.empty(R, 1, **f32), weights=torch.empty(R, MF, **f32), gradient_error=torch.empty((), **f32),
                    inside_sphere=torch.empty(R, M, **f32), depth=torch.empty(R, **f32), global_color=torch.empty(R, 3, **f32) if gcolor is not None else None,
@@ -148,15 +150,12 @@ class CompositeBg(torch.autograd.Function):
         cout = _lib.CnrOutputs(**{k: ptr(out.get(k)) for k in _lib.OUTPUT_FIELDS})
         scratch, nb = lib.scratch("cnr_composite_background_scratch_bytes", dev, R)
         lib.call("cnr_composite_background_forward", C.byref(cin), C.byref(cout), ptr(scratch), nb, stream_of(t["z_vals"]))
-        ctx.lib, ctx.meta = lib, (R, M, MF, float(sample_dist), float(cos_anneal_ratio), gcolor is not None, background_rgb is not None, variance.shape)
-        ctx.save_for_backward(*[t[k] if t[k] is not None else torch.empty(0, **f32) for k in
-                                ("rays_o", "rays_d", "z_vals", "z_feed", "sdf", "grads", "color", "gcolor", "bg_alpha", "bg_color", "variance", "bg")],
-                              out["weights"], out["eik_sums"])
+        ctx.lib, ctx.meta = lib, (R, M, MF, float(sample_dist), float(cos_anneal_ratio), gcolor is not None, variance.shape)
+        save_named(ctx, **t, weights=out["weights"], eik_sums=out["eik_sums"])
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(out["inside_sphere"], out["eik_sums"])
-        ctx.has_gc = gcolor is not None
-        res = [out[k] for k in _COMP_OUT if out[k] is not None]
-        return (*res, out["inside_sphere"], out["eik_sums"])
+        diff, non_diff = composite_output_names(gcolor is not None)
+        ctx.mark_non_differentiable(*[out[k] for k in non_diff])
+        return tuple(out[k] for k in diff + non_diff)
 
     @staticmethod
     def _cin(t, R, M, MF, sample_dist, cos_anneal_ratio):
@@ -169,15 +168,12 @@ class CompositeBg(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gouts):
         lib = ctx.lib
-        R, M, MF, sample_dist, car, has_gc, has_bg, var_shape = ctx.meta
-        sv = ctx.saved_tensors
-        keys = ("rays_o", "rays_d", "z_vals", "z_feed", "sdf", "grads", "color", "gcolor", "bg_alpha", "bg_color", "variance", "bg")
-        t = {k: (v if v.numel() > 0 else None) for k, v in zip(keys, sv[:12])}
-        weights, eik_sums = sv[12], sv[13]
+        R, M, MF, sample_dist, car, has_gc, var_shape = ctx.meta
+        t, _ = saved_named(ctx)
+        weights, eik_sums = t["weights"], t["eik_sums"]
         dev = weights.device
         f32 = dict(dtype=torch.float32, device=dev)
-        names = [k for k in _COMP_OUT if has_gc or k != "global_color"]
-        g = {k: (v.contiguous().float() if v is not None else None) for k, v in zip(names, gouts[:len(names)])}
+        g = {k: grad_f32(v) for k, v in zip(composite_output_names(has_gc)[0], gouts)}
         go = _lib.CnrOutGrads(**{k: ptr(g.get(k)) for k in _lib.OUT_GRAD_FIELDS})
         cin = CompositeBg._cin(t, R, M, MF, sample_dist, car)
         cout = _lib.CnrOutputs(**{k: ptr({"weights": weights, "eik_sums": eik_sums}.get(k)) for k in _lib.OUTPUT_FIELDS})

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import ptr, stream_of
+from ._lib import dense_f32, ptr, save_named, saved_named, stream_of
 
 __all__ = ["FocalNet", "PoseNet", "Cameras", "cameras_from_state_dict"]
 
@@ -32,10 +32,6 @@ _POSE_MODE = {"3d": 0, "6d": 1}
 
 def _library(library, dev):
     return _lib.library_for(library, dev, ("camera parameters", "evaluated"))
-
-
-def _f32(t):
-    return t.detach().contiguous().float()
 
 
 class _CameraFunction(torch.autograd.Function):
@@ -47,10 +43,10 @@ class _CameraFunction(torch.autograd.Function):
         num_cams, pose_mode, order, fx_only, H, W = meta
         dev = (r if r is not None else fx).device
         f32 = dict(dtype=torch.float32, device=dev)
-        rc, tc = (_f32(r), _f32(t)) if r is not None else (None, None)
-        ic = _f32(init_c2w) if init_c2w is not None and r is not None else None
-        fxc = _f32(fx).reshape(-1) if fx is not None else None
-        fyc = _f32(fy).reshape(-1) if fy is not None and fx is not None else None
+        rc, tc = dense_f32(r), dense_f32(t if r is not None else None)
+        ic = dense_f32(init_c2w if r is not None else None)
+        fxc = dense_f32(fx, -1)
+        fyc = dense_f32(fy if fx is not None else None, -1)
         B = (ids.shape[0] if ids is not None else num_cams) if r is not None else 0
         c2w = torch.empty(B, 4, 4, **f32) if r is not None else None
         focal = torch.empty(2, **f32) if fx is not None else None
@@ -62,16 +58,14 @@ class _CameraFunction(torch.autograd.Function):
                      ptr(fxc), ptr(fyc), ptr(ids if pose else None), B, ptr(c2w if pose else None), ptr(focal), stream_of(dev))
         ctx.lib, ctx.cfg, ctx.B = lib, cfg, B
         ctx.shapes = (fx.shape if fx is not None else None, fy.shape if fy is not None else None)
-        saved = (ids, rc, tc, ic, fxc, fyc)
-        ctx.present = tuple(x is not None for x in saved)
-        ctx.save_for_backward(*[x for x in saved if x is not None])
+        save_named(ctx, ids=ids, r=rc, t=tc, init_c2w=ic, fx=fxc, fy=fyc)
         ctx.set_materialize_grads(False)
         return (c2w if c2w is not None else torch.empty(0, 4, 4, **f32)), (focal if focal is not None else torch.empty(0, **f32))
 
     @staticmethod
     def backward(ctx, d_c2w, d_focal):
-        it = iter(ctx.saved_tensors)
-        ids, rc, tc, ic, fxc, fyc = (next(it) if here else None for here in ctx.present)
+        sv, _ = saved_named(ctx)
+        ids, rc, tc, ic, fxc, fyc = (sv[k] for k in ("ids", "r", "t", "init_c2w", "fx", "fy"))
         need_r, need_t, need_fx, need_fy = (ctx.needs_input_grad[i] for i in (3, 4, 6, 7))
         B = ctx.B
         pose = (need_r or need_t) and B > 0 and d_c2w is not None
@@ -87,8 +81,8 @@ class _CameraFunction(torch.autograd.Function):
         if focal and d_fx is None and d_fy is None:
             focal = False
         if pose or focal:
-            g_c = _f32(d_c2w) if pose else None
-            g_f = _f32(d_focal) if focal else None
+            g_c = dense_f32(d_c2w) if pose else None
+            g_f = dense_f32(d_focal) if focal else None
             ctx.lib.call("cnr_camera_backward", C.byref(ctx.cfg), ptr(rc if pose else None), ptr(tc if pose else None),
                          ptr(ic if pose else None), ptr(fxc if focal else None), ptr(fyc if focal else None), ptr(ids if pose else None), B,
                          ptr(g_c), ptr(g_f), ptr(d_r), ptr(d_t), ptr(d_fx), ptr(d_fy), stream_of(dev))

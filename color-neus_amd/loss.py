@@ -39,7 +39,7 @@ def compute_loss(render_dict, rgb_gt, mask=None, lambda_fine=1.0, lambda_eikonal
 # ---------------------------------------------------------------------------------------------------------------------
 import ctypes as _C
 
-from ._lib import CnrLossConfig, ptr, resolve_library, stream_of
+from ._lib import CnrLossConfig, ptr, resolve_library, save_named, saved_named, stream_of
 
 _SCRATCH = {}   # (library path, device, stream) -> the loss scratch of that stream
 
@@ -66,6 +66,7 @@ class _FusedLoss(torch.autograd.Function):
         per_ray = drel is not None and drel.dim() == 1    # [R] sums over samples and rgb (renderer training_outputs="loss_only")
         M = (n_samples_ if per_ray else drel.shape[1]) if drel is not None else 1
         dev = color.device
+        # .contiguous() without a cast (not _lib.dense_f32): the inputs are the renderer's float32 outputs, their dtype is not touched here
         color_c, gt_c = color.contiguous(), gt.contiguous()
         wsum_c = wsum.reshape(-1).contiguous()
         drel_c = drel.contiguous() if drel is not None else None
@@ -96,10 +97,9 @@ class _FusedLoss(torch.autograd.Function):
             eik_factor = out8[6]
         loss, rgb_loss, eik, mask_out, rel_out, mean_rel = out8[:6].unbind(0)
         ctx.lib, ctx.lcfg, ctx.Rg, ctx.M = lib, lcfg, Rg, M
-        ctx.has = (use_mask, use_rel, eik_factor is not None)
+        ctx.has = (use_mask, use_rel)
         ctx.shapes = (color.shape, wsum.shape, tuple(drel.shape) if drel is not None else None)
-        ctx.save_for_backward(color_c, wsum_c, gt_c, mask_c if mask_c is not None else torch.empty(0, device=dev), mean_rel,
-                              eik_factor if eik_factor is not None else mean_rel)
+        save_named(ctx, color=color_c, wsum=wsum_c, gt=gt_c, mask=mask_c, mean_rel=mean_rel, eik_factor=eik_factor)
         # only ``loss`` carries gradients: the four components are logging values (the reference's loss_dict entries are read with
         # .item(), NeuS_Trainer.py:155-171); back-propagating through them would bypass the fused coefficients, so they are all
         # non-differentiable outputs rather than some silently yielding zero gradients
@@ -110,12 +110,12 @@ class _FusedLoss(torch.autograd.Function):
     def backward(ctx, g_loss, *_unused):
         if g_loss is None:   # nothing depends on ``loss`` (cannot happen through the components: they are non-differentiable)
             return (None,) * 13
-        color_c, wsum_c, gt_c, mask_c, mean_rel, eik_factor = ctx.saved_tensors
-        has_mask, has_rel, has_factor = ctx.has
+        sv, _ = saved_named(ctx)
+        color_c, wsum_c, gt_c, mask_t, mean_rel, eik_factor = (sv[k] for k in ("color", "wsum", "gt", "mask", "mean_rel", "eik_factor"))
+        has_mask, has_rel = ctx.has
         lib, lcfg, Rg, M = ctx.lib, ctx.lcfg, ctx.Rg, ctx.M
         dev = color_c.device
         R = color_c.shape[0]
-        mask_t = mask_c if mask_c.numel() else None
         # coefficients on the device from the (device-resident) upstream gradient: no host -> device copy, hence no host stall
         g = g_loss.to(torch.float32)
         d_color = torch.empty_like(color_c)
@@ -127,7 +127,7 @@ class _FusedLoss(torch.autograd.Function):
         # d mean(delta_relight * mask)^2 / d delta_relight[r, j, c] = 2 mean / n * mask[r]: one value per ray, written by the same launch
         per_ray = torch.empty(R, dtype=torch.float32, device=dev) if want_drel else None
         lib.call("cnr_loss_backward", _C.byref(lcfg), ptr(color_c), ptr(wsum_c), ptr(gt_c), ptr(mask_g), R, int(M), ptr(g.reshape(-1).contiguous()),
-                 ptr(mean_rel), ptr(eik_factor if has_factor else None), Rg, int(has_mask), int(has_rel), ptr(coef), ptr(d_color), ptr(d_wsum),
+                 ptr(mean_rel), ptr(eik_factor), Rg, int(has_mask), int(has_rel), ptr(coef), ptr(d_color), ptr(d_wsum),
                  ptr(per_ray), stream_of(color_c))
         d_drel = None
         if want_drel:

@@ -20,7 +20,7 @@ import warnings
 
 import torch
 
-from ._lib import library_for, ptr, stream_of
+from ._lib import dense_f32, grad_f32, library_for, ptr, save_named, saved_named, stream_of
 from ._lib import resolve_library as _library
 
 
@@ -100,7 +100,7 @@ class PixelSampler:
         if masks.shape[0] != self.n_images or masks[0].numel() != self.pixels_per_image or (self.mask_shape not in (None, tuple(masks.shape))):
             raise ValueError(f"mask stack {tuple(masks.shape)} does not match the sampler's "
                              f"{self.mask_shape or (self.n_images, self.pixels_per_image)}")
-        m = masks.detach().contiguous().float()
+        m = dense_f32(masks)
         if self.order is None:
             n = self.n_images
             self.order = torch.empty(n, self.pixels_per_image, dtype=torch.int32, device=self.device)
@@ -192,17 +192,16 @@ class _GenRays(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lib, pix_idx, n, c2w, focal, H, W, normalize, opengl, image, mask, origin, radius, want_nearfar):
         dev = c2w.device
-        c2w_c = c2w.detach().reshape(-1, 4, 4).contiguous().float()
-        focal_c = focal.detach().reshape(-1).contiguous().float().to(dev)
+        c2w_c = dense_f32(c2w, -1, 4, 4)
+        focal_c = dense_f32(focal, -1).to(dev)
         # every operand is dereferenced on c2w's device.  The image / mask stacks must already live there: moving a host-resident stack
         # (about 1 GB for DTU) on every step would be a silent per-step upload, so that is an error like the device mismatch the reference's
         # torch ops would raise; the small operands (focal, origin, the index list) are moved.
         for name, t in (("image", image), ("mask", mask)):
             if t is not None and t.device != dev:
                 raise ValueError(f"{name} is on {t.device} but c2w is on {dev}: keep the image / mask stacks on the device that generates the rays")
-        img = image.detach().contiguous().float() if image is not None else None
-        msk = mask.detach().contiguous().float() if mask is not None else None
-        org = origin.detach().reshape(-1).contiguous().float().to(dev) if origin is not None else None
+        img, msk = dense_f32(image), dense_f32(mask)
+        org = dense_f32(origin, -1).to(dev) if origin is not None else None
         idx = pix_idx.to(dev).contiguous().to(torch.int64) if pix_idx is not None else None
         n_cams = c2w_c.shape[0]
         for name, t in (("image", img), ("mask", msk)):
@@ -226,33 +225,30 @@ class _GenRays(torch.autograd.Function):
                  ptr(org), float(radius), ptr(rays_o), ptr(rays_d), ptr(rgb), ptr(msel), ptr(near), ptr(far),
                  ptr(_bad_counter(dev)) if idx is not None else C.c_void_p(0), stream_of(c2w_c))
         ctx.lib, ctx.meta = lib, (n, H, W, int(normalize), int(opengl), float(radius), c2w.shape, focal.shape)
-        ctx.save_for_backward(idx if idx is not None else torch.empty(0, dtype=torch.int64, device=dev), c2w_c, focal_c,
-                              org if org is not None else torch.empty(0, device=dev))
-        outs = [rays_o, rays_d]
-        nd = [t for t in (rgb, msel) if t is not None]
-        ctx.mark_non_differentiable(*nd)
+        save_named(ctx, idx=idx, c2w=c2w_c, focal=focal_c, origin=org)
+        ctx.mark_non_differentiable(*[t for t in (rgb, msel) if t is not None])
         ctx.n_extra = (rgb is not None, msel is not None, want_nearfar)
-        return tuple(outs + [rgb if rgb is not None else torch.empty(0, device=dev), msel if msel is not None else torch.empty(0, device=dev),
-                             near if near is not None else torch.empty(0, device=dev), far if far is not None else torch.empty(0, device=dev)])
+        return (rays_o, rays_d, rgb if rgb is not None else torch.empty(0, device=dev), msel if msel is not None else torch.empty(0, device=dev),
+                near if near is not None else torch.empty(0, device=dev), far if far is not None else torch.empty(0, device=dev))
 
     @staticmethod
     def backward(ctx, d_o, d_d, _d_rgb, _d_mask, d_near, d_far):
-        idx, c2w_c, focal_c, org = ctx.saved_tensors
+        sv, _ = saved_named(ctx)
+        idx, c2w_c, focal_c, org = sv["idx"], sv["c2w"], sv["focal"], sv["origin"]
         n, H, W, normalize, opengl, radius, c2w_shape, focal_shape = ctx.meta
         dev = c2w_c.device
         need = ctx.needs_input_grad
         if not (need[3] or need[4]):
             return (None,) * 14
-        z3 = lambda g: g.contiguous().float() if g is not None else None
-        d_o, d_d = z3(d_o), z3(d_d)
+        d_o, d_d = grad_f32(d_o), grad_f32(d_d)
         has_nf = ctx.n_extra[2] and d_near is not None and d_far is not None and d_near.numel() == n
-        d_near = z3(d_near) if has_nf else None
-        d_far = z3(d_far) if has_nf else None
+        d_near = grad_f32(d_near) if has_nf else None
+        d_far = grad_f32(d_far) if has_nf else None
         d_c2w = torch.empty_like(c2w_c)
         d_focal = torch.empty(2, dtype=torch.float32, device=dev)
         scratch, nb = ctx.lib.scratch("cnr_gen_rays_backward", dev, nbytes=c2w_c.shape[0] * 2 * 4)   # n_cams * 2 floats: the header's formula
-        ctx.lib.call("cnr_gen_rays_backward", ptr(idx if idx.numel() else None), n, ptr(c2w_c), c2w_c.shape[0], ptr(focal_c), H, W, normalize, opengl,
-                     ptr(org if org.numel() else None), radius, ptr(d_o), ptr(d_d), ptr(d_near), ptr(d_far), ptr(d_c2w), ptr(d_focal),
+        ctx.lib.call("cnr_gen_rays_backward", ptr(idx), n, ptr(c2w_c), c2w_c.shape[0], ptr(focal_c), H, W, normalize, opengl,
+                     ptr(org), radius, ptr(d_o), ptr(d_d), ptr(d_near), ptr(d_far), ptr(d_c2w), ptr(d_focal),
                      ptr(scratch), nb, stream_of(c2w_c))
         return (None, None, None, d_c2w.reshape(c2w_shape) if need[3] else None, d_focal.reshape(focal_shape) if need[4] else None,
                 None, None, None, None, None, None, None, None, None)

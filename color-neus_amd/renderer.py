@@ -13,40 +13,54 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import param_array, ptr, stream_of
+from ._lib import dense_f32, grad_f32, param_array, ptr, save_named, saved_named, stream_of
 from .config import RenderConfig, config_from_node
 
 _OUT_DIFF = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error", "depth",
              "global_color", "delta_relight"]
 _SAMPLE_OUT = ["sdf_samples", "color_samples", "global_color_samples"]   # per-sample network outputs (only with want_samples)
+_NON_DIFF_OUT = ["inside_sphere", "z_vals", "eik_sums"]
 _RETURN_KEYS = ["color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max", "gradients", "weights", "gradient_error", "inside_sphere",
                 "depth", "global_color", "delta_relight_ray_sum", "delta_relight", "z_vals", "eik_sums"]   # of NeuSRenderer.forward's dict
 
 
-def _alloc_outputs(cfg, R, device, mode):
-    """The output tensors of one render call, keyed by _lib.OUTPUT_FIELDS' names (None: not produced, passed as NULL).  ``mode``:
+def _output_shapes(color_type, mode, R=0, M=0):
+    """The shape of every output of one render call, keyed by _lib.OUTPUT_FIELDS' names (None: not produced, passed as NULL).  ``mode``:
     "saving" (the training dict), "loss_only" (what compute_loss needs: no [R][M][3] tensors, the relight term as per-ray sums),
     "with_samples" (the dict plus the per-sample network outputs for the N_OUTSIDE mixing) or "forward_only" (same entries as "saving")."""
-    M, color = cfg.n_total, cfg.type == "Color_NeuS"
+    color = color_type == "Color_NeuS"
     loss_only, samples = mode == "loss_only", mode == "with_samples"
-    f32 = dict(dtype=torch.float32, device=device)
-    return dict(color_fine=torch.empty(R, 3, **f32), s_val=torch.empty(R, 1, **f32), cdf_fine=torch.empty(R, M, **f32),
-                weight_sum=torch.empty(R, 1, **f32), weight_max=torch.empty(R, 1, **f32),
-                gradients=None if loss_only else torch.empty(R, M, 3, **f32), weights=torch.empty(R, M, **f32),
-                gradient_error=torch.empty((), **f32), inside_sphere=torch.empty(R, M, **f32), depth=torch.empty(R, **f32),
-                global_color=torch.empty(R, 3, **f32) if color else None,
-                delta_relight=torch.empty(R, M, 3, **f32) if (color and not loss_only) else None,
-                delta_relight_ray_sum=torch.empty(R, **f32) if (color and loss_only) else None,
-                z_vals=torch.empty(R, M, **f32), eik_sums=torch.empty(2, **f32),
-                sdf_samples=torch.empty(R, M, **f32) if samples else None,
-                color_samples=torch.empty(R, M, 3, **f32) if samples else None,
-                global_color_samples=torch.empty(R, M, 3, **f32) if (samples and color) else None)
+    return dict(color_fine=(R, 3), s_val=(R, 1), cdf_fine=(R, M), weight_sum=(R, 1), weight_max=(R, 1),
+                gradients=None if loss_only else (R, M, 3), weights=(R, M), gradient_error=(), inside_sphere=(R, M), depth=(R,),
+                global_color=(R, 3) if color else None, delta_relight=(R, M, 3) if (color and not loss_only) else None,
+                delta_relight_ray_sum=(R,) if (color and loss_only) else None, z_vals=(R, M), eik_sums=(2,),
+                sdf_samples=(R, M) if samples else None, color_samples=(R, M, 3) if samples else None,
+                global_color_samples=(R, M, 3) if (samples and color) else None)
+
+
+def _alloc_outputs(cfg, R, device, mode):
+    """The output tensors of one render call: an uninitialised float32 tensor for every entry of _output_shapes, None for the others."""
+    return {k: None if shape is None else torch.empty(shape, dtype=torch.float32, device=device)
+            for k, shape in _output_shapes(cfg.type, mode, R, cfg.n_total).items()}
+
+
+def _render_output_names(color_type, mode):
+    """(differentiable names, per-sample names, non-differentiable names) of the tuple _RenderFunction returns, in its order: the outputs
+    _output_shapes says the call produces.  The one place that order is stated: whoever names the tuple's entries does it through here."""
+    made = {k for k, shape in _output_shapes(color_type, mode).items() if shape is not None}
+    return ([k for k in _OUT_DIFF + ["delta_relight_ray_sum"] if k in made], [k for k in _SAMPLE_OUT if k in made], list(_NON_DIFF_OUT))
+
+
+def _render(owner, mode, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio, prune_eps, params):
+    """_RenderFunction.apply in ``mode`` ("saving", "with_samples" or "loss_only"): its outputs as {name: tensor}."""
+    want = {"saving": False, "with_samples": True, "loss_only": "loss_only"}[mode]   # the edge's want_samples argument
+    res = _RenderFunction.apply(owner, rays_o, rays_d, near, far, t_rand, z_override, background_rgb, cos_anneal_ratio, prune_eps, want, *params)
+    return dict(zip(sum(_render_output_names(owner.rcfg.type, mode), []), res))
 
 
 def _rays_f32(rays_o, rays_d, near, far):
     """The four ray inputs as the contiguous float32 tensors the library reads (near / far flattened)."""
-    return (rays_o.detach().contiguous().float(), rays_d.detach().contiguous().float(),
-            near.detach().reshape(-1).contiguous().float(), far.detach().reshape(-1).contiguous().float())
+    return dense_f32(rays_o), dense_f32(rays_d), dense_f32(near, -1), dense_f32(far, -1)
 
 
 def _inputs(rays_o, rays_d, near, far, t_rand=None, z_override=None, background_rgb=None, cos_anneal_ratio=0.0, prune_eps=0.0):
@@ -87,56 +101,40 @@ class _RenderFunction(torch.autograd.Function):
         ctx.owner = owner
         # tensors go through save_for_backward (outputs held in a plain attribute would form an uncollectable
         # tensor -> grad_fn -> ctx -> tensor cycle and leak the multi-GB context buffer every step)
-        ctx.cfg_aux = (float(cos_anneal_ratio), z_override is not None, t_rand is not None, background_rgb is not None, len(plist),
-                       float(prune_eps))
-        saved = [rays_o_c, rays_d_c, near_c, far_c, out["z_vals"],
-                 out["gradients"] if out["gradients"] is not None else torch.empty(0, dtype=torch.float32, device=rays_o.device), ctx_buf]
-        if t_rand is not None:
-            saved.append(t_rand)
-        if background_rgb is not None:
-            saved.append(background_rgb)
-        ctx.save_for_backward(*saved, *plist)
+        ctx.cfg_aux = (float(cos_anneal_ratio), z_override is not None, float(prune_eps))
+        save_named(ctx, plist, rays_o=rays_o_c, rays_d=rays_d_c, near=near_c, far=far_c, z_vals=out["z_vals"], gradients=out["gradients"],
+                   ctx_buf=ctx_buf, t_rand=t_rand, background_rgb=background_rgb)
         ctx.rays_need_grad = rays_o.requires_grad or rays_d.requires_grad
         # z is an affine function of near / far only without importance sampling (NeuS.py:311-313; with it z is built under no_grad, :343)
         ctx.nearfar_need_grad = (near.requires_grad or far.requires_grad) and cfg.n_importance == 0 and z_override is None
         ctx.nearfar_shapes = (near.shape, far.shape)
         ctx.set_materialize_grads(False)   # outputs the loss does not use arrive as None in backward (which passes NULL), not as zero tensors
-        ctx.mark_non_differentiable(out["inside_sphere"], out["z_vals"], out["eik_sums"])
-        ctx.sample_names = [k for k in _SAMPLE_OUT if out[k] is not None]
-        ctx.diff_names = [k for k in _OUT_DIFF + ["delta_relight_ray_sum"] if out.get(k) is not None]
-        res = [out[k] for k in ctx.diff_names] + [out[k] for k in ctx.sample_names] + \
-              [out["inside_sphere"], out["z_vals"], out["eik_sums"]]
-        return tuple(res)
+        diff, samples, non_diff = _render_output_names(cfg.type, mode)
+        ctx.mark_non_differentiable(*[out[k] for k in non_diff])
+        ctx.grad_names = diff + samples   # the outputs whose gradients backward receives, in the tuple's order
+        return tuple(out[k] for k in diff + samples + non_diff)
 
     @staticmethod
     def backward(ctx, *gouts):
-        owner = ctx.owner
-        lib, ccfg = owner._lib, owner._ccfg
-        car, had_override, has_trand, has_bg, nparams, prune_eps = ctx.cfg_aux
+        lib, ccfg = ctx.owner._lib, ctx.owner._ccfg
+        car, had_override, prune_eps = ctx.cfg_aux
         if prune_eps > 0:
             raise RuntimeError("prune_eps > 0 is inference-only (early-termination compaction); call under torch.no_grad()")
-        sv = list(ctx.saved_tensors)
-        rays_o, rays_d, near, far, z_vals, gradients, ctx_buf = sv[:7]
-        pos = 7
-        t_rand = sv[pos] if has_trand else None
-        pos += 1 if has_trand else 0
-        background_rgb = sv[pos] if has_bg else None
-        pos += 1 if has_bg else 0
-        plist = sv[pos:pos + nparams]
+        sv, plist = saved_named(ctx)
+        rays_o, rays_d, near, far, z_vals, ctx_buf = (sv[k] for k in ("rays_o", "rays_d", "near", "far", "z_vals", "ctx_buf"))
         R = rays_o.shape[0]
-        names = ctx.diff_names + ctx.sample_names
         gmap = {}
-        for k, g in zip(names, gouts[:len(names)]):
+        for k, g in zip(ctx.grad_names, gouts):
             if k == "delta_relight_ray_sum":   # d loss / d (sum_jc delta[r, j, c]) = the per-ray gradient of every delta[r, j, c]
                 if g is not None:
-                    gmap["delta_relight_per_ray"] = g.reshape(-1).contiguous().float()
+                    gmap["delta_relight_per_ray"] = grad_f32(g.reshape(-1))
                 continue
             if k == "delta_relight" and g is not None and g.dim() == 3 and g.stride(1) == 0 and g.stride(2) == 0:
                 # a gradient that is constant along each ray and over rgb (what the relight loss term produces, loss.compute_loss_fused
                 # hands it over as an expanded view): pass the per-ray vector, never materialise [R][M][3]
-                gmap["delta_relight_per_ray"] = g[:, 0, 0].contiguous().float()
+                gmap["delta_relight_per_ray"] = grad_f32(g[:, 0, 0])
                 continue
-            gmap[k] = g.contiguous().float() if g is not None else None
+            gmap[k] = grad_f32(g)
         cg = _lib.CnrOutGrads(**{k: ptr(gmap.get(k)) for k in _lib.OUT_GRAD_FIELDS})
         flat, dparams, darr = _lib.flat_grads(plist, rays_o.device)
         d_o = torch.empty_like(rays_o) if ctx.rays_need_grad else None
@@ -145,8 +143,8 @@ class _RenderFunction(torch.autograd.Function):
         d_far = torch.empty_like(far) if ctx.nearfar_need_grad else None
         gin = _lib.CnrInGrads(d_params=C.cast(darr, C.POINTER(C.c_void_p)), d_rays_o=ptr(d_o), d_rays_d=ptr(d_d),
                               d_near=ptr(d_near), d_far=ptr(d_far))
-        cin = _inputs(rays_o, rays_d, near, far, t_rand, z_vals if had_override else None, background_rgb, car)
-        cout = _lib.CnrOutputs(z_vals=ptr(z_vals), gradients=ptr(gradients) if gradients.numel() else None)   # the only forward outputs backward reads (gradients: NULL = kept in the context buffer)
+        cin = _inputs(rays_o, rays_d, near, far, sv["t_rand"], z_vals if had_override else None, sv["background_rgb"], car)
+        cout = _lib.CnrOutputs(z_vals=ptr(z_vals), gradients=ptr(sv["gradients"]))   # the only forward outputs backward reads (gradients: NULL = kept in the context buffer)
         scratch, nbytes = lib.scratch("cnr_bwd_scratch_bytes", rays_o.device, C.byref(ccfg), R)
         lib.call("cnr_render_backward", C.byref(ccfg), param_array(plist), C.byref(cin), C.byref(cout), ptr(ctx_buf), ctx_buf.numel(),
                  C.byref(cg), C.byref(gin), ptr(scratch), nbytes, stream_of(rays_o))
@@ -169,8 +167,7 @@ def sample_pdf(bins, weights, n_samples, det=False, library=None):
     device: the hierarchical sampler's own kernel (cnr_sample_pdf; NeuS.up_sample passes det=True, NeuS.py:180).  det=False: the uniform draws come
     from torch.rand on the CPU generator with the reference's shape and call order (ray_utils.py:135-136), the inversion runs in the same kernel."""
     lib = _lib.resolve_library(library)
-    bins = bins.detach().contiguous().float()
-    weights = weights.detach().contiguous().float()
+    bins, weights = dense_f32(bins), dense_f32(weights)
     n = bins.shape[-1]
     assert weights.shape[-1] == n - 1 and bins.shape[:-1] == weights.shape[:-1]
     R = bins.numel() // n
@@ -222,17 +219,17 @@ _QUERY_MAX_POINTS = 1 << 20
 _QUERY_MAX_BYTES = 16 << 30
 
 
-class _SdfQueryBinding:
-    """What ``_SDFNet``'s query methods need besides its own parameters: the library and the C config.  Held as a plain attribute (not a
-    module, no parameters or buffers: state_dict and named_parameters stay those of the reference); a deepcopy shares it, since it holds
-    nothing of the copied module."""
+class _Binding:
+    """A renderer's one link to the library: the lazily resolved ``library`` argument, the C config, the parameter inventory, and the calls
+    that the renderer and its ``sdf_network`` both make.  Held as a plain attribute of both (not a module, no parameters or buffers:
+    state_dict and named_parameters stay those of the reference); a deepcopy shares it, since it holds nothing of the copied module."""
 
     def __init__(self, library, rcfg):
         self._library_arg = library
         self._lib_obj = None
         self.ccfg = _lib.c_config(rcfg)
         self.d_out = rcfg.sdf_d_out
-        self._names = None
+        self._inventory = self._names = None
         self._max_pts = {}
 
     def __deepcopy__(self, memo):
@@ -244,10 +241,16 @@ class _SdfQueryBinding:
             self._lib_obj = _lib.resolve_library(self._library_arg)
         return self._lib_obj
 
+    def inventory(self):
+        """[(name, rows, cols)] of the configuration's parameters in the library's canonical order."""
+        if self._inventory is None:
+            self._inventory = self.lib.param_inventory(self.ccfg)
+        return self._inventory
+
     def names(self):
         """(number of canonical parameters, sdf_network parameter names in canonical order, without the prefix)."""
         if self._names is None:
-            inv = self.lib.param_inventory(self.ccfg)
+            inv = self.inventory()
             self._names = (len(inv), [n[len("sdf_network."):] for n, _, _ in inv if n.startswith("sdf_network.")])
         return self._names
 
@@ -279,6 +282,21 @@ class _SdfQueryBinding:
                ptr(grad), ptr(cbuf), nb, stream_of(x))
         return sdf, feat, grad, (cbuf if keep_ctx else None)
 
+    def evaluate(self, entry, bytes_fn, size_args, params, dev, *args, at_least=0):
+        """An evaluation entry point ``entry(cfg, params, *args, scratch, scratch_bytes, stream)`` on ``dev``: ``params`` (the canonical
+        inventory, or its leading sdf_network entries) are detached and go as the pointer array, the scratch is what the size function
+        ``bytes_fn(cfg, *size_args)`` asks for."""
+        plist = [p.detach().contiguous() for p in params]
+        scratch, nb = self.lib.scratch(bytes_fn, dev, C.byref(self.ccfg), *size_args, at_least=at_least)
+        self.lib.call(entry, C.byref(self.ccfg), self.param_array(plist), *args, ptr(scratch), nb, stream_of(dev))
+
+    def sdf_eval(self, x, params, sign=1.0):
+        """cnr_sdf_eval: sign * sdf [n, 1] at the float32 points x [n, 3] (0 < n), nothing kept for a backward pass."""
+        n = x.shape[0]
+        out = torch.empty(n, 1, dtype=torch.float32, device=x.device)
+        self.evaluate("cnr_sdf_eval", "cnr_sdf_eval_scratch_bytes", (n,), params, x.device, ptr(x), n, float(sign), ptr(out))
+        return out
+
 
 class _SdfQueryFunction(torch.autograd.Function):
     """autograd edge around cnr_sdf_query_forward / cnr_sdf_query_backward: outputs sdf [n, 1], then feat [n, F] (want_feat), then
@@ -290,7 +308,7 @@ class _SdfQueryFunction(torch.autograd.Function):
         plist = [p.detach().contiguous() for p in params]
         sdf, feat, grad, cbuf = binding.forward(x.detach(), plist, want_grad, want_feat, keep_ctx=True)
         ctx.binding, ctx.want_grad, ctx.want_feat = binding, want_grad, want_feat
-        ctx.save_for_backward(x.detach(), cbuf, *plist)
+        save_named(ctx, plist, x=x.detach(), cbuf=cbuf)
         ctx.set_materialize_grads(False)   # unused outputs arrive as None and go to the library as NULL
         return tuple(t for t in (sdf, feat, grad) if t is not None)
 
@@ -298,13 +316,12 @@ class _SdfQueryFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, *gouts):
         binding, L = ctx.binding, ctx.binding.lib
-        x, cbuf, *plist = ctx.saved_tensors
+        sv, plist = saved_named(ctx)
+        x, cbuf = sv["x"], sv["cbuf"]
         gouts = list(gouts)
-        d_sdf = gouts.pop(0)
-        d_feat = gouts.pop(0) if ctx.want_feat else None
-        d_grad = gouts.pop(0) if ctx.want_grad else None
-        cont = lambda g: g.contiguous().float() if g is not None else None
-        d_sdf, d_feat, d_grad = cont(d_sdf), cont(d_feat), cont(d_grad)
+        d_sdf = grad_f32(gouts.pop(0))
+        d_feat = grad_f32(gouts.pop(0)) if ctx.want_feat else None
+        d_grad = grad_f32(gouts.pop(0)) if ctx.want_grad else None
         n, dev = x.shape[0], x.device
         need_x, need_p = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
         d_x = torch.empty(n, 3, dtype=torch.float32, device=dev) if need_x else None
@@ -355,7 +372,7 @@ class _SDFNet(nn.Module):
                     b.zero_()
                     nn.init.normal_(w, 0.0, math.sqrt(2) / math.sqrt(out_dim))
             setattr(self, f"lin{l}", _wrap(w, b, c.sdf_weight_norm))
-        self._query = None   # _SdfQueryBinding, set by the renderer
+        self._query = None   # the renderer's _Binding, set by it
 
     # -- the reference's methods (fields.py:81-115) ------------------------------------------------------------------------------------------
     def _query_params(self):
@@ -404,7 +421,7 @@ class _SDFNet(nn.Module):
         x = self._points(x)
         if self._query is not None and x.shape[0] > 0 and not (torch.is_grad_enabled() and
                                                                (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
-            return self._sdf_eval(x)
+            return self._query.sdf_eval(x, self._query_params())
         return self._run(x, False, False)[0]
 
     def sdf_hidden_appearance(self, x):
@@ -415,15 +432,6 @@ class _SDFNet(nn.Module):
         backward); like the reference it sets x.requires_grad."""
         x.requires_grad_(True)
         return self._run(self._points(x), True, False)[2].unsqueeze(1)
-
-    def _sdf_eval(self, x):
-        q, n = self._query, x.shape[0]
-        L = q.lib
-        params = [p.detach().contiguous() for p in self._query_params()]
-        out = torch.empty(n, 1, dtype=torch.float32, device=x.device)
-        scratch, nb = L.scratch("cnr_sdf_eval_scratch_bytes", x.device, C.byref(q.ccfg), n)
-        L.call("cnr_sdf_eval", C.byref(q.ccfg), q.param_array(params), ptr(x), n, 1.0, ptr(out), ptr(scratch), nb, stream_of(x))
-        return out
 
 
 class _ColorNet(nn.Module):
@@ -486,24 +494,18 @@ class NeuSRenderer(nn.Module):
         if self.n_outside > 0:   # NeRF++ background (NeuS.py:87-91): parameters here, arithmetic in the library (background.py)
             from .background import NeRF
             self.nerf = NeRF()
-        self._library_arg = library
-        self._lib_obj = None
-        self._ccfg = _lib.c_config(rcfg)
         self._order = None
-        self.sdf_network._query = _SdfQueryBinding(library, rcfg)   # (a plain attribute: no child module, no state)
+        self._binding = self.sdf_network._query = _Binding(library, rcfg)   # (a plain attribute: no child module, no state)
 
     # -- library plumbing -------------------------------------------------------------------------------------------
-    @property
-    def _lib(self):
-        if self._lib_obj is None:
-            self._lib_obj = _lib.resolve_library(self._library_arg)
-        return self._lib_obj
+    _lib = property(lambda self: self._binding.lib)      # the RenderLibrary and the CnrConfig, as the edges, tests and tools read them
+    _ccfg = property(lambda self: self._binding.ccfg)
 
     def _ordered_params(self):
         """Parameters in the library's canonical order (names = reference state_dict names)."""
         if self._order is None:
             # nerf.*: the background network has its own inventory (cnr_nerf_param_info)
-            self._order = _lib.ordered_names(self._lib.param_inventory(self._ccfg), dict(self.named_parameters()), exempt_prefix="nerf.")
+            self._order = _lib.ordered_names(self._binding.inventory(), dict(self.named_parameters()), exempt_prefix="nerf.")
         named = dict(self.named_parameters())
         return [named[k] for k in self._order]
 
@@ -577,13 +579,8 @@ class NeuSRenderer(nn.Module):
                 raise ValueError("training_outputs='loss_only' belongs to the training step, not to a forward-only call")
             out = _render_forward_only(self, rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps, params)
         else:
-            res = _RenderFunction.apply(self, rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps,
-                                        "loss_only" if loss_only else False, *params)
-            color = self.rcfg.type == "Color_NeuS"
-            names = [k for k in _OUT_DIFF if not (k in ("global_color", "delta_relight") and not color) and not (loss_only and k in ("gradients", "delta_relight"))]
-            if loss_only and color:
-                names.append("delta_relight_ray_sum")
-            out = dict(zip(names + ["inside_sphere", "z_vals", "eik_sums"], res))
+            out = _render(self, "loss_only" if loss_only else "saving", rays_o, rays_d, near, far, t_rand, z_vals, bg, cos_anneal_ratio, prune_eps,
+                          params)
         # the reference's dict in its key order, then the extra keys (not in the reference dict): z_vals, and eik_sums =
         # {sum relax*(|g|-1)^2, sum relax}, needed by ray-sharded training
         return {k: out[k] for k in _RETURN_KEYS if out.get(k) is not None}
@@ -600,11 +597,11 @@ class NeuSRenderer(nn.Module):
 
     def up_sample(self, rays_o, rays_d, z_vals, sdf, n_importance, inv_s):
         """NeuS.up_sample (NeuS.py:136-181): n_importance new sample positions per ray from the current z / sdf."""
-        z = z_vals.detach().contiguous().float()
+        z = dense_f32(z_vals)
         R, n = z.shape
         out = torch.empty(R, int(n_importance), dtype=torch.float32, device=z.device)
-        self._lib.call("cnr_up_sample", ptr(rays_o.detach().contiguous().float()), ptr(rays_d.detach().contiguous().float()), ptr(z),
-                       ptr(sdf.detach().reshape(R, n).contiguous().float()), R, n, int(n_importance), float(inv_s), ptr(out), stream_of(z))
+        self._lib.call("cnr_up_sample", ptr(dense_f32(rays_o)), ptr(dense_f32(rays_d)), ptr(z), ptr(dense_f32(sdf, R, n)), R, n,
+                       int(n_importance), float(inv_s), ptr(out), stream_of(z))
         return out
 
     # -- N_OUTSIDE > 0 (NeuS.py:313-369): four library calls chained by autograd (background.py); no tensor arithmetic here ------------
@@ -623,15 +620,11 @@ class NeuSRenderer(nn.Module):
         z_feed, _src = B.OutsideZ.apply(lib, far, t_out, z_vals, int(self.n_samples), int(self.n_outside))
         nparams = self.nerf.ordered_params(lib)
         bg_alpha, bg_color = B.Background.apply(lib, self.nerf.config(), sample_dist, rays_o, rays_d, z_feed, *nparams)
-        res = _RenderFunction.apply(self, rays_o, rays_d, near, far, None, z_vals, None, 0.0, 0.0, True, *params)
+        f = _render(self, "with_samples", rays_o, rays_d, near, far, None, z_vals, None, 0.0, 0.0, params)
         color = rc.type == "Color_NeuS"
-        names = [k for k in _OUT_DIFF if color or k not in ("global_color", "delta_relight")] + \
-                [k for k in _SAMPLE_OUT if color or k != "global_color_samples"] + ["inside_sphere", "z_vals", "eik_sums"]
-        f = dict(zip(names, res))
         cres = B.CompositeBg.apply(lib, sample_dist, float(cos_anneal_ratio), bg, rays_o, rays_d, z_vals, z_feed, f["sdf_samples"], f["gradients"],
                                    f["color_samples"], f.get("global_color_samples"), bg_alpha, bg_color, self.deviation_network.variance)
-        cnames = [k for k in B._COMP_OUT if color or k != "global_color"] + ["inside_sphere", "eik_sums"]
-        c = dict(zip(cnames, cres))
+        c = dict(zip(sum(B.composite_output_names(color), []), cres))
         out = {k: c[k] for k in ("color_fine", "s_val", "cdf_fine", "weight_sum", "weight_max")}
         out.update(gradients=f["gradients"], weights=c["weights"], gradient_error=c["gradient_error"], inside_sphere=c["inside_sphere"], depth=c["depth"])
         if color:
@@ -647,53 +640,43 @@ class NeuSRenderer(nn.Module):
         R = len(rays_o)
         rays = _rays_f32(rays_o, rays_d, near, far)
         z = torch.empty(R, rc.n_total, dtype=torch.float32, device=dev)
-        plist, parr = self._param_array()
         cin = _inputs(*rays, t_rand)
-        buf, nb = self._lib.scratch("cnr_ctx_bytes", dev, C.byref(self._ccfg), R)
-        self._lib.call("cnr_sample_z", C.byref(self._ccfg), parr, C.byref(cin), ptr(z), ptr(buf), nb, stream_of(rays[0]))
+        self._binding.evaluate("cnr_sample_z", "cnr_ctx_bytes", (R,), self._ordered_params(), dev, C.byref(cin), ptr(z))
         return z
 
     # -- evaluation paths (NeuS.py:14-64, 410-420) ---------------------------------------------------------------------
     def _param_array(self):
+        """(detached ordered parameters, their pointer array) for a direct call of an entry point (the methods below go through evaluate)."""
         plist = [p.detach().contiguous() for p in self._ordered_params()]
         return plist, param_array(plist)
 
     def sdf(self, pts, sign=1.0):
         """sdf_network.sdf(pts) (fields.py:99) on the device, any number of points."""
-        pts = pts.detach().reshape(-1, 3).contiguous().float()
-        n = pts.shape[0]
-        out = torch.empty(n, 1, dtype=torch.float32, device=pts.device)
-        if n == 0:   # (the C ABI takes n_points > 0)
-            return out
-        plist, parr = self._param_array()
-        scratch, nb = self._lib.scratch("cnr_sdf_eval_scratch_bytes", pts.device, C.byref(self._ccfg), n)
-        self._lib.call("cnr_sdf_eval", C.byref(self._ccfg), parr, ptr(pts), n, float(sign), ptr(out), ptr(scratch), nb, stream_of(pts))
-        return out
+        pts = dense_f32(pts, -1, 3)
+        if pts.shape[0] == 0:   # (the C ABI takes n_points > 0)
+            return torch.empty(0, 1, dtype=torch.float32, device=pts.device)
+        return self._binding.sdf_eval(pts, self._ordered_params(), sign)
 
     def extract_fields(self, bound_min, bound_max, device, resolution):
         """u = -sdf on linspace(bound_min, bound_max, resolution)^3 (NeuS.py:14-28); stays on the device, one D2H at the end."""
         bmin, bmax = _lib.float3(bound_min), _lib.float3(bound_max)
-        dev = torch.device(device)
-        u = torch.empty(resolution, resolution, resolution, dtype=torch.float32, device=dev)
-        plist, parr = self._param_array()
-        scratch, nb = self._lib.scratch("cnr_sdf_grid_scratch_bytes", dev, C.byref(self._ccfg), resolution)
-        self._lib.call("cnr_sdf_grid", C.byref(self._ccfg), parr, bmin, bmax, resolution, ptr(u), ptr(scratch), nb, stream_of(u))
+        u = torch.empty(resolution, resolution, resolution, dtype=torch.float32, device=torch.device(device))
+        self._binding.evaluate("cnr_sdf_grid", "cnr_sdf_grid_scratch_bytes", (resolution,), self._ordered_params(), u.device, bmin, bmax,
+                               resolution, ptr(u))
         return u
 
     def extract_fields_slab(self, bound_min, bound_max, device, resolution, x_begin, x_end):
         """Rows x in [x_begin, x_end) of extract_fields' lattice (same values): the unit of the sharded evaluation (parallel.sharded_extract_fields)."""
         bmin, bmax = _lib.float3(bound_min), _lib.float3(bound_max)
-        dev = torch.device(device)
-        u = torch.empty(x_end - x_begin, resolution, resolution, dtype=torch.float32, device=dev)
-        plist, parr = self._param_array()
-        scratch, nb = self._lib.scratch("cnr_sdf_grid_slab_scratch_bytes", dev, C.byref(self._ccfg), resolution, x_begin, x_end, at_least=1)
-        self._lib.call("cnr_sdf_grid_slab", C.byref(self._ccfg), parr, bmin, bmax, resolution, x_begin, x_end, ptr(u), ptr(scratch), nb, stream_of(u))
+        u = torch.empty(x_end - x_begin, resolution, resolution, dtype=torch.float32, device=torch.device(device))
+        self._binding.evaluate("cnr_sdf_grid_slab", "cnr_sdf_grid_slab_scratch_bytes", (resolution, x_begin, x_end), self._ordered_params(),
+                               u.device, bmin, bmax, resolution, x_begin, x_end, ptr(u), at_least=1)
         return u
 
     def marching_cubes(self, u, bound_min, bound_max, threshold=0.0):
         """Iso-surface of a device-resident lattice u[x][y][z] (cnr_mc_count / cnr_mc_emit): returns device tensors
         (vertices [V, 3] float32 in world coordinates, triangles [F, 3] int32)."""
-        u = u.detach().contiguous().float()
+        u = dense_f32(u)
         res = u.shape[0]
         assert u.shape == (res, res, res)
         lib = self._lib
@@ -728,14 +711,12 @@ class NeuSRenderer(nn.Module):
 
     def vertex_colors(self, vertices):
         """extract_color on device tensors: ``vertices`` [V, 3] on the renderer's device -> rgb [V, 3] float32 there, no host round trip."""
-        pts = vertices.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        pts = dense_f32(vertices, -1, 3)
         n = pts.shape[0]
         rgb = torch.empty(n, 3, dtype=torch.float32, device=pts.device)
-        if n == 0:
-            return rgb
-        plist, parr = self._param_array()
-        scratch, nb = self._lib.scratch("cnr_vertex_color_scratch_bytes", pts.device, C.byref(self._ccfg), n)
-        self._lib.call("cnr_vertex_color", C.byref(self._ccfg), parr, ptr(pts), n, ptr(rgb), ptr(scratch), nb, stream_of(pts))
+        if n > 0:
+            self._binding.evaluate("cnr_vertex_color", "cnr_vertex_color_scratch_bytes", (n,), self._ordered_params(), pts.device, ptr(pts), n,
+                                   ptr(rgb))
         return rgb
 
     def extract_color(self, vertices, device):

@@ -134,8 +134,8 @@ def _composite(library, dev, color_type):
     tn = {k: vals[k].to(dev).requires_grad_(True) for k in names}
     res = B.CompositeBg.apply(lib, sd, car, bg_rgb.to(dev), o.to(dev), tn["rays_d"], tn["z"], tn["zf"], tn["sdf"], tn["grads"], tn["col"], tn.get("gcol"), tn["bga"],
                               tn["bgc"], tn["var"])
-    cn_ = [k for k in B._COMP_OUT if color_type or k != "global_color"] + ["inside_sphere", "eik_sums"]
-    outn = dict(zip(cn_, res))
+    diff, non_diff = B.composite_output_names(color_type)
+    outn = dict(zip(diff + non_diff, res))
     sum((outn[k] * coefs[k].float().to(dev).reshape(outn[k].shape)).sum() for k in keys).backward()
     bad = {}
     for k in keys + ["inside_sphere"]:

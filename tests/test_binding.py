@@ -1,5 +1,6 @@
 """CPU: the Python binding layer above the C ABI (color_neus_amd._lib): the signature table against the header's prototypes, the one call
-path and its error text, the pointer-array, flat-gradient-buffer and inventory helpers, and the output allocation of a render call."""
+path and its error text, the pointer-array, flat-gradient-buffer and inventory helpers, the output allocation of a render call, and what the
+autograd edges share: the coercion, the saving of optional tensors, the names of the render outputs."""
 import ctypes as C
 import os
 import re
@@ -7,6 +8,7 @@ import re
 import pytest
 import torch
 
+import _golden as G
 import _native as N
 import color_neus_amd as cn
 from color_neus_amd import _lib, optim, renderer
@@ -156,3 +158,155 @@ def test_output_allocation_per_mode(typ, mode):
             assert out[k] is None, k
         else:
             assert out[k] is not None and tuple(out[k].shape) == shape and out[k].dtype == _F32 and out[k].device.type == "cpu", k
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the autograd edges' shared bookkeeping: output names, optional saved tensors, no reference cycle
+# ---------------------------------------------------------------------------------------------------------------------
+def _tiny(name, lib):
+    """(renderer on the CPU emulation library, [rays_o, rays_d, near, far], ground-truth colours, mask) of a tiny fixture"""
+    fx = G.load(name)
+    ocfg, P = G.weights_of(name, fx)
+    rays = [torch.from_numpy(fx[k]) for k in ("rays_o", "rays_d", "jit:near", "jit:far")]
+    return N.make_renderer(ocfg, P, lib, "cpu"), rays, torch.from_numpy(fx["rgb_gt"]), torch.from_numpy(fx["mask"])
+
+
+_FIXTURE = {("NeuS", False): "tiny_neus_sharp", ("NeuS", True): "tiny_neus_outside", ("Color_NeuS", False): "tiny_sharp",
+            ("Color_NeuS", True): "tiny_outside"}      # (type, N_OUTSIDE > 0)
+
+
+@pytest.mark.parametrize("mode", ["saving", "loss_only", "with_samples"])
+@pytest.mark.parametrize("typ", ["NeuS", "Color_NeuS"])
+def test_output_names_against_shapes_and_the_returned_dict(lib, monkeypatch, typ, mode):
+    """The tuple of _RenderFunction.apply has one entry per name of _render_output_names, each with the shape _alloc_outputs gives that name,
+    and NeuSRenderer.forward's dict holds under every key the very tensor of that name's position -- in "with_samples" mode (N_OUTSIDE > 0)
+    through CompositeBg and composite_output_names, with and without global_color."""
+    from color_neus_amd import background as B
+    r, rays, _, _ = _tiny(_FIXTURE[(typ, mode == "with_samples")], lib)
+    seen = {}
+
+    def spy(cls, key):
+        orig = cls.apply
+
+        def apply(*args):
+            seen[key] = (args, orig(*args))
+            return seen[key][1]
+        monkeypatch.setattr(cls, "apply", apply)
+    spy(renderer._RenderFunction, "render")
+    spy(B.CompositeBg, "composite")
+    out = r(*rays, perturb_overwrite=0, training_outputs="loss_only" if mode == "loss_only" else "dict")
+    _, res = seen["render"]
+    names = sum(renderer._render_output_names(typ, mode), [])
+    assert len(set(names)) == len(names) == len(res)
+    shapes = renderer._alloc_outputs(r.rcfg, len(rays[0]), torch.device("cpu"), mode)
+    assert sorted(names) == sorted(k for k, t in shapes.items() if t is not None)
+    for k, t in zip(names, res):
+        assert t.shape == shapes[k].shape and t.dtype == _F32, k
+    at = lambda k: res[names.index(k)].data_ptr()
+    if mode != "with_samples":
+        assert "composite" not in seen
+        assert set(out) == set(names) & set(renderer._RETURN_KEYS)
+        for k, t in out.items():
+            assert t.data_ptr() == at(k), k
+        return
+    cargs, cres = seen["composite"]
+    has_gc = typ == "Color_NeuS"
+    cnames = sum(B.composite_output_names(has_gc), [])
+    assert len(set(cnames)) == len(cnames) == len(cres) and ("global_color" in cnames) == has_gc
+    # what the renderer hands to CompositeBg by name: sdf, grads, color, gcolor (arguments 8 .. 11)
+    for i, k in ((8, "sdf_samples"), (9, "gradients"), (10, "color_samples"), (11, "global_color_samples")):
+        assert (cargs[i].data_ptr() == at(k)) if k in names else (cargs[i] is None), k
+    z_vals, MF = cargs[6], cargs[7].shape[1]
+    cshape = dict(color_fine=(len(z_vals), 3), s_val=(len(z_vals), 1), cdf_fine=z_vals.shape, weight_sum=(len(z_vals), 1), weight_max=(len(z_vals), 1),
+                  weights=(len(z_vals), MF), gradient_error=(), depth=(len(z_vals),), global_color=(len(z_vals), 3), inside_sphere=z_vals.shape,
+                  eik_sums=(2,))
+    for k, t in zip(cnames, cres):
+        assert tuple(t.shape) == tuple(cshape[k]), k
+    for k, t in out.items():
+        want = cres[cnames.index(k)] if k in cnames else z_vals if k == "z_vals" else res[names.index(k)]
+        assert t.data_ptr() == want.data_ptr(), k
+    assert set(out) == set(cnames) | {"z_vals", "gradients"} | ({"delta_relight"} if has_gc else set())
+
+
+class _StubCtx:
+    """What save_named / saved_named use of an autograd context."""
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+def test_saved_named_keeps_absent_and_empty_apart():
+    ctx = _StubCtx()
+    a, empty, b = torch.arange(3.0), torch.empty(0, 3), torch.ones(2, dtype=torch.int64)
+    tail = [torch.zeros(1), torch.zeros(2), torch.empty(0)]
+    _lib.save_named(ctx, tail, a=a, gone=None, empty=empty, also_gone=None, b=b)
+    assert len(ctx.saved_tensors) == 3 + 3        # nothing stands in for the absent ones
+    named, got_tail = _lib.saved_named(ctx)
+    assert list(named) == ["a", "gone", "empty", "also_gone", "b"]
+    assert named["a"] is a and named["b"] is b
+    assert named["empty"] is empty and named["empty"].numel() == 0      # a real zero-element tensor comes back as itself
+    assert named["gone"] is None and named["also_gone"] is None
+    assert len(got_tail) == 3 and all(x is y for x, y in zip(got_tail, tail))
+    _lib.save_named(ctx, x=None)                  # no tail, nothing present
+    assert ctx.saved_tensors == () and _lib.saved_named(ctx) == ({"x": None}, [])
+
+
+def test_dense_f32_is_a_view_of_a_dense_float32_tensor():
+    t = torch.arange(6.0).reshape(2, 3).requires_grad_(True)
+    d = _lib.dense_f32(t)
+    assert d.data_ptr() == t.data_ptr() and not d.requires_grad and _lib.dense_f32(None) is None and _lib.grad_f32(None) is None
+    assert _lib.dense_f32(t, -1).shape == (6,) and _lib.dense_f32(t, -1).data_ptr() == t.data_ptr()
+    h = _lib.dense_f32(t.double().t(), 3, 2)
+    assert h.dtype == _F32 and h.is_contiguous() and torch.equal(h, t.detach().t())
+    g = _lib.grad_f32(t.t())
+    assert g.is_contiguous() and g.requires_grad and torch.equal(g, t.t())
+
+
+def test_no_edge_keeps_its_buffers_in_a_reference_cycle(lib, monkeypatch):
+    """Every context / scratch buffer the edges take dies by reference counting alone (gc disabled, no gc.collect()) once the outputs, the
+    loss and the gradients' owners are gone: nothing of an edge sits in a tensor -> grad_fn -> ctx -> tensor cycle.  The fused loss'
+    scratch is left out: loss._loss_scratch keeps it per stream on purpose."""
+    import gc
+    import weakref
+    refs = []
+    orig = _lib.RenderLibrary.scratch
+
+    def scratch(self, bytes_fn, *args, **kw):
+        buf, nb = orig(self, bytes_fn, *args, **kw)
+        if bytes_fn != "cnr_loss_scratch_bytes":
+            refs.append((bytes_fn, weakref.ref(buf)))
+        return buf, nb
+    monkeypatch.setattr(_lib.RenderLibrary, "scratch", scratch)
+
+    def alive():
+        return [name for name, ref in refs if ref() is not None]
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        r, rays, gt, mask = _tiny("tiny_sharp", lib)          # a Color_NeuS step
+        out = r(*rays)
+        loss, loss_dict = cn.compute_loss_fused(out, gt, mask, library=lib)
+        loss.backward()
+        del out, loss, loss_dict, r
+        assert {"cnr_ctx_bytes", "cnr_bwd_scratch_bytes"} <= {name for name, _ in refs} and not alive(), alive()
+        r, rays, gt, mask = _tiny("tiny_sharp", lib)          # a forward whose backward never runs: the context buffer goes with the outputs
+        out = r(*rays, training_outputs="loss_only")
+        assert alive() == ["cnr_ctx_bytes"]
+        del out
+        assert not alive(), alive()
+        n = len(refs)
+        r, rays, gt, mask = _tiny("tiny_outside", lib)        # the background edges
+        out = r(*rays)
+        loss, loss_dict = cn.compute_loss(out, gt, mask)
+        loss.backward()
+        del out, loss, loss_dict
+        assert {"cnr_background_ctx_bytes", "cnr_composite_background_scratch_bytes"} <= {name for name, _ in refs[n:]} and not alive(), alive()
+        x = torch.rand(9, 3, generator=torch.Generator().manual_seed(1)) - 0.5
+        g = r.sdf_network.gradient(x)                         # a point query with a backward
+        held = alive()
+        (g.norm(dim=-1) - 1.0).pow(2).mean().backward()
+        del g, x, r
+        assert held == ["cnr_sdf_query_ctx_bytes"] and not alive(), (held, alive())
+    finally:
+        if was_enabled:
+            gc.enable()

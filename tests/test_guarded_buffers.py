@@ -578,8 +578,8 @@ def _composite(library, dev, g, color_type):
     tn = {k: v.to(dev).requires_grad_(True) for k, v in vals.items() if v is not None}
     res = B.CompositeBg.apply(lib, 2.0 / 16, 0.3, torch.tensor([0.2, 0.5, 0.7]).to(dev), o.to(dev), tn["rays_d"], tn["z"], tn["zf"], tn["sdf"], tn["grads"],
                               tn["col"], tn.get("gcol"), tn["bga"], tn["bgc"], tn["var"])
-    names = [k for k in B._COMP_OUT if color_type or k != "global_color"] + ["inside_sphere", "eik_sums"]
-    outn = dict(zip(names, res))
+    diff, non_diff = B.composite_output_names(color_type)
+    outn = dict(zip(diff + non_diff, res))
     sum((t * _coef(t)).sum() for t in res if t.requires_grad).backward()
     out = {"out:" + k: v.detach() for k, v in outn.items()}
     out.update({"grad:" + k: v.grad for k, v in tn.items() if v.grad is not None})
