@@ -14,7 +14,7 @@ from .meshio import write_ply, write_png  # noqa: F401
 from .metrics import (nearest_neighbors, chamfer_distance, mesh_metrics, compute_chamfer_distance, point_mesh_distance, surface_metrics,  # noqa: F401
                       compute_surface_metrics)  # noqa: F401
 from .imaging import image_metrics, psnr, ssim, mse2psnr, PSNR, SSIM, cmap, panel, validate_image, rasterize_mesh, mesh_view_metrics  # noqa: F401
-from .meshops import connected_components, clean_mesh, sample_surface  # noqa: F401
+from .meshops import connected_components, clean_mesh, sample_surface, ViewMasks, dilate_masks, view_votes, cull_mesh, MeshCuller  # noqa: F401
 from .rays import PixelSampler  # noqa: F401
 from .cameras import FocalNet, PoseNet, Cameras, cameras_from_state_dict  # noqa: F401
 from .optim import ClipAdam  # noqa: F401
@@ -24,4 +24,4 @@ __all__ = ["RenderConfig", "config_from_node", "load_library", "library_path", "
            "metrics", "nearest_neighbors", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance",
            "point_mesh_distance", "surface_metrics", "compute_surface_metrics", "sample_surface",
            "imaging", "image_metrics", "psnr", "ssim", "mse2psnr", "PSNR", "SSIM", "cmap", "panel", "validate_image", "rasterize_mesh", "mesh_view_metrics", "write_png",
-           "meshops", "connected_components", "clean_mesh", "PixelSampler", "cameras", "FocalNet", "PoseNet", "Cameras", "cameras_from_state_dict"]
+           "meshops", "connected_components", "clean_mesh", "ViewMasks", "dilate_masks", "view_votes", "cull_mesh", "MeshCuller", "PixelSampler", "cameras", "FocalNet", "PoseNet", "Cameras", "cameras_from_state_dict"]

@@ -22,6 +22,7 @@
 #include "cnr_raster.h"
 #include "cnr_meshcc.h"
 #include "cnr_surface.h"
+#include "cnr_cull.h"
 
 namespace cnr {
 
@@ -771,17 +772,18 @@ void be_mesh_components(const MeshComponents& p, cnr_stream) {
   meshcc_unkey(best, &p.summary[2], &p.summary[3]);
 }
 
-void be_mesh_select(const MeshSelect& p, cnr_stream) {
-  const int thr = meshcc_threshold(p.min_faces, p.min_ratio, p.summary[3]);
+// twin of meshcc_scan_kernel: the running counts in element order
+void mesh_keep_scan(const MeshKeepScan& p, cnr_stream) {
   p.totals[0] = p.totals[1] = 0;
-  for (long v = 0; v < p.V; ++v) {
-    p.keep_vertex[v] = meshcc_keep_vertex(p, v, thr);
-    p.vertex_map[v] = p.keep_vertex[v] ? p.totals[0]++ : -1;
-  }
-  for (long f = 0; f < p.F; ++f) {
-    p.keep_face[f] = meshcc_keep_face(p, f, thr);
-    p.face_map[f] = p.keep_face[f] ? p.totals[1]++ : -1;
-  }
+  for (long v = 0; v < p.V; ++v) p.vertex_map[v] = p.keep_vertex[v] ? p.totals[0]++ : -1;
+  for (long f = 0; f < p.F; ++f) p.face_map[f] = p.keep_face[f] ? p.totals[1]++ : -1;
+}
+
+void be_mesh_select(const MeshSelect& p, cnr_stream s) {
+  const int thr = meshcc_threshold(p.min_faces, p.min_ratio, p.summary[3]);
+  for (long v = 0; v < p.V; ++v) p.keep_vertex[v] = meshcc_keep_vertex(p, v, thr);
+  for (long f = 0; f < p.F; ++f) p.keep_face[f] = meshcc_keep_face(p, f, thr);
+  mesh_keep_scan({p.keep_vertex, p.keep_face, p.V, p.F, p.vertex_map, p.face_map, p.totals}, s);
 }
 
 void be_mesh_compact(const MeshCompact& p, cnr_stream) {
@@ -824,6 +826,52 @@ void be_point_mesh_distance(const PointMeshDist& p, cnr_stream) {
     p.keys[i] = nn_key(best, besti);
     surf_finish(p, i);
   }
+}
+
+// ---- cnr_cull.hip
+// twins of cull_pack_kernel / cull_hdilate_kernel / cull_vdilate_kernel: the same three word functions, one word after the other
+void be_mask_dilate(const MaskDilate& p, cnr_stream) {
+  const long rows = p.n * p.H;
+#pragma omp parallel for schedule(static)
+  for (long row = 0; row < rows; ++row)
+    for (int k = 0; k < p.Wq; ++k) p.bits[row * p.Wq + k] = cull_pack_word(p.masks + row * p.W, p.W, k);
+#pragma omp parallel for schedule(static)
+  for (long row = 0; row < rows; ++row)
+    for (int k = 0; k < p.Wq; ++k) p.row_bits[row * p.Wq + k] = cull_hdilate_word(p.bits + row * p.Wq, p.Wq, p.W, k, p.radius);
+#pragma omp parallel for schedule(static)
+  for (long row = 0; row < rows; ++row) {
+    const long img = row / p.H;
+    const int j = (int)(row - img * p.H);
+    for (int k = 0; k < p.Wq; ++k) p.bits[row * p.Wq + k] = cull_vdilate_word(p.row_bits + img * p.H * p.Wq, p.H, p.Wq, j, k, p.radius);
+  }
+}
+
+// twin of cull_votes_kernel: the cameras once, then cull_vote per (vertex, view), a vertex's four counts carried through its views
+void be_mesh_view_votes(const MeshViewVotes& p, cnr_stream) {
+  std::vector<RasterCam> cams((size_t)p.n_views);
+  for (long n = 0; n < p.n_views; ++n) cams[(size_t)n] = raster_cam_of(p.c2w + n * 16, p.focal + n * 2, p.origin, p.radius, p.H, p.W);
+  const float tol1 = 1.0f + p.depth_tol;
+#pragma omp parallel for schedule(static)
+  for (long v = 0; v < p.V; ++v) {
+    int c[4] = {0, 0, 0, 0};
+    for (long n = 0; n < p.n_views; ++n)
+      cull_vote(cams[(size_t)n], p.vertices + v * 3, p.opengl, p.z_near, p.H, p.W, p.Wq, p.mask_bits ? p.mask_bits + n * p.H * p.Wq : nullptr,
+                p.depth ? p.depth + n * p.H * p.W : nullptr, tol1, c);
+    for (int k = 0; k < 4; ++k) p.counts[v * 4 + k] += c[k];
+  }
+}
+
+// twins of cull_clear_kernel / cull_faces_kernel, then the shared scan
+void be_mesh_cull_select(const MeshCullSelect& p, cnr_stream s) {
+  p.dropped[0] = 0;
+  for (long v = 0; v < p.V; ++v) p.keep_vertex[v] = 0;
+  for (long f = 0; f < p.F; ++f) {
+    const int k = cull_face(p, f);
+    p.keep_face[f] = k > 0 ? 1 : 0;
+    if (k < 0) ++p.dropped[0];
+    if (k > 0) cull_mark(p, f);
+  }
+  mesh_keep_scan({p.keep_vertex, p.keep_face, p.V, p.F, p.vertex_map, p.face_map, p.totals}, s);
 }
 
 }  // namespace cnr

@@ -41,6 +41,14 @@ struct MeshSelect {
 };
 void be_mesh_select(const MeshSelect& p, cnr_stream s);
 
+// the keep flags of a selection scanned into the index maps and totals = {V', F'}: the one carried scan (meshcc_scan_kernel) behind
+// cnr_mesh_select and cnr_mesh_cull_select (cnr_cull.h)
+struct MeshKeepScan {
+  const unsigned char* keep_vertex; const unsigned char* keep_face; long V, F;
+  int* vertex_map; int* face_map; int* totals;
+};
+void mesh_keep_scan(const MeshKeepScan& p, cnr_stream s);
+
 struct MeshCompact {
   const float* vertices; const float* colors /* or null */; const int* triangles; long F, V;
   const int* vertex_map; const int* face_map;

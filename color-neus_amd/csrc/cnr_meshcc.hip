@@ -12,6 +12,7 @@
 //   meshcc_summary_kernel   one lane decodes the key into summary[2..3]
 //   meshcc_keep_kernel      keep_vertex / keep_face from the rule of cnr_mesh_select
 //   meshcc_scan_kernel      two workgroups (vertices, faces): a single-workgroup carried exclusive scan of the keep flags -> the maps and totals
+//                           (mesh_keep_scan: also the scan of cnr_mesh_cull_select, cnr_cull.hip)
 //   meshcc_compact_kernel   one vertex and one face per lane through the maps
 //
 // The counts: a marching-cubes mesh is spatially ordered, so the 64 elements of a wave nearly always share one label; a wave whose flagged lanes
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(kMeshThreads) void meshcc_keep_kernel(const MeshSel
 // block_carried_scan's trip loop in this kernel's own words: here the flags are summed behind the bounds branches, so a thread's kMeshScanPer
 // loads are in flight together; through the function every load is waited for inside its branch (0.711 ms against 0.698 ms, the same
 // registers: profiles/eval_steps_refactor_ab.txt).
-__global__ __launch_bounds__(kMeshScanThreads) void meshcc_scan_kernel(const MeshSelect p) {
+__global__ __launch_bounds__(kMeshScanThreads) void meshcc_scan_kernel(const MeshKeepScan p) {
   __shared__ int wsum[1][kMeshScanThreads / 64];
   __shared__ int carry[1];
   const unsigned char* keep = blockIdx.x ? p.keep_face : p.keep_vertex;
@@ -178,6 +179,12 @@ __global__ __launch_bounds__(kMeshScanThreads) void meshcc_scan_kernel(const Mes
   if (threadIdx.x == 0) p.totals[blockIdx.x] = carry[0];
 }
 
+void mesh_keep_scan(const MeshKeepScan& p, cnr_stream s) {
+  const long n = p.V > p.F ? p.V : p.F;
+  TimingScope ts_("meshcc_scan_kernel", 2, 0, n, 0, 0, 0, s, 5.0 * ((double)p.V + (double)p.F) + 8.0);
+  hipLaunchKernelGGL(meshcc_scan_kernel, dim3(2), dim3(kMeshScanThreads), 0, s, p);
+}
+
 void be_mesh_select(const MeshSelect& p, cnr_stream s) {
   const double V = (double)p.V, F = (double)p.F;
   const long n = p.V > p.F ? p.V : p.F;
@@ -185,10 +192,7 @@ void be_mesh_select(const MeshSelect& p, cnr_stream s) {
     TimingScope ts_("meshcc_keep_kernel", 2, 0, n, 0, 0, 0, s, 9.0 * V + 21.0 * F);
     hipLaunchKernelGGL(meshcc_keep_kernel, dim3((unsigned)((n + kMeshThreads - 1) / kMeshThreads)), dim3(kMeshThreads), 0, s, p);
   }
-  {
-    TimingScope ts_("meshcc_scan_kernel", 2, 0, n, 0, 0, 0, s, 5.0 * (V + F) + 8.0);
-    hipLaunchKernelGGL(meshcc_scan_kernel, dim3(2), dim3(kMeshScanThreads), 0, s, p);
-  }
+  mesh_keep_scan({p.keep_vertex, p.keep_face, p.V, p.F, p.vertex_map, p.face_map, p.totals}, s);
   CNR_LAUNCH_CHECK("mesh_select");
 }
 

@@ -12,6 +12,7 @@
 #include "cnr_raster.h"
 #include "cnr_meshcc.h"
 #include "cnr_surface.h"
+#include "cnr_cull.h"
 
 using namespace cnr;
 
@@ -607,6 +608,63 @@ int cnr_point_mesh_distance(const float* query, int64_t n_query, const float* ve
   p.dist2 = dist2; p.face = face; p.closest = closest; p.keys = reinterpret_cast<unsigned long long*>(keys);
   be_point_mesh_distance(p, (cnr_stream)stream);
   return check_backend("point_mesh_distance");
+}
+
+// the two view entries share the image's size rule: the packed rows of a stack are indexed below 2^31 words
+static int cull_image_sizes(const char* what, int64_t n, int32_t H, int32_t W) {
+  if (n < 0) return fail("%s: the number of images must not be negative (got %lld)", what, (long long)n);
+  if (H < 1 || W < 1) return fail("%s: H and W must be at least 1 (got %d x %d)", what, H, W);
+  if ((int64_t)H * W >= (int64_t)1 << 31) return fail("%s: the image must have fewer than 2^31 pixels", what);
+  if (n > 0 && ((int64_t)1 << 31) / ((int64_t)H * ((W + 63) / 64)) <= n) return fail("%s: the packed stack must have fewer than 2^31 words", what);
+  return 0;
+}
+
+int cnr_mask_dilate(const float* masks, int64_t n_images, int32_t H, int32_t W, int32_t radius, uint64_t* row_bits, uint64_t* bits, void* stream) {
+  if (cull_image_sizes("mask_dilate", n_images, H, W)) return -1;
+  if (radius < 0 || radius > kCullMaxRadius) return fail("mask_dilate: radius must lie in [0, %d] (got %d)", kCullMaxRadius, radius);
+  if (n_images == 0) return 0;
+  if (!masks || !row_bits || !bits) return fail("mask_dilate: null argument");
+  if (reinterpret_cast<uintptr_t>(row_bits) % 8 != 0 || reinterpret_cast<uintptr_t>(bits) % 8 != 0)
+    return fail("mask_dilate: row_bits and bits must be 8-byte aligned");
+  MaskDilate p;
+  p.masks = masks; p.n = (long)n_images; p.H = H; p.W = W; p.Wq = (W + 63) / 64; p.radius = radius;
+  p.row_bits = reinterpret_cast<unsigned long long*>(row_bits); p.bits = reinterpret_cast<unsigned long long*>(bits);
+  be_mask_dilate(p, (cnr_stream)stream);
+  return check_backend("mask_dilate");
+}
+
+int cnr_mesh_view_votes(const float* vertices, int64_t n_vertices, const float* c2w, const float* focal, const float* origin, float radius,
+                        float z_near, int32_t opengl, int64_t n_views, int32_t H, int32_t W, const uint64_t* mask_bits, const float* depth,
+                        float depth_tol, int32_t* counts, void* stream) {
+  if (n_vertices < 0 || n_vertices >= (int64_t)1 << 31) return fail("mesh_view_votes: n_vertices must lie in [0, 2^31) (got %lld)", (long long)n_vertices);
+  if (cull_image_sizes("mesh_view_votes", n_views, H, W)) return -1;
+  if (n_views == 0 || n_vertices == 0) return 0;
+  if (!vertices || !c2w || !focal || !counts) return fail("mesh_view_votes: null argument");
+  if (reinterpret_cast<uintptr_t>(mask_bits) % 8 != 0) return fail("mesh_view_votes: mask_bits must be 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(counts) % 16 != 0) return fail("mesh_view_votes: counts must be 16-byte aligned (a vertex's row is one access)");
+  MeshViewVotes p;
+  p.vertices = vertices; p.V = (long)n_vertices; p.c2w = c2w; p.focal = focal; p.origin = origin; p.radius = radius; p.z_near = z_near;
+  p.opengl = opengl; p.n_views = (long)n_views; p.H = H; p.W = W; p.Wq = (W + 63) / 64;
+  p.mask_bits = reinterpret_cast<const unsigned long long*>(mask_bits); p.depth = depth; p.depth_tol = depth_tol; p.counts = counts;
+  be_mesh_view_votes(p, (cnr_stream)stream);
+  return check_backend("mesh_view_votes");
+}
+
+int cnr_mesh_cull_select(const int32_t* triangles, int64_t n_triangles, int64_t n_vertices, const int32_t* counts, int32_t min_views,
+                         int32_t max_outside, int32_t min_visible, int32_t face_rule, uint8_t* keep_vertex, uint8_t* keep_face, int32_t* vertex_map,
+                         int32_t* face_map, int32_t* totals, int32_t* dropped, void* stream) {
+  if (mesh_sizes("mesh_cull_select", n_triangles, n_vertices)) return -1;
+  if (face_rule != CNR_CULL_FACE_ALL && face_rule != CNR_CULL_FACE_ANY) return fail("mesh_cull_select: face_rule must be 0 (all) or 1 (any), got %d", face_rule);
+  if (min_views < 0 || max_outside < 0 || min_visible < 0)
+    return fail("mesh_cull_select: min_views, max_outside and min_visible must not be negative (got %d, %d, %d)", min_views, max_outside, min_visible);
+  if ((n_triangles > 0 && (!triangles || !keep_face || !face_map)) || (n_vertices > 0 && (!counts || !keep_vertex || !vertex_map)) || !totals || !dropped)
+    return fail("mesh_cull_select: null argument");
+  MeshCullSelect p;
+  p.triangles = triangles; p.F = (long)n_triangles; p.V = (long)n_vertices; p.counts = counts;
+  p.min_views = min_views; p.max_outside = max_outside; p.min_visible = min_visible; p.face_rule = face_rule;
+  p.keep_vertex = keep_vertex; p.keep_face = keep_face; p.vertex_map = vertex_map; p.face_map = face_map; p.totals = totals; p.dropped = dropped;
+  be_mesh_cull_select(p, (cnr_stream)stream);
+  return check_backend("mesh_cull_select");
 }
 
 }  // extern "C"

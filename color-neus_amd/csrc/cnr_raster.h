@@ -28,17 +28,19 @@ struct MeshRaster {
 void be_mesh_raster(const MeshRaster& p, cnr_stream s);
 
 // the camera of a call: R = c2w[:3,:3], t = (c2w[:3,3] - origin) / radius (as cnr_gen_rays normalises the ray origin; origin null: c2w[:3,3])
+// (raster_cam_of: from the arrays of one view, for the callers that hold a stack of views -- cnr_mesh_view_votes, cnr_cull.h)
 struct RasterCam { float R[9], t[3], fx, fy, cx, cy; };
-CNR_HD RasterCam raster_cam(const MeshRaster& p) {
+CNR_HD RasterCam raster_cam_of(const float* c2w, const float* focal, const float* origin, float radius, int H, int W) {
   RasterCam c;
   for (int r = 0; r < 3; ++r) {
-    for (int k = 0; k < 3; ++k) c.R[r * 3 + k] = p.c2w[r * 4 + k];
-    c.t[r] = p.origin ? (p.c2w[r * 4 + 3] - p.origin[r]) / p.radius : p.c2w[r * 4 + 3];
+    for (int k = 0; k < 3; ++k) c.R[r * 3 + k] = c2w[r * 4 + k];
+    c.t[r] = origin ? (c2w[r * 4 + 3] - origin[r]) / radius : c2w[r * 4 + 3];
   }
-  c.fx = p.focal[0]; c.fy = p.focal[1];
-  c.cx = (float)p.W * 0.5f; c.cy = (float)p.H * 0.5f;
+  c.fx = focal[0]; c.fy = focal[1];
+  c.cx = (float)W * 0.5f; c.cy = (float)H * 0.5f;
   return c;
 }
+CNR_HD RasterCam raster_cam(const MeshRaster& p) { return raster_cam_of(p.c2w, p.focal, p.origin, p.radius, p.H, p.W); }
 
 // vertex stage: camera frame by R^T (p - t), pinhole projection (the inverse of get_rays_at), snap to 1/256 pixel (round half to even)
 CNR_HD RasterVert raster_project(const RasterCam& c, const float* v, int opengl, float z_near) {

@@ -698,13 +698,16 @@ class NeuSRenderer(nn.Module):
         verts, tris, _, _ = meshops.clean_mesh(verts, tris, library=self._lib, **kw)
         return verts, tris
 
-    def extract_geometry(self, bound_min, bound_max, device, resolution, threshold=0.0, clean=None):
+    def extract_geometry(self, bound_min, bound_max, device, resolution, threshold=0.0, clean=None, cull=None):
         """NeuS.extract_geometry (NeuS.py:31-40): -sdf on the lattice, iso-surface at ``threshold``; (vertices np (V,3), triangles np (F,3)).
         The lattice stays in HBM and the surface is extracted there (the reference copies 512 MiB to the host for PyMCubes).
         ``clean`` (default None: the raw iso-surface, as the reference returns it): "largest" or a dict of ``meshops.clean_mesh`` keyword
-        arguments removes floaters on the device before the copy to the host."""
+        arguments removes floaters on the device before the copy to the host.  ``cull`` (default None): a ``meshops.MeshCuller``, applied
+        BEFORE ``clean``: what the views never constrained goes first, then the components are chosen among what is left."""
         u = self.extract_fields(bound_min, bound_max, device, resolution)
         verts, tris = self.marching_cubes(u, bound_min, bound_max, threshold)
+        if cull is not None:
+            verts, tris, _, _ = cull(verts, tris)
         if clean is not None:
             verts, tris = self._clean(verts, tris, clean)
         return verts.cpu().numpy().astype(np.float64), tris.cpu().numpy().astype(np.int64)
@@ -725,14 +728,17 @@ class NeuSRenderer(nn.Module):
         return self.vertex_colors(pts).cpu().numpy()
 
     def render_mesh_view(self, bound_min, bound_max, resolution, c2w, focal, H, W, threshold=0.0, opengl=False, origin=None, radius=1.0,
-                         z_near=1e-3, background=None, clean=None):
+                         z_near=1e-3, background=None, clean=None, cull=None):
         """The extracted, coloured mesh seen from a camera without leaving the device: extract_fields -> marching_cubes -> vertex colours
         (cnr_vertex_color) -> imaging.rasterize_mesh.  ``c2w`` [4, 4] on the renderer's device decides the device.  Returns rasterize_mesh's
         dict plus ``"vertices"``, ``"triangles"`` and ``"colors"`` (device tensors).  ``clean`` as in ``extract_geometry``: the floaters are
-        removed BEFORE the colours are evaluated, so the colour network does not run on debris.  Not differentiable."""
+        removed BEFORE the colours are evaluated, so the colour network does not run on debris; ``cull`` (a ``meshops.MeshCuller``, with
+        views of its own) likewise, before ``clean``.  Not differentiable."""
         from . import imaging
         u = self.extract_fields(bound_min, bound_max, c2w.device, resolution)
         verts, tris = self.marching_cubes(u, bound_min, bound_max, threshold)
+        if cull is not None:
+            verts, tris, _, _ = cull(verts, tris)
         if clean is not None:
             verts, tris = self._clean(verts, tris, clean)
         colors = self.vertex_colors(verts)

@@ -629,6 +629,57 @@ int cnr_point_mesh_distance(const float* query /* [n][3] */, int64_t n_query, co
                             int64_t n_triangles, float* dist2 /* [n] */, int32_t* face /* [n] */, float* closest /* [n][3] or NULL */,
                             uint64_t* keys /* [n] */, void* stream);
 
+/* ---- culling an extracted mesh against the views: what the cameras never constrained goes.  An SDF trained with masks is supervised only inside
+ * the union of the view cones through the masks; outside it the iso-surface grows sheets and caps that are ATTACHED to the object, so the
+ * component selection above keeps them.  Three entries: pack and dilate the mask stack, count per vertex over the views, turn the counts into
+ * cnr_mesh_select's flags, maps and totals (cnr_mesh_compact consumes them unchanged).  Integer work, and separately rounded fp32 in the vertex
+ * stage: the same bits on every run, launch order and build.  There is no size query and no scratch beyond row_bits: typed device arrays owned
+ * by the caller, sized by the formulas below.  Nothing is differentiable.
+ *
+ * cnr_mask_dilate: masks float [n_images][H][W]; foreground = mask > 0 (cnr_choose_pixels' rule: NaN and negatives are background).
+ *   Packed form: one bit per pixel, Wq = ceil(W / 64) uint64 words per row, [n_images][H][Wq]; bit b of word k is pixel 64 k + b; THE BITS AT
+ *   COLUMNS >= W ARE ZERO.  Output pixel (j, i) is set iff some foreground pixel (j', i') of the SAME image has |j - j'| <= radius and
+ *   |i - i'| <= radius: cv2.dilate with a (2 radius + 1)^2 box of ones, pixels outside the image being background.  radius == 0 is pure
+ *   packing; 0 <= radius <= 32767, and a radius beyond the image floods the rows and columns that hold a foreground pixel within reach.
+ *   row_bits: scratch, bits: the result, both uint64 [n_images][H][Wq], 8-byte aligned, contents need not be initialised.
+ *   n_images == 0 is a successful no-op.  Errors: n_images < 0; H or W < 1; H * W >= 2^31; n_images * H * Wq >= 2^31; a radius out of range;
+ *   a null pointer; row_bits or bits not 8-byte aligned.
+ *
+ * cnr_mesh_view_votes: per (vertex v, view n), with cnr_mesh_raster's camera and vertex stage for c2w[n], focal[n] and the shared origin / radius /
+ *   z_near / opengl (the same arithmetic: camera frame, pinhole projection, X = rint(256 u), Y = rint(256 v), zc):
+ *     usable = the vertex stage accepts the vertex (finite, zc > z_near, |u|, |v| < 2^21)
+ *     i = (X + 128) >> 8,  j = (Y + 128) >> 8   (arithmetic shift: the nearest pixel centre; centres sit at integer coordinates)
+ *     seen = usable and 0 <= i < W and 0 <= j < H
+ *     counts[v][0] += 1
+ *     counts[v][1] += seen
+ *     counts[v][2] += seen && (mask_bits == NULL || bit (j, i) of view n)
+ *     counts[v][3] += seen && (depth == NULL || !(zc > depth[n][j][i] * (1.0f + depth_tol)))    (the sum and the product one fp32 rounding each;
+ *                     a NaN depth -- no surface at that pixel, cnr_mesh_raster's value -- fails the comparison and counts as visible)
+ *   counts: int32 [n_vertices][4], 16-BYTE ALIGNED, ADDED TO: the caller zeroes it, and calls on one stream accumulate (views in chunks).  Each
+ *   row is read and written by one lane, once per call: no atomics.  mask_bits: cnr_mask_dilate's packed form for the same H, W, or NULL;
+ *   depth: float [n_views][H][W] (cnr_mesh_raster's depth maps) or NULL; c2w float [n_views][4][4], focal float [n_views][2], origin float [3]
+ *   or NULL, all device memory.  n_views == 0 and n_vertices == 0 are successful no-ops.  Errors: n_vertices < 0 or >= 2^31; the image errors
+ *   of cnr_mask_dilate with n_views for n_images; a null vertices, c2w, focal or counts; mask_bits not 8-byte or counts not 16-byte aligned.
+ *
+ * cnr_mesh_cull_select: with (total, seen, inside, visible) = counts[v], vertex v PASSES iff
+ *     seen >= min_views  &&  seen - inside <= max_outside  &&  visible >= min_visible.
+ *   A valid face (three indices in [0, n_vertices), as above) is kept iff all three of its vertices pass (face_rule 0) or any of them passes
+ *   (face_rule 1); an invalid face is never kept and is counted in dropped[0].  keep_vertex[v] = 1 iff some kept face names v (so with
+ *   face_rule 1 a vertex that does not pass can stay, and a passing vertex without a kept face goes).  keep_vertex uint8 [n_vertices],
+ *   keep_face uint8 [n_triangles], vertex_map int32 [n_vertices], face_map int32 [n_triangles], totals int32 [2] = {V', F'}: exactly
+ *   cnr_mesh_select's outputs; dropped int32 [1].  All overwritten.  n_triangles == 0 and n_vertices == 0 are legal, totals and dropped are
+ *   still written.  Errors: n_triangles or n_vertices negative or above 2^31 - 1; a face_rule other than 0 / 1; a negative min_views,
+ *   max_outside or min_visible; a null pointer to an array that is not empty, a null totals or dropped. */
+int cnr_mask_dilate(const float* masks /* [n][H][W] */, int64_t n_images, int32_t H, int32_t W, int32_t radius,
+                    uint64_t* row_bits /* scratch [n][H][Wq] */, uint64_t* bits /* out [n][H][Wq] */, void* stream);
+int cnr_mesh_view_votes(const float* vertices /* [V][3] */, int64_t n_vertices, const float* c2w /* [n][4][4] */, const float* focal /* [n][2] */,
+                        const float* origin /* [3] or NULL */, float radius, float z_near, int32_t opengl, int64_t n_views, int32_t H, int32_t W,
+                        const uint64_t* mask_bits /* [n][H][Wq] or NULL */, const float* depth /* [n][H][W] or NULL */, float depth_tol,
+                        int32_t* counts /* [V][4], ADDED to */, void* stream);
+int cnr_mesh_cull_select(const int32_t* triangles /* [F][3] */, int64_t n_triangles, int64_t n_vertices, const int32_t* counts /* [V][4] */,
+                         int32_t min_views, int32_t max_outside, int32_t min_visible, int32_t face_rule, uint8_t* keep_vertex, uint8_t* keep_face,
+                         int32_t* vertex_map, int32_t* face_map, int32_t* totals /* [2] */, int32_t* dropped /* [1] */, void* stream);
+
 /* ---- one plain fully-connected layer on the layer / weight-gradient kernels of the render path: y = act(x W^T + b), act = ReLU or none.
  * The NeRF++ background network of NeuS (NeRF, fields.py:192-274; N_OUTSIDE > 0, NeuS.py:95-134) is a chain of nn.Linear (+ ReLU) layers;
  * color-neus_amd/background.py evaluates each of them through these two entry points.  x [n][k], y / dy [n][n_out], W [n_out][k] and b [n_out]
