@@ -190,6 +190,8 @@ SIGNATURES = {
     "cnr_mask_dilate": (_int, [_FP, _i64, _i32, _i32, _i32, _FP, _FP, _FP]),
     "cnr_mesh_view_votes": (_int, [_FP, _i64, _FP, _FP, _FP, _f32, _f32, _i32, _i64, _i32, _i32, _FP, _FP, _f32, _FP, _FP]),
     "cnr_mesh_cull_select": (_int, [_FP, _i64, _i64, _FP, _i32, _i32, _i32, _i32, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
+    # ICP registration to a cloud or a mesh
+    "cnr_icp": (_int, [_FP, _i64, _FP, _i64, _FP, _i64, _FP, _i32, _f32, _i32, _i32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP]),
     # one plain fully-connected layer
     "cnr_linear_scratch_bytes": (_size, [_i64, _i32, _i32, _i32]),
     "cnr_linear_forward": (_int, [_FP, _i64, _i32, _FP, _FP, _i32, _i32, _FP, _FP, _size, _FP]),

@@ -1,7 +1,8 @@
 // Kernel launch interface of the render path between the host orchestration (the host units listed in cnr_plan.cpp, sharing cnr_plan.h) and the
 // kernels: weight preparation, the layer / chain / narrow / head / strip launches, sampler, compositor and prune, the *_finish kernels and the
 // point-query rows, the memset / column helpers, timing, ranges and the error check.  Every stand-alone family (loss, optimiser, rays, pixels,
-// cameras, marching cubes, nearest neighbour, image metrics, background, mesh raster, mesh components) has a header of its own: cnr_<family>.h.
+// cameras, marching cubes, nearest neighbour, image metrics, background, mesh raster, mesh components, mesh surface, mesh culling, registration)
+// has a header of its own: cnr_<family>.h.
 // Implemented twice: the .hip translation units (HIP, gfx950 -- the product) and cnr_kernels_emu.cpp (CPU emulation, tests only).
 #pragma once
 #include "cnr_common.h"

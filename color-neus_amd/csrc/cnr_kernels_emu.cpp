@@ -23,6 +23,7 @@
 #include "cnr_meshcc.h"
 #include "cnr_surface.h"
 #include "cnr_cull.h"
+#include "cnr_register.h"
 
 namespace cnr {
 
@@ -872,6 +873,38 @@ void be_mesh_cull_select(const MeshCullSelect& p, cnr_stream s) {
     if (k > 0) cull_mark(p, f);
   }
   mesh_keep_scan({p.keep_vertex, p.keep_face, p.V, p.F, p.vertex_map, p.face_map, p.totals}, s);
+}
+
+// ---- cnr_register.hip
+// twin of icp_move_kernel / icp_moments_kernel / icp_solve_kernel: the same icp_move / icp_pair / icp_finish; the chunk tree x[j] += x[j + h],
+// h = 128 .. 1, over 256 rows padded with zeros, then the chunks' rows added in chunk order from +0.0
+void be_icp_clear(void* p, size_t bytes, cnr_stream) { memset(p, 0, bytes); }
+void be_icp_step(const IcpStep& p, cnr_stream s) {
+  const IcpMap k = icp_map(p.transform);
+#pragma omp parallel for schedule(static)
+  for (long i = 0; i < p.n; ++i) icp_move(p, k, i);
+  icp_search(p, s);
+  const long chunks = (p.n + kIcpChunk - 1) / kIcpChunk;
+  long long n_inliers = 0, n_changed = 0;
+#pragma omp parallel for schedule(static) reduction(+ : n_inliers, n_changed)
+  for (long b = 0; b < chunks; ++b) {
+    std::vector<double> x((size_t)kIcpChunk * kIcpTerms, 0.0);
+    for (int j = 0; j < kIcpChunk && b * kIcpChunk + j < p.n; ++j) {
+      int inlier, changed;
+      icp_pair(p, b * kIcpChunk + j, &x[(size_t)j * kIcpTerms], &inlier, &changed);
+      n_inliers += inlier; n_changed += changed;
+    }
+    for (int h = kIcpChunk / 2; h >= 1; h >>= 1)
+      for (int j = 0; j < h; ++j)
+        for (int c = 0; c < kIcpTerms; ++c) x[(size_t)j * kIcpTerms + c] += x[(size_t)(j + h) * kIcpTerms + c];
+    for (int c = 0; c < kIcpTerms; ++c) p.partials[b * kIcpTerms + c] = x[c];
+  }
+  double S[kIcpTerms];
+  for (int c = 0; c < kIcpTerms; ++c) {
+    S[c] = 0.0;
+    for (long b = 0; b < chunks; ++b) S[c] += p.partials[b * kIcpTerms + c];
+  }
+  icp_finish(p, S, n_inliers, n_changed);
 }
 
 }  // namespace cnr

@@ -13,6 +13,7 @@
 #include "cnr_meshcc.h"
 #include "cnr_surface.h"
 #include "cnr_cull.h"
+#include "cnr_register.h"
 
 using namespace cnr;
 
@@ -665,6 +666,37 @@ int cnr_mesh_cull_select(const int32_t* triangles, int64_t n_triangles, int64_t 
   p.keep_vertex = keep_vertex; p.keep_face = keep_face; p.vertex_map = vertex_map; p.face_map = face_map; p.totals = totals; p.dropped = dropped;
   be_mesh_cull_select(p, (cnr_stream)stream);
   return check_backend("mesh_cull_select");
+}
+
+// ICP: `iterations` times move, search, moments and solve on the stream; the transform stays on the device between them
+int cnr_icp(const float* source, int64_t n_source, const float* target, int64_t n_target, const int32_t* triangles, int64_t n_triangles,
+            const double* pivots, int32_t with_scale, float max_dist2, int32_t iterations, int32_t resume, double* transform, double* history,
+            float* moved, float* matched, float* dist2, int32_t* idx, uint64_t* keys, double* partials, void* stream) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (n_source < 0 || n_source >= lim) return fail("icp: n_source must be in [0, 2^31) (got %lld)", (long long)n_source);
+  if (n_target < 1 || n_target >= lim) return fail("icp: n_target must be in [1, 2^31) (got %lld)", (long long)n_target);
+  if (n_triangles < 0 || n_triangles >= lim) return fail("icp: n_triangles must be in [0, 2^31) (got %lld)", (long long)n_triangles);
+  if ((triangles == nullptr) != (n_triangles == 0)) return fail("icp: triangles must be null exactly when n_triangles == 0 (a cloud target)");
+  if (iterations < 0) return fail("icp: iterations < 0");
+  if (!(max_dist2 >= 0.0f)) return fail("icp: max_dist2 must not be NaN or negative (+inf: no gate)");
+  if (n_source == 0 || iterations == 0) return 0;
+  if (!source || !target || !pivots || !transform || !history || !moved || !matched || !dist2 || !idx || !keys || !partials)
+    return fail("icp: null argument");
+  if (reinterpret_cast<uintptr_t>(transform) % 8 != 0 || reinterpret_cast<uintptr_t>(history) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(keys) % 8 != 0 || reinterpret_cast<uintptr_t>(partials) % 8 != 0)
+    return fail("icp: transform, history, keys and partials must be 8-byte aligned");
+  IcpStep p;
+  p.source = source; p.n = (long)n_source; p.target = target; p.m = (long)n_target; p.triangles = triangles; p.F = (long)n_triangles;
+  for (int r = 0; r < 3; ++r) { p.c_src[r] = pivots[r]; p.c_tgt[r] = pivots[3 + r]; }
+  p.with_scale = with_scale != 0; p.max_dist2 = max_dist2; p.transform = transform;
+  p.moved = moved; p.matched = matched; p.dist2 = dist2; p.idx = idx; p.keys = reinterpret_cast<unsigned long long*>(keys); p.partials = partials;
+  be_icp_clear(history, (size_t)iterations * 4 * sizeof(double), (cnr_stream)stream);
+  for (int k = 0; k < iterations; ++k) {
+    p.first = k == 0 && resume == 0;
+    p.history = history + (size_t)k * 4;
+    be_icp_step(p, (cnr_stream)stream);
+  }
+  return check_backend("icp");
 }
 
 }  // extern "C"

@@ -24,6 +24,14 @@ __device__ __forceinline__ int wave_min_int(int x) {
   for (int d = 32; d >= 1; d >>= 1) { const int y = __shfl_xor(x, d); x = y < x ? y : x; }
   return x;
 }
+// the halving tree x[j] += x[j + d], d = 32 .. 1, over the wave's 64 values in lane order: the result in lane 0 ONLY (the lanes whose partner
+// lies past the wave add their own value and are never read).  An order a sequential program restates with the same loop.
+template <class T>
+__device__ __forceinline__ T wave_fold_down(T x) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
+  return x;
+}
 // sum over the 16 lanes of a row (lane & ~15 .. | 15): butterfly d = 8 .. 1, the result in every lane of the row
 __device__ __forceinline__ float row16_sum(float x) {
 #pragma unroll

@@ -12,7 +12,7 @@ the current stream.  CUDA tensors go through the HIP library; CPU tensors only w
 CPU fallback).  NOTHING HERE IS DIFFERENTIABLE: inputs are detached and results carry no graph."""
 import torch
 
-from . import _lib, meshio, meshops
+from . import _lib, meshio, meshops, registration
 from ._lib import points3, ptr, stream_of
 
 __all__ = ["nearest_neighbors", "normalize_point_cloud", "chamfer_distance", "mesh_metrics", "compute_chamfer_distance", "point_mesh_distance",
@@ -64,7 +64,23 @@ def normalize_point_cloud(pc):
     return pc / m, centroid, m
 
 
-def chamfer_distance(x, y, norm=False, library=None):
+def _aligned(pred, gt, align, library, name):
+    """``align=`` of the metric functions: ``pred`` (a cloud, or a ``(vertices, triangles)`` mesh) moved onto ``gt`` before anything is sampled or
+    searched.  ``"rigid"`` / ``"similarity"`` run ``registration.icp(pred -> gt)`` from ``init="normalize"``; a ``Registration`` or a 4x4 matrix
+    is applied as given.  The registration runs with ``icp``'s own defaults -- a mesh ``pred`` is sampled with 20 000 points under seed 0, 50
+    iterations -- whatever ``n_samples`` / ``seed`` the metric itself uses; pass a ``Registration`` made with other settings to change that.  Returns ``(pred', {"transform": nested lists, "align_rms": the registration's rms, None for a bare matrix})``."""
+    if isinstance(align, str):
+        if align not in ("rigid", "similarity"):
+            raise ValueError(f"{name}: align must be None, 'rigid', 'similarity', a Registration or a 4x4 matrix (got {align!r})")
+        align = registration.icp(pred, gt, with_scale=align == "similarity", init="normalize", library=library)
+    matrix, rms = (align.matrix, align.rms) if isinstance(align, registration.Registration) else (registration.as_matrix(align), None)
+    info = {"transform": matrix.tolist(), "align_rms": rms}
+    if isinstance(pred, (tuple, list)):
+        return (registration.apply_transform(pred[0], matrix), pred[1]), info
+    return registration.apply_transform(pred, matrix), info
+
+
+def chamfer_distance(x, y, norm=False, library=None, align=None):
     """``mean_i min_j |x_i - y_j|^2 + mean_j min_i |x_i - y_j|^2`` as a 0-dim float64 tensor on the inputs' device: squared distances, the mean
     over the points of each direction, the two directions added.
 
@@ -72,10 +88,13 @@ def chamfer_distance(x, y, norm=False, library=None):
     ``point_reduction="mean"``, ``norm=2``; mesh_tools.py:68).  pytorch3d is not a dependency of this package, so that equivalence is stated from
     its documentation and not checked by the tests.  ``norm=True`` first applies ``normalize_point_cloud`` to each cloud separately, as the
     reference does.  The nearest-neighbour distances are float32 (``nearest_neighbors``); the two means are float64 sums of them.
-    Not differentiable."""
+    ``align`` (None: off) first moves ``x`` onto ``y``: ``"rigid"`` / ``"similarity"`` by ``registration.icp``, or a given ``Registration`` /
+    4x4 matrix.  Not differentiable."""
     x, y, lib = _pair(x, y, ("x", "y"), library)
     if x.shape[0] == 0 or y.shape[0] == 0:
         raise ValueError("chamfer_distance: empty point cloud")
+    if align is not None:
+        x = _aligned(x, y, align, lib, "chamfer_distance")[0].contiguous()
     if norm:
         x, y = normalize_point_cloud(x)[0].contiguous(), normalize_point_cloud(y)[0].contiguous()
     dxy, _ = _search(x, y, lib)
@@ -83,19 +102,25 @@ def chamfer_distance(x, y, norm=False, library=None):
     return dxy.to(torch.float64).mean() + dyx.to(torch.float64).mean()
 
 
-def mesh_metrics(pred, gt, thresholds=(0.01, 0.02, 0.05), library=None):
+def mesh_metrics(pred, gt, thresholds=(0.01, 0.02, 0.05), library=None, align=None):
     """The usual surface-reconstruction figures from ONE pair of searches (pred -> gt and gt -> pred), as a dict of Python floats:
 
     ``accuracy`` mean distance pred -> gt, ``completeness`` mean distance gt -> pred, ``chamfer_l1`` their mean, ``chamfer_l2`` the value of
     ``chamfer_distance(pred, gt)``, and per threshold t the keys ``"precision@t"``, ``"recall@t"``, ``"fscore@t"`` (t formatted with ``%g``,
     e.g. ``"fscore@0.02"``): the share of pred points / of gt points whose distance is < t, and 2PR / (P + R) (0 when P + R = 0).  Distances are sqrt of the float32 squared distances,
-    taken and averaged in float64.  Not differentiable."""
+    taken and averaged in float64.  ``align`` (None: off; ``"rigid"``, ``"similarity"``, a ``Registration`` or a 4x4 matrix) first moves ``pred``
+    onto ``gt`` (``registration.icp`` from ``init="normalize"``); the dict then also carries ``"transform"`` (the 4x4 matrix as nested lists) and
+    ``"align_rms"``.  Not differentiable."""
     p, g, lib = _pair(pred, gt, ("pred", "gt"), library)
     if p.shape[0] == 0 or g.shape[0] == 0:
         raise ValueError("mesh_metrics: empty point cloud")
+    info = {}
+    if align is not None:
+        p, info = _aligned(p, g, align, lib, "mesh_metrics")
+        p = p.contiguous()
     d2_pg, _ = _search(p, g, lib)
     d2_gp, _ = _search(g, p, lib)
-    return _figures(d2_pg, d2_gp, thresholds, None)
+    return {**_figures(d2_pg, d2_gp, thresholds, None), **info}
 
 
 def _mesh(mesh, name, dev=None):
@@ -154,7 +179,7 @@ def _figures(d2_pg, d2_gp, thresholds, max_dist):
     return out
 
 
-def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 0.05), exact=True, max_dist=None, library=None):
+def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 0.05), exact=True, max_dist=None, library=None, align=None):
     """The figures of ``mesh_metrics`` -- same keys, same definitions, float64 reductions -- measured between SURFACES instead of vertex clouds,
     so that they do not move with the tessellation.  ``pred`` is ``(vertices, triangles)``; ``gt`` is ``(vertices, triangles)`` or a bare
     ``(N, 3)`` cloud (a scanned ground truth, as DTU's).
@@ -163,7 +188,11 @@ def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 
     measured from the pred samples, completeness from the gt samples (or the gt cloud).  ``exact=True``: each point to the other SURFACE
     (``point_mesh_distance``; to the gt cloud's nearest point when gt is a cloud).  ``exact=False``: point to the other side's SAMPLES through
     ``cnr_nn_search`` -- ``mesh_metrics`` of the two sample sets.  ``max_dist`` clamps every distance before the means and thresholds (the DTU
-    protocol's outlier cap); ``chamfer_l2`` then clamps the squared distances at ``max_dist ** 2``.  Not differentiable."""
+    protocol's outlier cap); ``chamfer_l2`` then clamps the squared distances at ``max_dist ** 2``.  ``align`` (None: off; ``"rigid"``,
+    ``"similarity"``, a ``Registration`` or a 4x4 matrix) first moves the pred mesh onto ``gt`` -- ``registration.icp`` of its samples to the gt
+    surface (or cloud) from ``init="normalize"``, with ``icp``'s own ``n_samples=20000, seed=0`` and not this call's -- before anything is sampled
+    or measured; the dict then also carries ``"transform"`` and
+    ``"align_rms"``.  Not differentiable."""
     n_samples = int(n_samples)
     if n_samples <= 0:
         raise ValueError(f"surface_metrics: n_samples must be positive (got {n_samples})")
@@ -172,6 +201,10 @@ def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 
     pv, pt = _mesh(pred, "pred")
     dev = pv.device
     lib = _lib.library_for(library, dev, ("meshes", "compared"))
+    info = {}
+    if align is not None:
+        (pv, pt), info = _aligned((pv, pt), gt, align, lib, "surface_metrics")
+        pv = pv.contiguous()
     ps = meshops.sample_surface(pv, pt, n_samples, seed=seed, library=lib)[0]
     if isinstance(gt, (tuple, list)):
         gv, gtri = _mesh(gt, "gt", dev)
@@ -183,25 +216,26 @@ def surface_metrics(pred, gt, n_samples=100000, seed=0, thresholds=(0.01, 0.02, 
             raise ValueError("surface_metrics: the gt cloud is empty")
         d2_pg = _search(ps, gs, lib)[0]
     d2_gp = _closest_face(gs, pv, pt, lib)[0] if exact else _search(gs, ps, lib)[0]
-    return _figures(d2_pg, d2_gp, thresholds, max_dist)
+    return {**_figures(d2_pg, d2_gp, thresholds, max_dist), **info}
 
 
 def compute_surface_metrics(path_pred, path_gt, device="cuda", n_samples=100000, seed=0, thresholds=(0.01, 0.02, 0.05), exact=True, max_dist=None,
-                            library=None):
+                            library=None, align=None):
     """``surface_metrics`` on two PLY files (``meshio.read_ply_mesh``): ``path_pred`` must hold triangles; a ``path_gt`` without a face element
-    (or with an empty one) is taken as a cloud."""
+    (or with an empty one) is taken as a cloud.  ``align``: as in ``surface_metrics``."""
     pv, pt = meshio.read_ply_mesh(path_pred)
     gv, gt = meshio.read_ply_mesh(path_gt)
     if pt is None:
         raise ValueError(f"{path_pred}: the predicted mesh has no face element")
     pred = (torch.from_numpy(pv).to(device), torch.from_numpy(pt).to(device))
     gt = (torch.from_numpy(gv).to(device), torch.from_numpy(gt).to(device)) if gt is not None and gt.shape[0] else torch.from_numpy(gv).to(device)
-    return surface_metrics(pred, gt, n_samples=n_samples, seed=seed, thresholds=thresholds, exact=exact, max_dist=max_dist, library=library)
+    return surface_metrics(pred, gt, n_samples=n_samples, seed=seed, thresholds=thresholds, exact=exact, max_dist=max_dist, library=library,
+                           align=align)
 
 
-def compute_chamfer_distance(path_source, path_target, device="cuda", norm=False, library=None):
+def compute_chamfer_distance(path_source, path_target, device="cuda", norm=False, library=None, align=None):
     """The reference helper (mesh_tools.py:59-70; its ``deivce`` argument spelled ``device``) on the vertices of two PLY files:
-    ``chamfer_distance`` of the two vertex clouds on ``device``.  Not differentiable."""
+    ``chamfer_distance`` of the two vertex clouds on ``device`` (``align``: as there).  Not differentiable."""
     src = torch.from_numpy(meshio.read_ply_vertices(path_source)).to(device)
     tgt = torch.from_numpy(meshio.read_ply_vertices(path_target)).to(device)
-    return chamfer_distance(src, tgt, norm=norm, library=library)
+    return chamfer_distance(src, tgt, norm=norm, library=library, align=align)

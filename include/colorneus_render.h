@@ -680,6 +680,61 @@ int cnr_mesh_cull_select(const int32_t* triangles /* [F][3] */, int64_t n_triang
                          int32_t min_views, int32_t max_outside, int32_t min_visible, int32_t face_rule, uint8_t* keep_vertex, uint8_t* keep_face,
                          int32_t* vertex_map, int32_t* face_map, int32_t* totals /* [2] */, int32_t* dropped /* [1] */, void* stream);
 
+/* ---- ICP registration: the rigid or similarity map x' = s*R*x + t that takes a point set onto a cloud or a mesh, by iterated closest
+ * points.  With learnable cameras a reconstruction drifts by a similarity against its ground truth; the mesh metrics above then measure the
+ * drift.  One call enqueues `iterations` iterations on the stream with no host synchronisation and no allocation (capturable); the match of
+ * every iteration is cnr_nn_search's search (cloud target: triangles NULL, n_triangles 0, n_target points) or cnr_point_mesh_distance's (mesh
+ * target: n_target vertices, n_triangles faces) as they stand.  There is no size query and no scratch: every buffer is a typed device array
+ * owned by the caller, contents need not be initialised (transform, and idx with resume != 0, are inputs).  pivots is a HOST array
+ * {c_src[3], c_tgt[3]}, read when the call is issued: the moments are taken about them (the clouds' means keep the sums small).
+ * Every float and double operation below is ONE rounded operation in the written order (no FMA; / and sqrt correctly rounded): the same bits
+ * on every run, launch shape and build.  transform = {R row-major [9], t [3], s, 0, 0, 0}.  Iteration k:
+ *   1. move     m[r][c] = (float)(s*R[r][c]) (the double product rounded once), tf[r] = (float)t[r];
+ *               moved_i[r] = ((m[r][0]*x + m[r][1]*y) + m[r][2]*z) + tf[r] in fp32, (x, y, z) = source_i.
+ *   2. match    dist2_i, idx_i = the search of moved_i (the nearest target point / the closest face; lowest index on ties; NaN and -1
+ *               without a candidate); matched_i = that target point, or the closest point on that face (cnr_point_mesh_distance's
+ *               `closest`, evaluated with the moments), NaN when idx_i = -1.
+ *   3. moments  i is an inlier iff idx_i >= 0 and dist2_i <= max_dist2 (fp32; +inf: no gate).  a = (double)source_i - c_src (the ORIGINAL
+ *               point: the solved map is absolute, not an increment), b = (double)matched_i - c_tgt.  Eighteen fp64 terms: a (3), b (3),
+ *               b[r]*a[c] (9, row-major), a.a, b.b, (double)dist2_i, every dot product (x*x + y*y) + z*z; eighteen zeros for a non-inlier.
+ *               ONE summation order: chunks of 256 consecutive points padded with zeros, within a chunk the tree x[j] += x[j + h] for
+ *               h = 128, 64, ..., 1 (the chunk's sums: a row of partials), then the rows added one after the other in chunk order, from +0.0.
+ *               n_inliers and n_changed (idx_i differs from the previous iteration's) are integer counts.  With resume == 0 the first
+ *               iteration does not read idx and n_changed = n_source; with resume != 0 idx holds the previous call's last result.
+ *   4. solve    n = n_inliers; abar = Sa/n, bbar = Sb/n; C[r][c] = Sba[r][c] - Sb[r]*abar[c]; va = Saa - ((Sa0*abar0 + Sa1*abar1) + Sa2*abar2).
+ *               Horn's symmetric 4x4 matrix of C, with Sxy = C[y][x] (the source axis first):
+ *                 N00 = (Sxx + Syy) + Szz  N01 = Syz - Szy          N02 = Szx - Sxz          N03 = Sxy - Syx
+ *                                          N11 = (Sxx - Syy) - Szz  N12 = Sxy + Syx          N13 = Szx + Sxz
+ *                                                                   N22 = (Syy - Sxx) - Szz  N23 = Syz + Szy
+ *                                                                                            N33 = (Szz - Sxx) - Syy
+ *               TEN cyclic Jacobi sweeps, each the planes (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), V = I at the start.  A rotation whose
+ *               off-diagonal element N[p][q] is exactly 0 is skipped; otherwise theta = (N[q][q] - N[p][p]) / (2*N[p][q]),
+ *               tt = sgn(theta) / (|theta| + sqrt(theta*theta + 1)) (sgn(0) = +1), c = 1 / sqrt(tt*tt + 1), sn = tt*c, h = tt*N[p][q];
+ *               N[p][p] -= h, N[q][q] += h, N[p][q] = N[q][p] = 0; for the other two rows r: N[r][p] = c*arp - sn*arq, N[r][q] = sn*arp + c*arq
+ *               (arp, arq the old N[r][p], N[r][q]; mirrored); for every row r of V the same pair of expressions on V[r][p], V[r][q].
+ *               (w, x, y, z) = the column of V under the largest diagonal element (the lowest index on ties), each divided by
+ *               nrm = sqrt(((w*w + x*x) + y*y) + z*z), all four negated when w < 0.  A unit quaternion always gives a proper rotation:
+ *                 R = [1 - 2*(y*y + z*z), 2*(x*y - w*z), 2*(x*z + w*y);  2*(x*y + w*z), 1 - 2*(x*x + z*z), 2*(y*z - w*x);
+ *                      2*(x*z - w*y), 2*(y*z + w*x), 1 - 2*(x*x + y*y)]
+ *               s = (R[0][0]*C[0][0] + R[0][1]*C[0][1] + ..., the nine products added one after the other in row-major order) / va with
+ *               with_scale, else 1;  t[r] = (bbar[r] + c_tgt[r]) - s*((R[r][0]*p0 + R[r][1]*p1) + R[r][2]*p2), p = abar + c_src.
+ *               Degenerate -- n_inliers < 3, a sum that is not finite, va <= 0, or a result that is not finite or whose s is not positive:
+ *               the transform is left exactly as it was and the status is 1; else the status is 0.
+ *   5. history  history[k] = {n_inliers, n_changed, the sum of the inliers' dist2, status}, all measured under the transform iteration k
+ *               STARTED with; the counts are exact in a double.
+ * After the call moved, matched, dist2 and idx hold the last iteration's correspondence.  The transform is absolute and the sums have one
+ * order, so an iteration with n_changed == 0 and the same inlier set is a fixed point (every later iteration writes the same bits), and
+ * `a` iterations followed by a resume != 0 call of `b` give the bits of one call of a + b.  Nothing is differentiable.
+ * Errors (a negative status, the text in cnr_last_error): n_source < 0 or >= 2^31; n_target outside [1, 2^31); n_triangles < 0 or >= 2^31;
+ * triangles NULL with n_triangles != 0 or the reverse; iterations < 0; max_dist2 NaN or negative; a null pointer; transform, history, keys
+ * or partials not 8-byte aligned.  n_source == 0 or iterations == 0 is a successful no-op that leaves transform untouched. */
+int cnr_icp(const float* source /* [n][3] */, int64_t n_source, const float* target /* cloud [m][3], or mesh vertices [V][3] */, int64_t n_target,
+            const int32_t* triangles /* [F][3], or NULL with n_triangles == 0: cloud target */, int64_t n_triangles,
+            const double* pivots /* HOST [6]: c_src, c_tgt */, int32_t with_scale, float max_dist2, int32_t iterations, int32_t resume,
+            double* transform /* device [16], in/out */, double* history /* device [iterations][4] */, float* moved /* [n][3] */,
+            float* matched /* [n][3] */, float* dist2 /* [n] */, int32_t* idx /* [n] */, uint64_t* keys /* [n] */,
+            double* partials /* [ceil(n/256)][18] */, void* stream);
+
 /* ---- one plain fully-connected layer on the layer / weight-gradient kernels of the render path: y = act(x W^T + b), act = ReLU or none.
  * The NeRF++ background network of NeuS (NeRF, fields.py:192-274; N_OUTSIDE > 0, NeuS.py:95-134) is a chain of nn.Linear (+ ReLU) layers;
  * color-neus_amd/background.py evaluates each of them through these two entry points.  x [n][k], y / dy [n][n_out], W [n_out][k] and b [n_out]
