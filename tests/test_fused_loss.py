@@ -51,6 +51,95 @@ def test_fused_loss_matches_compute_loss_hip():
     _compare(cn.load_library(), "cuda:0")
 
 
+# R at which a grid-stride loop makes its second trip: the colour loop of the 256 x 256 forward launch from 21846 rays (3R terms), its per-ray
+# loops (BCE, the per-ray relight sums) from 65537, the backward launch (at most 1024 blocks) from 87382; 90001 is ragged everywhere.  The
+# [R][M][3] relight tensor wraps from 6R > 65536 on.
+WRAPPED_SIZES = [(53, 12), (21846, 4), (65537, 2), (87382, 2), (90001, 3)]
+
+
+def _leaves(case, per_ray, dtype):
+    """The renderer outputs the loss differentiates, as fresh leaves of ``dtype``.  per_ray: the training_outputs="loss_only" form, one sum
+    of delta_relight per ray (drawn as the float32 sums of the case's [R][M][3] tensor) instead of the tensor."""
+    out, gt, mask = case
+    lv = {k: out[k].detach().to(dtype).requires_grad_(True) for k in ("color_fine", "weight_sum", "gradient_error")}
+    if per_ray:
+        lv["delta_relight_ray_sum"] = out["delta_relight"].detach().sum(dim=(1, 2)).to(dtype).requires_grad_(True)
+    else:
+        lv["delta_relight"] = out["delta_relight"].detach().to(dtype).requires_grad_(True)
+    return lv
+
+
+def _compute_loss_of(lv, gt, mask, M, **kw):
+    """compute_loss on the leaves; the per-ray sums enter as the [R][M][3] tensor with the same mean (every entry of a ray = its sum / 3M)"""
+    import color_neus_amd as cn
+    rd = dict(lv)
+    if "delta_relight_ray_sum" in rd:
+        s = rd.pop("delta_relight_ray_sum")
+        rd["delta_relight"] = (s / (3.0 * M))[:, None, None].expand(s.shape[0], M, 3)
+    return cn.compute_loss(rd, gt.to(lv["color_fine"].dtype), None if mask is None else mask.to(lv["color_fine"].dtype), **kw)
+
+
+def _compare64(lib, device):
+    """compute_loss_fused against compute_loss in float64 at sizes where every strided loop of the three loss kernels has wrapped, both
+    forms of the relight term, all VARIANTS, with and without a mask: the loss, every returned part, and the gradient of every renderer
+    output, each against its own reference value (a gradient: against its largest reference entry; one whose reference is zero must be zero).
+
+    Tolerance: 4 x the worst distance of float32 compute_loss from the same reference over these inputs, per quantity (the HIP fold sums in
+    another order than torch or the emulation).  Measured on the CPU over the 100 cases, worst relative distance (float32 compute_loss / the
+    emulation build): loss 3.5e-7 / 2.7e-7; rgb_fine_loss 1.4e-7 / 5.9e-8; mask_loss 6.2e-7 / 6.2e-7; relight_loss 8.4e-6 / 1.1e-7;
+    d color_fine 5.9e-8 / 5.9e-8; d weight_sum 1.1e-7 / 7.5e-8; d gradient_error 1.5e-8 / 1.5e-8; d delta_relight
+    1.2e-6 / 1.1e-7; d delta_relight_ray_sum 4.1e-6 / 9.0e-8; eikonal_loss 0 / 0 (the value is
+    handed through).  torch's float32 mean of the zero-mean relight tensor cancels worse than the kernels' fixed-order fold, hence the larger
+    figures of the relight terms.  The run prints its own figures before it asserts."""
+    import color_neus_amd as cn
+    rel = lambda x, ref: abs(float(x) - float(ref)) / abs(float(ref)) if float(ref) != 0.0 else (0.0 if float(x) == 0.0 else float("inf"))
+    rows = []                                  # (case, quantity, distance of float32 compute_loss, distance of the fused loss)
+    for R, M in WRAPPED_SIZES:
+        case = _case(device, R=R, M=M, seed=R)
+        out, gt, mask = case
+        for per_ray in (False, True):
+            for kw in VARIANTS:
+                for use_mask in (True, False):
+                    m = mask if use_mask else None
+                    res = {}
+                    for name, dtype in (("ref", torch.float64), ("f32", torch.float32), ("fused", torch.float32)):
+                        lv = _leaves(case, per_ray, dtype)
+                        if name == "fused":
+                            rd = dict(lv, weights=torch.empty(R, M, device=device)) if per_ray else lv
+                            loss, parts = cn.compute_loss_fused(rd, gt, m, library=lib, **kw)
+                        else:
+                            loss, parts = _compute_loss_of(lv, gt, m, M, **kw)
+                        grads = torch.autograd.grad(loss * 1.0, list(lv.values()), allow_unused=True)
+                        res[name] = (parts, {k: (torch.zeros_like(lv[k]) if g is None else g).detach().double() for k, g in zip(lv, grads)})
+                    (p64, g64), (p32, g32), (pf, gf) = res["ref"], res["f32"], res["fused"]
+                    assert set(pf) == set(p64), (R, per_ray, kw, use_mask)
+                    tag = (R, M, per_ray, tuple(kw.items()), use_mask)
+                    for k in p64:
+                        rows.append((tag, k, rel(p32[k], p64[k]), rel(pf[k], p64[k])))
+                    for k in g64:
+                        den = float(g64[k].abs().max())
+                        dist = lambda g: float((g - g64[k]).abs().max()) / den if den > 0.0 else (0.0 if float(g.abs().max()) == 0.0 else float("inf"))
+                        rows.append((tag, "d " + k, dist(g32[k]), dist(gf[k])))
+    bad = []
+    for q in sorted({r[1] for r in rows}):
+        yard, got = max(r[2] for r in rows if r[1] == q), max(r[3] for r in rows if r[1] == q)
+        print("fused loss, %s: float32 compute_loss within %.2e of float64, the library within %.2e" % (q, yard, got))
+        bad += ["%s at %r: %.3g > 4 x %.3g" % (q, r[0], r[3], yard) for r in rows if r[1] == q and not r[3] <= 4.0 * yard]
+    assert not bad, "\n".join(bad[:40])
+
+
+@pytest.mark.skipif(not os.path.isfile(N.EMU_LIB), reason="emulation library not built")
+def test_fused_loss_wrapped_loops_against_float64_emu():
+    import color_neus_amd as cn
+    _compare64(cn.load_library(N.EMU_LIB), "cpu")
+
+
+@pytest.mark.gpu
+def test_fused_loss_wrapped_loops_against_float64_hip():
+    import color_neus_amd as cn
+    _compare64(cn.load_library(), "cuda:0")
+
+
 @pytest.mark.gpu
 def test_fused_loss_end_to_end_gradients_match():
     """A whole training step with the fused loss gives the parameter gradients of the step with the torch loss."""
@@ -170,7 +259,9 @@ def _one_launch_forms(library, device):
     g = torch.Generator().manual_seed(7)
     p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
     st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else C.c_void_p(0)
-    for R, M, use_mask, per_ray in ((4096, 128, True, False), (1000, 16, True, True), (53, 12, False, False), (1, 8, True, True)):
+    # (30000 rays: every block of the 256 x 256 forward launch has made a second trip through the colour loop, with M = 2 through the relight loop too)
+    for R, M, use_mask, per_ray in ((4096, 128, True, False), (1000, 16, True, True), (53, 12, False, False), (1, 8, True, True),
+                                    (30000, 2, True, True), (30000, 2, False, False)):
         color = torch.rand(R, 3, generator=g).to(device); gt = torch.rand(R, 3, generator=g).to(device)
         wsum = torch.rand(R, generator=g).to(device); mask = (torch.rand(R, generator=g) > 0.3).float().to(device) if use_mask else None
         drel = (torch.randn(R, generator=g) if per_ray else torch.randn(R, M, 3, generator=g) * 0.1).to(device)

@@ -655,10 +655,13 @@ def test_fused_loss_hip(R, use_mask, sharded):
     _run(HIP, _fused_loss, R, use_mask, sharded, gate=_gate_fused_loss(R))
 
 
-def _clip_adam(library, dev, g):
-    """One ClipAdam step on the tensor shapes of test_clip_adam._run"""
+def _clip_adam(library, dev, g, group="seven"):
+    """One ClipAdam step on the tensor shapes of test_clip_adam._run ("seven"), or on that module's group of 73 tensors ("split": two
+    launches of 64 and 9 tensors, the second one's chunk sums behind the first one's in the scratch, tensors of 64, 65 and 74 chunks --
+    cnr_clip_adam_scratch_bytes of a split call, exact-size and poisoned)"""
+    import test_clip_adam as CA
     gen = torch.Generator().manual_seed(3)
-    shapes = [(257, 256), (256,), (256, 1), (1,), (3, 259), (217, 39), (65536 // 64, 70)]
+    shapes = [(257, 256), (256,), (256, 1), (1,), (3, 259), (217, 39), (65536 // 64, 70)] if group == "seven" else [(n,) for n in CA._group_sizes()]
     ps = [torch.randn(s, generator=gen).to(dev).requires_grad_(True) for s in shapes]
     opt = cn.ClipAdam(ps, lr=5e-4, betas=(0.9, 0.99), eps=1e-8, max_norm=0.05, library=library)
     for p in ps:
@@ -670,12 +673,12 @@ def _clip_adam(library, dev, g):
     return res
 
 
-def _gate_clip_adam():
+def _gate_clip_adam(group="seven"):
     import test_clip_adam as CA
-    return lambda library, dev: CA._run(library, dev, steps=2)
+    return (lambda library, dev: CA._run(library, dev, steps=2)) if group == "seven" else (lambda library, dev: CA._group_check(library, dev))
 
 
-CLIP_ADAM = _cases(_clip_adam, [()])
+CLIP_ADAM = _cases(_clip_adam, [(), ("split",)])
 
 
 def test_clip_adam_emu():
@@ -685,6 +688,15 @@ def test_clip_adam_emu():
 @pytest.mark.gpu
 def test_clip_adam_hip():
     _run(HIP, _clip_adam, gate=_gate_clip_adam())
+
+
+def test_clip_adam_split_call_emu():
+    _run(EMU, _clip_adam, "split", gate=_gate_clip_adam("split"))
+
+
+@pytest.mark.gpu
+def test_clip_adam_split_call_hip():
+    _run(HIP, _clip_adam, "split", gate=_gate_clip_adam("split"))
 
 
 # =====================================================================================================================================

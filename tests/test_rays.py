@@ -88,6 +88,60 @@ def _backward(library, dev):
         assert float(cd.grad[:, 3].abs().max()) == 0.0     # bottom row of the pose matrices
 
 
+def _own_poses(n_cams, g):
+    """camera-to-world matrices of the test's own: random rotations (QR of a Gaussian draw, determinant fixed to +1), random translations"""
+    q, r = torch.linalg.qr(torch.randn(n_cams, 3, 3, generator=g, dtype=torch.float64))
+    q = q * torch.sign(torch.diagonal(r, dim1=1, dim2=2))[:, None, :]
+    q[:, :, 0] = q[:, :, 0] * torch.sign(torch.linalg.det(q))[:, None]
+    assert bool((torch.linalg.det(q) > 0.999).all())
+    c2w = torch.eye(4, dtype=torch.float64).repeat(n_cams, 1, 1)
+    c2w[:, :3, :3], c2w[:, :3, 3] = q, torch.randn(n_cams, 3, generator=g, dtype=torch.float64)
+    return c2w.float()
+
+
+def _backward_wrapped(library, dev):
+    """The backward beyond one trip of its ray loop: each camera's workgroup walks ALL n rays 256 at a time.  700 rays (three trips, the
+    last one ragged; all four waves of a block hold non-zero partial sums) over cameras 0, 1, 2 and 4 of 5 -- camera 3 has no ray, camera 4
+    only five, one in each trip and two more, so d c2w is held per camera, against that camera's own largest reference entry."""
+    g = torch.Generator().manual_seed(9)
+    H, W, n, n_cams = 12, 17, 700, 5
+    c2w, focal = _own_poses(n_cams, g), torch.tensor([15.0, 16.5])
+    origin, radius = torch.tensor([0.1, -0.2, 0.05]), 1.7
+    few = torch.tensor([3, 300, 400, 600, 699])
+    cam = torch.tensor([0, 1, 2])[torch.randint(0, 3, (n,), generator=g)]
+    cam[few] = 4
+    idx = cam * (H * W) + torch.randint(0, H * W, (n,), generator=g)
+    lib = rays._library(library)
+
+    def run(idx, co, normalize, opengl):
+        cd, fd = c2w.clone().to(dev).requires_grad_(True), focal.clone().to(dev).requires_grad_(True)     # (clone: on the CPU .to() is the tensor itself)
+        o, d, _, _, near, far = rays._generate(lib, idx.to(dev), idx.shape[0], cd, fd, H, W, normalize, opengl, origin=origin, radius=radius, want_nearfar=True)
+        (sum((a * b.to(dev)).sum() for a, b in zip((o, d, near, far), co))).backward()
+        return [t.detach().cpu() for t in (o, d, near, far)], cd.grad.cpu(), fd.grad.cpu()
+
+    for normalize, opengl in ((True, False), (False, True)):
+        co = [torch.randn(n, 3, generator=g), torch.randn(n, 3, generator=g), torch.randn(n, generator=g), torch.randn(n, generator=g)]
+        c64, f64 = c2w.double().requires_grad_(True), focal.double().requires_grad_(True)
+        ref = _torch_rays(c64, f64, idx, H, W, normalize, opengl, origin.double(), radius)
+        sum((a * b.double()).sum() for a, b in zip(ref, co)).backward()
+        outs, dc, df = run(idx, co, normalize, opengl)
+        for a, b in zip(outs, ref):
+            assert torch.allclose(a.double(), b.detach(), atol=2e-6)
+        for c in (0, 1, 2, 4):
+            err, den = float((dc[c].double() - c64.grad[c]).abs().max()), float(c64.grad[c].abs().max())
+            assert err < 2e-5 * den, (normalize, opengl, c, err / den)
+        assert float((df.double() - f64.grad).abs().max()) < 2e-5 * float(f64.grad.abs().max())
+        assert float(dc[3].abs().max()) == 0.0 and float(c64.grad[3].abs().max()) == 0.0     # the camera without rays
+        assert float(dc[:, 3].abs().max()) == 0.0                                            # bottom row of the pose matrices
+        # ray 256 is the first ray of the second trip: with a zero cotangent on it, the 257-ray run folds exactly what the 256-ray run folds
+        co256 = [t[:256] for t in co]
+        co257 = [torch.cat([t[:256], torch.zeros_like(t[256:257])]) for t in co]
+        _, dc256, df256 = run(idx[:256], co256, normalize, opengl)
+        _, dc257, df257 = run(idx[:257], co257, normalize, opengl)
+        assert torch.equal(dc256, dc257) and torch.equal(df256, df257), (normalize, opengl)
+        assert float(dc256.abs().max()) > 0.0
+
+
 def _bad_indices(library, dev):
     """A caller-supplied index outside [0, n_cams * H * W): the kernel reads nothing for it (the image / mask / pose reads would be out of
     bounds), that ray's outputs are NaN, its backward contributes nothing, and every other ray is untouched."""
@@ -143,6 +197,16 @@ def test_get_rays_at_and_near_far_emu():
 @emu
 def test_pose_and_focal_gradients_emu():
     _backward(N.EMU_LIB, "cpu")
+
+
+@emu
+def test_pose_and_focal_gradients_beyond_one_trip_emu():
+    _backward_wrapped(N.EMU_LIB, "cpu")
+
+
+@pytest.mark.gpu
+def test_pose_and_focal_gradients_beyond_one_trip_hip():
+    _backward_wrapped(None, "cuda:0")
 
 
 @pytest.mark.gpu
